@@ -2,7 +2,7 @@
 """Headline benchmark: mel-frames/s of the F5-TTS flow-matching sampler (CFM.sample: 32 Euler steps x (cond + uncond) DiT
 evaluations, CFG 2, sway -1) on MI355X, at BASELINE.json's C2: F5TTS_Base, bf16, batch 32, seq_len 1024, NFE 32.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--workload C2|C4|vocos]
+  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--workload C2|C4|vocos] [--dump-outputs DIR]
 
 A "step" is one full sample() over one synthetic batch of fixed-length utterances that is already resident in HBM.
 
@@ -27,6 +27,9 @@ One JSON line on rank 0 with the driver's contract fields plus
 The default C2 run on one GPU also measures C4 (2 timed sample() calls + in-situ kernel table) and C5 afterwards and reports them under
 "workloads": {"C4": {value, ms_per_step, attention_frac, ...}, "C5": {value, rtf, head_gbs, cpu_baseline, ...}} (--no-extra skips them);
 the C2 fields are unchanged.
+  --dump-outputs DIR  after the timed steps, write what the last timed step returned (the mels of sample(), gathered over all ranks, or
+      the waveforms of Vocos.decode) as DIR/<name>.npy in float32.  Weights and inputs are seeded, so the same arguments give the same
+      inputs on every run and two builds can be compared output for output.  Above 64 MB in all, a fixed seeded subset of rows is written.
 """
 from __future__ import annotations
 
@@ -46,10 +49,26 @@ sys.path.insert(0, ROOT)
 
 BASE_ARCH = dict(dim=1024, depth=22, heads=16, ff_mult=2, text_dim=512, text_mask_padding=False, conv_layers=4, pe_attn_head=1)
 VOCAB = 2545
-MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16, MI355X data sheet
 MFMA_F32_PEAK_TFLOPS = 157.3    # fp32-input MFMA (the vocoder backbone)
-HBM_PEAK_GBS = 8000.0           # HBM3E spec (6.3 TB/s achievable, same guide)
+HBM_PEAK_GBS = 8000.0           # HBM3E spec (6.3 TB/s achievable)
 WORKLOADS = {"C2": (32, 1024), "C4": (8, 4096)}
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor as <out_dir>/<name>.npy in float32.  When they exceed DUMP_LIMIT_BYTES together, every array keeps
+    a seeded, sorted subset of its rows (all axes but the last flattened) in the same share of the budget."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = max(1, int(rows.shape[0] * DUMP_LIMIT_BYTES / total))
+            a = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def synth_weights(model, seed=0):
@@ -148,8 +167,9 @@ def launch_children(args):
     sys.exit(rc)
 
 
-def bench_vocos(args, dev, T=None, B=None, steps=None, warmup=None):
-    """C5: Vocos.decode on the generated part of a C2 (T = 683) or C4 (T = 2731) batch.  Returns the result record."""
+def bench_vocos(args, dev, T=None, B=None, steps=None, warmup=None, dump_dir=None):
+    """C5: Vocos.decode on the generated part of a C2 (T = 683) or C4 (T = 2731) batch.  Returns the result record; with dump_dir, the
+    waveforms of the last timed decode go to dump_dir/wave.npy."""
     import torch
     from eraxvif5tts_amd import _lib
     from eraxvif5tts_amd.vocos import Vocos
@@ -174,6 +194,8 @@ def bench_vocos(args, dev, T=None, B=None, steps=None, warmup=None):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     assert torch.isfinite(wave).all()
+    if dump_dir:
+        dump_outputs(dump_dir, {"wave": wave})
     frames = B * T * steps
     audio_s = B * (T - 1) * 256 / 24000.0 * steps
     # ISTFT head alone (HBM-bound): HIP events around f5_vocoder_istft_head on this stream
@@ -463,7 +485,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="C2 run: skip the C4 / C5 measurements recorded under `workloads`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus is None:
@@ -479,6 +504,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
     import torch
+    torch.manual_seed(0)  # DiT() draws its non-zero initial weights from the global generator: the same weights on every run
     backend = "none"
     if world > 1:
         import torch.distributed as dist
@@ -504,7 +530,7 @@ def main():
     if args.workload == "vocos":
         if world > 1:
             sys.exit("bench.py: --workload vocos is a single-GPU measurement")
-        print(json.dumps(bench_vocos(args, dev)), flush=True)
+        print(json.dumps(bench_vocos(args, dev, dump_dir=args.dump_outputs)), flush=True)
         return
 
     wl_B, wl_N = WORKLOADS[args.workload]
@@ -571,6 +597,13 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path receives: sample()'s mels of the last step, every rank's share in utterance order
+        mel = out
+        if world > 1:
+            counts = [len(split_between_processes(list(range(B_req)), r, world)) if args.scaling == "strong" else B_req for r in range(world)]
+            mel = torch.cat([g[:n] for g, n in zip(gathered, counts)])
+        dump_outputs(args.dump_outputs, {"mel": mel})
     devices = [torch.cuda.get_device_name(dev)]
     per_rank = None
     if world > 1:
