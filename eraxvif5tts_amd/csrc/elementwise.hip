@@ -908,13 +908,15 @@ int launch_convert_back(int precision_in, const void* src, int lds, int rows, in
     return 0;
 }
 
-// A_base row m = [ cond[m][0..mel) masked by lens | 0 pad to melp | text_embed[m][0..td) ]
+// A_base row m = [ cond[m][0..mel) masked by lens (or by cmask) | 0 pad to melp | text_embed[m][0..td) ]
 template <typename TO>
-__global__ __launch_bounds__(256) void pack_base_kernel(const float* __restrict__ cond, const int32_t* __restrict__ lens, const float* __restrict__ te,
-                                                        int B, int N, int mel, int melp, int td, int zero_cond, TO* __restrict__ dst, int ldd) {
+__global__ __launch_bounds__(256) void pack_base_kernel(const float* __restrict__ cond, const int32_t* __restrict__ lens, const uint8_t* __restrict__ cmask,
+                                                        const float* __restrict__ te, int B, int N, int mel, int melp, int td, int zero_cond,
+                                                        TO* __restrict__ dst, int ldd) {
     const int row = blockIdx.x;
     const int b = row / N, p = row % N;
-    const bool keep = !zero_cond && (lens == nullptr || p < lens[b]);  // step_cond = where(cond_mask, cond, 0) (cfm.py:148-150)
+    // step_cond = where(cond_mask, cond, 0) (cfm.py:148-150); cond_mask = frame < lens, or lens_mask & edit_mask when cmask is given (cfm.py:123-127)
+    const bool keep = !zero_cond && (cmask ? cmask[row] != 0 : (lens == nullptr || p < lens[b]));
     for (int c = threadIdx.x; c < melp + td; c += 256) {
         float v;
         if (c < melp)
@@ -924,13 +926,15 @@ __global__ __launch_bounds__(256) void pack_base_kernel(const float* __restrict_
         dst[(size_t)row * ldd + c] = from_f32<TO>(v);
     }
 }
-int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, const float* text_embed, int B, int N, int mel, int melp,
-                     int td, int zero_cond, void* dst, int ldd, hipStream_t stream) {
+int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, const uint8_t* cmask, const float* text_embed, int B, int N, int mel,
+                     int melp, int td, int zero_cond, void* dst, int ldd, hipStream_t stream) {
     if (B * N <= 0) return 0;
     if (precision_out == F5_PREC_BF16)
-        hipLaunchKernelGGL((pack_base_kernel<bf16_t>), dim3(B * N), dim3(256), 0, stream, cond, lens, text_embed, B, N, mel, melp, td, zero_cond, (bf16_t*)dst, ldd);
+        hipLaunchKernelGGL((pack_base_kernel<bf16_t>), dim3(B * N), dim3(256), 0, stream, cond, lens, cmask, text_embed, B, N, mel, melp, td, zero_cond,
+                           (bf16_t*)dst, ldd);
     else
-        hipLaunchKernelGGL((pack_base_kernel<float>), dim3(B * N), dim3(256), 0, stream, cond, lens, text_embed, B, N, mel, melp, td, zero_cond, (float*)dst, ldd);
+        hipLaunchKernelGGL((pack_base_kernel<float>), dim3(B * N), dim3(256), 0, stream, cond, lens, cmask, text_embed, B, N, mel, melp, td, zero_cond,
+                           (float*)dst, ldd);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -959,17 +963,18 @@ int launch_cfg_step(const float* x_base, const float* vc, const float* vu, int l
 }
 
 __global__ __launch_bounds__(256) void final_where_kernel(const float* __restrict__ cond, const float* __restrict__ x, const int32_t* __restrict__ lens,
-                                                          int B, int N, int mel, float* __restrict__ out) {
+                                                          const uint8_t* __restrict__ cmask, int B, int N, int mel, float* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)B * N * mel) return;
     const int row = (int)(i / mel);
     const int b = row / N, p = row % N;
-    out[i] = p < lens[b] ? cond[i] : x[i];
+    const bool keep = cmask ? cmask[row] != 0 : p < lens[b];
+    out[i] = keep ? cond[i] : x[i];
 }
-int launch_final_where(const float* cond, const float* x, const int32_t* lens, int B, int N, int mel, float* out, hipStream_t stream) {
+int launch_final_where(const float* cond, const float* x, const int32_t* lens, const uint8_t* cmask, int B, int N, int mel, float* out, hipStream_t stream) {
     const size_t total = (size_t)B * N * mel;
     if (total == 0) return 0;
-    hipLaunchKernelGGL(final_where_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, cond, x, lens, B, N, mel, out);
+    hipLaunchKernelGGL(final_where_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, cond, x, lens, cmask, B, N, mel, out);
     F5_LAUNCH_CHECK();
     return 0;
 }

@@ -105,13 +105,13 @@ int compute_text_embed(f5_plan_s* p, const int32_t* text, int nt, int B, int N, 
 
 // base[rows, D] = b_in + W_cond . cond + W_text . text_embed for `nb` batch rows starting at row offset row0
 int compute_base(f5_plan_s* p, const float* cond, const int32_t* lens, const float* te, int nb, int N, int zero_cond, size_t row0,
-                        hipStream_t st) {
+                        hipStream_t st, const uint8_t* cmask) {
     f5_model_s* m = p->m;
     const f5_dit_config& c = m->cfg;
     const int D = c.dim, td = m->in_td, P = c.precision, kct = MELP + m->td_pad;  // (columns td .. td_pad stay zero: the arena zero-fills)
     const size_t es = f5_elem_size(P);
     void* ab = (char*)p->abase + row0 * kct * es;
-    F5_TRY(launch_pack_base(P, cond, lens, te, nb, N, c.mel_dim, MELP, td, zero_cond, ab, kct, st));
+    F5_TRY(launch_pack_base(P, cond, lens, cmask, te, nb, N, c.mel_dim, MELP, td, zero_cond, ab, kct, st));
     GemmParams g = gp_zero();
     g.A = ab; g.lda = kct; g.W = m->w_ct; g.ldw = kct; g.M = nb * N; g.N = D; g.K = kct;
     g.bias = m->b_in; g.out_f = p->base + row0 * D; g.ldof = D;

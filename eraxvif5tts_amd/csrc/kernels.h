@@ -81,14 +81,15 @@ int launch_gemv_rows(const float* in, int ldi, int rows, const float* W, const f
 // f32 [rows, cols] -> activation dtype [rows, ldo] with zero padding of columns cols..padcols-1
 int launch_convert_pad(int precision_out, const float* src, int lds, int rows, int cols, int padcols, void* dst, int ldo, hipStream_t stream);
 int launch_convert_back(int precision_in, const void* src, int lds, int rows, int cols, float* dst, int ldd, hipStream_t stream);
-// A_base rows: [cond(mel, padded to melp) | text_embed(td)] per branch (see model.cpp)
-int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, const float* text_embed, int B, int N, int mel, int melp,
-                     int td, int zero_cond, void* dst, int ldd, hipStream_t stream);
+// A_base rows: [cond(mel, padded to melp) | text_embed(td)] per branch (see model.cpp); the cond half is kept where cmask[b][n] != 0 when cmask
+// (u8 [B, N]) is given, else where n < lens[b] (lens null: every frame); zero_cond zeroes it everywhere
+int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, const uint8_t* cmask, const float* text_embed, int B, int N, int mel,
+                     int melp, int td, int zero_cond, void* dst, int ldd, hipStream_t stream);
 // x_out = x_base + coef[0] * (vc + (vc - vu) * cfg)   (cfm.py:173 + torchdiffeq step); vu == null -> x_base + coef * vc
 int launch_cfg_step(const float* x_base, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* coef,
                     float* x_out, float* x_out2 /*or null*/, hipStream_t stream);
-// out = frame < lens[b] ? cond : x   (cfm.py:200-202)
-int launch_final_where(const float* cond, const float* x, const int32_t* lens, int B, int N, int mel, float* out, hipStream_t stream);
+// out = frame < lens[b] ? cond : x   (cfm.py:200-202); with cmask (u8 [B, N], or null): out = cmask[b][frame] ? cond : x
+int launch_final_where(const float* cond, const float* x, const int32_t* lens, const uint8_t* cmask, int B, int N, int mel, float* out, hipStream_t stream);
 // mask[b][n] = n < durations[b]
 int launch_len_mask(const int32_t* durations, int B, int N, uint8_t* mask, hipStream_t stream);
 int launch_rowbits(const uint8_t* mask, int rows, uint8_t* bits, hipStream_t stream);

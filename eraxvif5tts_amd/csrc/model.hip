@@ -481,6 +481,7 @@ extern "C" int f5_plan_create(f5_model_t m, int max_batch, int max_seq, int max_
         if ((rc = A.alloc_t(&p->cond_in, bn * mel))) break;
         if ((rc = A.alloc_t(&p->text_in, bn))) break;
         if ((rc = A.alloc_t(&p->lens_in, (size_t)max_batch))) break;
+        if ((rc = A.alloc_t(&p->cmask_in, bn))) break;
         if ((rc = A.alloc_t(&p->dur_in, (size_t)max_batch))) break;
         // RoPE table for positions < max_seq: angle = p * inv_freq_j in fp32, as x_transformers computes it
         const int rope_n = max_seq + (un ? 1 : 0);

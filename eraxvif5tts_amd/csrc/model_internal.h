@@ -87,6 +87,7 @@ struct GraphEntry {
     float cfg;
     int epoch;
     uint64_t fold_id = 0;  // the FoldTable whose addresses the capture baked (0 = none)
+    int cmask_on = 0;      // captured with the staged per-frame condition mask (f5_sample_masked)
     std::vector<int> rn;   // ragged sample(): the utterances' frame counts (empty: a uniform batch)
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
@@ -95,6 +96,7 @@ struct GraphEntry {
 struct SampleArgs {
     int B, N, nt, steps, method, cfg_on, mask_on;
     float cfg;
+    int cmask_on = 0;  // the condition mask is the staged cmask_in (f5_sample_masked), not the lens prefix
 };
 // f5_sample_ragged: utterances of different frame counts concatenated along the token axis.  One CFG half holds utterance i at rows
 // [off[i], off[i] + n[i]) followed by at least RAGGED_GAP rows that are kept ZERO wherever the position conv reads them, so the conv's own
@@ -129,6 +131,7 @@ struct f5_plan_s {
     uint8_t *filler = nullptr, *mask = nullptr, *rowbits = nullptr;
     const uint8_t* rowbits_src = nullptr;  // the row mask `rowbits` was built from (GemmParams::rowbits)
     int32_t *text_in = nullptr, *lens_in = nullptr, *dur_in = nullptr;
+    uint8_t* cmask_in = nullptr;  // staged condition mask of f5_sample_masked, u8 [max_batch, max_seq]
     int rope_n = 0;
     int gemm_kernel = -1, attn_kernel = -1;  // -1 = auto (tuned kernel when it supports the problem)
     // Range guard of the fp16 residual stream (bf16 production mode): the LayerNorm passes raise `sat_flag` (device word) when an element of
@@ -228,7 +231,9 @@ int tap_f32(f5_plan_s* p, const std::string& name, const float* src, int ld, int
 int tap_t(f5_plan_s* p, const std::string& name, const void* src, int ld, int rows, int cols, hipStream_t st);
 int compute_modulation(f5_plan_s* p, const float* tvals_dev, int n, hipStream_t st);
 int compute_text_embed(f5_plan_s* p, const int32_t* text, int nt, int B, int N, int drop_text, float* out, hipStream_t st);
-int compute_base(f5_plan_s* p, const float* cond, const int32_t* lens, const float* te, int nb, int N, int zero_cond, size_t row0, hipStream_t st);
+// cmask: u8 [nb, N] condition mask that replaces the lens prefix (f5_sample_masked), or null
+int compute_base(f5_plan_s* p, const float* cond, const int32_t* lens, const float* te, int nb, int N, int zero_cond, size_t row0, hipStream_t st,
+                 const uint8_t* cmask = nullptr);
 int net_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, int time_row, int per_batch_rows, const uint8_t* mask, hipStream_t st);
 int check_plan_shape(f5_plan_s* p, int B, int N);
 // ---- one evaluation per backbone

@@ -22,10 +22,11 @@ static int sample_body(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
     // (the AdaLN modulation rows of all evaluation times are already in p->mod: f5_sample keeps them across calls)
     // text embeddings are constants of the whole sample() (the reference caches them per branch, dit.py:202-210)
     F5_TRY(compute_text_embed(p, p->text_in, a.nt, B, N, 0, p->te[0], st));
-    F5_TRY(compute_base(p, p->cond_in, p->lens_in, p->te[0], B, N, 0, 0, st));
+    const uint8_t* cmask = a.cmask_on ? p->cmask_in : nullptr;  // read from the plan buffer: a replay sees the current call's mask
+    F5_TRY(compute_base(p, p->cond_in, p->lens_in, p->te[0], B, N, 0, 0, st, cmask));
     if (a.cfg_on) {
         F5_TRY(compute_text_embed(p, p->text_in, a.nt, B, N, 1, p->te[1], st));
-        F5_TRY(compute_base(p, p->cond_in, p->lens_in, p->te[1], B, N, 1, (size_t)bn, st));
+        F5_TRY(compute_base(p, p->cond_in, p->lens_in, p->te[1], B, N, 1, (size_t)bn, st, cmask));
     }
     const uint8_t* mask = nullptr;
     if (a.mask_on) {
@@ -85,11 +86,12 @@ static int run_sample_loop(f5_plan_s* p, const SampleArgs& a, int use_graph, hip
         }
         for (auto& g : p->graphs)
             if (g.B == a.B && g.N == a.N && g.nt == a.nt && g.steps == a.steps && g.method == a.method && g.cfg_on == a.cfg_on &&
-                g.mask_on == a.mask_on && g.cfg == a.cfg && g.fold_id == (p->fold && g_ln_fold ? p->fold->id : 0) &&
+                g.mask_on == a.mask_on && g.cmask_on == a.cmask_on && g.cfg == a.cfg && g.fold_id == (p->fold && g_ln_fold ? p->fold->id : 0) &&
                 g.rn == (p->rg ? p->rg->n : std::vector<int>()))
                 ge = &g;
         if (!ge) {
             GraphEntry g{a.B, a.N, a.nt, a.steps, a.method, a.cfg_on, a.mask_on, a.cfg, g_tuning_epoch, (p->fold && g_ln_fold) ? p->fold->id : 0};
+            g.cmask_on = a.cmask_on;
             if (p->rg) g.rn = p->rg->n;
             if (!p->cap_stream) F5_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
             F5_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed));
@@ -143,7 +145,7 @@ static int guard_check_and_fallback(f5_plan_s* p, const SampleArgs& a, int use_g
 static int finish_outputs(f5_plan_s* p, const SampleArgs& a, float* out, float* trajectory, hipStream_t st) {
     const int mel = p->m->cfg.mel_dim;
     const size_t state = (size_t)a.B * a.N * mel;
-    F5_TRY(launch_final_where(p->cond_in, p->traj + (size_t)a.steps * state, p->lens_in, a.B, a.N, mel, out, st));
+    F5_TRY(launch_final_where(p->cond_in, p->traj + (size_t)a.steps * state, p->lens_in, a.cmask_on ? p->cmask_in : nullptr, a.B, a.N, mel, out, st));
     if (trajectory) F5_HIP(hipMemcpyAsync(trajectory, p->traj, (size_t)(a.steps + 1) * state * sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
 }
@@ -246,9 +248,10 @@ int finish_if_pending(f5_plan_s* p) {
     return 0;
 }
 
-extern "C" int f5_sample(f5_plan_t p, int B, int N, const float* cond, const int32_t* text, int nt, const int32_t* lens,
-                         const int32_t* durations, const float* y0, const float* tgrid_host, int steps, float cfg_strength, int ode_method,
-                         float* out, float* trajectory, int use_graph, f5_stream_t stream) {
+// f5_sample and f5_sample_masked: cond_mask (dev u8 [B, N]) or null = the lens prefix
+static int sample_impl(f5_plan_t p, int B, int N, const float* cond, const int32_t* text, int nt, const int32_t* lens, const int32_t* durations,
+                       const float* y0, const float* tgrid_host, int steps, float cfg_strength, int ode_method, float* out, float* trajectory,
+                       int use_graph, f5_stream_t stream, const uint8_t* cond_mask) {
     F5_TRY(check_plan_shape(p, B, N));
     if (!cond || !text || !lens || !y0 || !tgrid_host || !out) return f5_fail(F5_EINVAL, "null argument");
     if (steps <= 0 || nt <= 0) return f5_fail(F5_EINVAL, "steps and nt must be positive");
@@ -270,8 +273,9 @@ extern "C" int f5_sample(f5_plan_t p, int B, int N, const float* cond, const int
     F5_HIP(hipMemcpy2DAsync(p->text_in, (size_t)nt_eff * 4, text, (size_t)nt * 4, (size_t)nt_eff * 4, B, hipMemcpyDeviceToDevice, st));
     F5_HIP(hipMemcpyAsync(p->lens_in, lens, B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     if (durations) F5_HIP(hipMemcpyAsync(p->dur_in, durations, B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (cond_mask) F5_HIP(hipMemcpyAsync(p->cmask_in, cond_mask, (size_t)bn, hipMemcpyDeviceToDevice, st));
 
-    SampleArgs a{B, N, nt_eff, steps, ode_method, cfg_strength >= 1e-5f ? 1 : 0, durations ? 1 : 0, cfg_strength};  // cfm.py:167
+    SampleArgs a{B, N, nt_eff, steps, ode_method, cfg_strength >= 1e-5f ? 1 : 0, durations ? 1 : 0, cfg_strength, cond_mask ? 1 : 0};  // cfm.py:167
     const bool guarded = plan_res_f16(p) && p->sat_check && !p->timing;
     F5_TRY(run_sample_loop(p, a, use_graph, st));
     p->pending = PendingSample{};
@@ -283,6 +287,21 @@ extern "C" int f5_sample(f5_plan_t p, int B, int N, const float* cond, const int
         F5_TRY(guard_check_and_fallback(p, a, use_graph, st));
     }
     return finish_outputs(p, a, out, trajectory, st);
+}
+
+extern "C" int f5_sample(f5_plan_t p, int B, int N, const float* cond, const int32_t* text, int nt, const int32_t* lens,
+                         const int32_t* durations, const float* y0, const float* tgrid_host, int steps, float cfg_strength, int ode_method,
+                         float* out, float* trajectory, int use_graph, f5_stream_t stream) {
+    return sample_impl(p, B, N, cond, text, nt, lens, durations, y0, tgrid_host, steps, cfg_strength, ode_method, out, trajectory, use_graph,
+                       stream, nullptr);
+}
+
+extern "C" int f5_sample_masked(f5_plan_t p, int B, int N, const float* cond, const int32_t* text, int nt, const int32_t* lens,
+                                const int32_t* durations, const float* y0, const float* tgrid_host, int steps, float cfg_strength,
+                                int ode_method, const uint8_t* cond_mask, float* out, float* trajectory, int use_graph, f5_stream_t stream) {
+    if (!cond_mask) return f5_fail(F5_EINVAL, "null cond_mask");
+    return sample_impl(p, B, N, cond, text, nt, lens, durations, y0, tgrid_host, steps, cfg_strength, ode_method, out, trajectory, use_graph,
+                       stream, cond_mask);
 }
 
 extern "C" int f5_sample_finish(f5_plan_t p, f5_stream_t stream) {
@@ -401,7 +420,7 @@ extern "C" int f5_sample_ragged(f5_plan_t p, int B, const int32_t* frames_host, 
     src = 0;
     for (int u = 0; u < B; ++u) {
         const size_t off = rg.off[u];
-        F5_TRY(launch_final_where(p->cond_in + off * mel, xf + off * mel, p->lens_in + u, 1, rg.n[u], mel, out + src * mel, st));
+        F5_TRY(launch_final_where(p->cond_in + off * mel, xf + off * mel, p->lens_in + u, nullptr, 1, rg.n[u], mel, out + src * mel, st));
         src += (size_t)rg.n[u];
     }
     (void)total;

@@ -275,14 +275,15 @@ class DiT(nn.Module):
 
     # ------------------------------------------------------------------ whole-loop entry used by CFM.sample
     def native_sample(self, cond, text, lens, durations, y0, tgrid, steps, cfg_strength, method="euler", use_mask=True,
-                      return_trajectory=False, use_graph=True, defer_guard=False):
-        """cond/y0 f32 [B,N,mel] on the GPU, text int [B,nt] (-1 padded), lens/durations int [B], tgrid f32 [steps+1] (any device)."""
+                      return_trajectory=False, use_graph=True, defer_guard=False, cond_mask=None):
+        """cond/y0 f32 [B,N,mel] on the GPU, text int [B,nt] (-1 padded), lens/durations int [B], tgrid f32 [steps+1] (any device).
+        cond_mask: bool [B,N] (speech editing: lens_to_mask(lens) & edit_mask) in place of the lens prefix (f5_sample_masked), or None."""
         lib = _lib.load()
         B, N = cond.shape[0], cond.shape[1]
         evals = steps * (2 if method == "midpoint" else 1)
         # capturing + instantiating a ~5000-node graph costs about as much as one small sample(): only replay shapes that recur
         # (serving with fixed buckets, batch inference); one-off shapes (free-form generate()) run eagerly on the stream
-        key = (B, N, int(text.shape[1]), steps, method, float(cfg_strength), bool(use_mask))
+        key = (B, N, int(text.shape[1]), steps, method, float(cfg_strength), bool(use_mask), cond_mask is not None)
         seen = self._seen_shapes.get(key, 0)
         self._seen_shapes[key] = seen + 1
         if use_graph == "auto":
@@ -300,9 +301,16 @@ class DiT(nn.Module):
         meth = {"euler": _lib.F5_ODE_EULER, "midpoint": _lib.F5_ODE_MIDPOINT}[method]
         # defer_guard: f5_sample enqueues and returns without its one synchronisation (the fp16 range-guard read); finish_pending() does it
         _lib.check(lib.f5_plan_set_option(plan, b"residual_guard", 2 if defer_guard else 1), "plan_set_option")
-        _lib.check(lib.f5_sample(plan, B, N, _lib.ptr(cond), _lib.ptr(ids), ids.shape[1], _lib.ptr(lens32), _lib.ptr(dur32), _lib.ptr(y0),
-                                 C.c_void_p(tg.data_ptr()), steps, float(cfg_strength), meth, _lib.ptr(out), _lib.ptr(traj),
-                                 int(bool(use_graph)), _lib.stream_ptr()), "sample")
+        if cond_mask is None:
+            _lib.check(lib.f5_sample(plan, B, N, _lib.ptr(cond), _lib.ptr(ids), ids.shape[1], _lib.ptr(lens32), _lib.ptr(dur32), _lib.ptr(y0),
+                                     C.c_void_p(tg.data_ptr()), steps, float(cfg_strength), meth, _lib.ptr(out), _lib.ptr(traj),
+                                     int(bool(use_graph)), _lib.stream_ptr()), "sample")
+        else:
+            cm = cond_mask.to(device=dev, dtype=torch.uint8).contiguous()
+            assert tuple(cm.shape) == (B, N), (tuple(cm.shape), (B, N))
+            _lib.check(lib.f5_sample_masked(plan, B, N, _lib.ptr(cond), _lib.ptr(ids), ids.shape[1], _lib.ptr(lens32), _lib.ptr(dur32), _lib.ptr(y0),
+                                            C.c_void_p(tg.data_ptr()), steps, float(cfg_strength), meth, _lib.ptr(cm), _lib.ptr(out), _lib.ptr(traj),
+                                            int(bool(use_graph)), _lib.stream_ptr()), "sample_masked")
         if defer_guard:
             self._pending[plan.value] = (plan, torch.cuda.current_stream())
             return out, traj

@@ -3,8 +3,9 @@
 ``sample()`` follows reference cfm.py:82-208 step by step on the host (mel of a raw-wave prompt, text -> ids, duration
 rule, masks, per-sample seeded noise, sway-sampled time grid) and hands the whole ODE loop -- ``steps`` x (cond + uncond
 DiT evaluation, CFG combine, Euler/midpoint update) and the final ``where(cond_mask, cond, y)`` -- to ONE native call
-(``f5_sample`` in include/f5hip.h, hipGraph-replayed) when the backbone is the HIP ``DiT``.  For any other backbone
-object (plug point A accepts arbitrary modules) the same loop is driven from Python over ``transformer(...)`` calls.
+(``f5_sample`` in include/f5hip.h, hipGraph-replayed; ``f5_sample_masked`` for speech editing's ``edit_mask``) when the backbone is the
+HIP ``DiT``.  For any other backbone object (plug point A accepts arbitrary modules) the same loop is driven from Python over
+``transformer(...)`` calls.
 ``forward()`` (the training loss, cfm.py:210-283) is outside the hot path and not provided.
 """
 from __future__ import annotations
@@ -46,13 +47,14 @@ class CFM(nn.Module):
     @torch.no_grad()
     def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None, seed=None,
                max_duration=4096, vocoder=None, no_ref_audio=False, duplicate_test=False, t_inter=0.1, edit_mask=None,
-               y0=None, return_trajectory=True, use_graph="auto", defer_guard=False, noise_device=None):
+               y0=None, return_trajectory=True, use_graph="auto", defer_guard=False, noise_device=None, edit_native=True):
         """Same arguments and return value ``(out, trajectory)`` as the reference.  Extra keyword-only knobs:
         ``y0`` (explicit initial noise, zero-padded [b, N, mel]: parity tests), ``noise_device`` ("cpu": draw the noise as the reference's
         CPU path does, cfm.py:178-183 with self.device = cpu; default ``self.noise_device``, None = the model's device), ``return_trajectory=False`` skips
         materialising the [steps+1, b, N, mel] trajectory (returned as None), ``use_graph`` = True / False / "auto" (default: replay a hipGraph from the second call with the same shape on),
         ``defer_guard=True`` returns without the call's one stream synchronisation (several sample() calls can then be in flight on several
-        streams); ``transformer.finish_pending()`` completes them."""
+        streams); ``transformer.finish_pending()`` completes them.  ``edit_mask`` calls run on the native sampler too (f5_sample_masked: the
+        per-frame cond_mask replaces the lens prefix); ``edit_native=False`` sends them to the Python driver instead (parity tests)."""
         self.eval()
         if cond.ndim == 2:  # raw wave
             cond = self.mel_spec(cond)
@@ -110,13 +112,15 @@ class CFM(nn.Module):
         method = self.odeint_kwargs.get("method", "euler")
 
         native = getattr(self.transformer, "native_sample", None)
-        if native is not None and edit_mask is None:
-            # lens-prefix cond_mask and duration-prefix key mask are rebuilt on the device by the kernels
+        if native is not None and (edit_mask is None or edit_native):
+            # lens-prefix cond_mask and duration-prefix key mask are rebuilt on the device by the kernels; an edit_mask call hands the
+            # [b, N] cond_mask (lens_to_mask(lens) & edit_mask, False-padded) over as it is
             # a batch whose durations are all equal has an all-true key mask (cfm.py:152-155 builds it anyway): the kernels' unmasked
             # forms compute the same thing
             use_mask = mask is not None and bool((duration != max_dur).any())
             out, trajectory = native(cond, text, lens, duration, y0, t, steps, cfg_strength, method=method, use_mask=use_mask,
-                                     return_trajectory=return_trajectory, use_graph=use_graph, defer_guard=defer_guard)
+                                     return_trajectory=return_trajectory, use_graph=use_graph, defer_guard=defer_guard,
+                                     cond_mask=None if edit_mask is None else cond_mask.squeeze(-1))
             out = out.to(step_cond.dtype)
         else:
             out, trajectory = self._sample_python(step_cond, cond, cond_mask, text, mask, y0, t, cfg_strength, method, return_trajectory)
@@ -178,7 +182,7 @@ class CFM(nn.Module):
         return [o.unsqueeze(0).to(cond.dtype) for o in torch.split(out, frames)]
 
     def _sample_python(self, step_cond, cond, cond_mask, text, mask, y0, t, cfg_strength, method, return_trajectory):
-        """Generic driver over ``transformer(...)`` calls (non-native backbones, edit_mask): same fixed-grid update rules."""
+        """Generic driver over ``transformer(...)`` calls (non-native backbones, edit_native=False): same fixed-grid update rules."""
         def fn(tt, x):
             pred = self.transformer(x=x, cond=step_cond, text=text, time=tt, mask=mask, drop_audio_cond=False, drop_text=False, cache=True)
             if cfg_strength < 1e-5:

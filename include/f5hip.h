@@ -133,6 +133,18 @@ F5_API int f5_sample(f5_plan_t p, int B, int N, const float* cond, const int32_t
               const int32_t* durations, const float* y0, const float* tgrid_host, int steps, float cfg_strength,
               int ode_method, float* out, float* trajectory, int use_graph, f5_stream_t stream);
 
+/* Speech editing (reference infer/speech_edit.py -> CFM.sample(edit_mask=...), cfm.py:123-127): f5_sample with a per-frame condition mask in
+ * place of the lens prefix.  Same arguments as f5_sample, plus
+ *   cond_mask dev u8 [B, N]      1 = keep the prompt frame (lens_to_mask(lens) & edit_mask, False-padded to N); it replaces `frame < lens`
+ *                                both in step_cond = where(cond_mask, cond, 0) (cfm.py:148-150) and in the final where(cond_mask, cond, y(1))
+ *                                (cfm.py:200-202); `lens` is still read and must be valid.  The CFG null branch zeroes every frame as before.
+ * The mask is staged into the plan, so a replayed hipGraph reads this call's mask; masked and unmasked calls keep separate captures.  The
+ * deferred range guard (f5_sample_finish) and the fp32 fallback rerun reuse the staged mask.  f5_sample(...) computes exactly what
+ * f5_sample_masked(..., cond_mask = (frame < lens), ...) computes. */
+F5_API int f5_sample_masked(f5_plan_t p, int B, int N, const float* cond, const int32_t* text, int nt, const int32_t* lens,
+                     const int32_t* durations, const float* y0, const float* tgrid_host, int steps, float cfg_strength,
+                     int ode_method, const uint8_t* cond_mask, float* out, float* trajectory, int use_graph, f5_stream_t stream);
+
 /* Deferred range-guard check (plan option "residual_guard" = 2): f5_sample then enqueues everything and returns without synchronising, so one
  * host thread can feed several plans on several streams (F5TTSWrapper.generate runs the text chunks of a call concurrently that way: they
  * are independent, reference infer/f5tts_wrapper.py:476-533).  f5_sample_finish(plan, stream) synchronises the stream, reads the flag and, if
