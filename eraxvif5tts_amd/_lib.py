@@ -11,7 +11,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("F5HIP_LIB") or os.path.join(_HERE, "lib", "libf5hip.so")
 
 F5_PREC_BF16, F5_PREC_FP32 = 0, 1
-F5_ODE_EULER, F5_ODE_MIDPOINT = 0, 1
+F5_ODE_EULER, F5_ODE_MIDPOINT, F5_ODE_RK4, F5_ODE_HEUN2, F5_ODE_HEUN3 = 0, 1, 2, 3, 4
+# odeint_kwargs["method"] -> F5_ODE_* (torchdiffeq's fixed-grid names; f5_ode_evals_per_step gives the evaluations per step)
+ODE_METHODS = {"euler": F5_ODE_EULER, "midpoint": F5_ODE_MIDPOINT, "rk4": F5_ODE_RK4, "heun2": F5_ODE_HEUN2, "heun3": F5_ODE_HEUN3}
 F5_ROPE_ADJACENT, F5_ROPE_HALF_SPLIT = 0, 1
 F5_BACKBONE_DIT, F5_BACKBONE_UNETT, F5_BACKBONE_MMDIT = 0, 1, 2
 F5_SKIP = {"concat": 0, "add": 1, "none": 2}
@@ -64,6 +66,7 @@ _PROTOS = {
     "f5_plan_create": (_I, [_P, _I, _I, _I, C.POINTER(_P)]),
     "f5_plan_destroy": (_I, [_P]),
     "f5_plan_workspace_bytes": (C.c_int64, [_P]),
+    "f5_ode_evals_per_step": (_I, [_I]),
     "f5_sample": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _F, _I, _P, _P, _I, _P]),
     "f5_sample_masked": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _F, _I, _P, _P, _P, _I, _P]),
     "f5_sample_finish": (_I, [_P, _P]),

@@ -962,6 +962,74 @@ int launch_cfg_step(const float* x_base, const float* vc, const float* vu, int l
     return 0;
 }
 
+// ----------------------------------------------------------------------------- CFG combine + one stage of an explicit Runge-Kutta step
+// (rk4 / heun2 / heun3; kernels.h: RkStage).  One launch after every network evaluation of such a step, V consecutive elements of one row per
+// thread (V = 4: mel a multiple of 4; vc / vu rows are MELP-strided, y0 / slots / outputs contiguous [rows, mel]).  Every branch depends on
+// kernel arguments only, so all lanes take the same path.  Arithmetic, with explicit FMAs: f = fma(vc - vu, cfg, vc);
+// w = fma(wf, f, fma(wk[nk-1], k_{nk-1}, ... fma(wk[0], k_0, 0))); out = fma(dt * w, post, y0).
+template <int V> struct VecF;
+template <> struct VecF<1> { using T = float; };
+template <> struct VecF<4> { using T = float4; };
+template <int V> __device__ __forceinline__ void vload(const float* p, float (&v)[V]) {
+    const typename VecF<V>::T x = *reinterpret_cast<const typename VecF<V>::T*>(p);
+    __builtin_memcpy(v, &x, sizeof(x));
+}
+template <int V> __device__ __forceinline__ void vstore(float* p, const float (&v)[V]) {
+    typename VecF<V>::T x;
+    __builtin_memcpy(&x, v, sizeof(x));
+    *reinterpret_cast<typename VecF<V>::T*>(p) = x;
+}
+template <int V>
+__global__ __launch_bounds__(256) void rk_stage_kernel(const float* __restrict__ y0, const float* __restrict__ vc, const float* __restrict__ vu, int ldv,
+                                                       int rows, int mel, float cfg, const float* __restrict__ dtp, RkStage sg,
+                                                       const float* __restrict__ slots, size_t slot_stride, float* __restrict__ kst,
+                                                       float* __restrict__ out) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int per_row = mel / V;
+    if (g >= (size_t)rows * per_row) return;
+    const int r = (int)(g / per_row), c = (int)(g % per_row) * V;
+    const size_t i = (size_t)r * mel + c;
+    float f[V], w[V], y[V];
+    vload<V>(vc + (size_t)r * ldv + c, f);
+    if (vu) {
+        float u[V];
+        vload<V>(vu + (size_t)r * ldv + c, u);
+#pragma unroll
+        for (int e = 0; e < V; ++e) f[e] = __builtin_fmaf(f[e] - u[e], cfg, f[e]);  // pred + (pred - null_pred) * cfg_strength (cfm.py:173)
+    }
+    if (kst) vstore<V>(kst + i, f);
+#pragma unroll
+    for (int e = 0; e < V; ++e) w[e] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        if (j < sg.nk) {
+            float k[V];
+            vload<V>(slots + (size_t)j * slot_stride + i, k);
+#pragma unroll
+            for (int e = 0; e < V; ++e) w[e] = __builtin_fmaf(sg.wk[j], k[e], w[e]);
+        }
+    const float dt = dtp[0];
+    vload<V>(y0 + i, y);
+#pragma unroll
+    for (int e = 0; e < V; ++e) y[e] = __builtin_fmaf(dt * __builtin_fmaf(sg.wf, f[e], w[e]), sg.post, y[e]);
+    vstore<V>(out + i, y);
+}
+int launch_rk_stage(const float* y0, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* dt, const RkStage& sg,
+                    const float* slots, size_t slot_stride, float* kst, float* out, hipStream_t stream) {
+    if (rows <= 0) return 0;
+    if (sg.nk < 0 || sg.nk > 3 || (sg.nk > 0 && !slots)) return f5_fail(F5_EINVAL, "rk stage: bad slot count %d", sg.nk);
+    auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    const bool vec = mel % 4 == 0 && ldv % 4 == 0 && slot_stride % 4 == 0 && a16(y0) && a16(vc) && a16(vu) && a16(slots) && a16(kst) && a16(out);
+    const size_t total = (size_t)rows * (vec ? mel / 4 : mel);
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    if (vec)
+        hipLaunchKernelGGL(rk_stage_kernel<4>, grid, block, 0, stream, y0, vc, vu, ldv, rows, mel, cfg, dt, sg, slots, slot_stride, kst, out);
+    else
+        hipLaunchKernelGGL(rk_stage_kernel<1>, grid, block, 0, stream, y0, vc, vu, ldv, rows, mel, cfg, dt, sg, slots, slot_stride, kst, out);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
 __global__ __launch_bounds__(256) void final_where_kernel(const float* __restrict__ cond, const float* __restrict__ x, const int32_t* __restrict__ lens,
                                                           const uint8_t* __restrict__ cmask, int B, int N, int mel, float* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

@@ -2,7 +2,7 @@
 //
 // Reference semantics followed (paths under /root/reference/src/f5_tts):
 //   model/backbones/dit.py:185-233  DiT.forward          model/cfm.py:82-208   CFM.sample
-//   model/modules.py:301-336,610-641 AdaLN / DiTBlock     torchdiffeq fixed-grid euler / midpoint
+//   model/modules.py:301-336,610-641 AdaLN / DiTBlock     torchdiffeq fixed-grid euler / midpoint / rk4 / heun2 / heun3
 //
 // MI355X-first restructuring (algebraically identical):
 //   * time is one scalar per evaluation, so every AdaLN modulation vector of every block is computed ONCE per

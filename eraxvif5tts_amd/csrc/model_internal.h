@@ -46,7 +46,9 @@ struct FoldTable {
     }
 };
 static const size_t F5_FOLD_TABLES = 2;
-static const int F5_FOLD_MAX_EVALS = 64;  // 64 evaluation times x 231 MB (F5TTS_Base) = 14.8 GB; longer grids run the unfolded path
+// 64 evaluation times x 231 MB (F5TTS_Base) = 14.8 GB; longer grids run the unfolded path.  The cap counts evaluation times, not steps:
+// rk4 with 8 steps (32 times) is folded, rk4 with 32 steps (128 times) is not.
+static const int F5_FOLD_MAX_EVALS = 64;
 
 struct f5_model_s {
     f5_dit_config cfg;

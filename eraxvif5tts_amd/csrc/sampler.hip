@@ -2,6 +2,65 @@
 // hipGraph capture / replay, the fp16 range guard and its fp32 fallback, the LayerNorm-fold tables of a time grid, and the ragged sampler.
 #include "model_internal.h"
 
+// ----------------------------------------------------------------------------- fixed-grid solvers
+// torchdiffeq's fixed-grid family, chosen by odeint_kwargs["method"] (cfm.py:197).  Evaluation j of step s has the evaluation index
+// evals * s + j (its AdaLN rows, fold-table entry and p->coefs word) and runs at t0 + c[j] * dt in fp32, as torchdiffeq computes it; rk4's
+// last evaluation is at t1 itself.  Euler and midpoint update with launch_cfg_step; the Runge-Kutta methods launch launch_rk_stage after
+// every evaluation with stage[j]: the slopes it combines, the slot its own slope is kept in (slot[j], -1: not needed later) and its output
+// (the next stage's input p->xmid, or y1 = traj[s + 1] after the last stage).  Their p->coefs word is dt.  The combinations restate
+// torchdiffeq's step functions (heun2 / heun3 tableaux, rk4 = rk4_alt_step_func, the 3/8 rule):
+//   rk4    x2 = y0 + dt k1 (1/3)    x3 = y0 + dt (k2 - k1 (1/3))    x4 = y0 + dt (k1 - k2 + k3)    y1 = y0 + dt (k1 + 3 k2 + 3 k3 + k4) / 8
+//   heun2  x2 = y0 + dt k1                                                                        y1 = y0 + dt (k1 / 2 + k2 / 2)
+//   heun3  x2 = y0 + dt k1 (1/3)    x3 = y0 + dt k2 (2/3)                                         y1 = y0 + dt (k1 / 4 + 3 k3 / 4)
+// (the kernel forms each of them as one FMA chain; torchdiffeq's rk4 groups the last one as (k1 + 3 (k2 + k3) + k4) * dt * 0.125).
+// Slope slots live in the tail of p->traj, past the steps + 1 states of the trajectory: a method with E evaluations per step keeps at most
+// E - 1 slopes, and E * steps <= max_evals with steps >= 1 gives steps + 1 + (E - 1) <= max_evals + 1 states, which is what traj holds.
+struct OdeMethod {
+    int evals;       // network evaluations per step
+    float c[4];      // evaluation times t0 + c[j] * dt
+    bool last_at_t1; // the last evaluation runs at t1 (rk4_alt_step_func: k4 = f(t1, ...))
+    RkStage stage[4];
+    int slot[4];
+};
+static const float ODE_THIRD = 1.0f / 3.0f, ODE_TWO_THIRDS = 2.0f / 3.0f;
+static const OdeMethod ODE_METHODS[] = {
+    /* F5_ODE_EULER */ {1, {0.f}, false, {}, {-1, -1, -1, -1}},
+    /* F5_ODE_MIDPOINT */ {2, {0.f, 0.5f}, false, {}, {-1, -1, -1, -1}},
+    /* F5_ODE_RK4 */
+    {4, {0.f, ODE_THIRD, ODE_TWO_THIRDS, 1.f}, true,
+     {{{0.f, 0.f, 0.f}, 1.f, ODE_THIRD, 0}, {{-ODE_THIRD, 0.f, 0.f}, 1.f, 1.f, 1}, {{1.f, -1.f, 0.f}, 1.f, 1.f, 2}, {{1.f, 3.f, 3.f}, 1.f, 0.125f, 3}},
+     {0, 1, 2, -1}},
+    /* F5_ODE_HEUN2 */ {2, {0.f, 1.f}, false, {{{0.f, 0.f, 0.f}, 1.f, 1.f, 0}, {{0.5f, 0.f, 0.f}, 0.5f, 1.f, 1}}, {0, -1, -1, -1}},
+    /* F5_ODE_HEUN3 */
+    {3, {0.f, ODE_THIRD, ODE_TWO_THIRDS}, false,
+     {{{0.f, 0.f, 0.f}, 1.f, ODE_THIRD, 0}, {{0.f, 0.f, 0.f}, 1.f, ODE_TWO_THIRDS, 0}, {{0.25f, 0.f, 0.f}, 0.75f, 1.f, 1}},
+     {0, -1, -1, -1}},
+};
+static const OdeMethod* ode_method_of(int ode_method) {
+    return ode_method >= 0 && ode_method < (int)(sizeof(ODE_METHODS) / sizeof(ODE_METHODS[0])) ? &ODE_METHODS[ode_method] : nullptr;
+}
+
+extern "C" int f5_ode_evals_per_step(int ode_method) {
+    const OdeMethod* om = ode_method_of(ode_method);
+    return om ? om->evals : f5_fail(F5_EINVAL, "bad ode_method %d", ode_method);
+}
+
+// the evaluations of one Runge-Kutta step from xs = traj[s] to xn = traj[s + 1] (rows: token rows of one CFG half)
+static int rk_step(f5_plan_s* p, const SampleArgs& a, int s, const float* xs, float* xn, int rows, int nb, int N, const uint8_t* mask, hipStream_t st) {
+    const OdeMethod& om = *ode_method_of(a.method);
+    const int mel = p->m->cfg.mel_dim;
+    const size_t state = (size_t)rows * mel;
+    float* slots = p->traj + (size_t)(a.steps + 1) * state;  // (see the slot invariant above)
+    const float* vu = a.cfg_on ? p->vout + (size_t)rows * MELP : nullptr;
+    for (int j = 0; j < om.evals; ++j) {
+        const int ev = om.evals * s + j;
+        F5_TRY(net_eval(p, j == 0 ? xs : p->xmid, rows, nb, N, ev, 0, mask, st));
+        F5_TRY(launch_rk_stage(xs, p->vout, vu, MELP, rows, mel, a.cfg, p->coefs + ev, om.stage[j], slots, state,
+                               om.slot[j] >= 0 ? slots + (size_t)om.slot[j] * state : nullptr, j == om.evals - 1 ? xn : p->xmid, st));
+    }
+    return 0;
+}
+
 // ----------------------------------------------------------------------------- public: sample
 
 // everything between the staged inputs and the final state traj[steps]; capturable (no syncs, no allocations)
@@ -12,7 +71,6 @@ static int sample_body(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
     f5_model_s* m = p->m;
     const f5_dit_config& c = m->cfg;
     const int B = a.B, N = a.N, mel = c.mel_dim, bn = B * N;
-    const int nev = a.method == F5_ODE_MIDPOINT ? 2 * a.steps : a.steps;
     const size_t state = (size_t)bn * mel;
     // range guard of the fp16 residual stream: cleared by a KERNEL node of the graph, so every replay starts clean.  (Not hipMemsetAsync: on
     // ROCm 7.2 the 32-byte memset node captured here cleared the words on the first launch of the instantiated graph and filled them with
@@ -53,11 +111,13 @@ static int sample_body(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
         if (a.method == F5_ODE_EULER) {
             F5_TRY(net_eval(p, xs, bn, nb, N, s, 0, mask, st));
             F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, bn, mel, a.cfg, p->coefs + s, xn, nullptr, st));
-        } else {
+        } else if (a.method == F5_ODE_MIDPOINT) {
             F5_TRY(net_eval(p, xs, bn, nb, N, 2 * s, 0, mask, st));
             F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, bn, mel, a.cfg, p->coefs + 2 * s, p->xmid, nullptr, st));
             F5_TRY(net_eval(p, p->xmid, bn, nb, N, 2 * s + 1, 0, mask, st));
             F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, bn, mel, a.cfg, p->coefs + 2 * s + 1, xn, nullptr, st));
+        } else {
+            F5_TRY(rk_step(p, a, s, xs, xn, bn, nb, N, mask, st));
         }
     }
     return 0;
@@ -210,7 +270,9 @@ static int acquire_fold(f5_plan_s* p, const std::vector<float>& tv, hipStream_t 
 // evaluation times / step coefficients of a fixed grid (fp32 op order of torchdiffeq's fixed-grid solvers) -> p->tvals / p->coefs, and the
 // AdaLN rows of every evaluation time -> p->mod (kept across calls with the same grid on the same stream)
 static int stage_time_grid(f5_plan_s* p, const float* tgrid_host, int steps, int ode_method, hipStream_t st) {
-    const int nev = ode_method == F5_ODE_MIDPOINT ? 2 * steps : steps;
+#pragma clang fp contract(off)  // t0 + dt * c rounded twice, as torchdiffeq's fp32 tensors compute it
+    const OdeMethod& om = *ode_method_of(ode_method);
+    const int E = om.evals, nev = E * steps;
     std::vector<float> tv(nev), cf(nev);
     for (int s = 0; s < steps; ++s) {
         const float t0 = tgrid_host[s], t1 = tgrid_host[s + 1];
@@ -218,12 +280,17 @@ static int stage_time_grid(f5_plan_s* p, const float* tgrid_host, int steps, int
         if (ode_method == F5_ODE_EULER) {
             tv[s] = t0;
             cf[s] = dt;
-        } else {
+        } else if (ode_method == F5_ODE_MIDPOINT) {
             const float half = 0.5f * dt;
             tv[2 * s] = t0;
             cf[2 * s] = half;
             tv[2 * s + 1] = t0 + half;
             cf[2 * s + 1] = dt;
+        } else {
+            for (int j = 0; j < E; ++j) {
+                tv[E * s + j] = j == 0 ? t0 : (j == E - 1 && om.last_at_t1) ? t1 : t0 + dt * om.c[j];
+                cf[E * s + j] = dt;
+            }
         }
     }
     // The time MLP and every AdaLN row depend only on the evaluation times: a server calls sample() with the same grid every time,
@@ -255,8 +322,9 @@ static int sample_impl(f5_plan_t p, int B, int N, const float* cond, const int32
     F5_TRY(check_plan_shape(p, B, N));
     if (!cond || !text || !lens || !y0 || !tgrid_host || !out) return f5_fail(F5_EINVAL, "null argument");
     if (steps <= 0 || nt <= 0) return f5_fail(F5_EINVAL, "steps and nt must be positive");
-    if (ode_method != F5_ODE_EULER && ode_method != F5_ODE_MIDPOINT) return f5_fail(F5_EINVAL, "bad ode_method");
-    const int nev = ode_method == F5_ODE_MIDPOINT ? 2 * steps : steps;
+    const OdeMethod* om = ode_method_of(ode_method);
+    if (!om) return f5_fail(F5_EINVAL, "bad ode_method %d", ode_method);
+    const int nev = om->evals * steps;
     if (nev > p->maxE) return f5_fail(F5_EINVAL, "%d evaluations exceed the plan's max_evals=%d", nev, p->maxE);
     F5_TRY(finish_if_pending(p));
     hipStream_t st = (hipStream_t)stream;
@@ -347,11 +415,13 @@ static int sample_body_ragged(f5_plan_s* p, const SampleArgs& a, hipStream_t st)
         if (a.method == F5_ODE_EULER) {
             F5_TRY(net_eval(p, xs, T, nb, T, s, 0, nullptr, st));
             F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + s, xn, nullptr, st));
-        } else {
+        } else if (a.method == F5_ODE_MIDPOINT) {
             F5_TRY(net_eval(p, xs, T, nb, T, 2 * s, 0, nullptr, st));
             F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + 2 * s, p->xmid, nullptr, st));
             F5_TRY(net_eval(p, p->xmid, T, nb, T, 2 * s + 1, 0, nullptr, st));
             F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + 2 * s + 1, xn, nullptr, st));
+        } else {
+            F5_TRY(rk_step(p, a, s, xs, xn, T, nb, T, nullptr, st));
         }
     }
     return 0;
@@ -366,8 +436,9 @@ extern "C" int f5_sample_ragged(f5_plan_t p, int B, const int32_t* frames_host, 
     f5_model_s* m = p->m;
     if (m->cfg.backbone != F5_BACKBONE_DIT) return f5_fail(F5_ENOTSUP, "f5_sample_ragged: DiT backbone only");
     if (B <= 0 || B > p->maxB || steps <= 0 || nt <= 0 || nt > p->maxN) return f5_fail(F5_EINVAL, "bad B / steps / nt for this plan");
-    if (ode_method != F5_ODE_EULER && ode_method != F5_ODE_MIDPOINT) return f5_fail(F5_EINVAL, "bad ode_method");
-    const int nev = ode_method == F5_ODE_MIDPOINT ? 2 * steps : steps;
+    const OdeMethod* om = ode_method_of(ode_method);
+    if (!om) return f5_fail(F5_EINVAL, "bad ode_method %d", ode_method);
+    const int nev = om->evals * steps;
     if (nev > p->maxE) return f5_fail(F5_EINVAL, "%d evaluations exceed the plan's max_evals=%d", nev, p->maxE);
     if (!p->taps.empty() || p->timing) return f5_fail(F5_ESTATE, "f5_sample_ragged: stage taps / in-situ timing are not available here");
     Ragged rg;

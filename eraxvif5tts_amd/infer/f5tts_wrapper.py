@@ -37,7 +37,10 @@ _CONFIG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__fil
 
 
 class F5TTSWrapper:
-    """A wrapper class for F5-TTS that preprocesses reference audio once and allows for repeated TTS generation."""
+    """A wrapper class for F5-TTS that preprocesses reference audio once and allows for repeated TTS generation.
+
+    ``ode_method`` is the fixed-grid solver of the sampler: "euler", "midpoint", "rk4", "heun2" or "heun3" (1 / 2 / 4 / 2 / 3 network
+    evaluations per step of ``nfe_step``)."""
 
     def __init__(self, model_name: str = "F5TTS_v1_Base", ckpt_path: Optional[str] = None, vocab_file: Optional[str] = None,
                  vocoder_name: str = "vocos", use_local_vocoder: bool = False, vocoder_path: Optional[str] = None,

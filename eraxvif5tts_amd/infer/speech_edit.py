@@ -60,7 +60,7 @@ def edit_speech(model, vocoder, audio, sr, target_text, parts_to_edit, *, fix_du
                 sway_sampling_coef=-1.0, seed=None, target_rms=0.1):
     """Regenerate ``parts_to_edit`` of ``audio`` so that the whole recording says ``target_text``.
 
-    model: a ``CFM`` over a HIP backbone (its ``odeint_kwargs`` choose Euler / midpoint); vocoder: plug point B (``.decode(mel)`` as Vocos, or
+    model: a ``CFM`` over a HIP backbone (its ``odeint_kwargs`` choose the fixed-grid solver: euler, midpoint, rk4, heun2 or heun3); vocoder: plug point B (``.decode(mel)`` as Vocos, or
     called as BigVGAN); audio: waveform [n] or [channels, n] at ``sr`` Hz (tensor or array).  Returns ``(wave [1, samples], mel [1, n_mels,
     frames])`` on the model's device, the wave scaled back to the recording's loudness when it was boosted.
 

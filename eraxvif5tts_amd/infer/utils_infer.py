@@ -30,7 +30,7 @@ n_fft = 1024
 mel_spec_type = "vocos"
 target_rms = 0.1
 cross_fade_duration = 0.15
-ode_method = "euler"
+ode_method = "euler"  # torchdiffeq fixed-grid solver: euler, midpoint, rk4, heun2 or heun3 (model.cfm.ODE_METHODS)
 nfe_step = 32  # 16, 32
 cfg_strength = 2.0
 sway_sampling_coef = -1.0

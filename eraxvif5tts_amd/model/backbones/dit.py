@@ -53,6 +53,13 @@ def _param_spec(dim, depth, heads, dim_head, ff_inner, mel_dim, vocab, text_dim,
     return spec
 
 
+def _ode_code(method):
+    """odeint_kwargs["method"] -> F5_ODE_* (_lib.ODE_METHODS); ValueError naming the supported set for anything else."""
+    if method not in _lib.ODE_METHODS:
+        raise ValueError(f"unsupported ODE method {method!r}: the fixed-grid solvers are {sorted(_lib.ODE_METHODS)}")
+    return _lib.ODE_METHODS[method]
+
+
 def _register(root: nn.Module, dotted: str, tensor: torch.Tensor, buffer=False):
     mod = root
     parts = dotted.split(".")
@@ -279,8 +286,9 @@ class DiT(nn.Module):
         """cond/y0 f32 [B,N,mel] on the GPU, text int [B,nt] (-1 padded), lens/durations int [B], tgrid f32 [steps+1] (any device).
         cond_mask: bool [B,N] (speech editing: lens_to_mask(lens) & edit_mask) in place of the lens prefix (f5_sample_masked), or None."""
         lib = _lib.load()
+        meth = _ode_code(method)
         B, N = cond.shape[0], cond.shape[1]
-        evals = steps * (2 if method == "midpoint" else 1)
+        evals = steps * lib.f5_ode_evals_per_step(meth)
         # capturing + instantiating a ~5000-node graph costs about as much as one small sample(): only replay shapes that recur
         # (serving with fixed buckets, batch inference); one-off shapes (free-form generate()) run eagerly on the stream
         key = (B, N, int(text.shape[1]), steps, method, float(cfg_strength), bool(use_mask), cond_mask is not None)
@@ -298,7 +306,6 @@ class DiT(nn.Module):
         tg = tgrid.detach().to("cpu", torch.float32).contiguous()
         out = torch.empty_like(cond)
         traj = torch.empty(steps + 1, B, N, self.mel_dim, device=dev, dtype=torch.float32) if return_trajectory else None
-        meth = {"euler": _lib.F5_ODE_EULER, "midpoint": _lib.F5_ODE_MIDPOINT}[method]
         # defer_guard: f5_sample enqueues and returns without its one synchronisation (the fp16 range-guard read); finish_pending() does it
         _lib.check(lib.f5_plan_set_option(plan, b"residual_guard", 2 if defer_guard else 1), "plan_set_option")
         if cond_mask is None:
@@ -324,8 +331,9 @@ class DiT(nn.Module):
         lib = _lib.load()
         if self.BACKBONE != _lib.F5_BACKBONE_DIT:
             raise NotImplementedError("ragged sampling is built for the DiT backbone")
+        meth = _ode_code(method)
         B = len(frames)
-        evals = steps * (2 if method == "midpoint" else 1)
+        evals = steps * lib.f5_ode_evals_per_step(meth)
         # the plan must hold T = sum(round_up(n_i + 16, 16)) rows per CFG half and (B + 1) text rows: size it by total rows, not by the longest
         # utterance (seq is capped at 4096 by plan(), so utterances near that length need a larger batch dimension)
         seq = min(4096, -(-(max(max(frames), int(text.shape[1])) + 32) // 64) * 64)
@@ -340,7 +348,6 @@ class DiT(nn.Module):
         assert cond_cat.shape[0] == int(fr.sum()) == y0_cat.shape[0]
         tg = tgrid.detach().to("cpu", torch.float32).contiguous()
         out = torch.empty_like(cond_cat)
-        meth = {"euler": _lib.F5_ODE_EULER, "midpoint": _lib.F5_ODE_MIDPOINT}[method]
         _lib.check(lib.f5_plan_set_option(plan, b"residual_guard", 1), "plan_set_option")
         # a list of frame counts that recurs (batch inference over fixed buckets, a server's chunk pattern) replays its hipGraph from the second
         # call on; one-off shapes run eagerly (capturing costs about one small sample())

@@ -2,10 +2,13 @@
 
 ``sample()`` follows reference cfm.py:82-208 step by step on the host (mel of a raw-wave prompt, text -> ids, duration
 rule, masks, per-sample seeded noise, sway-sampled time grid) and hands the whole ODE loop -- ``steps`` x (cond + uncond
-DiT evaluation, CFG combine, Euler/midpoint update) and the final ``where(cond_mask, cond, y)`` -- to ONE native call
+DiT evaluations, CFG combine, fixed-grid update) and the final ``where(cond_mask, cond, y)`` -- to ONE native call
 (``f5_sample`` in include/f5hip.h, hipGraph-replayed; ``f5_sample_masked`` for speech editing's ``edit_mask``) when the backbone is the
 HIP ``DiT``.  For any other backbone object (plug point A accepts arbitrary modules) the same loop is driven from Python over
 ``transformer(...)`` calls.
+The solver is ``odeint_kwargs["method"]``, one of torchdiffeq's fixed-grid methods (``ODE_METHODS``): euler, midpoint, rk4 (torchdiffeq's
+``rk4_alt_step_func``, the 3/8 rule), heun2, heun3 -- 1 / 2 / 4 / 2 / 3 network evaluations per step.  Adaptive solvers, the Adams family and
+other odeint options raise ``ValueError`` before any work.
 ``forward()`` (the training loss, cfm.py:210-283) is outside the hot path and not provided.
 """
 from __future__ import annotations
@@ -17,6 +20,56 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .modules import MelSpec
 from .utils import default, exists, lens_to_mask, list_str_to_idx, list_str_to_tensor
+
+
+def _euler(fn, t0, t1, y):
+    return (t1 - t0) * fn(t0, y)
+
+
+def _midpoint(fn, t0, t1, y):
+    dt = t1 - t0
+    half = 0.5 * dt
+    return dt * fn(t0 + half, y + fn(t0, y) * half)
+
+
+def _rk4(fn, t0, t1, y):  # torchdiffeq rk4_alt_step_func (the 3/8 rule): what method="rk4" runs
+    dt = t1 - t0
+    k1 = fn(t0, y)
+    k2 = fn(t0 + dt * (1 / 3), y + dt * k1 * (1 / 3))
+    k3 = fn(t0 + dt * (2 / 3), y + dt * (k2 - k1 * (1 / 3)))
+    k4 = fn(t1, y + dt * (k1 - k2 + k3))
+    return (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+
+
+def _heun2(fn, t0, t1, y):  # tableau c = [0, 1], a21 = 1, b = [1/2, 1/2]
+    dt = t1 - t0
+    k1 = fn(t0, y)
+    k2 = fn(t0 + dt, y + dt * k1)
+    return dt * (k1 * 0.5 + k2 * 0.5)
+
+
+def _heun3(fn, t0, t1, y):  # tableau c = [0, 1/3, 2/3], a21 = 1/3, a32 = 2/3, b = [1/4, 0, 3/4]
+    dt = t1 - t0
+    k1 = fn(t0, y)
+    k2 = fn(t0 + dt * (1 / 3), y + dt * k1 * (1 / 3))
+    k3 = fn(t0 + dt * (2 / 3), y + dt * k2 * (2 / 3))
+    return dt * (k1 * 0.25 + k3 * 0.75)
+
+
+# torchdiffeq's fixed-grid solvers, fp32 operation order kept: method -> step(fn, t0, t1, y) = dy, with y1 = y + dy.  The native sampler runs
+# the same methods (include/f5hip.h: F5_ODE_*).
+ODE_METHODS = {"euler": _euler, "midpoint": _midpoint, "rk4": _rk4, "heun2": _heun2, "heun3": _heun3}
+
+
+def ode_method(odeint_kwargs):
+    """The fixed-grid method named by ``odeint_kwargs``; ValueError for anything this package does not run."""
+    extra = sorted(set(odeint_kwargs) - {"method"})
+    if extra:
+        raise ValueError(f"unsupported odeint_kwargs {extra}: only 'method' is taken (one of {sorted(ODE_METHODS)})")
+    method = odeint_kwargs.get("method", "euler")
+    if method not in ODE_METHODS:
+        raise ValueError(f"unsupported ODE method {method!r}: the fixed-grid solvers are {sorted(ODE_METHODS)}")
+    return method
 
 
 class CFM(nn.Module):
@@ -54,7 +107,10 @@ class CFM(nn.Module):
         materialising the [steps+1, b, N, mel] trajectory (returned as None), ``use_graph`` = True / False / "auto" (default: replay a hipGraph from the second call with the same shape on),
         ``defer_guard=True`` returns without the call's one stream synchronisation (several sample() calls can then be in flight on several
         streams); ``transformer.finish_pending()`` completes them.  ``edit_mask`` calls run on the native sampler too (f5_sample_masked: the
-        per-frame cond_mask replaces the lens prefix); ``edit_native=False`` sends them to the Python driver instead (parity tests)."""
+        per-frame cond_mask replaces the lens prefix); ``edit_native=False`` sends them to the Python driver instead (parity tests).
+        ``odeint_kwargs["method"]`` picks the fixed-grid solver (``ODE_METHODS``: euler, midpoint, rk4, heun2, heun3); any other method or
+        odeint option raises ``ValueError`` before any work."""
+        method = ode_method(self.odeint_kwargs)
         self.eval()
         if cond.ndim == 2:  # raw wave
             cond = self.mel_spec(cond)
@@ -109,7 +165,6 @@ class CFM(nn.Module):
         t = torch.linspace(t_start, 1, steps + 1, device=self.device, dtype=step_cond.dtype)
         if sway_sampling_coef is not None:
             t = t + sway_sampling_coef * (torch.cos(torch.pi / 2 * t) - 1 + t)
-        method = self.odeint_kwargs.get("method", "euler")
 
         native = getattr(self.transformer, "native_sample", None)
         if native is not None and (edit_mask is None or edit_native):
@@ -140,6 +195,7 @@ class CFM(nn.Module):
         same order -- and returns that list ([1, N_i, mel] each).  cond: mel [1, nc, mel] or raw wave [1, nw] (one prompt for every text), or
         [B, nc, mel] with ``lens`` (a prompt per utterance, zero-padded to a common nc as for ``sample()``); texts: list of str / list of token
         lists / id tensor; durations: list of ints."""
+        method = ode_method(self.odeint_kwargs)
         self.eval()
         native = getattr(self.transformer, "native_sample_ragged", None)
         if native is None:
@@ -176,13 +232,13 @@ class CFM(nn.Module):
         t = torch.linspace(0, 1, steps + 1, device=self.device, dtype=cond.dtype)
         if sway_sampling_coef is not None:
             t = t + sway_sampling_coef * (torch.cos(torch.pi / 2 * t) - 1 + t)
-        out = native(torch.cat(conds), text, lens, frames, torch.cat(noises), t, steps, cfg_strength, method=self.odeint_kwargs.get("method", "euler"),
+        out = native(torch.cat(conds), text, lens, frames, torch.cat(noises), t, steps, cfg_strength, method=method,
                      use_graph=use_graph)
         self.transformer.clear_cache()
         return [o.unsqueeze(0).to(cond.dtype) for o in torch.split(out, frames)]
 
     def _sample_python(self, step_cond, cond, cond_mask, text, mask, y0, t, cfg_strength, method, return_trajectory):
-        """Generic driver over ``transformer(...)`` calls (non-native backbones, edit_native=False): same fixed-grid update rules."""
+        """Generic driver over ``transformer(...)`` calls (non-native backbones, edit_native=False): the fixed-grid steps of ODE_METHODS."""
         def fn(tt, x):
             pred = self.transformer(x=x, cond=step_cond, text=text, time=tt, mask=mask, drop_audio_cond=False, drop_text=False, cache=True)
             if cfg_strength < 1e-5:
@@ -190,16 +246,12 @@ class CFM(nn.Module):
             null_pred = self.transformer(x=x, cond=step_cond, text=text, time=tt, mask=mask, drop_audio_cond=True, drop_text=True, cache=True)
             return pred + (pred - null_pred) * cfg_strength
 
+        if method not in ODE_METHODS:
+            raise ValueError(f"unsupported ODE method {method!r}: the fixed-grid solvers are {sorted(ODE_METHODS)}")
+        step = ODE_METHODS[method]
         y, traj = y0, [y0]
         for t0, t1 in zip(t[:-1], t[1:]):
-            dt = t1 - t0
-            if method == "euler":
-                y = y + dt * fn(t0, y)
-            elif method == "midpoint":
-                half = 0.5 * dt
-                y = y + dt * fn(t0 + half, y + fn(t0, y) * half)
-            else:
-                raise ValueError(f"unsupported fixed-grid ODE method: {method}")
+            y = y + step(fn, t0, t1, y)
             if return_trajectory:
                 traj.append(y)
         out = torch.where(cond_mask, cond, y)

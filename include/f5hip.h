@@ -48,9 +48,14 @@ extern "C" {
 #define F5_PREC_BF16 0 /* bf16 MFMA inputs, fp32 accumulate and arithmetic, fp32 ODE state, residual stream stored as fp16 (production) */
 #define F5_PREC_FP32 1 /* fp32-input MFMA everywhere (debug / parity mode, ~1/16 of the bf16 rate) */
 
-/* ODE solvers of torchdiffeq's fixed-grid family used by cfm.py:197 */
+/* ODE solvers of torchdiffeq's fixed-grid family used by cfm.py:197 (odeint_kwargs["method"]): euler, midpoint, and the explicit
+ * Runge-Kutta methods rk4 (rk4_alt_step_func, the 3/8 rule), heun2 and heun3.  Network evaluations per step: 1 / 2 / 4 / 2 / 3
+ * (f5_ode_evals_per_step).  Adaptive solvers and the Adams family are not provided. */
 #define F5_ODE_EULER 0
 #define F5_ODE_MIDPOINT 1
+#define F5_ODE_RK4 2
+#define F5_ODE_HEUN2 3
+#define F5_ODE_HEUN3 4
 
 typedef void* f5_stream_t; /* hipStream_t */
 typedef struct f5_model_s* f5_model_t;
@@ -114,8 +119,11 @@ F5_API int f5_model_destroy(f5_model_t m);
 
 /* ------------------------------------------------------------------ plan (workspace for one (batch, seq) bucket) */
 /* max_batch = utterances per call (CFG doubling is internal), max_seq = frames N, max_evals = network
- * evaluations times held at once (steps for euler, 2*steps for midpoint). */
+ * evaluations times held at once (steps * f5_ode_evals_per_step(method): steps for euler, 2*steps for midpoint and heun2, 3*steps for
+ * heun3, 4*steps for rk4).  A sample() with more evaluations than this returns F5_EINVAL before any work. */
 F5_API int f5_plan_create(f5_model_t m, int max_batch, int max_seq, int max_evals, f5_plan_t* out);
+/* network evaluations per step of an F5_ODE_* method (1 / 2 / 4 / 2 / 3), or F5_EINVAL for an unknown one */
+F5_API int f5_ode_evals_per_step(int ode_method);
 F5_API int f5_plan_destroy(f5_plan_t p);
 F5_API int64_t f5_plan_workspace_bytes(f5_plan_t p);
 
