@@ -54,8 +54,13 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     // (rmw), the time grid's table (stage_time_grid) and the tuned kernel at all four call sites.
     // Token counts that are not a multiple of the 256-row tile (8 x 1001 frames, every ragged batch): the four block GEMMs run over the rows
     // ROUNDED UP to 256 -- the workspace is padded to that anyway -- so that they stay on the persistent schedule with whole tiles only.  The rows
-    // past the last token compute on whatever the padding holds (finite: zero-filled arena, saturating fp16 stores) and nobody reads them:
-    // every other kernel works on `rows`, attention on the utterances' own rows.  (Round 4 first split such launches into whole tiles + a tail
+    // past the last token compute on whatever the padding holds (finite: zero-filled arena, saturating fp16 stores).  Their fp16 stream rows are
+    // never reset: the EPI_RESID epilogues keep adding gate * (A W + b) to them, evaluation after evaluation and call after call, until they sit
+    // at the saturation value.  What reads them: the four block GEMMs themselves (the out-projection and FF2 read-modify-write them, their
+    // partial row sums go to lnf_partial) and a folded consumer or producer that finishes the row statistics inside the kernel (gemm_w4.hip
+    // finish_stats, the 8-wave in-kernel form, fin_counter), which turns them into (mean, rstd) for its own epilogue.  GemmParams::lnf_rows = rows
+    // keeps them out of every stored statistics table and out of the fp16 range guard -- a padding row at +-65504 must not send the plan to fp32
+    // storage.  Nothing else reads them: every other kernel works on `rows`, attention on the utterances' own rows.  (Round 4 first split such launches into whole tiles + a tail
     // launch: 8 x 1001 346 against 288 ms per sample(), the ragged 4-chunk batch 210 against 183 ms -- the tail launches are pure latency.)
     const int rows_g = (rmw && g_gemm_pad_rows && rows >= 3584 /* from here on the fused projection takes the 256-wide persistent tile */ && rows % 256 != 0 && (size_t)((rows + 255) / 256 * 256) <= p->rows_cap) ? (rows + 255) / 256 * 256 : rows;
     const FoldTable* ft = p->fold;
@@ -101,6 +106,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     bool fin_site[2] = {false, false};  // [k & 1]: site k's statistics were finished by its producer
     auto lnf_producer = [&](GemmParams& g, int k, int tag, const PrefetchSet& pf, bool consumer_inkernel) {
         g.stats_out = p->lnf_partial; g.stats_ld = (int)p->rows_cap; g.stats_pivot = k > 0 ? lnfS[(k - 1) & 1] : nullptr;
+        g.lnf_rows = rows;  // (M = rows_g: the padding rows stay out of fin_stats and the range guard)
         const bool fin = g_ln_fold_fin && !consumer_inkernel && p->fin_counter && gemm_fast_resid_finishes(g);
         fin_site[k & 1] = fin;
         if (fin) {
@@ -113,6 +119,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     // consumer side of site k: finalized statistics (by the producer, or one more launch, which also prefetches `pf`) or the in-kernel form
     auto lnf_consumer = [&](GemmParams& g, int k, bool inkernel, int site, int tag, const PrefetchSet* pf) -> int {
         const float* pivots = k > 0 ? lnfS[(k - 1) & 1] : nullptr;
+        g.lnf_rows = rows;  // (M = rows_g: the padding rows stay out of lnf_stats_out and the range guard)
         if (!inkernel && fin_site[k & 1]) {
             g.lnf_stats = lnfS[k & 1];
         } else if (!inkernel) {

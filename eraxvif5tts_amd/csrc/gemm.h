@@ -88,6 +88,9 @@ struct GemmParams {
     // ticket; the last arriver acquires once and reads the partials with agent-scope loads; it also resets the ticket word.  Range guard: lnf_sat / lnf_sat_tag.
     unsigned* fin_counter;
     float* fin_stats;
+    // rows (global index, as row0) that hold tokens, 0 = all M: a launch over rows padded up to whole tiles (dit_eval: rows_g) computes the padded
+    // rows' statistics for its own epilogue, but stores none of them (lnf_stats_out, fin_stats) and keeps them out of the range guard
+    int lnf_rows;
     int tile_group;  // tuned kernel: token tiles per L2 patch (set by the launcher)
     int tile_reverse;  // tuned kernel: walk the tiles in the opposite order (producer / consumer cache experiments)
     int lean_epi;    // tuned kernel: whole tiles take the lean epilogue (set by the launcher; 0 = always the generic one)

@@ -237,6 +237,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
                     for (int j = 0; j < WM / 16; ++j) {
                         int m = m0 + wm * WM + j * 16 + fr;
                         const bool okrow = m < p.M;
+                        const bool tok = okrow && (p.lnf_rows == 0 || m + p.row0 < p.lnf_rows);  // (padding rows: this tile's epilogue only)
                         m = okrow ? m : p.M - 1;
                         float s1 = 0.f, s2 = 0.f;
                         if (p.lnf_ncols == 16) {  // dim 1024: all sixteen loads of a row in flight together (a runtime loop issues them one behind the other)
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
                         float mean, rstd, sumsq;
                         lnf_row_stats(s1, s2, pv, p.K, mean, rstd, sumsq);
                         lstr[j] = f32x2{mean, rstd};
-                        if (p.lnf_stats_out && n0 == 0 && wn == 0 && fq == 0 && okrow) {  // feature tile 0: the next producer's pivots, the range guard
+                        if (p.lnf_stats_out && n0 == 0 && wn == 0 && fq == 0 && tok) {  // feature tile 0: the next producer's pivots, the range guard
                             *reinterpret_cast<f32x2*>(p.lnf_stats_out + (size_t)m * 2) = lstr[j];
                             if (!(sumsq < 65504.0f * 65504.0f)) {
                                 bad = true;
@@ -958,7 +959,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
                 bool bad = false;
                 float sumsq = 0.f;
                 const int m = m0 + tid;
-                if (tid < BM && m < p.M) {
+                if (tid < BM && m < p.M && (p.lnf_rows == 0 || m + p.row0 < p.lnf_rows)) {  // (padding rows: no statistics, no guard)
                     const int ncols = p.N >> 6;
                     float s1 = 0.f, s2 = 0.f;
                     if (ncols == 16) {

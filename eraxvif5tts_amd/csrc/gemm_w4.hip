@@ -259,8 +259,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 *reinterpret_cast<f32x2*>(lnf_lds + 1024 + lane * 8) = f32x2{mean, rstd};
                 if (p.lnf_stats_out && n0 == 0 && wn == 0) {
                     const int m = m0 + wm * WROWS + lane;
-                    *reinterpret_cast<f32x2*>(p.lnf_stats_out + (size_t)m * 2) = f32x2{mean, rstd};
-                    lnf_raise_guard(p.lnf_sat, !(sumsq < 65504.0f * 65504.0f), sumsq, p.lnf_sat_tag, m + p.row0);
+                    const bool tok = p.lnf_rows == 0 || m + p.row0 < p.lnf_rows;  // (padding rows: statistics for this tile's epilogue only)
+                    if (tok) *reinterpret_cast<f32x2*>(p.lnf_stats_out + (size_t)m * 2) = f32x2{mean, rstd};
+                    lnf_raise_guard(p.lnf_sat, tok && !(sumsq < 65504.0f * 65504.0f), sumsq, p.lnf_sat_tag, m + p.row0);
                 }
             }
         }
