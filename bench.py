@@ -2,9 +2,13 @@
 """Headline benchmark: mel-frames/s of the F5-TTS flow-matching sampler (CFM.sample: 32 Euler steps x (cond + uncond) DiT
 evaluations, CFG 2, sway -1) on MI355X, at BASELINE.json's C2: F5TTS_Base, bf16, batch 32, seq_len 1024, NFE 32.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--workload C2|C4|vocos] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--full] [--scaling strong|weak] [--workload C2|C4|vocos] [--dump-outputs DIR]
 
 A "step" is one full sample() over one synthetic batch of fixed-length utterances that is already resident in HBM.
+
+A plain run does only what the headline figure needs: it sets up, runs the W warm-up and K timed steps, writes the outputs if
+--dump-outputs is given, and prints the result line.  Everything else the benchmark measures needs runs of its own and is measured
+only with --full (see below).
 
 Multi-GPU (--gpus N > 1): one process per GPU over RCCL (torch.distributed backend "nccl").  Started under torchrun (the driver's
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`) the ranks are used as given; started as a plain
@@ -15,21 +19,26 @@ process, relays rank 0's JSON line and exits with the child's code.  A WORLD_SIZ
   --scaling weak: 32 utterances per GPU.
 There is no collective inside the ODE loop; the all_gather of the finished mels is the only one.
 
-One JSON line on rank 0 with the driver's contract fields plus
+One JSON line on rank 0 with the driver's contract fields, "loop_tflops" / "loop_mfma_frac" (the algorithmic FLOPs of the timed steps,
+SURVEY.md 8d) and, with N > 1, "distributed.ranks" (per rank: wall time, HIP-event time of sample() and of the gather in each step).
+  --workload vocos (C5): Vocos.decode on [B, 100, T] (T = 683 at B = 32, or --seq-len T), frames/s.
+  --dump-outputs DIR  after the timed steps, write what the last timed step returned (the mels of sample(), gathered over all ranks, or
+      the waveforms of Vocos.decode) as DIR/<name>.npy in float32.  Weights and inputs are seeded, so the same arguments give the same
+      inputs on every run and two builds can be compared output for output.  Above 64 MB in all, a fixed seeded subset of rows is written.
+  --full  after the headline measurement, which it leaves unchanged, also records
   "roofline"      the dominant kernel (fused QKV projection GEMM): algorithmic FLOPs per launch / mean launch time measured here
                   with HIP event pairs on the launch stream, vs the 2.5 PFLOP/s dense bf16 MFMA peak; "kernels" lists the same
                   in-situ measurement for every kernel of a DiT block (GEMMs and attention against MFMA peak, the LayerNorm passes
                   against the 8 TB/s HBM peak); "traffic" is read from the newest profiles/*traffic*.json (a recorded rocprofv3 PMC
-                  pass, named in "traffic_source"), null when there is none for this shape;
+                  pass, named in "traffic_source"), null when there is none for this shape; with --workload vocos, the HBM
+                  roofline of the ISTFT head;
   "cpu_baseline"  the CPU oracle (oracle/cpu_ref.py, plain fp32 torch; the reference itself cannot travel) timed on this
-                  host's cores on a bounded sample, scaled linearly to the workload's NFE.
-  --workload vocos (C5): Vocos.decode on [B, 100, T] (T = 683 at B = 32, or --seq-len T), frames/s, HBM roofline of the ISTFT head.
-The default C2 run on one GPU also measures C4 (2 timed sample() calls + in-situ kernel table) and C5 afterwards and reports them under
-"workloads": {"C4": {value, ms_per_step, attention_frac, ...}, "C5": {value, rtf, head_gbs, cpu_baseline, ...}} (--no-extra skips them);
-the C2 fields are unchanged.
-  --dump-outputs DIR  after the timed steps, write what the last timed step returned (the mels of sample(), gathered over all ranks, or
-      the waveforms of Vocos.decode) as DIR/<name>.npy in float32.  Weights and inputs are seeded, so the same arguments give the same
-      inputs on every run and two builds can be compared output for output.  Above 64 MB in all, a fixed seeded subset of rows is written.
+                  host's cores on a bounded sample, scaled linearly to the workload's NFE (--no-cpu-baseline skips it);
+  "workloads"     the default C2 run on one GPU also measures C4 (2 timed sample() calls + in-situ kernel table), the 4 x 1024 shard
+                  and single-utterance shapes, generate()'s ragged chunks, the bucketed batch inference, BigVGAN and C5 afterwards:
+                  {"C4": {value, ms_per_step, attention_frac, ...}, "C5": {value, rtf, head_gbs, cpu_baseline, ...}, ...}
+                  (--no-extra skips them);
+  "distributed.ranks[].gather_only_ms"  with N > 1, the all_gather alone, every rank entering it together.
 """
 from __future__ import annotations
 
@@ -169,7 +178,7 @@ def launch_children(args):
 
 def bench_vocos(args, dev, T=None, B=None, steps=None, warmup=None, dump_dir=None):
     """C5: Vocos.decode on the generated part of a C2 (T = 683) or C4 (T = 2731) batch.  Returns the result record; with dump_dir, the
-    waveforms of the last timed decode go to dump_dir/wave.npy."""
+    waveforms of the last timed decode go to dump_dir/wave.npy.  With --full, the ISTFT head's roofline and the CPU baseline follow."""
     import torch
     from eraxvif5tts_amd import _lib
     from eraxvif5tts_amd.vocos import Vocos
@@ -198,40 +207,41 @@ def bench_vocos(args, dev, T=None, B=None, steps=None, warmup=None, dump_dir=Non
         dump_outputs(dump_dir, {"wave": wave})
     frames = B * T * steps
     audio_s = B * (T - 1) * 256 / 24000.0 * steps
-    # ISTFT head alone (HBM-bound): HIP events around f5_vocoder_istft_head on this stream
-    head = torch.randn(B, T, 1026, generator=g).to(dev) * 0.5
-    hw = voc.istft_head(head)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    iters = 20
-    e0.record()
-    for _ in range(iters):
-        hw = voc.istft_head(head)
-    e1.record()
-    torch.cuda.synchronize()
-    head_ms = e0.elapsed_time(e1) / iters
-    head_bytes = B * T * (1026 * 4 + 256 * 4)  # read 1026 coefficients + write 256 samples per frame = 5.1 KB
-    achieved = head_bytes / (head_ms * 1e-3) / 1e9
-    flops = 2.0 * B * T * (7 * 100 * 512 + 8 * (7 * 512 + 2 * 512 * 1536) + 512 * 1026)
     result = {
         "metric": "vocoder mel-frames/s", "value": round(frames / elapsed, 2), "unit": "mel-frames/s", "n_gpus": 1, "steps": steps,
         "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic", "rtf": round(elapsed / audio_s, 7),
         "config": {"workload": f"C5 Vocos.decode (vocos-mel-24khz shape, random init): mel [B={B}, 100, T={T}] -> wave [B, {(T - 1) * 256}]",
                    "global_batch": B, "frames": T},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": None, "kernel": "ISTFT head (exp/clip/cos/sin -> 1024-point inverse FFT in LDS -> window; overlap-add)",
-                     "launch": f"{head_bytes / 1e6:.1f} MB algorithmic (5.1 KB per frame) in {head_ms:.4f} ms, mean of {iters} calls (HIP events)",
-                     "backbone_tflops_f32": round(flops * steps / elapsed / 1e12, 2), "backbone_peak_f32": MFMA_F32_PEAK_TFLOPS},
     }
-    if not args.no_cpu_baseline:
-        cores = _host_cores()
-        bs = 2 if T <= 1024 else 1
-        cm = mel[:bs].cpu()
-        t0 = time.perf_counter()
-        cpu_ref.vocos_decode(V, cm)
-        dt = time.perf_counter() - t0
-        result["cpu_baseline"] = {"value": round(bs * T / dt, 2), "unit": "mel-frames/s", "cores": cores, "kind": "port",
-                                  "sample": f"oracle/cpu_ref.vocos_decode fp32 torch, B={bs} T={T} ({dt:.2f} s)"}
+    if args.full:  # measurements beyond the headline, each a run of its own
+        # ISTFT head alone (HBM-bound): HIP events around f5_vocoder_istft_head on this stream
+        head = torch.randn(B, T, 1026, generator=g).to(dev) * 0.5
+        hw = voc.istft_head(head)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        iters = 20
+        e0.record()
+        for _ in range(iters):
+            hw = voc.istft_head(head)
+        e1.record()
+        torch.cuda.synchronize()
+        head_ms = e0.elapsed_time(e1) / iters
+        head_bytes = B * T * (1026 * 4 + 256 * 4)  # read 1026 coefficients + write 256 samples per frame = 5.1 KB
+        achieved = head_bytes / (head_ms * 1e-3) / 1e9
+        flops = 2.0 * B * T * (7 * 100 * 512 + 8 * (7 * 512 + 2 * 512 * 1536) + 512 * 1026)
+        result["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                              "traffic": None, "kernel": "ISTFT head (exp/clip/cos/sin -> 1024-point inverse FFT in LDS -> window; overlap-add)",
+                              "launch": f"{head_bytes / 1e6:.1f} MB algorithmic (5.1 KB per frame) in {head_ms:.4f} ms, mean of {iters} calls (HIP events)",
+                              "backbone_tflops_f32": round(flops * steps / elapsed / 1e12, 2), "backbone_peak_f32": MFMA_F32_PEAK_TFLOPS}
+        if not args.no_cpu_baseline:
+            cores = _host_cores()
+            bs = 2 if T <= 1024 else 1
+            cm = mel[:bs].cpu()
+            t0 = time.perf_counter()
+            cpu_ref.vocos_decode(V, cm)
+            dt = time.perf_counter() - t0
+            result["cpu_baseline"] = {"value": round(bs * T / dt, 2), "unit": "mel-frames/s", "cores": cores, "kind": "port",
+                                      "sample": f"oracle/cpu_ref.vocos_decode fp32 torch, B={bs} T={T} ({dt:.2f} s)"}
     del voc
     torch.cuda.empty_cache()
     return result
@@ -470,6 +480,45 @@ def extra_workloads(args, dev, model, cfm):
     return out
 
 
+def full_measurements(args, dev, lib, model, cfm, batch, B, B_req, N, nfe, world, result):
+    """--full, rank 0, after the headline: the roofline (one extra eager sample() with in-situ kernel timing, then the MFMA-rate probe),
+    the CPU baseline and, for the default single-GPU C2 run, the other workloads.  Adds them to `result`."""
+    from eraxvif5tts_amd import _lib
+    cfg_on = args.cfg >= 1e-5
+    rows = (2 if cfg_on else 1) * B * N
+    ms_qkv, n_qkv, flops_qkv, kernels = insitu_kernels(model, cfm, batch, B, N, nfe, args)
+    achieved = flops_qkv / (ms_qkv * 1e-3) / 1e12
+    traffic, traffic_src = recorded_traffic("qkv", rows, N)
+    result["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                          "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4),
+                          "traffic": traffic, "traffic_source": traffic_src,
+                          "kernel": (("gemm_w4_kernel<QKV+RoPE epilogue" if getattr(insitu_kernels, "w4", False) else "gemm_fast_kernel<256,128,DENSE,QKV+RoPE epilogue") +
+                                     (",persistent grid,LayerNorm fold> (fp16 stream x per-time fp16 weights on v_mfma_f32_16x16x32_f16; 21 of the 22 launches per "
+                                      "evaluation, block 0's runs the bf16 build)" if any("LayerNorm folded" in k["kernel"] for k in kernels) else ",persistent grid>") +
+                                     (" [one wave per SIMD: 4 waves x 128x128, 256x256x64 stages, csrc/gemm_w4.hip]" if getattr(insitu_kernels, "w4", False) else "")),
+                          "launch": f"M={rows} N=3072 K=1024, {flops_qkv / 1e9:.1f} GFLOP, {ms_qkv:.4f} ms mean over {n_qkv} launches inside an "
+                                    f"eager sample() (HIP event pairs on the launch stream)",
+                          "kernels": kernels}
+    # what the matrix pipe itself sustains on THIS device (register-resident MFMA stream, no memory traffic): clock-limited with
+    # zero operands, power-limited with realistic ones -- context for `frac`, whose denominator stays the data-sheet peak
+    sus = {}
+    for label, rnd in (("zero_operands", 0), ("random_operands", 1)):
+        tf = C.c_float(0.0)
+        if lib.f5_bench_mfma_rate(rnd, C.byref(tf), _lib.stream_ptr()) == 0:
+            sus[label] = round(tf.value, 1)
+    result["roofline"]["mfma_sustained_tflops"] = sus or None
+    if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only (the other ranks would sit in the barrier for its 15 s)
+        result["cpu_baseline"] = cpu_baseline(model, N, nfe)
+    wl_B, wl_N = WORKLOADS[args.workload]
+    if world == 1 and args.workload == "C2" and not args.no_extra and (N, B_req) == (wl_N, wl_B) and args.precision == "bf16":
+        try:
+            result["workloads"] = extra_workloads(args, dev, model, cfm)
+        except Exception as e:  # noqa: BLE001  (the C2 line above is complete; a failing side workload must not take it down)
+            import traceback
+            traceback.print_exc()
+            result["workloads"] = {"error": f"{type(e).__name__}: {e}"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None)
@@ -482,9 +531,10 @@ def main():
     ap.add_argument("--nfe", type=int, default=32)
     ap.add_argument("--cfg", type=float, default=2.0)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the roofline, the CPU baseline and the other workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full run: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="C2 run: skip the C4 / C5 measurements recorded under `workloads`")
+    ap.add_argument("--no-extra", action="store_true", help="--full C2 run: skip the C4 / C5 measurements recorded under `workloads`")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
@@ -613,21 +663,22 @@ def main():
         names = [None] * world
         dist.all_gather_object(names, f"rank{rank}:cuda{torch.cuda.current_device()}:{devices[0]}")
         devices = names
-        # after the timed region: the collective alone, every rank entering it together (no skew inside the measurement)
-        tick["i"] = -1
-        g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        dist.barrier()
-        torch.cuda.synchronize()
-        g0.record()
-        for _ in range(5):
-            dist.all_gather(gathered, pad)
-        g1.record()
-        torch.cuda.synchronize()
         mine_rec = {"rank": rank, "utterances": B, "elapsed_s": round(own_elapsed, 6),
                     "sample_ms": round(sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps, 3),
                     "gather_ms_in_step": round(sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps, 3),  # includes waiting for slower ranks
-                    "gather_only_ms": round(g0.elapsed_time(g1) / 5, 3),
                     "mel_frames_per_s": round(B * N * args.steps / max(own_elapsed, 1e-9), 2)}
+        if args.full:
+            # after the timed region: the collective alone, every rank entering it together (no skew inside the measurement)
+            tick["i"] = -1
+            g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            dist.barrier()
+            torch.cuda.synchronize()
+            g0.record()
+            for _ in range(5):
+                dist.all_gather(gathered, pad)
+            g1.record()
+            torch.cuda.synchronize()
+            mine_rec["gather_only_ms"] = round(g0.elapsed_time(g1) / 5, 3)
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine_rec)
     assert torch.isfinite(out).all(), "non-finite mel output"
@@ -654,43 +705,13 @@ def main():
 
     if rank == 0:
         cfg_on = args.cfg >= 1e-5
-        rows = (2 if cfg_on else 1) * B * N
-        ms_qkv, n_qkv, flops_qkv, kernels = insitu_kernels(model, cfm, (cond, text, lens, duration), B, N, nfe, args)
-        achieved = flops_qkv / (ms_qkv * 1e-3) / 1e12
-        traffic, traffic_src = recorded_traffic("qkv", rows, N)
-        result["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                              "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4),
-                              "traffic": traffic, "traffic_source": traffic_src,
-                              "kernel": (("gemm_w4_kernel<QKV+RoPE epilogue" if getattr(insitu_kernels, "w4", False) else "gemm_fast_kernel<256,128,DENSE,QKV+RoPE epilogue") +
-                                         (",persistent grid,LayerNorm fold> (fp16 stream x per-time fp16 weights on v_mfma_f32_16x16x32_f16; 21 of the 22 launches per "
-                                          "evaluation, block 0's runs the bf16 build)" if any("LayerNorm folded" in k["kernel"] for k in kernels) else ",persistent grid>") +
-                                         (" [one wave per SIMD: 4 waves x 128x128, 256x256x64 stages, csrc/gemm_w4.hip]" if getattr(insitu_kernels, "w4", False) else "")),
-                              "launch": f"M={rows} N=3072 K=1024, {flops_qkv / 1e9:.1f} GFLOP, {ms_qkv:.4f} ms mean over {n_qkv} launches inside an "
-                                        f"eager sample() (HIP event pairs on the launch stream)",
-                              "kernels": kernels}
-        # what the matrix pipe itself sustains on THIS device (register-resident MFMA stream, no memory traffic): clock-limited with
-        # zero operands, power-limited with realistic ones -- context for `frac`, whose denominator stays the data-sheet peak
-        sus = {}
-        for label, rnd in (("zero_operands", 0), ("random_operands", 1)):
-            tf = C.c_float(0.0)
-            if lib.f5_bench_mfma_rate(rnd, C.byref(tf), _lib.stream_ptr()) == 0:
-                sus[label] = round(tf.value, 1)
-        result["roofline"]["mfma_sustained_tflops"] = sus or None
         # whole-loop MFMA fraction from the algorithmic FLOPs of SURVEY.md 8(d)
         per_token = 378.9e6 + 90112.0 * N
         total_flops = per_token * B_total * N * (2 if cfg_on else 1) * nfe * args.steps
         result["loop_tflops"] = round(total_flops / elapsed / 1e12 / world, 2)
         result["loop_mfma_frac"] = round(total_flops / elapsed / 1e12 / world / MFMA_BF16_PEAK_TFLOPS, 4)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only (the other ranks would sit in the barrier for its 15 s)
-            result["cpu_baseline"] = cpu_baseline(model, N, nfe)
-        if world == 1 and args.workload == "C2" and not args.no_extra and (N, B_req) == (wl_N, wl_B) and args.precision == "bf16":
-            del cond, text, lens, duration
-            try:
-                result["workloads"] = extra_workloads(args, dev, model, cfm)
-            except Exception as e:  # noqa: BLE001  (the C2 line above is complete; a failing side workload must not take it down)
-                import traceback
-                traceback.print_exc()
-                result["workloads"] = {"error": f"{type(e).__name__}: {e}"}
+        if args.full:
+            full_measurements(args, dev, lib, model, cfm, (cond, text, lens, duration), B, B_req, N, nfe, world, result)
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

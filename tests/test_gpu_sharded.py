@@ -77,7 +77,7 @@ def test_bench_gpus_flag_launches_the_ranks():
     env = _env()
     env["F5_BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", "strong", "--batch", "4", "--seq-len", "256", "--nfe", "2",
-           "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]

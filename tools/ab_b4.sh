@@ -3,10 +3,10 @@
 set -u
 cd "$(dirname "$0")/.."
 run() {  # batch, knobs
-  F5HIP_TUNING="$2" timeout -k 10 200 python bench.py --batch $1 --steps 5 --warmup 2 --no-cpu-baseline --no-extra > gpurun_out/abb4.json 2>/dev/null
-  python - "$1" "$2" <<'PY'
+  line=$(F5HIP_TUNING="$2" timeout -k 10 200 python bench.py --full --batch $1 --steps 5 --warmup 2 --no-cpu-baseline --no-extra 2>/dev/null | tail -1)
+  python - "$1" "$2" "$line" <<'PY'
 import json,sys
-d=json.loads(open("gpurun_out/abb4.json").read().strip().splitlines()[-1])
+d=json.loads(sys.argv[3])
 k=" ".join(f"{x['kernel']} {x['ms']*1e3:.1f}" for x in d['roofline']['kernels'][:7])
 print(f"B={sys.argv[1]} [{sys.argv[2]}]: {d['value']:.0f} | {k}")
 PY

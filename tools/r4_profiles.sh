@@ -5,7 +5,7 @@ set -u
 cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 O=gpurun_out/r4prof
 mkdir -p $O
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || tail -5 $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || tail -5 $O/bench_default.err
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2 -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra > $O/c2.log 2>&1 || tail -5 $O/c2.log
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4 -- python3 bench.py --workload C4 --steps 2 --warmup 1 --no-cpu-baseline > $O/c4.log 2>&1 || tail -5 $O/c4.log
 timeout -k 10 500 python3 tools/pmc_insitu_traffic.py collect $O/insitu > $O/insitu.log 2>&1

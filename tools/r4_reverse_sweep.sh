@@ -3,7 +3,7 @@
 # operand each GEMM reads (QKV / FF1 now read the stream the residual GEMM in front of them just wrote)
 OUT=gpurun_out
 for rev in 8 9 12 13 0 10 14 11 8; do
-  F5HIP_TUNING=gemm_reverse_sites=$rev python bench.py --no-extra --no-cpu-baseline --steps 3 --warmup 1 > $OUT/r4m_rev$rev.json 2> $OUT/r4m_rev$rev.err || { tail -5 $OUT/r4m_rev$rev.err; exit 1; }
+  F5HIP_TUNING=gemm_reverse_sites=$rev python bench.py --full --no-extra --no-cpu-baseline --steps 3 --warmup 1 > $OUT/r4m_rev$rev.json 2> $OUT/r4m_rev$rev.err || { tail -5 $OUT/r4m_rev$rev.err; exit 1; }
   python - <<PY
 import json
 j=json.loads(open("$OUT/r4m_rev$rev.json").read().strip().splitlines()[-1])
