@@ -88,6 +88,12 @@ _PROTOS = {
     "f5_op_layernorm_modulate": (_I, [_I, _I, _P, _P, _P, _P, _P]),
     "f5_op_attention": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "f5_op_conv_pos_embed": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_op_layernorm_res": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "f5_op_f32_to_f16": (_I, [C.c_int64, _P, _P, _P, _P]),
+    "f5_op_qknorm_rope": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "f5_op_dwconv7_ln": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_op_grn": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "f5_op_rmsnorm": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "f5_bench_gemm_site": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), _P]),
     "f5_bench_attention": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_float), _P]),
     "f5_bench_mfma_rate": (_I, [_I, C.POINTER(C.c_float), _P]),

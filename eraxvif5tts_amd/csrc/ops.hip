@@ -231,6 +231,153 @@ extern "C" int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const 
     return sync_and_release(a, st, rc);
 }
 
+// ----------------------------------------------------------------------------- row-wise kernels (test and diagnostic entry points)
+// Test staging of an fp16 stream: a plain cast (round to nearest, overflow to inf, NaN kept), so that a test can hand the kernels the values
+// a saturating producer never writes.  The model's own conversion is launch_f32_to_f16.
+__global__ __launch_bounds__(256) void stage_f16_kernel(const float* __restrict__ src, _Float16* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = (_Float16)src[i];
+}
+static int stage_f16(const float* src, void* dst, size_t n, hipStream_t st) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(stage_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, (_Float16*)dst, n);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int f5_op_layernorm_res(int precision, int xin_f16, int xout_f16, int rows, int dim, int ldx, int ldy, int ldo, const float* x,
+                                   const float* y, const float* y2, int ymode, const float* mul, const float* add, int mod_bstride,
+                                   int rows_per_batch, int add_one, int inplace, int sat_tag, float* out, float* xback, uint32_t* guard,
+                                   f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (rows <= 0 || dim <= 0 || !x || !mul || !add || !out || !xback) return f5_fail(F5_EINVAL, "bad argument");
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    if (ldx < dim || ldo < dim || (ldx & 3) || (ldo & 3) || (y && (ldy < dim || (ldy & 3)))) return f5_fail(F5_EINVAL, "leading dimensions below dim");
+    if ((ymode != 0 && !y) || (ymode == 3 && !y2)) return f5_fail(F5_EINVAL, "residual mode %d needs its branches", ymode);
+    if (inplace && xin_f16 != xout_f16) return f5_fail(F5_EINVAL, "in place needs one storage type");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t es = f5_elem_size(precision), xn = (size_t)rows * ldx;
+    DevArena a;
+    void *xs = nullptr, *xo = nullptr, *ys = nullptr, *y2s = nullptr, *os = nullptr;
+    unsigned* sat = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&xs, xn * (xin_f16 ? 2 : 4)))) break;
+        if ((rc = a.alloc(&os, (size_t)rows * ldo * es))) break;  // zeroed: the columns past dim must stay 0
+        if ((rc = a.alloc_t(&sat, 8))) break;
+        if (y && (rc = a.alloc(&ys, (size_t)rows * ldy * es))) break;
+        if (y2 && (rc = a.alloc(&y2s, (size_t)rows * ldy * es))) break;
+        if (inplace) xo = xs;
+        else if ((rc = a.alloc(&xo, xn * (xout_f16 ? 2 : 4)))) break;
+        if (xin_f16) {
+            if ((rc = stage_f16(x, xs, xn, st))) break;
+        } else {
+            F5_HIP(hipMemcpyAsync(xs, x, xn * 4, hipMemcpyDeviceToDevice, st));
+        }
+        if (y && (rc = launch_convert_pad(precision, y, ldy, rows, ldy, ldy, ys, ldy, st))) break;
+        if (y2 && (rc = launch_convert_pad(precision, y2, ldy, rows, ldy, ldy, y2s, ldy, st))) break;
+        if ((rc = launch_layernorm_res(precision, xs, xin_f16, xo, xout_f16, ldx, rows, dim, ys, ldy, y2s, ymode, mul, add, mod_bstride, rows_per_batch,
+                                       add_one, os, ldo, st, nullptr, guard ? sat : nullptr, sat_tag)))
+            break;
+        if ((rc = launch_convert_back(precision, os, ldo, rows, ldo, out, ldo, st))) break;
+        if ((rc = xout_f16 ? launch_f16_to_f32(xo, xback, xn, st) : launch_convert_back(F5_PREC_FP32, xo, ldx, rows, ldx, xback, ldx, st))) break;
+        if (guard) F5_HIP(hipMemcpyAsync(guard, sat, 6 * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
+extern "C" int f5_op_f32_to_f16(int64_t n, const float* src, float* dst, uint32_t* guard, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (n <= 0 || !src || !dst) return f5_fail(F5_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    DevArena a;
+    void* h = nullptr;
+    unsigned* sat = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&h, (size_t)n * 2))) break;
+        if ((rc = a.alloc_t(&sat, 8))) break;
+        if ((rc = launch_f32_to_f16(src, h, (size_t)n, st, guard ? sat : nullptr))) break;
+        if ((rc = launch_f16_to_f32(h, dst, (size_t)n, st))) break;
+        if (guard) F5_HIP(hipMemcpyAsync(guard, sat, 6 * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
+extern "C" int f5_op_qknorm_rope(int precision, int rows, int heads, int rope_heads, int rows_per_batch, const float* qkv, const float* wq,
+                                 const float* wk, const float* rope, float* out, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (rows <= 0 || heads <= 0 || rope_heads < 0 || rope_heads > heads || rows_per_batch <= 0 || !qkv || !wq || !wk || !out || (rope_heads && !rope))
+        return f5_fail(F5_EINVAL, "bad argument");
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    hipStream_t st = (hipStream_t)stream;
+    const int inner = heads * 64, ld = 3 * inner;
+    DevArena a;
+    void* q = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&q, (size_t)rows * ld * f5_elem_size(precision)))) break;
+        if ((rc = launch_convert_pad(precision, qkv, ld, rows, ld, ld, q, ld, st))) break;
+        if ((rc = launch_qknorm_rope(precision, q, ld, rows, inner, heads, rope_heads, wq, wk, rope, rows_per_batch, st))) break;
+        rc = launch_convert_back(precision, q, ld, rows, ld, out, ld, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
+extern "C" int f5_op_dwconv7_ln(int precision, int B, int N, int C, const float* x, const float* wt, const float* cbias, const float* ln_w,
+                                const float* ln_b, float* out, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (B <= 0 || N <= 0 || C <= 0 || !x || !wt || !cbias || !ln_w || !ln_b || !out) return f5_fail(F5_EINVAL, "bad argument");
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = B * N;
+    DevArena a;
+    void* o = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&o, (size_t)rows * C * f5_elem_size(precision)))) break;
+        if ((rc = launch_dwconv7_ln(precision, x, B, N, C, wt, cbias, ln_w, ln_b, o, C, st))) break;
+        rc = launch_convert_back(precision, o, C, rows, C, out, C, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
+extern "C" int f5_op_grn(int precision, int B, int N, int C, const float* h, const float* gamma, const float* beta, float* out, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (B <= 0 || N <= 0 || C <= 0 || !h || !gamma || !beta || !out) return f5_fail(F5_EINVAL, "bad argument");
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = B * N;
+    DevArena a;
+    void* hs = nullptr;
+    float* scratch = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&hs, (size_t)rows * C * f5_elem_size(precision)))) break;
+        if ((rc = a.alloc_t(&scratch, (size_t)B * C + B))) break;
+        if ((rc = launch_convert_pad(precision, h, C, rows, C, C, hs, C, st))) break;
+        if ((rc = launch_grn(precision, hs, B, N, C, gamma, beta, scratch, st))) break;
+        rc = launch_convert_back(precision, hs, C, rows, C, out, C, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
+extern "C" int f5_op_rmsnorm(int precision, int rows, int dim, const float* x, const float* g, float* out, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (rows <= 0 || dim <= 0 || !x || !g || !out) return f5_fail(F5_EINVAL, "bad argument");
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    hipStream_t st = (hipStream_t)stream;
+    DevArena a;
+    void* o = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&o, (size_t)rows * dim * f5_elem_size(precision)))) break;
+        if ((rc = launch_rmsnorm(precision, x, dim, rows, dim, g, o, dim, st))) break;
+        rc = launch_convert_back(precision, o, dim, rows, dim, out, dim, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
 // ----------------------------------------------------------------------------- in-process kernel timing (bench.py roofline leg)
 __global__ __launch_bounds__(256) void fill_random_kernel(uint16_t* dst, size_t n, uint32_t seed, float scale) {
     // counter-based hash -> uniform [-scale, scale) in bf16: random operands (zero-filled ones raise the clock and flatter MFMA rates)

@@ -279,6 +279,38 @@ F5_API int f5_op_attention(int precision, int kernel, int B, int N, int H, const
 F5_API int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const float* x, const float* w0, const float* b0,
                          const float* w1, const float* b1, float* out, f5_stream_t stream);
 
+/* Test and diagnostic entry points of the row-wise kernels: each stages its f32 device inputs into the dtypes the model path uses and calls
+ * the production launcher, so the launcher's own dispatch (and its tuning knobs) decides which kernel runs.  All pointers are device pointers.
+ *
+ * The LayerNorm pass of the residual stream (launch_layernorm_res): x [rows, ldx] is the stream, staged as fp16 (xin_f16; an exact cast, so
+ * the caller pre-rounds it) or fp32; y, y2 [rows, ldy] the residual branches (bf16 in the bf16 mode); ymode 0 = x, 1 = x + y written back,
+ * 2 = x + y not written back, 3 = (x + y) + y2 written back; mul / add f32 [nb][mod_bstride] (or [dim] when mod_bstride = 0), batch =
+ * row / rows_per_batch; out [rows, ldo] = LN(v) * (add_one + mul) + add in the precision's dtype, returned as f32 (columns past dim stay 0).
+ * inplace = 1 writes the stream back into its own buffer (the only form that takes the multi-row kernel), 0 into a zeroed one of the same
+ * leading dimension and storage type xout_f16; xback [rows, ldx] receives that buffer as f32.  guard (u32 [6] or NULL): the range guard's
+ * words (flag, largest finite |element| as float bits, NaN seen, pass bits, block bits, 0x7fffffff - smallest offending row), zeroed
+ * before the launch; sat_tag as the model passes it (pass | block << 4). */
+F5_API int f5_op_layernorm_res(int precision, int xin_f16, int xout_f16, int rows, int dim, int ldx, int ldy, int ldo, const float* x,
+                               const float* y, const float* y2, int ymode, const float* mul, const float* add, int mod_bstride,
+                               int rows_per_batch, int add_one, int inplace, int sat_tag, float* out, float* xback, uint32_t* guard,
+                               f5_stream_t stream);
+/* The saturating fp32 -> fp16 copy of the hoisted input embedding (launch_f32_to_f16): dst f32 [n] = the fp16 values, widened; guard as above */
+F5_API int f5_op_f32_to_f16(int64_t n, const float* src, float* dst, uint32_t* guard, f5_stream_t stream);
+/* qk_norm = "rms_norm" (launch_qknorm_rope): qkv f32 [rows, 3 * heads * 64] -> out, q and k of every head RMS-normalised over 64 features
+ * (eps 1e-6; weights wq, wk f32 [64]), then rotated on the first rope_heads heads by rope f32 [rows_per_batch][32][2] (cos, sin) at position
+ * row % rows_per_batch; the v third is copied through.  The precision's dtype in between. */
+F5_API int f5_op_qknorm_rope(int precision, int rows, int heads, int rope_heads, int rows_per_batch, const float* qkv, const float* wq,
+                             const float* wk, const float* rope, float* out, f5_stream_t stream);
+/* ConvNeXtV2 depthwise conv (k = 7, zero padding 3 inside each utterance) + LayerNorm(affine, eps 1e-6) (launch_dwconv7_ln): x f32 [B, N, C],
+ * wt f32 [7][C], cbias / ln_w / ln_b f32 [C] -> out f32 [B, N, C] (the precision's dtype in between) */
+F5_API int f5_op_dwconv7_ln(int precision, int B, int N, int C, const float* x, const float* wt, const float* cbias, const float* ln_w,
+                            const float* ln_b, float* out, f5_stream_t stream);
+/* ConvNeXtV2 GRN (launch_grn): h f32 [B, N, C] staged in the precision's dtype; out = gamma (h Nx) + beta + h with Nx = G / (mean_c G + 1e-6),
+ * G[b][c] = ||h[b, :, c]||_2 over the utterance's N tokens */
+F5_API int f5_op_grn(int precision, int B, int N, int C, const float* h, const float* gamma, const float* beta, float* out, f5_stream_t stream);
+/* RMSNorm of UNetT (launch_rmsnorm): out = x / max(||x||_2, 1e-12) * sqrt(dim) * g ; x f32 [rows, dim], g f32 [dim] */
+F5_API int f5_op_rmsnorm(int precision, int rows, int dim, const float* x, const float* g, float* out, f5_stream_t stream);
+
 /* in-process kernel timing for the roofline leg of bench.py: `iters` back-to-back launches of ONE kernel bracketed by HIP
  * events on `stream`, random bf16 operands; *ms_avg = mean device time per launch.
  * site: 0 fused QKV projection + RoPE, 1 FF1 + GELU-tanh, 2 FF2 + gated residual, 3 attention out-projection + gated residual. */

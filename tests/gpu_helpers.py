@@ -96,3 +96,171 @@ def op_ln_fold(epi, x, A, Wo, bo, gate, W, bias, scale, shift, pivot=None, act="
     _lib.check(lib.f5_op_ln_fold(epi, M, D, N, Kb, _lib.ptr(xs), *[_lib.ptr(t) for t in dev[:9]], _lib.ACT[act], _lib.ptr(dev[9]), rope_heads, seq,
                                  _lib.ptr(stats), _lib.ptr(out), _lib.stream_ptr()))
     return xs.cpu(), stats.cpu(), out.cpu()
+
+
+# ----------------------------------------------------------------------------- row-wise kernels (include/f5hip.h: test and diagnostic entry points)
+KNOB_DEFAULTS = {b"ln_rows": 2, b"ln_rows_min": 16384, b"ln_wide": 1, b"residual_f16": 1}
+
+
+class knobs:
+    """with knobs(ln_rows=4, ln_rows_min=1): ... -- tuning knobs set through f5_tuning_set, put back to their defaults on the way out."""
+
+    def __init__(self, **kv):
+        self.kv = {k.encode(): v for k, v in kv.items()}
+
+    def __enter__(self):
+        lib = _lib.load()
+        for k, v in self.kv.items():
+            _lib.check(lib.f5_tuning_set(k, v))
+        return self
+
+    def __exit__(self, *exc):
+        lib = _lib.load()
+        for k in self.kv:
+            _lib.check(lib.f5_tuning_set(k, KNOB_DEFAULTS[k]))
+        return False
+
+
+def _pad_cols(t, ld, fill):
+    """[rows, n] -> [rows, ld], the columns past n filled with `fill` (a kernel that reads them shows it)."""
+    out = torch.full((t.shape[0], ld), fill, dtype=torch.float32)
+    out[:, :t.shape[1]] = t
+    return out
+
+
+def op_layernorm_res(precision, x, y=None, y2=None, ymode=0, mul=None, add=None, mod_bstride=0, rows_per_batch=0, add_one=1, inplace=1,
+                     xin_f16=1, xout_f16=1, ldx=None, ldy=None, ldo=None, sat_tag=0):
+    """include/f5hip.h: f5_op_layernorm_res.  x [rows, dim] (the stream), y / y2 [rows, dim]; mul / add [dim] or [batches, mod_bstride].
+    Returns (out [rows, dim], written-back stream [rows, dim], guard words: 6 Python ints).  Padding columns of x / y / y2 hold NaN; the
+    helper asserts that the kernels leave the padding of `out` and of the stream buffer untouched."""
+    lib = _lib.load()
+    rows, dim = x.shape
+    ldx, ldy, ldo = ldx or dim, ldy or dim, ldo or dim
+    nan = float("nan")
+    xs = _pad_cols(x.float(), ldx, nan).cuda()
+    ys = None if y is None else _pad_cols(y.float(), ldy, nan).cuda()
+    y2s = None if y2 is None else _pad_cols(y2.float(), ldy, nan).cuda()
+    nb = -(-rows // (rows_per_batch or rows)) if mod_bstride else 1
+    need = (nb - 1) * mod_bstride + dim
+    m, a = [t.float().reshape(-1).contiguous().cuda() for t in (mul, add)]
+    assert m.numel() >= need and a.numel() >= need
+    out = torch.full((rows, ldo), 7.0, device="cuda")
+    xback = torch.full((rows, ldx), 7.0, device="cuda")
+    guard = torch.full((6,), -1, dtype=torch.int32, device="cuda")
+    rc = lib.f5_op_layernorm_res(precision, xin_f16, xout_f16, rows, dim, ldx, ldy, ldo, _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(y2s), ymode, _lib.ptr(m),
+                                 _lib.ptr(a), mod_bstride, rows_per_batch, add_one, inplace, sat_tag, _lib.ptr(out), _lib.ptr(xback), _lib.ptr(guard),
+                                 _lib.stream_ptr())
+    _lib.check(rc, "f5_op_layernorm_res")
+    out, xback = out.cpu(), xback.cpu()
+    assert (out[:, dim:] == 0).all(), "a LayerNorm kernel wrote past dim"
+    pad = xback[:, dim:]
+    assert (pad.isnan().all() if inplace else (pad == 0).all()), "a LayerNorm kernel wrote the stream past dim"
+    return out[:, :dim], xback[:, :dim], [int(v) & 0xffffffff for v in guard.cpu().tolist()]
+
+
+def op_layernorm_res_rc(precision, xin_f16, xout_f16, rows, dim, ymode=0, inplace=1, ldx=None):
+    """The return code of f5_op_layernorm_res for an argument set the launcher should refuse (no data checked)."""
+    lib = _lib.load()
+    ldx = ldx or dim
+    x = torch.zeros(rows, ldx, device="cuda")
+    y = torch.zeros(rows, ldx, device="cuda")
+    md = torch.zeros(ldx, device="cuda")
+    out = torch.zeros(rows, ldx, device="cuda")
+    xb = torch.zeros(rows, ldx, device="cuda")
+    return lib.f5_op_layernorm_res(precision, xin_f16, xout_f16, rows, dim, ldx, ldx, ldx, _lib.ptr(x), _lib.ptr(y), _lib.ptr(y), ymode, _lib.ptr(md),
+                                   _lib.ptr(md), 0, 0, 1, inplace, 0, _lib.ptr(out), _lib.ptr(xb), None, _lib.stream_ptr())
+
+
+def op_f32_to_f16(src):
+    """include/f5hip.h: f5_op_f32_to_f16.  Returns (the fp16 values as f32, guard words)."""
+    lib = _lib.load()
+    s = src.float().contiguous().cuda()
+    dst = torch.empty_like(s)
+    guard = torch.full((6,), -1, dtype=torch.int32, device="cuda")
+    _lib.check(lib.f5_op_f32_to_f16(s.numel(), _lib.ptr(s), _lib.ptr(dst), _lib.ptr(guard), _lib.stream_ptr()), "f5_op_f32_to_f16")
+    return dst.cpu(), [int(v) & 0xffffffff for v in guard.cpu().tolist()]
+
+
+def op_qknorm_rope(precision, qkv, heads, rope_heads, rows_per_batch, wq, wk, rope):
+    lib = _lib.load()
+    rows = qkv.shape[0]
+    ts = [None if t is None else t.float().contiguous().cuda() for t in (qkv, wq, wk, rope)]
+    out = torch.empty_like(ts[0])
+    _lib.check(lib.f5_op_qknorm_rope(precision, rows, heads, rope_heads, rows_per_batch, *[_lib.ptr(t) for t in ts], _lib.ptr(out), _lib.stream_ptr()),
+               "f5_op_qknorm_rope")
+    return out.cpu()
+
+
+def op_dwconv7_ln(precision, x, wt, cbias, ln_w, ln_b):
+    lib = _lib.load()
+    B, N, C = x.shape
+    ts = [t.float().contiguous().cuda() for t in (x, wt, cbias, ln_w, ln_b)]
+    out = torch.empty(B, N, C, device="cuda")
+    _lib.check(lib.f5_op_dwconv7_ln(precision, B, N, C, *[_lib.ptr(t) for t in ts], _lib.ptr(out), _lib.stream_ptr()), "f5_op_dwconv7_ln")
+    return out.cpu()
+
+
+def op_grn(precision, h, gamma, beta):
+    lib = _lib.load()
+    B, N, C = h.shape
+    ts = [t.float().contiguous().cuda() for t in (h, gamma, beta)]
+    out = torch.empty(B, N, C, device="cuda")
+    _lib.check(lib.f5_op_grn(precision, B, N, C, *[_lib.ptr(t) for t in ts], _lib.ptr(out), _lib.stream_ptr()), "f5_op_grn")
+    return out.cpu()
+
+
+def op_rmsnorm(precision, x, g):
+    lib = _lib.load()
+    rows, dim = x.shape
+    ts = [t.float().contiguous().cuda() for t in (x, g)]
+    out = torch.empty(rows, dim, device="cuda")
+    _lib.check(lib.f5_op_rmsnorm(precision, rows, dim, *[_lib.ptr(t) for t in ts], _lib.ptr(out), _lib.stream_ptr()), "f5_op_rmsnorm")
+    return out.cpu()
+
+
+def plan_guard_words(model):
+    """The fp16 range guard's record in the one plan `model` (a DiT) sampled with: residual_fallbacks and the five diagnostics
+    f5_plan_get_option reports (residual_guard_amax_bits, _nan, _pass, _blocks, _row), as unsigned values."""
+    lib = _lib.load()
+    (_, h), = model._plans
+    out = {}
+    for k in ("residual_fallbacks", "residual_guard_amax_bits", "residual_guard_nan", "residual_guard_pass", "residual_guard_blocks", "residual_guard_row"):
+        v = C.c_int(0)
+        _lib.check(lib.f5_plan_get_option(h, k.encode(), C.byref(v)))
+        out[k] = v.value & 0xffffffff
+    return out
+
+
+def bf16_ulp(ref):
+    """Spacing of bf16 at |ref| (fp64): 2^(floor(log2 |ref|) - 7), at least that of the smallest normal."""
+    _, e = torch.frexp(ref.abs().double())
+    return torch.pow(2.0, (e - 8).clamp(min=-133).double())
+
+
+def check_rounded(name, out, ref, scale, precision):
+    """Element-wise bound of a kernel output against its fp64 reference.  `scale` [same shape]: the magnitude of the largest term the kernel
+    evaluates in fp32 for that element; the slack is 8 fp32 ulps of it.  bf16 outputs: |out - ref| <= 1 bf16 ulp of ref + slack per element;
+    fp32 outputs: <= 1e-5 |ref| + slack.  Returns (worst error in the bound's units, signed error sum in bf16 ulps, count) for the bias check."""
+    ref = ref.double()
+    err = out.double() - ref
+    slack = 8 * 2.0 ** -23 * scale.double().abs()
+    if precision == 0:
+        ulp = bf16_ulp(ref)
+        bound = ulp + slack
+        keep = slack < 0.05 * ulp  # the rounding bias is read where fp32 evaluation error is negligible next to a bf16 ulp
+        signed = (err * torch.sign(ref) / ulp)[keep]
+        sums = (float(signed.sum()), int(signed.numel()))
+    else:
+        bound = 1e-5 * ref.abs() + slack
+        sums = (0.0, 0)
+    ratio = (err.abs() / bound)
+    worst = float(ratio.max())
+    bad = ratio > 1
+    if precision == 0:  # (in ulps where the fp32 slack is negligible; the bound's share everywhere)
+        in_ulp = float((err.abs() / ulp)[keep].max()) if keep.any() else float("nan")
+        print(f"  {name}: worst {in_ulp:.3f} bf16 ulp, {worst:.3f} of the bound")
+    else:
+        print(f"  {name}: worst {float((err.abs() / ref.abs().clamp(min=1e-30)).max()):.3e} relative, {worst:.3f} of the bound")
+    assert not bad.any(), (f"{name}: {int(bad.sum())} elements out of bound, first at {bad.nonzero()[0].tolist()}: "
+                           f"out {float(out.reshape(-1)[bad.reshape(-1).nonzero()[0]])} ref {float(ref.reshape(-1)[bad.reshape(-1).nonzero()[0]])}")
+    return worst, sums
