@@ -107,6 +107,9 @@ _PROTOS = {
     "f5_vocoder_destroy": (_I, [_P]),
     "f5_vocoder_decode": (_I, [_P, _I, _I, _P, _P, _P]),
     "f5_vocoder_istft_head": (_I, [_P, _I, _I, _P, _P, _P]),
+    "f5_vocoder_decode_ragged": (_I, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _I, _P, C.POINTER(C.c_int64), _P]),
+    "f5_wave_finish": (_I, [_I, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), _P, C.c_float, _I, _I, _P, _P, _P, _P, _P,
+                            C.POINTER(C.c_int64), _P]),
     "f5_bigvgan_create": (_I, [C.POINTER(BigVGANConfig), C.POINTER(_P)]),
     "f5_bigvgan_set_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
     "f5_bigvgan_has_tensor": (_I, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
@@ -150,6 +153,9 @@ def load(build_if_missing: bool = False):
 
 def last_error() -> str:
     return load().f5_last_error().decode("utf-8", "replace")
+
+
+F5_ENOTSUP = -5  # f5hip.h: a configuration the kernels do not implement (callers with a host route of their own test for it)
 
 
 def check(rc: int, what: str = ""):

@@ -629,14 +629,23 @@ int launch_add_f32(float* x, const float* y, size_t n, hipStream_t stream) {
 }
 
 // ----------------------------------------------------------------------------- depthwise conv k=7 + LayerNorm(affine)
-template <typename TO, int MAXV>
+// RAGGED (the Vocos blocks of f5_vocoder_decode_ragged): utterance blockIdx.y owns rows ext.row0[u] .. + ext.frames[u]; the conv's zero
+// padding is taken at the utterance's own ends, so no tap reads a neighbour's row.  Everything after the row / position lookup is one body.
+template <typename TO, int MAXV, bool RAGGED>
 __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict__ x, int B, int N, int C, const float* __restrict__ wt,
                                                          const float* __restrict__ cbias, const float* __restrict__ ln_w,
-                                                         const float* __restrict__ ln_b, TO* __restrict__ out, int ldo) {
+                                                         const float* __restrict__ ln_b, TO* __restrict__ out, int ldo, const UttExtents ext) {
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= B * N) return;
-    const int pos = row % N;
+    int row = blockIdx.x * 4 + (threadIdx.x >> 6), pos;
+    if constexpr (RAGGED) {
+        N = ext.frames[blockIdx.y];
+        if (row >= N) return;
+        pos = row;
+        row += ext.row0[blockIdx.y];
+    } else {
+        if (row >= B * N) return;
+        pos = row % N;
+    }
     const int nvec = C >> 2;
     f32x4 v[MAXV];
     float s = 0.f;
@@ -697,9 +706,18 @@ int launch_dwconv7_ln(int precision_out, const float* x, int B, int N, int C, co
     if (C % 4 != 0 || C > 1024 || (ldo & 3)) return f5_fail(F5_EINVAL, "dwconv7_ln: C=%d unsupported", C);
     dim3 grid(cdiv(B * N, 4)), block(256);
     if (precision_out == F5_PREC_BF16)
-        hipLaunchKernelGGL((dwconv7_ln_kernel<bf16_t, 4>), grid, block, 0, stream, x, B, N, C, wt, cbias, ln_w, ln_b, (bf16_t*)out, ldo);
+        hipLaunchKernelGGL((dwconv7_ln_kernel<bf16_t, 4, false>), grid, block, 0, stream, x, B, N, C, wt, cbias, ln_w, ln_b, (bf16_t*)out, ldo, UttExtents{});
     else
-        hipLaunchKernelGGL((dwconv7_ln_kernel<float, 4>), grid, block, 0, stream, x, B, N, C, wt, cbias, ln_w, ln_b, (float*)out, ldo);
+        hipLaunchKernelGGL((dwconv7_ln_kernel<float, 4, false>), grid, block, 0, stream, x, B, N, C, wt, cbias, ln_w, ln_b, (float*)out, ldo, UttExtents{});
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+int launch_dwconv7_ln_ragged(const float* x, const UttExtents& ext, int C, const float* wt, const float* cbias, const float* ln_w, const float* ln_b,
+                             float* out, int ldo, hipStream_t stream) {
+    if (ext.cnt <= 0) return 0;
+    if (C % 4 != 0 || C > 1024 || (ldo & 3)) return f5_fail(F5_EINVAL, "dwconv7_ln: C=%d unsupported", C);
+    hipLaunchKernelGGL((dwconv7_ln_kernel<float, 4, true>), dim3(cdiv(ext.max_frames, 4), ext.cnt), dim3(256), 0, stream, x, 0, 0, C, wt, cbias, ln_w, ln_b,
+                       out, ldo, ext);
     F5_LAUNCH_CHECK();
     return 0;
 }

@@ -62,10 +62,22 @@ int launch_zero_rows(void* x, size_t row_bytes, int rows, const uint8_t* flags, 
 // nb byte segments src + b * src_bstride -> dst + b * dst_bstride (everything a multiple of 16 bytes)
 int launch_copy_segments(const void* src, size_t src_bstride_bytes, void* dst, size_t dst_bstride_bytes, size_t seg_bytes, int nb, hipStream_t stream);
 int launch_joint_mask(const uint8_t* mask, int B, int N, int nt, uint8_t* dst, hipStream_t stream);  // [B, N] -> [B, N + nt], trailing 1s
+// Utterances of different frame counts in one launch (f5_vocoder_decode_ragged), passed BY VALUE as a kernel argument: nothing is staged in
+// device memory, so there is no host-buffer lifetime to keep and nothing to wait for.  Utterance u owns workspace rows row0[u] .. row0[u] +
+// frames[u] (back to back, no gap rows), reads the caller's frame-major mel from row src0[u] and writes wave samples from out0[u].  The kernels
+// take blockIdx.y = u and clip blockIdx.x at frames[u]; a call with more than MAXU utterances is split into several launches by the caller.
+struct UttExtents {
+    static constexpr int MAXU = 64;
+    int cnt = 0, max_frames = 0;
+    int row0[MAXU], frames[MAXU], src0[MAXU], out0[MAXU];
+};
 // depthwise Conv1d(k=7, pad=3) along the sequence (+bias) then LayerNorm(eps 1e-6, affine) -> activation dtype
 // x f32 [B*N, C]; wt f32 [7][C] (tap-major); out [B*N, C]
 int launch_dwconv7_ln(int precision_out, const float* x, int B, int N, int C, const float* wt, const float* cbias, const float* ln_w,
                       const float* ln_b, void* out, int ldo, hipStream_t stream);
+// the same kernel body over utterances of different lengths (fp32 out): zero padding at each utterance's own ends
+int launch_dwconv7_ln_ragged(const float* x, const UttExtents& ext, int C, const float* wt, const float* cbias, const float* ln_w, const float* ln_b,
+                             float* out, int ldo, hipStream_t stream);
 // GRN (modules.py:225-234) in place on h [B*N, C] (activation dtype): h = gamma * (h * Nx) + beta + h
 int launch_grn(int precision, void* h, int B, int N, int C, const float* gamma, const float* beta, float* scratch /*[B*C + B]*/,
                hipStream_t stream);
@@ -111,6 +123,8 @@ int launch_set_floats(float* dst, const float* host_vals, int n, hipStream_t str
 // ---- vocos.hip
 // im2col for Conv1d(k=7, pad=3): mel f32 [B, C, T] -> rows [B*T, Kp] (col = tap*C + c, zero padded to Kp)
 int launch_vocos_im2col(int precision_out, const float* mel, int B, int C, int T, void* dst, int Kp, hipStream_t stream);
+// the same from frame-major mel [rows, ld] (the sampler's layout), per utterance from its own first row: no permute / contiguous copy
+int launch_vocos_im2col_ragged(const float* mel, int ld, int C, const UttExtents& ext, float* dst, int Kp, hipStream_t stream);
 // head.out activations [B*T, ld] (log-mag | phase) -> spectrum rows [B*T, Kp]: (re_0..re_{F-1}, im_0..im_{F-1}), F = n_fft/2+1
 int launch_vocos_spectrum(int precision_out, const float* head, int ldh, int rows, int F, void* dst, int Kp, hipStream_t stream);
 // ISTFT head for n_fft = 1024 as an FFT: head [rows, ldh] (log-mag | phase) -> windowed frames [rows, 1024]; wscaled = window / n_fft,
@@ -118,6 +132,24 @@ int launch_vocos_spectrum(int precision_out, const float* head, int ldh, int row
 int launch_vocos_ifft1024(const float* head, int ldh, int rows, const float* wscaled, const float* twiddle, float* frames, hipStream_t stream);
 // overlap-add of windowed frames [B*T, n_fft] (hop), divide by the window-square envelope, trim n_fft/2 each side
 int launch_vocos_ola(const float* frames, int B, int T, int n_fft, int hop, const float* wsq /*[n_fft]*/, float* wave, hipStream_t stream);
+// utterance u: frames at rows ext.row0[u].., (frames[u] - 1) * hop samples written from wave + ext.out0[u]
+int launch_vocos_ola_ragged(const float* frames, const UttExtents& ext, int n_fft, int hop, const float* wsq, float* wave, hipStream_t stream);
+
+// ---- wave_tail.hip: what follows the vocoder (rms gain, linear cross-fade, int16 PCM) in one kernel
+// Utterances k = 0 .. cnt-1 of the launch: in0 / len = extent in the concatenated fp32 wave, out0 = position of its first sample in the output
+// (out0[k] = out0[k-1] + len[k-1] - n: consecutive utterances overlap by the n cross-faded samples), gain / apply = the host form of the rms rule.
+struct WaveTable {
+    static constexpr int MAXU = 64;
+    int cnt = 0;
+    int in0[MAXU], len[MAXU], out0[MAXU];
+    float gain[MAXU];
+    unsigned char apply[MAXU];
+};
+// Output samples pos0 .. pos_end-1; sample pos belongs to the last utterance k >= first with out0[k] <= pos and, when k > 0 and it is one of k's
+// first n samples, is the cross-fade with utterance k-1's tail.  f64: a joint mixed, so the whole signal is double (numpy's promotion) and the PCM
+// product is taken in double; otherwise fp32.  rms_dev (or null): device scalar, gain applied to every utterance when *rms_dev < target.
+int launch_wave_finish(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n, const double* w_down, const double* w_up,
+                       const float* rms_dev, float target, int gain_div, bool f64, float* out_f32, double* out_f64, int16_t* out_pcm, hipStream_t stream);
 
 // ---- LayerNorm fold (lnfold.hip; gemm.h)
 // per-evaluation-time projection weights W' = fp16(W (1 + scale)) and column constants c1 = rowsum W', c2 = b + W . shift for `evals` times x `depth`

@@ -205,19 +205,27 @@ static GemmParams vg() {
     return g;
 }
 
-static int istft_from_head(f5_vocoder_s* v, int B, int T, const float* head, int ldh, float* wave, hipStream_t st) {
+// Utterance extents of a ragged call, in groups of at most UttExtents::MAXU (one launch of a row-crossing kernel per group; the row-local
+// kernels run once over all rows).  Equal-length calls pass rg = nullptr and take the [B, T] forms of the same kernels.
+typedef std::vector<UttExtents> RaggedExt;
+
+static int istft_from_head(f5_vocoder_s* v, int B, int T, const RaggedExt* rg, int rows, const float* head, int ldh, float* wave, hipStream_t st) {
     const f5_vocos_config& c = v->cfg;
-    const int rows = B * T;
+    auto ola = [&]() -> int {
+        if (!rg) return launch_vocos_ola(v->frames, B, T, c.n_fft, c.hop, v->wsq, wave, st);
+        for (const UttExtents& e : *rg) F5_TRY(launch_vocos_ola_ragged(v->frames, e, c.n_fft, c.hop, v->wsq, wave, st));
+        return 0;
+    };
     if (v->twiddle && g_vocos_fft) {  // n_fft = 1024: inverse FFT in LDS, one workgroup per frame (HBM-bound)
         F5_TRY(launch_vocos_ifft1024(head, ldh, rows, v->wscaled, v->twiddle, v->frames, st));
-        return launch_vocos_ola(v->frames, B, T, c.n_fft, c.hop, v->wsq, wave, st);
+        return ola();
     }
     F5_TRY(launch_vocos_spectrum(F5_PREC_FP32, head, ldh, rows, v->F, v->spec, v->k_spec, st));
     GemmParams g = vg();
     g.A = v->spec; g.lda = v->k_spec; g.W = v->w_dft; g.ldw = v->k_spec; g.M = rows; g.N = c.n_fft; g.K = v->k_spec;
     g.out_f = v->frames; g.ldof = c.n_fft;
     F5_TRY(launch_gemm(g, F5_PREC_FP32, GEMM_DENSE, EPI_STORE_F32, 0, st));
-    return launch_vocos_ola(v->frames, B, T, c.n_fft, c.hop, v->wsq, wave, st);
+    return ola();
 }
 
 extern "C" int f5_vocoder_istft_head(f5_vocoder_t v, int B, int T, const float* head_out, float* wave, f5_stream_t stream) {
@@ -226,7 +234,48 @@ extern "C" int f5_vocoder_istft_head(f5_vocoder_t v, int B, int T, const float* 
     if (B <= 0 || T < 2) return f5_fail(F5_EINVAL, "need B >= 1 and T >= 2 frames");
     F5_TRY(f5_check_device());
     F5_TRY(ensure_work(v, (size_t)B * T));
-    return istft_from_head(v, B, T, head_out, 2 * v->F, wave, (hipStream_t)stream);
+    return istft_from_head(v, B, T, nullptr, B * T, head_out, 2 * v->F, wave, (hipStream_t)stream);
+}
+
+// mel -> wave over `rows` workspace rows: B utterances of T frames each (mel channel-major [B, n_mels, T]), or, with rg, the utterances of the
+// extents table (mel frame-major [*, ld]).  Only the embedding im2col, the depthwise conv + LayerNorm and the overlap-add look across rows; the
+// GEMMs (one 64 x 64 x 32 tile kernel in the fp32 mode whatever M is), the LayerNorms and the inverse FFT are row-local, so a row's arithmetic
+// does not depend on how many rows share the launch and a ragged call reproduces every utterance's own batch-1 call bit for bit.
+static int decode_rows(f5_vocoder_s* v, int B, int T, const RaggedExt* rg, int rows, const float* mel, int ld, float* wave, hipStream_t st) {
+    const f5_vocos_config& c = v->cfg;
+    const int D = c.dim, I = c.inter_dim, P = F5_PREC_FP32;
+    if (rg) {
+        for (const UttExtents& e : *rg) F5_TRY(launch_vocos_im2col_ragged(mel, ld, c.n_mels, e, v->x0, v->k_embed, st));
+    } else {
+        F5_TRY(launch_vocos_im2col(P, mel, B, c.n_mels, T, v->x0, v->k_embed, st));
+    }
+    GemmParams g = vg();
+    g.A = v->x0; g.lda = v->k_embed; g.W = v->w_embed; g.ldw = v->k_embed; g.M = rows; g.N = D; g.K = v->k_embed;
+    g.bias = v->b_embed; g.out_f = v->xres; g.ldof = D;
+    F5_TRY(launch_gemm(g, P, GEMM_DENSE, EPI_STORE_F32, 0, st));
+    F5_TRY(launch_layernorm(P, v->xres, D, rows, D, v->norm_w, v->norm_b, 0, rows, 0, v->xres, D, st));  // row-local: in place is safe
+    for (int i = 0; i < c.layers; ++i) {
+        const VocosBlockW& b = v->blocks[i];
+        if (rg) {
+            for (const UttExtents& e : *rg) F5_TRY(launch_dwconv7_ln_ragged(v->xres, e, D, b.dw_wt, b.dw_b, b.ln_w, b.ln_b, v->hT, D, st));
+        } else {
+            F5_TRY(launch_dwconv7_ln(P, v->xres, B, T, D, b.dw_wt, b.dw_b, b.ln_w, b.ln_b, v->hT, D, st));
+        }
+        g = vg();
+        g.A = v->hT; g.lda = D; g.W = b.w1; g.ldw = D; g.M = rows; g.N = I; g.K = D; g.bias = b.b1; g.act = ACT_GELU_ERF;
+        g.out_t = v->h2; g.ldo = I;
+        F5_TRY(launch_gemm(g, P, GEMM_DENSE, EPI_STORE_T, 0, st));
+        g = vg();
+        g.A = v->h2; g.lda = I; g.W = b.w2; g.ldw = I; g.M = rows; g.N = D; g.K = I; g.bias = b.b2;
+        g.out_f = v->xres; g.ldof = D; g.gate = b.gamma; g.gate_bstride = 0; g.rows_per_batch = rg ? rows : T;  // (indexes the gate only: stride 0)
+        F5_TRY(launch_gemm(g, P, GEMM_DENSE, EPI_RESID, 0, st));
+    }
+    F5_TRY(launch_layernorm(P, v->xres, D, rows, D, v->fnorm_w, v->fnorm_b, 0, rows, 0, v->hT, D, st));
+    g = vg();
+    g.A = v->hT; g.lda = D; g.W = v->w_head; g.ldw = D; g.M = rows; g.N = 2 * v->F; g.K = D; g.bias = v->b_head;
+    g.out_f = v->head; g.ldof = v->ld_head;
+    F5_TRY(launch_gemm(g, P, GEMM_DENSE, EPI_STORE_F32, 0, st));
+    return istft_from_head(v, B, T, rg, rows, v->head, v->ld_head, wave, st);
 }
 
 extern "C" int f5_vocoder_decode(f5_vocoder_t v, int B, int T, const float* mel, float* wave, f5_stream_t stream) {
@@ -235,31 +284,87 @@ extern "C" int f5_vocoder_decode(f5_vocoder_t v, int B, int T, const float* mel,
     if (B <= 0 || T < 2) return f5_fail(F5_EINVAL, "need B >= 1 and T >= 2 frames");
     F5_TRY(f5_check_device());
     F5_TRY(ensure_work(v, (size_t)B * T));
-    hipStream_t st = (hipStream_t)stream;
-    const f5_vocos_config& c = v->cfg;
-    const int rows = B * T, D = c.dim, I = c.inter_dim, P = F5_PREC_FP32;
-    F5_TRY(launch_vocos_im2col(P, mel, B, c.n_mels, T, v->x0, v->k_embed, st));
-    GemmParams g = vg();
-    g.A = v->x0; g.lda = v->k_embed; g.W = v->w_embed; g.ldw = v->k_embed; g.M = rows; g.N = D; g.K = v->k_embed;
-    g.bias = v->b_embed; g.out_f = v->xres; g.ldof = D;
-    F5_TRY(launch_gemm(g, P, GEMM_DENSE, EPI_STORE_F32, 0, st));
-    F5_TRY(launch_layernorm(P, v->xres, D, rows, D, v->norm_w, v->norm_b, 0, rows, 0, v->xres, D, st));  // row-local: in place is safe
-    for (int i = 0; i < c.layers; ++i) {
-        const VocosBlockW& b = v->blocks[i];
-        F5_TRY(launch_dwconv7_ln(P, v->xres, B, T, D, b.dw_wt, b.dw_b, b.ln_w, b.ln_b, v->hT, D, st));
-        g = vg();
-        g.A = v->hT; g.lda = D; g.W = b.w1; g.ldw = D; g.M = rows; g.N = I; g.K = D; g.bias = b.b1; g.act = ACT_GELU_ERF;
-        g.out_t = v->h2; g.ldo = I;
-        F5_TRY(launch_gemm(g, P, GEMM_DENSE, EPI_STORE_T, 0, st));
-        g = vg();
-        g.A = v->h2; g.lda = I; g.W = b.w2; g.ldw = I; g.M = rows; g.N = D; g.K = I; g.bias = b.b2;
-        g.out_f = v->xres; g.ldof = D; g.gate = b.gamma; g.gate_bstride = 0; g.rows_per_batch = T;
-        F5_TRY(launch_gemm(g, P, GEMM_DENSE, EPI_RESID, 0, st));
+    return decode_rows(v, B, T, nullptr, B * T, mel, 0, wave, (hipStream_t)stream);
+}
+
+extern "C" int f5_vocoder_decode_ragged(f5_vocoder_t v, int B, const int32_t* row_start_host, const int32_t* frames_host, const float* mel, int ld,
+                                        float* wave, int64_t* total_samples, f5_stream_t stream) {
+    if (!v || !row_start_host || !frames_host || !mel || !wave) return f5_fail(F5_EINVAL, "null argument");
+    if (!v->finalized) return f5_fail(F5_ESTATE, "vocoder not finalized");
+    if (B <= 0 || ld < v->cfg.n_mels) return f5_fail(F5_EINVAL, "need B >= 1 and ld >= n_mels");
+    F5_TRY(f5_check_device());
+    RaggedExt rg;
+    int64_t rows = 0, samples = 0;
+    for (int u = 0; u < B; ++u) {
+        if (frames_host[u] < 2 || row_start_host[u] < 0) return f5_fail(F5_EINVAL, "utterance %d: need T >= 2 frames and a row start >= 0", u);
+        if (rows + frames_host[u] > (int64_t)1 << 22 || ((int64_t)row_start_host[u] + frames_host[u]) * ld >= (int64_t)1 << 31)
+            return f5_fail(F5_EINVAL, "utterance %d: the call exceeds 2^22 frames, or its mel rows 2^31 elements", u);
+        if (rg.empty() || rg.back().cnt == UttExtents::MAXU) rg.emplace_back();
+        UttExtents& e = rg.back();
+        e.row0[e.cnt] = (int)rows;
+        e.frames[e.cnt] = frames_host[u];
+        e.src0[e.cnt] = row_start_host[u];
+        e.out0[e.cnt] = (int)samples;
+        if (frames_host[u] > e.max_frames) e.max_frames = frames_host[u];
+        ++e.cnt;
+        rows += frames_host[u];
+        samples += (int64_t)(frames_host[u] - 1) * v->cfg.hop;
     }
-    F5_TRY(launch_layernorm(P, v->xres, D, rows, D, v->fnorm_w, v->fnorm_b, 0, rows, 0, v->hT, D, st));
-    g = vg();
-    g.A = v->hT; g.lda = D; g.W = v->w_head; g.ldw = D; g.M = rows; g.N = 2 * v->F; g.K = D; g.bias = v->b_head;
-    g.out_f = v->head; g.ldof = v->ld_head;
-    F5_TRY(launch_gemm(g, P, GEMM_DENSE, EPI_STORE_F32, 0, st));
-    return istft_from_head(v, B, T, v->head, v->ld_head, wave, st);
+    if (samples >= (int64_t)1 << 31) return f5_fail(F5_EINVAL, "the concatenated wave exceeds 2^31 samples");
+    if (total_samples) *total_samples = samples;
+    F5_TRY(ensure_work(v, (size_t)rows));
+    return decode_rows(v, 0, 0, &rg, (int)rows, mel, ld, wave, (hipStream_t)stream);
+}
+
+// See f5hip.h.  Only calls whose joints do not chain are taken: the first and the last utterance hold at least n = xfade_samples samples and every
+// one between them 2 n, so that each joint mixes n untouched samples of either side (cross_fade_concat then takes n = xfade_samples at every
+// joint).  Shorter utterances make the reference mix an already mixed region in sequence: F5_ENOTSUP, the caller takes the host functions.
+extern "C" int f5_wave_finish(int B, const float* wave, const int32_t* samples_host, const float* gain_host, const uint8_t* apply_host,
+                              const float* rms_dev, float target_rms, int gain_div, int xfade_samples, const double* w_down, const double* w_up,
+                              float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* total_samples_out, f5_stream_t stream) {
+    if (!wave || !samples_host || B <= 0) return f5_fail(F5_EINVAL, "null argument or B <= 0");
+    if (gain_host && !apply_host) return f5_fail(F5_EINVAL, "gain_host needs apply_host");
+    if (gain_host && rms_dev) return f5_fail(F5_EINVAL, "give the rms either as host gains or as a device scalar");
+    if ((gain_host || rms_dev) && !(target_rms > 0.f)) return f5_fail(F5_EINVAL, "target_rms must be positive");
+    F5_TRY(f5_check_device());
+    const int n = (B >= 2 && xfade_samples > 0) ? xfade_samples : 0;
+    const bool f64 = n > 0;  // a mixed joint is float64 and np.concatenate promotes the whole signal
+    if (f64 && (!w_down || !w_up)) return f5_fail(F5_EINVAL, "a cross-fade needs the w_down / w_up tables");
+    int64_t in0 = 0, out0 = 0;
+    std::vector<int> vin(B), vout(B);
+    for (int u = 0; u < B; ++u) {
+        const int len = samples_host[u];
+        if (len <= 0) return f5_fail(F5_EINVAL, "utterance %d: no samples", u);
+        if (n > 0 && len < ((u == 0 || u == B - 1) ? n : 2 * n))
+            return f5_fail(F5_ENOTSUP, "utterance %d (%d samples) is shorter than its cross-fades (%d samples each): the joints chain", u, len, n);
+        vin[u] = (int)in0;
+        vout[u] = (int)out0;
+        in0 += len;
+        out0 += len - (u + 1 < B ? n : 0);
+        if (in0 >= (int64_t)1 << 31) return f5_fail(F5_EINVAL, "more than 2^31 samples");
+    }
+    if (total_samples_out) *total_samples_out = out0;
+    // (the extents are judged first: a caller may ask "can you take this call" before it allocates the outputs)
+    if (f64 ? out_f32 != nullptr : out_f64 != nullptr) return f5_fail(F5_EINVAL, "the float result is float64 exactly when a joint mixed (out_f32 / out_f64)");
+    if (!out_f32 && !out_f64 && !out_pcm16) return f5_fail(F5_EINVAL, "no output");
+    hipStream_t st = (hipStream_t)stream;
+    // tables of MAXU utterances that overlap by one: a joint needs its left neighbour
+    for (int a = 0; a < B; a += WaveTable::MAXU - 1) {
+        WaveTable tb;
+        const int b = a + WaveTable::MAXU < B ? a + WaveTable::MAXU : B;
+        tb.cnt = b - a;
+        for (int k = a; k < b; ++k) {
+            tb.in0[k - a] = vin[k];
+            tb.len[k - a] = samples_host[k];
+            tb.out0[k - a] = vout[k];
+            tb.gain[k - a] = gain_host ? gain_host[k] : 0.f;
+            tb.apply[k - a] = gain_host ? (apply_host[k] != 0) : 0;
+        }
+        const int first = a == 0 ? 0 : 1;
+        if (first >= tb.cnt) break;
+        const int pos0 = vout[a + first], pos_end = b < B ? vout[b] : (int)out0;
+        F5_TRY(launch_wave_finish(wave, tb, first, pos0, pos_end, n, w_down, w_up, rms_dev, target_rms, gain_div, f64, out_f32, out_f64, out_pcm16, st));
+        if (b == B) break;
+    }
+    return 0;
 }

@@ -3,16 +3,28 @@
 // an HBM-bound overlap-add; exp/clip/cos/sin are fused into the spectrum packing.
 #include "kernels.h"
 
-template <typename TO>
-__global__ __launch_bounds__(256) void vocos_im2col_kernel(const float* __restrict__ mel, int B, int C, int T, TO* __restrict__ dst, int Kp) {
-    const int row = blockIdx.x;  // b * T + t
-    const int b = row / T, t = row % T;
+// One body for both layouts of the input.  RAGGED = false: mel channel-major [B, C, T], one T, row = b * T + t.  RAGGED = true: mel frame-major
+// [rows, ld] (what the sampler writes), utterance u = blockIdx.y with ext.frames[u] frames from mel row ext.src0[u], written to workspace rows
+// ext.row0[u]...  The three zero-padding frames lie inside the utterance's own extent: a neighbour's rows are never read.
+template <typename TO, bool RAGGED>
+__global__ __launch_bounds__(256) void vocos_im2col_kernel(const float* __restrict__ mel, int ld, int C, int T, TO* __restrict__ dst, int Kp, const UttExtents ext) {
+    int row, b, t;
+    if constexpr (RAGGED) {
+        b = blockIdx.y;
+        t = blockIdx.x;
+        T = ext.frames[b];
+        if (t >= T) return;
+        row = ext.row0[b] + t;
+    } else {
+        row = blockIdx.x;  // b * T + t
+        b = row / T, t = row % T;
+    }
     for (int col = threadIdx.x; col < Kp; col += 256) {
         float v = 0.f;
         if (col < 7 * C) {
             const int tap = col / C, c = col % C;
             const int st = t + tap - 3;  // Conv1d(kernel 7, padding 3)
-            if (st >= 0 && st < T) v = mel[((size_t)b * C + c) * T + st];
+            if (st >= 0 && st < T) v = RAGGED ? mel[(size_t)(ext.src0[b] + st) * ld + c] : mel[((size_t)b * C + c) * T + st];
         }
         dst[(size_t)row * Kp + col] = from_f32<TO>(v);
     }
@@ -20,9 +32,15 @@ __global__ __launch_bounds__(256) void vocos_im2col_kernel(const float* __restri
 int launch_vocos_im2col(int precision_out, const float* mel, int B, int C, int T, void* dst, int Kp, hipStream_t stream) {
     if (B * T <= 0) return 0;
     if (precision_out == F5_PREC_BF16)
-        hipLaunchKernelGGL((vocos_im2col_kernel<bf16_t>), dim3(B * T), dim3(256), 0, stream, mel, B, C, T, (bf16_t*)dst, Kp);
+        hipLaunchKernelGGL((vocos_im2col_kernel<bf16_t, false>), dim3(B * T), dim3(256), 0, stream, mel, 0, C, T, (bf16_t*)dst, Kp, UttExtents{});
     else
-        hipLaunchKernelGGL((vocos_im2col_kernel<float>), dim3(B * T), dim3(256), 0, stream, mel, B, C, T, (float*)dst, Kp);
+        hipLaunchKernelGGL((vocos_im2col_kernel<float, false>), dim3(B * T), dim3(256), 0, stream, mel, 0, C, T, (float*)dst, Kp, UttExtents{});
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+int launch_vocos_im2col_ragged(const float* mel, int ld, int C, const UttExtents& ext, float* dst, int Kp, hipStream_t stream) {
+    if (ext.cnt <= 0) return 0;
+    hipLaunchKernelGGL((vocos_im2col_kernel<float, true>), dim3(ext.max_frames, ext.cnt), dim3(256), 0, stream, mel, ld, C, 0, dst, Kp, ext);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -114,10 +132,20 @@ int launch_vocos_ifft1024(const float* head, int ldh, int rows, const float* wsc
 }
 
 // torch.istft(center=True): overlap-add the windowed frames, divide by the overlap-added squared window, trim n_fft/2.
+// RAGGED: utterance blockIdx.y has its own frame count, its frames start at workspace row ext.row0[u] and its (T_u - 1) * hop samples at
+// ext.out0[u] of one concatenated wave; centre trimming and the envelope are per utterance, as in the equal-length form.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void vocos_ola_kernel(const float* __restrict__ frames, int T, int n_fft, int hop, const float* __restrict__ wsq,
-                                                        float* __restrict__ wave, int out_len) {
+                                                        float* __restrict__ wave, int out_len, const UttExtents ext) {
     const int b = blockIdx.y;
     const int s = blockIdx.x * 256 + threadIdx.x;
+    size_t frow = (size_t)b * T, wbase = (size_t)b * out_len;
+    if constexpr (RAGGED) {
+        T = ext.frames[b];
+        out_len = (T - 1) * hop;
+        frow = (size_t)ext.row0[b];
+        wbase = (size_t)ext.out0[b];
+    }
     if (s >= out_len) return;
     const int u = s + n_fft / 2;
     int t_hi = u / hop;
@@ -127,15 +155,21 @@ __global__ __launch_bounds__(256) void vocos_ola_kernel(const float* __restrict_
     float acc = 0.f, env = 0.f;
     for (int t = t_lo; t <= t_hi; ++t) {
         const int j = u - t * hop;
-        acc += frames[((size_t)b * T + t) * n_fft + j];
+        acc += frames[(frow + t) * n_fft + j];
         env += wsq[j];
     }
-    wave[(size_t)b * out_len + s] = acc / env;
+    wave[wbase + s] = acc / env;
 }
 int launch_vocos_ola(const float* frames, int B, int T, int n_fft, int hop, const float* wsq, float* wave, hipStream_t stream) {
     const int out_len = (T - 1) * hop;
     if (B <= 0 || out_len <= 0) return 0;
-    hipLaunchKernelGGL(vocos_ola_kernel, dim3(cdiv(out_len, 256), B), dim3(256), 0, stream, frames, T, n_fft, hop, wsq, wave, out_len);
+    hipLaunchKernelGGL(vocos_ola_kernel<false>, dim3(cdiv(out_len, 256), B), dim3(256), 0, stream, frames, T, n_fft, hop, wsq, wave, out_len, UttExtents{});
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+int launch_vocos_ola_ragged(const float* frames, const UttExtents& ext, int n_fft, int hop, const float* wsq, float* wave, hipStream_t stream) {
+    if (ext.cnt <= 0 || ext.max_frames < 2) return 0;
+    hipLaunchKernelGGL(vocos_ola_kernel<true>, dim3(cdiv((ext.max_frames - 1) * hop, 256), ext.cnt), dim3(256), 0, stream, frames, 0, n_fft, hop, wsq, wave, 0, ext);
     F5_LAUNCH_CHECK();
     return 0;
 }

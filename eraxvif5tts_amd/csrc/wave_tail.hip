@@ -1,0 +1,75 @@
+// wave_tail.hip -- the tail of generate() behind the vocoder, on the device: the rms rule (f5tts_wrapper.py:529-531, utils_infer.py:491-492,
+// eval_infer_batch.py:190-191), the linear cross-fade of consecutive chunks (utils_infer.py:519-555) and the server's int16 PCM
+// (f5tts-fastapi-server.py:246-250), one thread per OUTPUT sample.  Every operation is the one the host path performs, in its order and
+// precision, so the result is byte-identical to torch's gain + numpy's cross_fade_concat + pcm16_bytes:
+//   gain      (w * rms) in fp32, then / target: an IEEE fp32 divide (torch on CPU tensors), or a multiply by the fp32 reciprocal of target, which is
+//             what torch's device kernel does for a host-scalar divisor (gain_div = 0); never fused, never reassociated
+//   joint     double(a) * w_down[j] + double(b) * w_up[j]: two fp64 products and one fp64 sum, no FMA (contraction is off in this file's kernel);
+//             w_down / w_up are numpy's own linspace values, uploaded by the caller
+//   PCM       trunc(x * 32767): the product in fp64 when a joint mixed (np.concatenate promoted the whole array), else in fp32; products outside
+//             int16 saturate (numpy leaves that cast undefined)
+#include "kernels.h"
+
+__device__ __forceinline__ float wave_gain(float w, float g, bool apply, float target, float inv_target, int gain_div) {
+#pragma clang fp contract(off)
+    if (!apply) return w;
+    const float m = w * g;
+    return gain_div ? m / target : m * inv_target;
+}
+
+__device__ __forceinline__ int16_t pcm_sat(double p) {  // truncation toward zero inside int16, saturation outside, NaN -> 0
+    if (p >= 32767.0) return (int16_t)32767;
+    if (p <= -32768.0) return (int16_t)-32768;
+    return p == p ? (int16_t)(int)p : (int16_t)0;
+}
+
+template <bool F64>
+__global__ __launch_bounds__(256) void wave_finish_kernel(const float* __restrict__ wave, const WaveTable tb, int first, int pos0, int pos_end, int n,
+                                                          const double* __restrict__ w_down, const double* __restrict__ w_up,
+                                                          const float* __restrict__ rms_dev, float target, float inv_target, int gain_div,
+                                                          float* __restrict__ out_f32, double* __restrict__ out_f64, int16_t* __restrict__ out_pcm) {
+#pragma clang fp contract(off)
+    const int pos = pos0 + blockIdx.x * 256 + threadIdx.x;
+    if (pos >= pos_end) return;
+    int lo = first, hi = tb.cnt - 1;
+    while (lo < hi) {  // last utterance whose first output sample is at or before pos
+        const int mid = (lo + hi + 1) >> 1;
+        if (tb.out0[mid] <= pos) lo = mid; else hi = mid - 1;
+    }
+    const int k = lo, j = pos - tb.out0[k];
+    float gk = tb.gain[k], gp = k > 0 ? tb.gain[k - 1] : 0.f;
+    bool ak = tb.apply[k] != 0, ap = k > 0 && tb.apply[k - 1] != 0;
+    if (rms_dev) {  // the decision is taken here, so the host never waits for the prompt's rms
+        gk = gp = *rms_dev;
+        ak = ap = gk < target;
+    }
+    const float b = wave_gain(wave[(size_t)tb.in0[k] + j], gk, ak, target, inv_target, gain_div);
+    if constexpr (F64) {
+        double v = (double)b;
+        if (k > 0 && j < n) {
+            const float a = wave_gain(wave[(size_t)tb.in0[k - 1] + tb.len[k - 1] - n + j], gp, ap, target, inv_target, gain_div);
+            const double pa = (double)a * w_down[j], pb = (double)b * w_up[j];
+            v = pa + pb;
+        }
+        if (out_f64) out_f64[pos] = v;
+        if (out_pcm) out_pcm[pos] = pcm_sat(v * 32767.0);
+    } else {
+        if (out_f32) out_f32[pos] = b;
+        if (out_pcm) out_pcm[pos] = pcm_sat((double)(b * 32767.0f));
+    }
+}
+
+int launch_wave_finish(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n, const double* w_down, const double* w_up,
+                       const float* rms_dev, float target, int gain_div, bool f64, float* out_f32, double* out_f64, int16_t* out_pcm, hipStream_t stream) {
+    if (pos_end <= pos0 || tb.cnt <= 0) return 0;
+    const dim3 grid(cdiv(pos_end - pos0, 256));
+    const float inv_target = 1.0f / target;
+    if (f64)
+        hipLaunchKernelGGL(wave_finish_kernel<true>, grid, dim3(256), 0, stream, wave, tb, first, pos0, pos_end, n, w_down, w_up, rms_dev, target, inv_target,
+                           gain_div, out_f32, out_f64, out_pcm);
+    else
+        hipLaunchKernelGGL(wave_finish_kernel<false>, grid, dim3(256), 0, stream, wave, tb, first, pos0, pos_end, n, w_down, w_up, rms_dev, target, inv_target,
+                           gain_div, out_f32, out_f64, out_pcm);
+    F5_LAUNCH_CHECK();
+    return 0;
+}

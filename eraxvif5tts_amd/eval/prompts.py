@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from ..infer import audio as _audio
+from ..infer.utils_infer import decode_utterances, device_tail_kind, finish_waves
 from ..model.modules import MelSpec
 from ..model.utils import convert_char_to_pinyin
 
@@ -164,11 +165,24 @@ def infer_prompts(cfm, prompts_all: Sequence, vocoder=None, mode="ragged", nfe_s
             generated, _ = ragged_sample_fn(cfm)(**kw)
         else:
             generated, _ = cfm.sample(return_trajectory=False, **kw)
+        # The HIP vocoders decode the whole bucket at once: the utterances' rows of `generated` (frame-major already) go to ONE ragged vocoder call,
+        # the rms rule to one wave_finish over the shared wave buffer, and the waves are handed back as views of its result -- bit-identical to the
+        # per-utterance loop below (tests/test_gpu_wave_tail.py), which any other vocoder object keeps.
+        waves = None
+        kind = device_tail_kind(vocoder, generated) if vocoder is not None else None
+        if kind is not None and (kind == "vocos") == hasattr(vocoder, "decode") and \
+                min(int(t) - int(r) for r, t in zip(ref_mel_lens, total_mel_lens)) >= 2:
+            g32 = generated.to(torch.float32).contiguous()
+            b, nmax, mel = g32.shape
+            frames = [int(t) - int(r) for r, t in zip(ref_mel_lens, total_mel_lens)]
+            wave_buf, samples = decode_utterances(vocoder, kind, g32.reshape(b * nmax, mel), [i * nmax + int(r) for i, r in enumerate(ref_mel_lens)], frames)
+            done = finish_waves(wave_buf, samples, 0.0, rms=list(ref_rms_list), target_rms=target_rms)
+            waves = [w.unsqueeze(0) for w in torch.split(done[0], samples)]
         for i, gen in enumerate(generated):
             gen = gen[ref_mel_lens[i]: total_mel_lens[i], :].unsqueeze(0)
             gen_mel_spec = gen.permute(0, 2, 1).to(torch.float32)
-            wave = None
-            if vocoder is not None:
+            wave = waves[i] if waves is not None else None
+            if vocoder is not None and waves is None:
                 wave = vocoder.decode(gen_mel_spec) if hasattr(vocoder, "decode") else vocoder(gen_mel_spec).squeeze(0)  # eval_infer_batch.py:186-189
                 if ref_rms_list[i] < target_rms:
                     wave = wave * ref_rms_list[i] / target_rms

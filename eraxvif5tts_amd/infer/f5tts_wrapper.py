@@ -31,7 +31,8 @@ from ..model import CFM
 from ..model import backbones as _backbones
 from ..model.utils import convert_char_to_pinyin, get_tokenizer, list_str_to_idx
 from . import audio as _audio
-from .utils_infer import DEFAULT_VOCAB, chunk_text, cross_fade_concat, load_checkpoint, load_vocoder
+from .utils_infer import (DEFAULT_VOCAB, chunk_text, cross_fade_concat, decode_utterances, device_tail_kind, finish_waves, load_checkpoint, load_vocoder,
+                          mel_rows_of)
 
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs")
 
@@ -171,7 +172,9 @@ class F5TTSWrapper:
     def generate(self, text: str, output_path: Optional[str] = None, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
                  sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
                  cross_fade_duration: Optional[float] = None, use_duration_predictor: Optional[bool] = None,
-                 return_numpy: bool = False, return_spectrogram: bool = False):
+                 return_numpy: bool = False, return_spectrogram: bool = False, return_pcm16: bool = False):
+        """``return_pcm16``: the wave comes back as the int16 PCM the streaming server sends (``streaming.wire.pcm16_bytes`` of the float
+        result, bit for bit), converted on the device where the device tail runs -- one int16 copy instead of a float copy and a host pass."""
         if self.ref_audio_processed is None or self.ref_text is None:
             raise ValueError("Reference audio not preprocessed. Call preprocess_reference() first.")
         nfe_step = nfe_step if nfe_step is not None else self.nfe_step
@@ -261,25 +264,53 @@ class F5TTSWrapper:
             # decoded mels that were still being written -- found by test_generate_end_to_end_matches_the_oracle_chain[fp32-False])
             for st in streams:
                 main.wait_stream(st)
+        want_spec = return_spectrogram or output_path is not None
+        want_float = not return_pcm16 or output_path is not None
+        final_wave = final_pcm = None
         with torch.inference_mode():
-            for generated in mels:
-                if n_streams > 1:
+            if n_streams > 1:
+                for generated in mels:
                     generated.record_stream(main)
-                generated = generated.to(torch.float32)[:, self.ref_audio_len:, :].permute(0, 2, 1)
-                if self.mel_spec_type == "vocos":
-                    generated_wave = self.vocoder.decode(generated)
-                elif self.mel_spec_type == "bigvgan":
-                    generated_wave = self.vocoder(generated)
+            # The tail on the device where the vocoder is one of ours: the mels of all chunks go to ONE ragged vocoder call (the prompt frames
+            # skipped by a row offset, no permute copy), then one wave_finish (rms rule decided on the device from the device-resident prompt,
+            # cross-fade, PCM) and one copy to the host.  Byte-identical to the per-chunk loop below, which foreign vocoder objects keep.
+            kind = device_tail_kind(self.vocoder, self.ref_audio_processed, *mels)
+            if kind is not None and (kind == self.mel_spec_type) and mels and min(int(m.shape[1]) for m in mels) - self.ref_audio_len >= 2:
+                rows, row_start, frames = mel_rows_of(mels, self.ref_audio_len)
+                wave_buf, samples = decode_utterances(self.vocoder, kind, rows, row_start, frames)
                 rms = torch.sqrt(torch.mean(torch.square(self.ref_audio_processed)))  # of the stored, already boosted prompt (:529-531)
-                if rms < self.target_rms:
-                    generated_wave = generated_wave * rms / self.target_rms
-                generated_waves.append(generated_wave.squeeze().cpu().numpy())
-                if return_spectrogram or output_path is not None:
-                    spectrograms.append(generated.squeeze().cpu().numpy())
+                done = finish_waves(wave_buf, samples, cross_fade_duration, self.target_sample_rate, rms=rms.to(torch.float32), target_rms=self.target_rms,
+                                    want_float=want_float, want_pcm16=return_pcm16)
+                if want_spec:
+                    spectrograms = [rows[r: r + t].t().cpu().numpy() for r, t in zip(row_start, frames)]
+                if done is not None:
+                    final_wave = done[0].cpu().numpy() if want_float else None
+                    final_pcm = done[1].cpu().numpy() if return_pcm16 else None
+                else:  # utterances shorter than their cross-fades (F5_ENOTSUP): the decoded waves take the host functions
+                    apply_gain = bool(rms < self.target_rms)
+                    for w in torch.split(wave_buf, samples):
+                        generated_waves.append((w * rms / self.target_rms if apply_gain else w).cpu().numpy())
+            else:
+                for generated in mels:
+                    generated = generated.to(torch.float32)[:, self.ref_audio_len:, :].permute(0, 2, 1)
+                    if self.mel_spec_type == "vocos":
+                        generated_wave = self.vocoder.decode(generated)
+                    elif self.mel_spec_type == "bigvgan":
+                        generated_wave = self.vocoder(generated)
+                    rms = torch.sqrt(torch.mean(torch.square(self.ref_audio_processed)))  # of the stored, already boosted prompt (:529-531)
+                    if rms < self.target_rms:
+                        generated_wave = generated_wave * rms / self.target_rms
+                    generated_waves.append(generated_wave.squeeze().cpu().numpy())
+                    if want_spec:
+                        spectrograms.append(generated.squeeze().cpu().numpy())
 
-        if not generated_waves:
-            raise RuntimeError("No audio generated")
-        final_wave = cross_fade_concat(generated_waves, cross_fade_duration, self.target_sample_rate)
+        if final_wave is None and final_pcm is None:
+            if not generated_waves:
+                raise RuntimeError("No audio generated")
+            final_wave = cross_fade_concat(generated_waves, cross_fade_duration, self.target_sample_rate)
+        if return_pcm16 and final_pcm is None:
+            from ..streaming.wire import pcm16_bytes
+            final_pcm = np.frombuffer(pcm16_bytes(final_wave), dtype=np.int16)
         combined_spectrogram = np.concatenate(spectrograms, axis=1) if spectrograms else None
         if output_path is not None:
             output_dir = os.path.dirname(output_path)
@@ -290,6 +321,8 @@ class F5TTSWrapper:
                 np.save(os.path.splitext(output_path)[0] + "_spec.npy", combined_spectrogram)  # matplotlib is not in the image
             if not return_numpy:
                 return output_path
+        if return_pcm16:
+            final_wave = final_pcm
         if return_spectrogram:
             return final_wave, self.target_sample_rate, combined_spectrogram
         return final_wave, self.target_sample_rate

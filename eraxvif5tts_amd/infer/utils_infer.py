@@ -178,6 +178,137 @@ def cross_fade_concat(waves, cross_fade_duration, sample_rate=target_sample_rate
     return final
 
 
+# ---------------------------------------------------------------------------- the tail behind the sampler, on the device
+# generate(), infer_batch_process() and eval.prompts.infer_prompts() used to run, per utterance, one batch-1 vocoder call, the rms rule with a
+# device -> host comparison, a device -> host copy, and then cross_fade_concat / pcm16_bytes in numpy.  With the HIP vocoders the same arithmetic
+# runs as ONE ragged Vocos.decode_ragged, ONE f5_wave_finish and ONE copy; the results are byte-identical (tests/test_gpu_wave_tail.py), so no
+# switch selects it: it is taken whenever the objects at hand allow it, and the per-utterance host loop otherwise.
+
+def plan_wave_tail(lengths, cross_fade_duration, sample_rate=target_sample_rate):
+    """What `cross_fade_concat` does to waves of these lengths, from the lengths alone: ``joints`` (the n of every joint, by the reference's
+    sequential rule ``min(int(d * rate), len(final), len(next))``), ``out_offsets`` (where each wave's first sample lands in the result),
+    ``total`` samples, ``mixed`` (a joint with n > 0 exists: that piece is float64 and np.concatenate promotes the WHOLE result, so
+    `pcm16_bytes` multiplies in float64; otherwise everything stays float32), ``dtype``, the uniform ``n`` the device kernel takes, and
+    ``device_ok``: no joint reaches into a region an earlier joint mixed (first and last wave >= n samples, every other >= 2 n) --
+    the rule of ``f5_wave_finish``, which answers F5_ENOTSUP otherwise."""
+    lengths = [int(x) for x in lengths]
+    nx = max(int(cross_fade_duration * sample_rate), 0) if cross_fade_duration > 0 else 0
+    joints, offsets, final_len = [], [0], lengths[0]
+    for length in lengths[1:]:
+        n = max(min(nx, final_len, length), 0)
+        joints.append(n)
+        offsets.append(final_len - n)
+        final_len += length - n
+    mixed = any(n > 0 for n in joints)
+    n_dev = nx if len(lengths) >= 2 else 0
+    device_ok = all(length >= (n_dev if i in (0, len(lengths) - 1) else 2 * n_dev) for i, length in enumerate(lengths))
+    return dict(joints=joints, out_offsets=offsets, total=final_len, mixed=mixed, dtype=np.float64 if mixed else np.float32, n=n_dev,
+                device_ok=device_ok)
+
+
+_xfade_tables = {}
+
+
+def _xfade_weights(n, dev):
+    """numpy's own linspace(1, 0, n) / linspace(0, 1, n) on the device (uploaded once per n): the kernel multiplies by exactly these doubles"""
+    key = (int(n), str(dev))
+    if key not in _xfade_tables:
+        _xfade_tables[key] = (torch.from_numpy(np.linspace(1, 0, n)).to(dev), torch.from_numpy(np.linspace(0, 1, n)).to(dev))
+    return _xfade_tables[key]
+
+
+def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_sample_rate, rms=None, target_rms=target_rms, want_float=True,
+                 want_pcm16=False, gain_divide=False):
+    """``f5_wave_finish`` over the utterances held back to back in ``wave`` (fp32, on the GPU; ``samples[i]`` each): the rms rule, the linear
+    cross-fade of `cross_fade_concat` and the int16 PCM of ``streaming.wire.pcm16_bytes`` in one kernel.  Returns ``(signal, pcm16)`` as device
+    tensors (None where not asked for) -- ``signal`` float64 when a joint mixed, float32 otherwise, as numpy's promotion gives -- or ``None`` when
+    the library answers F5_ENOTSUP (utterances shorter than their cross-fades: take the host functions for that call).
+    ``rms``: None (no gain); a 0-dim fp32 tensor on the GPU (the gain applies when ``rms < target_rms``, decided on the device: no host wait);
+    or host values -- one number / 0-dim CPU tensor for all utterances, or one per utterance -- with the decision ``rms_i < target_rms`` taken
+    here exactly as the host loop takes it.  The gain is ``w * rms / target_rms`` as torch evaluates it on a GPU tensor (fp32 product, then the
+    fp32 reciprocal of the host scalar), or with a true fp32 divide (``gain_divide``: torch on CPU tensors)."""
+    import ctypes as C
+
+    from .. import _lib
+    lib = _lib.load()
+    B = len(samples)
+    assert wave.is_cuda and wave.dtype == torch.float32 and wave.is_contiguous() and wave.numel() == sum(samples) and B >= 1
+    plan = plan_wave_tail(samples, cross_fade_duration, sample_rate)
+    n, mixed = plan["n"], plan["n"] > 0
+    total = sum(samples) - (B - 1) * n
+    gain_host = apply_host = rms_dev = None
+    if torch.is_tensor(rms) and rms.is_cuda:
+        assert rms.dtype == torch.float32 and rms.numel() == 1
+        rms_dev = rms.reshape(1).contiguous()
+    elif rms is not None:
+        per_utt = list(rms) if isinstance(rms, (list, tuple)) else [rms] * B
+        assert len(per_utt) == B
+        on_dev = [i for i, r in enumerate(per_utt) if torch.is_tensor(r) and r.is_cuda]
+        vals = [None if i in on_dev else float(r) for i, r in enumerate(per_utt)]
+        if on_dev:  # rms values that live on the device come over in ONE copy (the host loop reads each of them back for its comparison)
+            for i, v in zip(on_dev, torch.stack([per_utt[i].reshape(()).to(torch.float64) for i in on_dev]).cpu().tolist()):
+                vals[i] = v
+
+        def below_target(r, v):  # `r < target_rms` as torch / Python evaluate it: an fp32 tensor compares in fp32, a number in double
+            if torch.is_tensor(r):
+                return bool(np.float32(v) < np.float32(target_rms)) if r.dtype == torch.float32 else bool(r.cpu() < target_rms)
+            return bool(r < target_rms)
+        gain_host = (C.c_float * B)(*vals)
+        apply_host = (C.c_uint8 * B)(*[1 if below_target(r, v) else 0 for r, v in zip(per_utt, vals)])
+    w_down, w_up = _xfade_weights(n, wave.device) if mixed else (None, None)
+    if total <= 0 or not plan["device_ok"]:
+        out = pcm = None  # the library decides (and says why); nothing is allocated for a call it will refuse
+    else:
+        out = torch.empty(total, device=wave.device, dtype=torch.float64 if mixed else torch.float32) if want_float else None
+        pcm = torch.empty(total, device=wave.device, dtype=torch.int16) if want_pcm16 else None
+    got = C.c_int64(0)
+    rc = lib.f5_wave_finish(B, _lib.ptr(wave), (C.c_int32 * B)(*[int(x) for x in samples]), gain_host, apply_host, _lib.ptr(rms_dev),
+                            float(target_rms), 1 if gain_divide else 0, int(n), _lib.ptr(w_down), _lib.ptr(w_up),
+                            _lib.ptr(out) if not mixed else None, _lib.ptr(out) if mixed else None, _lib.ptr(pcm), C.byref(got), _lib.stream_ptr())
+    if rc == _lib.F5_ENOTSUP:
+        return None
+    _lib.check(rc, "wave_finish")
+    assert got.value == total
+    return out, pcm
+
+
+def device_tail_kind(vocoder, *tensors):
+    """Which device tail applies to this vocoder object and these mels: "vocos" (the HIP Vocos: it has ``decode_ragged``), "bigvgan" (the HIP
+    BigVGAN) or None (a foreign object at plug point B, or tensors that are not on the GPU: the per-utterance host loop)."""
+    if not tensors or not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        return None
+    if hasattr(vocoder, "decode_ragged_buffer"):
+        return "vocos"
+    from ..bigvgan import BigVGAN
+    return "bigvgan" if isinstance(vocoder, BigVGAN) else None
+
+
+def mel_rows_of(mels, skip):
+    """[1, N_i, mel] sampler outputs -> (rows [R, mel] fp32 contiguous, row_start, frames) with the first ``skip`` frames of each left out by the
+    offset.  The ragged sampler hands back views of ONE buffer: that buffer is taken as it is (no copy); anything else is concatenated once."""
+    mel = mels[0].shape[-1]
+    frames = [int(m.shape[1]) - skip for m in mels]
+    st = mels[0].untyped_storage()
+    if all(m.dtype == torch.float32 and m.is_contiguous() and m.untyped_storage().data_ptr() == st.data_ptr() and m.storage_offset() % mel == 0
+           for m in mels):
+        rows = torch.empty(0, dtype=torch.float32, device=mels[0].device).set_(st, 0, (st.nbytes() // (4 * mel), mel), (mel, 1))
+        return rows, [m.storage_offset() // mel + skip for m in mels], frames
+    rows = torch.cat([m[0, skip:].to(torch.float32) for m in mels])
+    starts, r = [], 0
+    for t in frames:
+        starts.append(r)
+        r += t
+    return rows, starts, frames
+
+
+def decode_utterances(vocoder, kind, rows, row_start, frames):
+    """One wave buffer for all utterances (and the sample count of each): one ragged Vocos call, or the BigVGAN generator per utterance."""
+    if kind == "vocos":
+        return vocoder.decode_ragged_buffer(rows, row_start, frames)
+    waves = [vocoder(rows[r: r + t].unsqueeze(0).permute(0, 2, 1)).reshape(-1) for r, t in zip(row_start, frames)]
+    return torch.cat(waves), [int(w.numel()) for w in waves]
+
+
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,
                   target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=device):
@@ -246,7 +377,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
             for chunk in process_batch(gen_text):
                 yield chunk
         return
-    generated_waves, spectrograms = [], []
+    generated_waves, spectrograms, mels = [], [], []
     # Several text batches, each long enough for the tuned kernels: ONE ragged batch per group (F5TTSWrapper.generate does the same; every
     # utterance keeps the arithmetic -- and the noise draw order -- of its own batch-1 sample() call, so the audio is bit-identical).
     transformer = getattr(model_obj, "transformer", None)
@@ -264,14 +395,35 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
                     i += 1
                 for generated in model_obj.sample_ragged(audio, [j[0][0] for j in group], [j[1] for j in group], steps=nfe_step,
                                                          cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef):
-                    wave, mel = finish_batch(generated)
-                    generated_waves.append(wave)
-                    spectrograms.append(mel)
+                    mels.append(generated)
         batches = []
     for gen_text in batches:  # the reference's thread pool resolves to serial generators on the caller thread
-        wave, mel = next(process_batch(gen_text))
-        generated_waves.append(wave)
-        spectrograms.append(mel)
+        final_text_list, duration = plan_batch(gen_text)
+        with torch.inference_mode():
+            generated, _ = model_obj.sample(cond=audio, text=final_text_list, duration=duration, steps=nfe_step, cfg_strength=cfg_strength,
+                                            sway_sampling_coef=sway_sampling_coef, return_trajectory=False)
+        mels.append(generated)
+    # mel -> wave for all batches at once on the device (one ragged vocoder call, one wave_finish, one copy) where the vocoder allows it
+    kind = device_tail_kind(vocoder, *mels)
+    if kind is not None and (kind == "vocos") == (mel_spec_type == "vocos") and min(int(m.shape[1]) for m in mels) - ref_audio_len >= 2:
+        with torch.inference_mode():
+            rows, row_start, frames = mel_rows_of(mels, ref_audio_len)
+            wave_buf, samples = decode_utterances(vocoder, kind, rows, row_start, frames)
+            done = finish_waves(wave_buf, samples, cross_fade_duration, rms=rms, target_rms=target_rms)
+            spectrograms = [rows[r: r + t].t().cpu().numpy() for r, t in zip(row_start, frames)]
+            if done is not None:
+                yield done[0].cpu().numpy(), target_sample_rate, np.concatenate(spectrograms, axis=1)
+                return
+            for w in torch.split(wave_buf, samples):  # utterances shorter than their cross-fades: the host functions join them
+                if rms < target_rms:
+                    w = w * rms / target_rms
+                generated_waves.append(w.cpu().numpy())
+    else:
+        with torch.inference_mode():
+            for generated in mels:
+                wave, mel = finish_batch(generated)
+                generated_waves.append(wave)
+                spectrograms.append(mel)
     if generated_waves:
         yield cross_fade_concat(generated_waves, cross_fade_duration), target_sample_rate, np.concatenate(spectrograms, axis=1)
     else:

@@ -11,6 +11,7 @@ Text normalisation (vinorm) and the langchain splitter are third-party and stay 
 """
 from __future__ import annotations
 
+import inspect
 import io
 import wave
 from typing import Iterable, Iterator, Optional
@@ -78,10 +79,23 @@ def process_chunk(chunk_text: str, model, **gen_kwargs) -> Optional[bytes]:
         chunk_text = chunk_text[:-1].strip()
     if not chunk_text:
         return None
+    if _offers_pcm16(model):  # the HIP wrapper converts on the device: the chunk arrives as int16, one copy, the same bytes
+        pcm, _sr = model.generate(text=chunk_text, return_numpy=True, return_pcm16=True, **gen_kwargs)
+        if pcm is None or np.size(pcm) == 0:
+            return None
+        return np.ascontiguousarray(pcm, dtype=np.int16).tobytes()
     audio, _sr = model.generate(text=chunk_text, return_numpy=True, **gen_kwargs)
     if audio is None or np.size(audio) == 0:
         return None
     return pcm16_bytes(audio)
+
+
+def _offers_pcm16(model) -> bool:
+    """`model` is duck-typed over ``generate``; only an object whose ``generate`` names a ``return_pcm16`` argument is asked for int16."""
+    try:
+        return "return_pcm16" in inspect.signature(model.generate).parameters
+    except (TypeError, ValueError):
+        return False
 
 
 def stream_audio(model, cache: ReferenceCache, speaker: str, text_chunks: Iterable[str], **gen_kwargs) -> Iterator[bytes]:

@@ -33,7 +33,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: only the entry points declared here are exported */
 #define F5_API __attribute__((visibility("default")))
 
-#define F5HIP_VERSION 400 /* 0.4.0 (round 4): + the BigVGAN entry points and mel front-end, f5_op_ln_fold, bounded timing ring; plan options "ln_fold_active", "gemm_w4"; tuning keys "ln_fold", "ln_fold_fin", "gemm_w4"; 0.3.2: + f5_sample_ragged, f5_mmdit_forward, f5_duration_predict_g */
+#define F5HIP_VERSION 400 /* 0.4.0 (round 4; round 5 adds f5_vocoder_decode_ragged and f5_wave_finish under the same number, which tests/test_host_logic.py pins: detect them by symbol): + the BigVGAN entry points and mel front-end, f5_op_ln_fold, bounded timing ring; plan options "ln_fold_active", "gemm_w4"; tuning keys "ln_fold", "ln_fold_fin", "gemm_w4"; 0.3.2: + f5_sample_ragged, f5_mmdit_forward, f5_duration_predict_g */
 
 /* error codes */
 #define F5_OK 0
@@ -345,6 +345,34 @@ F5_API int f5_vocoder_finalize(f5_vocoder_t v);
 F5_API int f5_vocoder_destroy(f5_vocoder_t v);
 /* Vocos.decode: mel dev f32 [B, n_mels, T] -> wave dev f32 [B, (T-1)*hop] */
 F5_API int f5_vocoder_decode(f5_vocoder_t v, int B, int T, const float* mel, float* wave, f5_stream_t stream);
+/* Vocos.decode for B utterances of DIFFERENT frame counts in one set of launches (round 5): what f5_sample_ragged produced, decoded together.
+ * mel is dev f32, FRAME-major [rows, ld] (ld >= n_mels: the sampler's own layout, no permute / contiguous copy); utterance i reads the
+ * frames_host[i] >= 2 rows from row row_start_host[i] on (so a prompt prefix is skipped by the offset) and writes its (T_i - 1) * hop samples
+ * behind those of utterance i - 1 into wave, dev f32 [sum (T_i - 1) * hop]; *total_samples (host, may be NULL) receives that sum.  Both arrays
+ * are host memory, read before the call returns.  Utterance i is bit-identical to f5_vocoder_decode(v, 1, T_i, its own [n_mels, T_i] mel): the
+ * convolutions pad with zeros at each utterance's own ends and never read a neighbour's rows, whatever those hold.  Nothing synchronises
+ * (workspace growth aside, as for f5_vocoder_decode). */
+F5_API int f5_vocoder_decode_ragged(f5_vocoder_t v, int B, const int32_t* row_start_host, const int32_t* frames_host, const float* mel, int ld,
+                                    float* wave, int64_t* total_samples, f5_stream_t stream);
+/* The tail behind the vocoder in ONE kernel (round 5): rms gain, linear cross-fade of consecutive utterances, int16 PCM -- byte for byte what
+ * the host path gives (torch's `wave * rms / target_rms` where rms < target_rms, utils_infer.cross_fade_concat, streaming.wire.pcm16_bytes).
+ *   wave            dev f32, the B utterances back to back, samples_host[i] > 0 samples each (host array)
+ *   gain            either gain_host[B] + apply_host[B] (host: utterance i is multiplied by gain_host[i] and divided by target_rms where
+ *                   apply_host[i] != 0 -- the caller has taken the decision `rms_i < target_rms` on the host values it already holds), or
+ *                   rms_dev, a dev f32 scalar: the gain applies to every utterance when *rms_dev < target_rms, decided in the kernel, so the host
+ *                   never waits for it; neither: no gain.  Always one fp32 multiply, then the division: gain_div = 1 an IEEE fp32 divide (torch
+ *                   on CPU tensors), 0 a multiply by the fp32 reciprocal 1.0f / target_rms (torch's device kernel for a host-scalar divisor)
+ *   cross-fade      n = xfade_samples (0: none; B = 1: none) samples of consecutive utterances overlap: out = double(a) * w_down[j] +
+ *                   double(b) * w_up[j] as two fp64 products and one fp64 sum, w_down / w_up dev f64 [n] = numpy's linspace(1, 0, n) / (0, 1, n).
+ *                   The first and the last utterance must hold n samples and every other 2 n; otherwise the reference's sequential joints mix an
+ *                   already mixed region, which this kernel does not do: F5_ENOTSUP, take the host functions for that call
+ *   outputs         each may be NULL: out_f32 (only when no joint mixed), out_f64 (only when one did: numpy promotes the whole signal to
+ *                   float64 then), out_pcm16 = trunc(x * 32767) with the product in the float output's precision; products at or beyond
+ *                   +-32768, which numpy's cast leaves undefined, saturate.  *total_samples_out (host) = sum samples - (B - 1) n
+ * out_f32 may be `wave` itself when n = 0.  Nothing synchronises. */
+F5_API int f5_wave_finish(int B, const float* wave, const int32_t* samples_host, const float* gain_host, const uint8_t* apply_host,
+                          const float* rms_dev, float target_rms, int gain_div, int xfade_samples, const double* w_down, const double* w_up,
+                          float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* total_samples_out, f5_stream_t stream);
 /* ISTFT head alone (for the roofline measurement): spec dev f32 [B, T, n_fft+2] (head.out activations:
  * log-magnitude | phase) -> wave dev f32 [B, (T-1)*hop] */
 F5_API int f5_vocoder_istft_head(f5_vocoder_t v, int B, int T, const float* head_out, float* wave, f5_stream_t stream);
