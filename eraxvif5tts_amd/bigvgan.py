@@ -173,3 +173,39 @@ class BigVGAN(nn.Module):
         out = torch.empty(b, 1, T * up, device=mel.device, dtype=torch.float32)
         _lib.check(lib.f5_bigvgan_forward(self.native(), b, T, _lib.ptr(mel), _lib.ptr(out), _lib.stream_ptr()), "bigvgan_forward")
         return out
+
+    def _total_up(self):
+        up = 1
+        for u in self.h["upsample_rates"]:
+            up *= u
+        return up
+
+    @torch.no_grad()
+    def decode_ragged_buffer(self, mel_rows: torch.Tensor, row_start, frames):
+        """Utterances of different frame counts in ONE set of launches (``f5_bigvgan_decode_ragged``).  ``mel_rows`` is frame-major
+        ``[rows, ld]`` fp32 on the GPU -- what the sampler writes, no permute / contiguous copy; utterance i is the ``frames[i]`` rows from
+        row ``row_start[i]`` on (a prompt prefix is skipped through the offset).  Returns ``(wave, samples)``: one fp32 buffer holding the
+        utterances back to back and the ``T_i * prod(upsample_rates)`` sample count of each -- the form ``utils_infer.finish_waves`` takes.
+        Every utterance is bit-identical to ``forward`` of its own ``[1, num_mels, T_i]`` mel."""
+        lib = _lib.load()
+        assert mel_rows.is_cuda and mel_rows.dtype == torch.float32 and mel_rows.ndim == 2 and mel_rows.is_contiguous(), \
+            "decode_ragged takes contiguous fp32 mel rows [rows, ld] on the GPU"
+        rows, ld = mel_rows.shape
+        B = len(frames)
+        assert B >= 1 and len(row_start) == B and ld >= self.h["num_mels"]
+        row_start, frames = [int(r) for r in row_start], [int(t) for t in frames]
+        for r, t in zip(row_start, frames):
+            assert r >= 0 and t >= 1 and r + t <= rows, f"utterance rows {r} .. {r + t} outside the {rows} mel rows (need T >= 1)"
+        up = self._total_up()
+        samples = [t * up for t in frames]
+        wave = torch.empty(sum(samples), device=mel_rows.device, dtype=torch.float32)
+        total = C.c_int64(0)
+        _lib.check(lib.f5_bigvgan_decode_ragged(self.native(), B, (C.c_int32 * B)(*row_start), (C.c_int32 * B)(*frames), _lib.ptr(mel_rows), ld,
+                                                _lib.ptr(wave), C.byref(total), _lib.stream_ptr()), "bigvgan_decode_ragged")
+        assert total.value == wave.numel()
+        return wave, samples
+
+    def decode_ragged(self, mel_rows: torch.Tensor, row_start, frames):
+        """``decode_ragged_buffer`` as a list of ``[1, 1, T_i * prod(upsample_rates)]`` views of the one wave buffer."""
+        wave, samples = self.decode_ragged_buffer(mel_rows, row_start, frames)
+        return [w.reshape(1, 1, -1) for w in torch.split(wave, samples)]

@@ -14,9 +14,20 @@
 // MI355X form: activations are TIME-major [T, C] fp32 (rows = time: every Conv1d is an im2col + GEMM on the fp32-input MFMA tile kernel, exact fp32
 // products; the transposed convolution is a polyphase GEMM: k = R u, so every output sample takes R input frames, one GEMM of N = u x C_out);
 // the anti-aliased activation is ONE kernel (a 32-step x 32/64-channel tile staged in LDS: up-sampling, snake and down-sampling never touch HBM);
-// the residual add of a block's second convolution rides in the GEMM epilogue (EPI_RESID).  One utterance at a time (the wrapper decodes per chunk).
+// the residual add of a block's second convolution rides in the GEMM epilogue (EPI_RESID).
+//
+// RAGGED (f5_bigvgan_decode_ragged): the utterances of a call sit back to back in the workspace and go through ONE set of launches.  At a stage
+// with cumulative up-sampling factor U, utterance u owns rows U * off[u] .. U * (off[u] + T_u).  The GEMMs, the residual copies, the mean over the
+// AMP blocks and the final clamp / tanh are row-local: they run once over all rows, with the K of a batch-1 call, so a row's arithmetic does not
+// depend on how many rows share the launch.  The four kernel families that look across rows (im2col, the transposed convolution's gather and
+// scatter, the anti-aliased snake) take the extents table BY VALUE (UttExtents, kernels.h: at most 64 utterances per launch) and stop at the
+// utterance's own first and last row, so every utterance gets the bits of its own f5_bigvgan_forward(v, 1, T_u, ...) whatever its neighbours
+// hold.  The polyphase GEMM of the transposed convolution needs T_u + 1 gather rows per utterance: there utterance u starts at row U * off[u] + u.
+// f5_bigvgan_forward runs the same body without a table, one utterance at a time as before.
+#include <climits>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "gemm.h"
 #include "kernels.h"
@@ -44,7 +55,7 @@ struct f5_bigvgan_s {
     SlotMap slots;
     bool finalized = false;
     DevArena arena, work;
-    size_t work_T = 0;
+    size_t work_T = 0, work_B = 0;  // the workspace holds work_T frames in work_B utterances (one more gather row per utterance)
     BvConv conv_pre, conv_post;
     std::vector<BvUp> ups;
     std::vector<BvBlock> blocks;
@@ -55,10 +66,36 @@ struct f5_bigvgan_s {
 };
 
 // ----------------------------------------------------------------------------- kernels
-// col[t][tap * C + c] = x[t + (tap - (k - 1) / 2) * dil][c] (0 outside [0, T)); columns k * C .. Kp - 1 are zero.  chan_major: x is [C][T] (the mel input)
+// The kernels that look across rows exist in two forms of one body.  EXT = BvNoExt: one utterance of T rows.  EXT = UttExtents (ragged): blockIdx.y
+// is the utterance, which owns ext.frames[u] * up rows from row ext.row0[u] * up on (up = the stage's cumulative
+// up-sampling factor, so one table serves every stage); blockIdx.x is clipped at its length.  The table is looked up with the block index only
+// (uniform: scalar loads from the kernel arguments, no scratch).
+struct BvNoExt {
+    int unused;
+};
+template <typename EXT> constexpr bool bv_ragged = std::is_same<EXT, UttExtents>::value;
+
+// col[t][tap * C + c] = x[t + (tap - (k - 1) / 2) * dil][c] (0 outside [0, T)); columns k * C .. Kp - 1 are zero.  chan_major: x is [C][T] (the mel input
+// of f5_bigvgan_forward).  Ragged: T is the utterance's own row count, so a tap outside it contributes 0 and never reads a neighbour's row; with
+// src_ld > 0 (conv_pre) x is the caller's frame-major mel [*, src_ld], read from row ext.src0[u].
+template <typename EXT>
 __global__ __launch_bounds__(256) void bv_im2col_kernel(const float* __restrict__ x, int T, int C, int k, int dil, int Kp, int chan_major,
-                                                        float* __restrict__ col, size_t total) {
+                                                        float* __restrict__ col, size_t total, int up, int src_ld, const EXT ext) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    int ldx = C;
+    if constexpr (bv_ragged<EXT>) {
+        const int u = blockIdx.y;
+        T = ext.frames[u] * up;
+        total = (size_t)T * Kp;
+        const size_t r0 = (size_t)ext.row0[u] * up;
+        col += r0 * Kp;
+        if (src_ld > 0) {
+            x += (size_t)ext.src0[u] * src_ld;
+            ldx = src_ld;
+        } else {
+            x += r0 * C;
+        }
+    }
     if (i >= total) return;
     const int q = (int)(i % Kp);
     const int t = (int)(i / Kp);
@@ -66,13 +103,24 @@ __global__ __launch_bounds__(256) void bv_im2col_kernel(const float* __restrict_
     if (q < k * C) {
         const int tap = q / C, c = q - tap * C;
         const int s = t + (tap - (k - 1) / 2) * dil;
-        if (s >= 0 && s < T) v = chan_major ? x[(size_t)c * T + s] : x[(size_t)s * C + c];
+        if (s >= 0 && s < T) v = chan_major ? x[(size_t)c * T + s] : x[(size_t)s * ldx + c];
     }
     col[i] = v;
 }
-// transposed convolution, gather side: col[t0][m * C + c] = x[t0 - m][c] for t0 in [0, T], m in [0, R)
-__global__ __launch_bounds__(256) void bv_up_gather_kernel(const float* __restrict__ x, int T, int C, int R, int Kp, float* __restrict__ col, size_t total) {
+// transposed convolution, gather side: col[t0][m * C + c] = x[t0 - m][c] for t0 in [0, T], m in [0, R).  Ragged: utterance ubase + u of the launch
+// set has its T + 1 gather rows from row ext.row0[u] * up + ubase + u on.
+template <typename EXT>
+__global__ __launch_bounds__(256) void bv_up_gather_kernel(const float* __restrict__ x, int T, int C, int R, int Kp, float* __restrict__ col, size_t total,
+                                                           int up, int ubase, const EXT ext) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if constexpr (bv_ragged<EXT>) {
+        const int u = blockIdx.y;
+        T = ext.frames[u] * up;
+        total = (size_t)(T + 1) * Kp;
+        const size_t r0 = (size_t)ext.row0[u] * up;
+        x += r0 * C;
+        col += (r0 + ubase + u) * Kp;
+    }
     if (i >= total) return;
     const int q = (int)(i % Kp);
     const int t0 = (int)(i / Kp);
@@ -84,10 +132,20 @@ __global__ __launch_bounds__(256) void bv_up_gather_kernel(const float* __restri
     }
     col[i] = v;
 }
-// transposed convolution, scatter side: y[p][co] = tmp[t0][r * Cout + co] + bias[co] with q = p + pad, t0 = q / u, r = q % u, p in [0, T u)
+// transposed convolution, scatter side: y[p][co] = tmp[t0][r * Cout + co] + bias[co] with q = p + pad, t0 = q / u, r = q % u, p in [0, T u).  Ragged:
+// the utterance's tmp rows start where its gather rows do, its y rows at ext.row0[u] * up * u.
+template <typename EXT>
 __global__ __launch_bounds__(256) void bv_up_scatter_kernel(const float* __restrict__ tmp, int T, int Cout, int u, int pad, const float* __restrict__ bias,
-                                                            float* __restrict__ y, size_t total) {
+                                                            float* __restrict__ y, size_t total, int up, int ubase, const EXT ext) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if constexpr (bv_ragged<EXT>) {
+        const int ut = blockIdx.y;
+        T = ext.frames[ut] * up;
+        total = (size_t)T * u * Cout;
+        const size_t r0 = (size_t)ext.row0[ut] * up;
+        tmp += (r0 + ubase + ut) * ((size_t)u * Cout);
+        y += r0 * u * Cout;
+    }
     if (i >= total) return;
     const int co = (int)(i % Cout);
     const int p = (int)(i / Cout);
@@ -100,14 +158,28 @@ struct BvFilters {
 // Anti-aliased SnakeBeta, one kernel.  Output step t needs the activated up-sampled signal z[n], n = 2t - 5 .. 2t + 6 (replicate-clamped to [0, 2T));
 // z[n] = snake(up[n]), up[n] = 2 sum_m xpad[m] f_up[n + 15 - 2m] over the six m with 0 <= n + 15 - 2m <= 11, xpad[m] = x[clamp(m - 5, 0, T - 1)].
 // Tile: TT = 32 output steps x CW channels; x rows t0 - 6 .. t0 + TT + 5 and z values 2 t0 - 5 .. 2 t0 + 2 TT + 4 live in LDS.
-template <int CW>
+// Ragged: grid (time tiles of the longest utterance x channel blocks, utterances), channel blocks fastest as in the one-utterance form.  T is the
+// utterance's own row count and x / out start at its first row, so both replicate paddings clamp to its own first and last row and a tile never
+// straddles two utterances; a tile past its end returns before it touches LDS.
+template <int CW, typename EXT>
 __global__ __launch_bounds__(256) void bv_aa_snake_kernel(const float* __restrict__ x, int T, int C, const float* __restrict__ alpha, const float* __restrict__ invb,
-                                                          BvFilters f, float* __restrict__ out) {
+                                                          BvFilters f, float* __restrict__ out, int up, const EXT ext) {
     constexpr int TT = 32, NX = TT + 12, NZ = 2 * TT + 10, TY = 256 / CW;
     __shared__ float xs[NX][CW], zs[NZ][CW];
+    int cb = blockIdx.x, tb = blockIdx.y;
+    if constexpr (bv_ragged<EXT>) {
+        const int u = blockIdx.y, ncb = (C + CW - 1) / CW;
+        T = ext.frames[u] * up;
+        tb = blockIdx.x / ncb;
+        cb = blockIdx.x - tb * ncb;
+        if (tb * TT >= T) return;
+        const size_t r0 = (size_t)ext.row0[u] * up;
+        x += r0 * C;
+        out += r0 * C;
+    }
     const int cl = threadIdx.x % CW, ty = threadIdx.x / CW;
-    const int c = blockIdx.x * CW + cl;
-    const int t0 = blockIdx.y * TT;
+    const int c = cb * CW + cl;
+    const int t0 = tb * TT;
     const bool okc = c < C;
     for (int r = ty; r < NX; r += TY) {
         int s = t0 - 6 + r;
@@ -337,24 +409,172 @@ extern "C" int f5_bigvgan_destroy(f5_bigvgan_t v) {
 
 static unsigned bv_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
-static int bv_conv(f5_bigvgan_s* v, const BvConv& cv, const float* x, int T, int dil, int chan_major, float* out, bool residual, hipStream_t st) {
+// One launch set of a ragged call: the extents tables (at most UttExtents::MAXU utterances each: the row-crossing kernels launch once per table, the
+// row-local ones once over all rows) of `cnt` utterances holding `frames` mel frames back to back.  row0 counts frames from the start of the set.
+struct BvRagged {
+    std::vector<UttExtents> tabs;
+    int cnt = 0, frames = 0;
+};
+int g_bigvgan_group_frames = 2048;  // tuning knob ("bigvgan_group_frames"): frame budget of one launch set (bounds the im2col workspace; measured: profiles/r5_bigvgan_ragged_ab.md)
+
+// x: T rows (ragged: of all utterances, `up` rows per mel frame; src_ld > 0: conv_pre from the caller's frame-major mel) -> out [T, cout]
+static int bv_conv(f5_bigvgan_s* v, const BvConv& cv, const float* x, int T, int dil, int chan_major, float* out, bool residual, const BvRagged* rg, int up,
+                   int src_ld, hipStream_t st) {
     const size_t total = (size_t)T * cv.kp;
-    hipLaunchKernelGGL(bv_im2col_kernel, dim3(bv_blocks(total)), dim3(256), 0, st, x, T, cv.cin, cv.k, dil, cv.kp, chan_major, v->col, total);
-    F5_LAUNCH_CHECK();
+    if (rg) {
+        for (const UttExtents& e : rg->tabs) {
+            hipLaunchKernelGGL(bv_im2col_kernel<UttExtents>, dim3(bv_blocks((size_t)e.max_frames * up * cv.kp), (unsigned)e.cnt), dim3(256), 0, st, x, 0, cv.cin,
+                               cv.k, dil, cv.kp, 0, v->col, (size_t)0, up, src_ld, e);
+            F5_LAUNCH_CHECK();
+        }
+    } else {
+        hipLaunchKernelGGL(bv_im2col_kernel<BvNoExt>, dim3(bv_blocks(total)), dim3(256), 0, st, x, T, cv.cin, cv.k, dil, cv.kp, chan_major, v->col, total, 1, 0,
+                           BvNoExt{});
+        F5_LAUNCH_CHECK();
+    }
     GemmParams g;
     memset(&g, 0, sizeof(g));
     g.A = v->col; g.lda = cv.kp; g.W = cv.w; g.ldw = cv.kp; g.M = T; g.N = cv.cout; g.K = cv.kp; g.bias = cv.b; g.out_f = out; g.ldof = cv.cout;
     g.rows_per_batch = T;
     return launch_gemm(g, F5_PREC_FP32, GEMM_DENSE, residual ? EPI_RESID : EPI_STORE_F32, 0, st);
 }
-static int bv_snake(f5_bigvgan_s* v, const BvSnake& s, const float* x, int T, int C, float* out, hipStream_t st) {
+static int bv_snake(f5_bigvgan_s* v, const BvSnake& s, const float* x, int T, int C, float* out, const BvRagged* rg, int up, hipStream_t st) {
     BvFilters f;
     memcpy(f.up, v->up_f, sizeof(f.up));
     memcpy(f.dn, v->dn_f, sizeof(f.dn));
+    if (rg) {
+        for (const UttExtents& e : rg->tabs) {
+            const unsigned tiles = (unsigned)(((size_t)e.max_frames * up + 31) / 32);
+            if (C % 64 == 0)
+                hipLaunchKernelGGL((bv_aa_snake_kernel<64, UttExtents>), dim3(tiles * (unsigned)(C / 64), (unsigned)e.cnt), dim3(256), 0, st, x, 0, C, s.a, s.invb, f,
+                                   out, up, e);
+            else
+                hipLaunchKernelGGL((bv_aa_snake_kernel<32, UttExtents>), dim3(tiles * (unsigned)((C + 31) / 32), (unsigned)e.cnt), dim3(256), 0, st, x, 0, C, s.a,
+                                   s.invb, f, out, up, e);
+            F5_LAUNCH_CHECK();
+        }
+        return 0;
+    }
     if (C % 64 == 0)
-        hipLaunchKernelGGL(bv_aa_snake_kernel<64>, dim3((unsigned)(C / 64), (unsigned)((T + 31) / 32)), dim3(256), 0, st, x, T, C, s.a, s.invb, f, out);
+        hipLaunchKernelGGL((bv_aa_snake_kernel<64, BvNoExt>), dim3((unsigned)(C / 64), (unsigned)((T + 31) / 32)), dim3(256), 0, st, x, T, C, s.a, s.invb, f, out, 1,
+                           BvNoExt{});
     else
-        hipLaunchKernelGGL(bv_aa_snake_kernel<32>, dim3((unsigned)((C + 31) / 32), (unsigned)((T + 31) / 32)), dim3(256), 0, st, x, T, C, s.a, s.invb, f, out);
+        hipLaunchKernelGGL((bv_aa_snake_kernel<32, BvNoExt>), dim3((unsigned)((C + 31) / 32), (unsigned)((T + 31) / 32)), dim3(256), 0, st, x, T, C, s.a, s.invb, f,
+                           out, 1, BvNoExt{});
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+// ConvTranspose1d in place on v->x: T rows (ragged: `up` rows per mel frame) -> T * u rows
+static int bv_upsample(f5_bigvgan_s* v, const BvUp& up, int T, const BvRagged* rg, int upf, hipStream_t st) {
+    const size_t rows = (size_t)T + (rg ? rg->cnt : 1);
+    if (rg) {
+        int ubase = 0;
+        for (const UttExtents& e : rg->tabs) {
+            hipLaunchKernelGGL(bv_up_gather_kernel<UttExtents>, dim3(bv_blocks(((size_t)e.max_frames * upf + 1) * up.kp), (unsigned)e.cnt), dim3(256), 0, st, v->x, 0,
+                               up.cin, up.R, up.kp, v->col, (size_t)0, upf, ubase, e);
+            F5_LAUNCH_CHECK();
+            ubase += e.cnt;
+        }
+    } else {
+        const size_t tg = rows * up.kp;
+        hipLaunchKernelGGL(bv_up_gather_kernel<BvNoExt>, dim3(bv_blocks(tg)), dim3(256), 0, st, v->x, T, up.cin, up.R, up.kp, v->col, tg, 1, 0, BvNoExt{});
+        F5_LAUNCH_CHECK();
+    }
+    GemmParams g;
+    memset(&g, 0, sizeof(g));
+    g.A = v->col; g.lda = up.kp; g.W = up.w; g.ldw = up.kp; g.M = (int)rows; g.N = up.u * up.cout; g.K = up.kp; g.out_f = v->tmp; g.ldof = up.u * up.cout;
+    F5_TRY(launch_gemm(g, F5_PREC_FP32, GEMM_DENSE, EPI_STORE_F32, 0, st));
+    if (rg) {
+        int ubase = 0;
+        for (const UttExtents& e : rg->tabs) {
+            hipLaunchKernelGGL(bv_up_scatter_kernel<UttExtents>, dim3(bv_blocks((size_t)e.max_frames * upf * up.u * up.cout), (unsigned)e.cnt), dim3(256), 0, st,
+                               v->tmp, 0, up.cout, up.u, up.pad, up.b, v->x, (size_t)0, upf, ubase, e);
+            F5_LAUNCH_CHECK();
+            ubase += e.cnt;
+        }
+    } else {
+        const size_t ts = (size_t)T * up.u * up.cout;
+        hipLaunchKernelGGL(bv_up_scatter_kernel<BvNoExt>, dim3(bv_blocks(ts)), dim3(256), 0, st, v->tmp, T, up.cout, up.u, up.pad, up.b, v->x, ts, 1, 0, BvNoExt{});
+        F5_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+static size_t bv_total_up(const f5_bigvgan_config& c) {
+    size_t total_up = 1;
+    for (int i = 0; i < c.num_upsamples; ++i) total_up *= (size_t)c.upsample_rates[i];
+    return total_up;
+}
+
+// the workspace for T frames in nb utterances (grown once per longest call; not a per-call allocation)
+static int bv_ensure_work(f5_bigvgan_s* v, size_t T, size_t nb, hipStream_t st) {
+    if (T <= v->work_T && nb <= v->work_B) return 0;
+    const f5_bigvgan_config& c = v->cfg;
+    T = std::max(T, v->work_T);
+    nb = std::max(nb, v->work_B);
+    F5_HIP(hipStreamSynchronize(st));
+    v->work.release();
+    v->work_T = v->work_B = 0;
+    size_t act = T * c.upsample_initial_channel, col = T * v->conv_pre.kp, tmp = 0;
+    size_t Ti = T;
+    int ch = c.upsample_initial_channel;
+    for (int i = 0; i < c.num_upsamples; ++i) {
+        const BvUp& up = v->ups[i];
+        col = std::max(col, (Ti + nb) * (size_t)up.kp);
+        tmp = std::max(tmp, (Ti + nb) * (size_t)up.u * up.cout);
+        Ti *= (size_t)up.u;
+        ch /= 2;
+        act = std::max(act, Ti * (size_t)ch);
+        for (int j = 0; j < c.num_kernels; ++j) col = std::max(col, Ti * (size_t)v->blocks[(size_t)i * c.num_kernels + j].c1[0].kp);
+    }
+    col = std::max(col, Ti * (size_t)v->conv_post.kp);
+    F5_TRY(v->work.alloc_t(&v->x, act, false));
+    F5_TRY(v->work.alloc_t(&v->y, act, false));
+    F5_TRY(v->work.alloc_t(&v->xt, act, false));
+    F5_TRY(v->work.alloc_t(&v->xt2, act, false));
+    F5_TRY(v->work.alloc_t(&v->xs, act, false));
+    F5_TRY(v->work.alloc_t(&v->col, col, false));
+    F5_TRY(v->work.alloc_t(&v->tmp, tmp, false));
+    v->work_T = T;
+    v->work_B = nb;
+    return 0;
+}
+
+// mel -> wave over T mel frames: one utterance (mel channel-major [num_mels][T]), or, with rg, the utterances of one launch set back to back (mel
+// frame-major [*, ld], read through the tables' src0).  wave receives T * prod(upsample_rates) samples.
+static int bv_generate(f5_bigvgan_s* v, const BvRagged* rg, int T, const float* mel, int ld, float* wave, hipStream_t st) {
+    const f5_bigvgan_config& c = v->cfg;
+    int Ti = T, ch = c.upsample_initial_channel, U = 1;
+    F5_TRY(bv_conv(v, v->conv_pre, mel, Ti, 1, rg ? 0 : 1, v->x, false, rg, U, rg ? ld : 0, st));
+    for (int i = 0; i < c.num_upsamples; ++i) {
+        const BvUp& up = v->ups[i];
+        F5_TRY(bv_upsample(v, up, Ti, rg, U, st));
+        Ti *= up.u;
+        U *= up.u;
+        ch /= 2;
+        const size_t n = (size_t)Ti * ch;
+        for (int j = 0; j < c.num_kernels; ++j) {
+            const BvBlock& blk = v->blocks[(size_t)i * c.num_kernels + j];
+            F5_HIP(hipMemcpyAsync(v->y, v->x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            for (int t = 0; t < 3; ++t) {
+                F5_TRY(bv_snake(v, blk.act[2 * t], v->y, Ti, ch, v->xt, rg, U, st));
+                F5_TRY(bv_conv(v, blk.c1[t], v->xt, Ti, blk.dil[t], 0, v->xt2, false, rg, U, 0, st));
+                F5_TRY(bv_snake(v, blk.act[2 * t + 1], v->xt2, Ti, ch, v->xt, rg, U, st));
+                F5_TRY(bv_conv(v, blk.c2[t], v->xt, Ti, 1, 0, v->y, true, rg, U, 0, st));  // y += conv2(...)
+            }
+            if (j == 0)
+                F5_HIP(hipMemcpyAsync(v->xs, v->y, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            else {
+                hipLaunchKernelGGL(bv_axpby_kernel, dim3(bv_blocks(n)), dim3(256), 0, st, v->xs, v->y, 1.0f, 1.0f, n);
+                F5_LAUNCH_CHECK();
+            }
+        }
+        hipLaunchKernelGGL(bv_axpby_kernel, dim3(bv_blocks(n)), dim3(256), 0, st, v->x, v->xs, 0.0f, 1.0f / (float)c.num_kernels, n);
+        F5_LAUNCH_CHECK();
+    }
+    F5_TRY(bv_snake(v, v->act_post, v->x, Ti, ch, v->xt, rg, U, st));
+    F5_TRY(bv_conv(v, v->conv_post, v->xt, Ti, 1, 0, v->y, false, rg, U, 0, st));
+    hipLaunchKernelGGL(bv_final_kernel, dim3(bv_blocks((size_t)Ti)), dim3(256), 0, st, v->y, c.use_tanh_at_final, wave, (size_t)Ti);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -365,79 +585,55 @@ extern "C" int f5_bigvgan_forward(f5_bigvgan_t v, int B, int T, const float* mel
     if (!v->finalized) return f5_fail(F5_ESTATE, "f5_bigvgan_finalize must be called first");
     F5_TRY(f5_check_device());
     hipStream_t st = (hipStream_t)stream;
-    const f5_bigvgan_config& c = v->cfg;
-    size_t total_up = 1;
-    for (int i = 0; i < c.num_upsamples; ++i) total_up *= (size_t)c.upsample_rates[i];
-    if ((size_t)T > v->work_T) {  // grow the workspace (once per longest chunk; not a per-call allocation)
-        F5_HIP(hipStreamSynchronize(st));
-        v->work.release();
-        v->work_T = 0;
-        size_t act = (size_t)T * c.upsample_initial_channel, col = (size_t)T * v->conv_pre.kp, tmp = 0;
-        size_t Ti = T;
-        int ch = c.upsample_initial_channel;
-        for (int i = 0; i < c.num_upsamples; ++i) {
-            const BvUp& up = v->ups[i];
-            col = std::max(col, (Ti + 1) * (size_t)up.kp);
-            tmp = std::max(tmp, (Ti + 1) * (size_t)up.u * up.cout);
-            Ti *= (size_t)up.u;
-            ch /= 2;
-            act = std::max(act, Ti * (size_t)ch);
-            for (int j = 0; j < c.num_kernels; ++j) col = std::max(col, Ti * (size_t)v->blocks[(size_t)i * c.num_kernels + j].c1[0].kp);
+    const size_t total_up = bv_total_up(v->cfg);
+    F5_TRY(bv_ensure_work(v, (size_t)T, 1, st));
+    for (int b = 0; b < B; ++b) F5_TRY(bv_generate(v, nullptr, T, mel + (size_t)b * v->cfg.num_mels * T, 0, wave + (size_t)b * T * total_up, st));
+    return 0;
+}
+
+// See f5hip.h.  The utterance list is cut, in order, into launch sets of at most g_bigvgan_group_frames frames (an utterance longer than that is a
+// set of its own); every check is made, and the workspace grown to the largest set, before the first launch.
+extern "C" int f5_bigvgan_decode_ragged(f5_bigvgan_t v, int B, const int32_t* row_start_host, const int32_t* frames_host, const float* mel, int ld,
+                                        float* wave, int64_t* total_samples, f5_stream_t stream) {
+    if (!v || !row_start_host || !frames_host || !mel || !wave) return f5_fail(F5_EINVAL, "null argument");
+    if (!v->finalized) return f5_fail(F5_ESTATE, "f5_bigvgan_finalize must be called first");
+    if (B <= 0 || ld < v->cfg.num_mels) return f5_fail(F5_EINVAL, "need B >= 1 and ld >= num_mels");
+    for (const BvUp& up : v->ups)
+        if (up.pad > up.u) return f5_fail(F5_ENOTSUP, "ragged decode: a transposed convolution with kernel > 3 x rate reads past its T + 1 gather rows");
+    F5_TRY(f5_check_device());
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total_up = (int64_t)bv_total_up(v->cfg);
+    std::vector<BvRagged> sets;
+    std::vector<int64_t> set_frame0;
+    int64_t frames = 0;
+    size_t max_frames = 0, max_cnt = 0;
+    for (int u = 0; u < B; ++u) {
+        const int t = frames_host[u];
+        if (t < 1 || row_start_host[u] < 0) return f5_fail(F5_EINVAL, "utterance %d: need T >= 1 frames and a row start >= 0", u);
+        // rows of the last stage (plus one gather row per utterance) and wave samples are 32-bit in the kernels; so are the mel row numbers
+        if ((frames + t) * total_up + B > (int64_t)INT_MAX || (int64_t)row_start_host[u] + t > (int64_t)INT_MAX)
+            return f5_fail(F5_EINVAL, "utterance %d: the call's rows or samples exceed 32-bit indexing", u);
+        if (sets.empty() || sets.back().frames + (int64_t)t > (int64_t)g_bigvgan_group_frames) {
+            sets.emplace_back();
+            set_frame0.push_back(frames);
         }
-        col = std::max(col, Ti * (size_t)v->conv_post.kp);
-        F5_TRY(v->work.alloc_t(&v->x, act, false));
-        F5_TRY(v->work.alloc_t(&v->y, act, false));
-        F5_TRY(v->work.alloc_t(&v->xt, act, false));
-        F5_TRY(v->work.alloc_t(&v->xt2, act, false));
-        F5_TRY(v->work.alloc_t(&v->xs, act, false));
-        F5_TRY(v->work.alloc_t(&v->col, col, false));
-        F5_TRY(v->work.alloc_t(&v->tmp, tmp, false));
-        v->work_T = (size_t)T;
+        BvRagged& s = sets.back();
+        if (s.tabs.empty() || s.tabs.back().cnt == UttExtents::MAXU) s.tabs.emplace_back();
+        UttExtents& e = s.tabs.back();
+        e.row0[e.cnt] = s.frames;
+        e.frames[e.cnt] = t;
+        e.src0[e.cnt] = row_start_host[u];
+        e.out0[e.cnt] = (int)((int64_t)s.frames * total_up);
+        if (t > e.max_frames) e.max_frames = t;
+        ++e.cnt;
+        ++s.cnt;
+        s.frames += t;
+        frames += t;
+        max_frames = std::max(max_frames, (size_t)s.frames);
+        max_cnt = std::max(max_cnt, (size_t)s.cnt);
     }
-    for (int b = 0; b < B; ++b) {
-        const float* m = mel + (size_t)b * c.num_mels * T;
-        int Ti = T, ch = c.upsample_initial_channel;
-        F5_TRY(bv_conv(v, v->conv_pre, m, Ti, 1, 1, v->x, false, st));
-        for (int i = 0; i < c.num_upsamples; ++i) {
-            const BvUp& up = v->ups[i];
-            {
-                const size_t rows = (size_t)Ti + 1, tg = rows * up.kp;
-                hipLaunchKernelGGL(bv_up_gather_kernel, dim3(bv_blocks(tg)), dim3(256), 0, st, v->x, Ti, up.cin, up.R, up.kp, v->col, tg);
-                F5_LAUNCH_CHECK();
-                GemmParams g;
-                memset(&g, 0, sizeof(g));
-                g.A = v->col; g.lda = up.kp; g.W = up.w; g.ldw = up.kp; g.M = (int)rows; g.N = up.u * up.cout; g.K = up.kp; g.out_f = v->tmp; g.ldof = up.u * up.cout;
-                F5_TRY(launch_gemm(g, F5_PREC_FP32, GEMM_DENSE, EPI_STORE_F32, 0, st));
-                const size_t ts = (size_t)Ti * up.u * up.cout;
-                hipLaunchKernelGGL(bv_up_scatter_kernel, dim3(bv_blocks(ts)), dim3(256), 0, st, v->tmp, Ti, up.cout, up.u, up.pad, up.b, v->x, ts);
-                F5_LAUNCH_CHECK();
-            }
-            Ti *= up.u;
-            ch /= 2;
-            const size_t n = (size_t)Ti * ch;
-            for (int j = 0; j < c.num_kernels; ++j) {
-                const BvBlock& blk = v->blocks[(size_t)i * c.num_kernels + j];
-                F5_HIP(hipMemcpyAsync(v->y, v->x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-                for (int t = 0; t < 3; ++t) {
-                    F5_TRY(bv_snake(v, blk.act[2 * t], v->y, Ti, ch, v->xt, st));
-                    F5_TRY(bv_conv(v, blk.c1[t], v->xt, Ti, blk.dil[t], 0, v->xt2, false, st));
-                    F5_TRY(bv_snake(v, blk.act[2 * t + 1], v->xt2, Ti, ch, v->xt, st));
-                    F5_TRY(bv_conv(v, blk.c2[t], v->xt, Ti, 1, 0, v->y, true, st));  // y += conv2(...)
-                }
-                if (j == 0)
-                    F5_HIP(hipMemcpyAsync(v->xs, v->y, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-                else {
-                    hipLaunchKernelGGL(bv_axpby_kernel, dim3(bv_blocks(n)), dim3(256), 0, st, v->xs, v->y, 1.0f, 1.0f, n);
-                    F5_LAUNCH_CHECK();
-                }
-            }
-            hipLaunchKernelGGL(bv_axpby_kernel, dim3(bv_blocks(n)), dim3(256), 0, st, v->x, v->xs, 0.0f, 1.0f / (float)c.num_kernels, n);
-            F5_LAUNCH_CHECK();
-        }
-        F5_TRY(bv_snake(v, v->act_post, v->x, Ti, ch, v->xt, st));
-        F5_TRY(bv_conv(v, v->conv_post, v->xt, Ti, 1, 0, v->y, false, st));
-        hipLaunchKernelGGL(bv_final_kernel, dim3(bv_blocks((size_t)Ti)), dim3(256), 0, st, v->y, c.use_tanh_at_final, wave + (size_t)b * T * total_up, (size_t)Ti);
-        F5_LAUNCH_CHECK();
-    }
+    if (total_samples) *total_samples = frames * total_up;
+    F5_TRY(bv_ensure_work(v, max_frames, max_cnt, st));
+    for (size_t k = 0; k < sets.size(); ++k) F5_TRY(bv_generate(v, &sets[k], sets[k].frames, mel, ld, wave + (size_t)(set_frame0[k] * total_up), st));
     return 0;
 }

@@ -181,7 +181,7 @@ def cross_fade_concat(waves, cross_fade_duration, sample_rate=target_sample_rate
 # ---------------------------------------------------------------------------- the tail behind the sampler, on the device
 # generate(), infer_batch_process() and eval.prompts.infer_prompts() used to run, per utterance, one batch-1 vocoder call, the rms rule with a
 # device -> host comparison, a device -> host copy, and then cross_fade_concat / pcm16_bytes in numpy.  With the HIP vocoders the same arithmetic
-# runs as ONE ragged Vocos.decode_ragged, ONE f5_wave_finish and ONE copy; the results are byte-identical (tests/test_gpu_wave_tail.py), so no
+# runs as ONE ragged decode (Vocos.decode_ragged / BigVGAN.decode_ragged), ONE f5_wave_finish and ONE copy; the results are byte-identical (tests/test_gpu_wave_tail.py), so no
 # switch selects it: it is taken whenever the objects at hand allow it, and the per-utterance host loop otherwise.
 
 def plan_wave_tail(lengths, cross_fade_duration, sample_rate=target_sample_rate):
@@ -273,14 +273,15 @@ def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_samp
 
 
 def device_tail_kind(vocoder, *tensors):
-    """Which device tail applies to this vocoder object and these mels: "vocos" (the HIP Vocos: it has ``decode_ragged``), "bigvgan" (the HIP
-    BigVGAN) or None (a foreign object at plug point B, or tensors that are not on the GPU: the per-utterance host loop)."""
+    """Which device tail applies to this vocoder object and these mels: "bigvgan" (the HIP BigVGAN: ``T * up`` samples per utterance), "vocos"
+    (the HIP Vocos, or an object with its ``decode_ragged_buffer``: ``(T - 1) * hop`` samples) or None (a foreign object at plug point B, or
+    tensors that are not on the GPU: the per-utterance host loop).  Both of ours have ``decode_ragged_buffer``: the class tells them apart."""
     if not tensors or not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
         return None
-    if hasattr(vocoder, "decode_ragged_buffer"):
-        return "vocos"
     from ..bigvgan import BigVGAN
-    return "bigvgan" if isinstance(vocoder, BigVGAN) else None
+    if isinstance(vocoder, BigVGAN):
+        return "bigvgan"
+    return "vocos" if hasattr(vocoder, "decode_ragged_buffer") else None
 
 
 def mel_rows_of(mels, skip):
@@ -302,11 +303,10 @@ def mel_rows_of(mels, skip):
 
 
 def decode_utterances(vocoder, kind, rows, row_start, frames):
-    """One wave buffer for all utterances (and the sample count of each): one ragged Vocos call, or the BigVGAN generator per utterance."""
-    if kind == "vocos":
-        return vocoder.decode_ragged_buffer(rows, row_start, frames)
-    waves = [vocoder(rows[r: r + t].unsqueeze(0).permute(0, 2, 1)).reshape(-1) for r, t in zip(row_start, frames)]
-    return torch.cat(waves), [int(w.numel()) for w in waves]
+    """One wave buffer for all utterances (and the sample count of each) from ONE ragged call of either HIP vocoder (``kind`` is
+    `device_tail_kind`'s answer: both classes take the same arguments, the sample counts differ)."""
+    assert kind in ("vocos", "bigvgan")
+    return vocoder.decode_ragged_buffer(rows, row_start, frames)
 
 
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,

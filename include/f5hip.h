@@ -33,7 +33,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: only the entry points declared here are exported */
 #define F5_API __attribute__((visibility("default")))
 
-#define F5HIP_VERSION 400 /* 0.4.0 (round 4; round 5 adds f5_vocoder_decode_ragged and f5_wave_finish under the same number, which tests/test_host_logic.py pins: detect them by symbol): + the BigVGAN entry points and mel front-end, f5_op_ln_fold, bounded timing ring; plan options "ln_fold_active", "gemm_w4"; tuning keys "ln_fold", "ln_fold_fin", "gemm_w4"; 0.3.2: + f5_sample_ragged, f5_mmdit_forward, f5_duration_predict_g */
+#define F5HIP_VERSION 400 /* 0.4.0 (round 4; round 5 adds f5_vocoder_decode_ragged, f5_wave_finish and f5_bigvgan_decode_ragged (+ tuning key "bigvgan_group_frames") under the same number, which tests/test_host_logic.py pins: detect them by symbol): + the BigVGAN entry points and mel front-end, f5_op_ln_fold, bounded timing ring; plan options "ln_fold_active", "gemm_w4"; tuning keys "ln_fold", "ln_fold_fin", "gemm_w4"; 0.3.2: + f5_sample_ragged, f5_mmdit_forward, f5_duration_predict_g */
 
 /* error codes */
 #define F5_OK 0
@@ -404,6 +404,17 @@ F5_API int f5_bigvgan_finalize(f5_bigvgan_t v);
 F5_API int f5_bigvgan_destroy(f5_bigvgan_t v);
 /* mel dev f32 [B][num_mels][T] -> wave dev f32 [B][T * prod(upsample_rates)]  (BigVGAN.forward, the [B, 1, samples] result without its unit axis) */
 F5_API int f5_bigvgan_forward(f5_bigvgan_t v, int B, int T, const float* mel, float* wave, f5_stream_t stream);
+/* Utterances of DIFFERENT frame counts through one set of launches (round 5; the shape of f5_vocoder_decode_ragged).  mel: dev f32, FRAME-major
+ * [rows, ld] with ld >= num_mels (the sampler's own buffer: no permute / contiguous copy; columns past num_mels are never read).  Utterance i
+ * reads frames_host[i] >= 1 rows from row row_start_host[i] on and writes its T_i * prod(upsample_rates) samples directly behind those of
+ * utterance i - 1 in `wave`; *total_samples (may be NULL) receives the sum.  Both arrays are host memory, read before the call returns.
+ * Utterance i is bit-identical to f5_bigvgan_forward(v, 1, T_i, its own [num_mels, T_i] mel): the convolutions pad with zeros and the
+ * anti-aliased activations replicate at each utterance's own ends and never read a neighbour's rows, whatever those hold.  The list is cut, in
+ * order, into launch sets of at most "bigvgan_group_frames" frames (tuning key, default 2048; a longer utterance is a set of its own), which
+ * bounds the workspace and changes no bit.  F5_EINVAL, before any launch: B <= 0, ld < num_mels, a negative row start, a frame count below 1,
+ * rows or samples beyond 32-bit indexing.  Nothing synchronises (workspace growth aside, as for f5_bigvgan_forward). */
+F5_API int f5_bigvgan_decode_ragged(f5_bigvgan_t v, int B, const int32_t* row_start_host, const int32_t* frames_host, const float* mel, int ld,
+                                    float* wave, int64_t* total_samples, f5_stream_t stream);
 
 /* ------------------------------------------------------------------ reference-audio front-end on the device
  * Replaces the two torchaudio transforms of the path:
