@@ -803,6 +803,7 @@ static bool picks_wide(int B, int N, int H, bool masked, int ldq, int bstride) {
 
 int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& segs, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
                             int bstride) {
+    if (segs.cnt < 0 || segs.cnt > AttnSegs::MAX || segs.nbr < 1) return f5_fail(F5_EINVAL, "attention_ragged: a table holds at most %d utterances", AttnSegs::MAX);
     const size_t es = precision == F5_PREC_BF16 ? 2 : 4;
     AttnSegs grp[2];  // [0] utterances with n % 64 == 0 (unmasked build), [1] the others -- as each one's own launch would pick
     int maxn[2] = {0, 0};
@@ -823,6 +824,20 @@ int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& 
     }
     for (int k = 0; k < 2; ++k)
         if (grp[k].cnt > 0) F5_TRY(launch_attention_pipe_segs(k == 1, segs.nbr, grp[k], maxn[k], H, qkv, ldq, out, ldo, stream, bstride));
+    return 0;
+}
+
+int launch_attention_ragged_all(int precision, int attn_kernel_opt, int nbr, int cnt, const int* off, const int* n, int H, const void* qkv, int ldq, void* out,
+                                int ldo, hipStream_t stream, int bstride) {
+    for (int u0 = 0; u0 < cnt; u0 += AttnSegs::MAX) {
+        AttnSegs sg;
+        sg.nbr = nbr;
+        for (int u = u0; u < cnt && u < u0 + AttnSegs::MAX; ++u) {
+            sg.off[sg.cnt] = off[u];
+            sg.n[sg.cnt++] = n[u];
+        }
+        F5_TRY(launch_attention_ragged(precision, attn_kernel_opt, sg, H, qkv, ldq, out, ldo, stream, bstride));
+    }
     return 0;
 }
 

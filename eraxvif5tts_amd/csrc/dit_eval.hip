@@ -227,15 +227,8 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         }
         if (rg) {  // every utterance gets the computation of the launch its own batch-1 sample() makes, on its rows of both halves; the ones
                    // that launch would give to the pipelined kernel share launches (grid.z = utterance x branch, 12 utterances per table)
-            for (size_t u0 = 0; u0 < rg->n.size(); u0 += 12) {
-                AttnSegs sg;
-                sg.nbr = nb;
-                for (size_t u = u0; u < rg->n.size() && u < u0 + 12; ++u) {
-                    sg.off[sg.cnt] = rg->off[u];
-                    sg.n[sg.cnt++] = rg->n[u];
-                }
-                F5_TRY(launch_attention_ragged(P, p->attn_kernel, sg, c.heads, p->qkv, 3 * inner, p->cT, inner, st, N));
-            }
+            F5_TRY(launch_attention_ragged_all(P, p->attn_kernel, nb, (int)rg->n.size(), rg->off.data(), rg->n.data(), c.heads, p->qkv, 3 * inner, p->cT, inner,
+                                               st, N));
         } else {
             int kind = 0;
             if (p->attn_kernel != 0 && attention_fast_supported(P, N, c.heads)) kind = 1;

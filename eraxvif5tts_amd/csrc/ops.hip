@@ -170,6 +170,35 @@ extern "C" int f5_op_attention(int precision, int kernel, int B, int N, int H, c
     return sync_and_release(a, st, rc);
 }
 
+// The ragged sampler's attention call (dit_eval.hip) on its own: `cnt` utterances at rows off[u] .. off[u] + n[u] of each of the `nbr` branches,
+// the branches `rows` apart (the batch stride).  `out` is staged into the activation dtype first, so rows no launch writes come back as given.
+extern "C" int f5_op_attention_ragged(int precision, int attn_kernel, int nbr, int cnt, const int* off, const int* n, int H, int rows, int ldq_extra,
+                                      int ldo_extra, const float* qkv, float* out, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (nbr <= 0 || cnt <= 0 || H <= 0 || rows <= 0 || ldq_extra < 0 || ldo_extra < 0 || !off || !n || !qkv || !out) return f5_fail(F5_EINVAL, "bad argument");
+    if ((long)nbr * rows > 0x7fffffffL) return f5_fail(F5_EINVAL, "f5_op_attention_ragged: nbr * rows exceeds the row index range");
+    for (int u = 0; u < cnt; ++u) {
+        if (n[u] < 1) return f5_fail(F5_EINVAL, "f5_op_attention_ragged: utterance %d has no rows (n = %d)", u, n[u]);
+        if (off[u] < 0 || (long)off[u] + n[u] > rows)
+            return f5_fail(F5_EINVAL, "f5_op_attention_ragged: utterance %d (rows %d .. %ld) lies outside the %d rows of a branch", u, off[u], (long)off[u] + n[u], rows);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int inner = H * 64, ldq = 3 * inner + ldq_extra, ldo = inner + ldo_extra, all = nbr * rows;
+    const size_t es = f5_elem_size(precision);
+    DevArena a;
+    void *q = nullptr, *o = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&q, (size_t)all * ldq * es))) break;
+        if ((rc = a.alloc(&o, (size_t)all * ldo * es))) break;
+        if ((rc = launch_convert_pad(precision, qkv, ldq, all, ldq, ldq, q, ldq, st))) break;
+        if ((rc = launch_convert_pad(precision, out, ldo, all, ldo, ldo, o, ldo, st))) break;
+        if ((rc = launch_attention_ragged_all(precision, attn_kernel, nbr, cnt, off, n, H, q, ldq, o, ldo, st, rows))) break;
+        rc = launch_convert_back(precision, o, ldo, all, ldo, out, ldo, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
 int g_op_conv_kernel = 0;  // tuning knob ("op_conv_kernel"): f5_op_conv_pos_embed runs the tuned conv kernels (bf16)
 
 extern "C" int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const float* x, const float* w0, const float* b0, const float* w1,

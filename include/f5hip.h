@@ -274,6 +274,14 @@ F5_API int f5_op_layernorm_modulate(int rows, int dim, const float* x, const flo
  * -> out f32 [B, N, H*64].  kernel: 0 = reference kernel, 1 = tuned flash kernel (bf16). */
 F5_API int f5_op_attention(int precision, int kernel, int B, int N, int H, const float* qkv, const uint8_t* mask, float* out,
                     f5_stream_t stream);
+/* The attention call of the ragged sampler (f5_sample_ragged) on its own: `cnt` utterances of lengths n[u] at row offsets off[u] (host int
+ * arrays) inside each of `nbr` branches that lie `rows` rows apart (the batch stride of every launch).  qkv f32 [nbr * rows, 3*H*64 +
+ * ldq_extra], out f32 [nbr * rows, H*64 + ldo_extra] (the extras widen the leading dimensions, normally 0).  attn_kernel 0 = reference
+ * kernels only, non-zero = the sampler's own selection (shared pipelined launches, or a launch of its own, per utterance).  `out` is staged
+ * into the precision's dtype before the launches, so every element no launch writes comes back as the caller left it.  Refused before any
+ * launch: n[u] < 1, off[u] < 0, off[u] + n[u] > rows. */
+F5_API int f5_op_attention_ragged(int precision, int attn_kernel, int nbr, int cnt, const int* off, const int* n, int H, int rows,
+                                  int ldq_extra, int ldo_extra, const float* qkv, float* out, f5_stream_t stream);
 /* ConvPositionEmbedding (modules.py:167-190): x f32 [B, N, dim] -> mish(conv(mish(conv(x)))) ; weights f32
  * [dim, dim/16, 31] + bias [dim] (two layers) */
 F5_API int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const float* x, const float* w0, const float* b0,

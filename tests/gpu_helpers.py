@@ -61,6 +61,26 @@ def op_attention(precision, kernel, qkv, mask=None):
     return out.cpu()
 
 
+def op_attention_ragged_rc(precision, attn_kernel, nbr, off, n, H, rows, qkv, out, ldq_extra=0, ldo_extra=0):
+    """include/f5hip.h: f5_op_attention_ragged.  qkv [nbr * rows, 3 * H * 64 + ldq_extra], out [nbr * rows, H * 64 + ldo_extra] (pre-filled by
+    the caller: what no launch writes comes back unchanged).  Returns (return code, out on the host)."""
+    lib = _lib.load()
+    cnt = len(n)
+    assert len(off) == cnt and qkv.shape == (nbr * rows, 3 * H * 64 + ldq_extra) and out.shape == (nbr * rows, H * 64 + ldo_extra)
+    q = qkv.cuda().float().contiguous()
+    o = out.cuda().float().contiguous().clone()
+    rc = lib.f5_op_attention_ragged(precision, attn_kernel, nbr, cnt, (C.c_int * cnt)(*off), (C.c_int * cnt)(*n), H, rows, ldq_extra, ldo_extra,
+                                    _lib.ptr(q), _lib.ptr(o), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    return rc, o.cpu()
+
+
+def op_attention_ragged(precision, attn_kernel, nbr, off, n, H, rows, qkv, out, ldq_extra=0, ldo_extra=0):
+    rc, o = op_attention_ragged_rc(precision, attn_kernel, nbr, off, n, H, rows, qkv, out, ldq_extra, ldo_extra)
+    _lib.check(rc, "f5_op_attention_ragged")
+    return o
+
+
 def op_conv_pos(precision, x, w0, b0, w1, b1):
     lib = _lib.load()
     B, N, D = x.shape
