@@ -1,6 +1,39 @@
 // dit_eval.hip -- one evaluation of the DiT backbone (reference model/backbones/dit.py:185-233, model/modules.py:301-336,610-641).
 #include "model_internal.h"
 
+// LayerNorm fold: which of an evaluation's two folded projections (QKV, FF1) take their row statistics from the producer's partial sums inside
+// their own kernel.  `rows` token rows, `rows_g` with the padding of the block GEMMs.  Otherwise one stats_finalize launch sits in front.
+struct LnfInkernel {
+    bool qkv, ff1;
+};
+static LnfInkernel lnf_inkernel_sites(const f5_plan_s* p, int rows, int rows_g) {
+    const f5_dit_config& c = p->m->cfg;
+    const int D = c.dim, inner = p->m->inner, ff = c.ff_inner;
+    LnfInkernel ink{false, false};
+    if (!p->lnf_stats2) return ink;
+    auto narrow_tile = [&](int M, int N) {  // the 8-wave kernel gives this projection a tile narrower than 256 (statistics held in registers)
+        GemmParams t = gp_zero();
+        t.M = M; t.N = N; t.K = D; t.lda = D; t.ldw = D;
+        return gemm_fast_lnf_inkernel(t);
+    };
+    // knob "ln_fold_inkernel": the 8-wave kernel's in-kernel form wherever its tile allows (QKV as dit_eval launches it: q|k and v apart under split_v)
+    if (g_ln_fold_inkernel) {
+        const int tiles_m = (rows + 255) / 256, ncu = f5_cu_count();
+        const bool sv = inner % 256 == 0 && tiles_m * (2 * inner / 256) <= ncu && tiles_m * (3 * inner / 256) > ncu && tiles_m * (2 * inner / 256) >= 160;
+        ink.qkv = narrow_tile(rows, sv ? 2 * inner : 3 * inner);
+        if (sv) ink.qkv = ink.qkv && narrow_tile(rows, inner);
+        ink.ff1 = narrow_tile(rows, ff);
+    }
+    // ... and on the one-wave-per-SIMD kernel's 128-row tiles the consumer finishes the statistics by default (gemm_w4.hip: finish_stats; small
+    // batches, where the two statistics launches of a block were 13 of its 102 us).  Only where the 8-wave kernel could take the launch in the
+    // same form, should the other kernel refuse it.
+    if (!c.qk_norm) {
+        if (!ink.qkv && gemm_w4_lnf_inkernel(rows_g, 3 * inner, D) != 0 && narrow_tile(rows_g, 3 * inner)) ink.qkv = true;
+        if (!ink.ff1 && gemm_w4_lnf_inkernel(rows_g, ff, D) != 0 && narrow_tile(rows_g, ff)) ink.ff1 = true;
+    }
+    return ink;
+}
+
 // one network evaluation over `nb` batch rows (rows = nb*N) whose noisy mel rows are x[xrows, mel] (xrows divides rows);
 // modulation row for batch b is modp + b * mod_bstride.  Result: p->vout [rows, MELP] f32.
 int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float* modp, int mod_bstride, const uint8_t* mask,
@@ -57,11 +90,10 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     // past the last token compute on whatever the padding holds (finite: zero-filled arena, saturating fp16 stores).  Their fp16 stream rows are
     // never reset: the EPI_RESID epilogues keep adding gate * (A W + b) to them, evaluation after evaluation and call after call, until they sit
     // at the saturation value.  What reads them: the four block GEMMs themselves (the out-projection and FF2 read-modify-write them, their
-    // partial row sums go to lnf_partial) and a folded consumer or producer that finishes the row statistics inside the kernel (gemm_w4.hip
-    // finish_stats, the 8-wave in-kernel form, fin_counter), which turns them into (mean, rstd) for its own epilogue.  GemmParams::lnf_rows = rows
-    // keeps them out of every stored statistics table and out of the fp16 range guard -- a padding row at +-65504 must not send the plan to fp32
-    // storage.  Nothing else reads them: every other kernel works on `rows`, attention on the utterances' own rows.  (Round 4 first split such launches into whole tiles + a tail
-    // launch: 8 x 1001 346 against 288 ms per sample(), the ragged 4-chunk batch 210 against 183 ms -- the tail launches are pure latency.)
+    // partial row sums go to lnf_partial) and a folded consumer that finishes the row statistics inside its kernel (gemm_w4.hip finish_stats, the
+    // 8-wave in-kernel form), which turns them into (mean, rstd) for its own epilogue.  GemmParams::lnf_rows = rows keeps them out of every stored
+    // statistics table and out of the fp16 range guard -- a padding row at +-65504 must not send the plan to fp32 storage.  Nothing else reads
+    // them: every other kernel works on `rows`, attention on the utterances' own rows.
     const int rows_g = (rmw && g_gemm_pad_rows && rows >= 3584 /* from here on the fused projection takes the 256-wide persistent tile */ && rows % 256 != 0 && (size_t)((rows + 255) / 256 * 256) <= p->rows_cap) ? (rows + 255) / 256 * 256 : rows;
     const FoldTable* ft = p->fold;
     const bool lnf = rmw && g_ln_fold && ft && p->lnf_stats && p->fold_eval >= 0 && p->fold_eval < (int)ft->tv.size() && p->gemm_kernel != 0 &&
@@ -70,59 +102,25 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     // LayerNorm sites of the folded evaluation, in order: k = 2l is block l's second LayerNorm (statistics: its out-projection), k = 2l - 1 its
     // first (statistics: FF2 of block l - 1).  Site k's (mean, rstd) go to table k & 1; its pivots -- the rows' previous means -- are site k - 1's,
     // in the other table (two tables: with the statistics taken inside the consumer kernel, sibling workgroups must still find the OLD means
-    // while feature tile 0's workgroups store the new ones).  A consumer launch on tiles narrower than 256 takes the statistics from the
-    // partial sums inside the kernel; the 256-wide tile needs them finalized by stats_finalize_kernel (same bits: lnf_stats_math.h).
+    // while feature tile 0's workgroups store the new ones).  A site's statistics are finished either inside the consumer kernel (ink: the
+    // one-wave-per-SIMD kernel's 128-row tiles, or the 8-wave kernel's tiles narrower than 256) or by one stats_finalize launch in front of
+    // it (same bits: lnf_stats_math.h).
     float* const lnfS[2] = {p->lnf_stats, p->lnf_stats2};
     PrefetchSet pf1f_prev{{nullptr, nullptr, nullptr, nullptr}, {0u, 0u, 0u, 0u}};
-    bool ink_qkv = false, ink_ff1 = false;
-    if (lnf && g_ln_fold_inkernel && p->lnf_stats2) {
-        GemmParams t = gp_zero();
-        t.M = rows; t.K = D; t.lda = D; t.ldw = D;
-        const int tiles_m = (rows + 255) / 256, ncu = f5_cu_count();
-        const bool sv = inner % 256 == 0 && tiles_m * (2 * inner / 256) <= ncu && tiles_m * (3 * inner / 256) > ncu && tiles_m * (2 * inner / 256) >= 160;
-        t.N = sv ? 2 * inner : 3 * inner;
-        ink_qkv = gemm_fast_lnf_inkernel(t);
-        if (sv) {
-            t.N = inner;
-            ink_qkv = ink_qkv && gemm_fast_lnf_inkernel(t);
-        }
-        t.N = ff;
-        ink_ff1 = gemm_fast_lnf_inkernel(t);
-    }
-    // ... and on the one-wave-per-SIMD kernel's 128-row tiles the consumer finishes the statistics by default (gemm_w4.hip: finish_stats; small
-    // batches, where the two statistics launches of a block were 13 of its 102 us).  Only where the 8-wave kernel could take the launch in the
-    // same form, should the other kernel refuse it.
-    if (lnf && p->lnf_stats2 && !c.qk_norm) {
-        GemmParams t = gp_zero();
-        t.M = rows_g; t.K = D; t.lda = D; t.ldw = D;
-        t.N = 3 * inner;
-        if (!ink_qkv && gemm_w4_lnf_inkernel(rows_g, 3 * inner, D) != 0 && gemm_fast_lnf_inkernel(t)) ink_qkv = true;
-        t.N = ff;
-        if (!ink_ff1 && gemm_w4_lnf_inkernel(rows_g, ff, D) != 0 && gemm_fast_lnf_inkernel(t)) ink_ff1 = true;
-    }
-    // producer side of site k (out-projection, FF2): the non-persistent schedules (small batches) finish the statistics inside the launch -- the
-    // workgroup that completes a block of token rows last turns the partial sums into (mean, rstd), carries the range guard and leaves nothing
-    // for a statistics launch to do (gemm.h: fin_counter; same bits as stats_finalize_kernel)
-    bool fin_site[2] = {false, false};  // [k & 1]: site k's statistics were finished by its producer
-    auto lnf_producer = [&](GemmParams& g, int k, int tag, const PrefetchSet& pf, bool consumer_inkernel) {
+    const LnfInkernel ink = lnf ? lnf_inkernel_sites(p, rows, rows_g) : LnfInkernel{false, false};
+    // producer side of site k (out-projection, FF2): partial row sums of the stream it stores
+    auto lnf_producer = [&](GemmParams& g, int k, const PrefetchSet& pf, bool consumer_inkernel) {
         g.stats_out = p->lnf_partial; g.stats_ld = (int)p->rows_cap; g.stats_pivot = k > 0 ? lnfS[(k - 1) & 1] : nullptr;
-        g.lnf_rows = rows;  // (M = rows_g: the padding rows stay out of fin_stats and the range guard)
-        const bool fin = g_ln_fold_fin && !consumer_inkernel && p->fin_counter && gemm_fast_resid_finishes(g);
-        fin_site[k & 1] = fin;
-        if (fin) {
-            g.fin_counter = p->fin_counter; g.fin_stats = lnfS[k & 1]; g.lnf_sat = sat; g.lnf_sat_tag = tag;
-        }
-        if (rows <= g_w_prefetch && r16 && g_w_prefetch && (fin || consumer_inkernel)) {  // no statistics launch behind this one: the GEMM itself touches the weights
+        g.lnf_rows = rows;  // (M = rows_g: the padding rows stay out of the range guard)
+        if (rows <= g_w_prefetch && r16 && g_w_prefetch && consumer_inkernel) {  // no statistics launch behind this one: the GEMM itself touches the weights
             g.pf_p[0] = pf.p[0]; g.pf_n[0] = pf.n[0]; g.pf_p[1] = pf.p[1]; g.pf_n[1] = pf.n[1];
         }
     };
-    // consumer side of site k: finalized statistics (by the producer, or one more launch, which also prefetches `pf`) or the in-kernel form
+    // consumer side of site k: statistics finalized by one more launch, which also prefetches `pf`, or the in-kernel form
     auto lnf_consumer = [&](GemmParams& g, int k, bool inkernel, int site, int tag, const PrefetchSet* pf) -> int {
         const float* pivots = k > 0 ? lnfS[(k - 1) & 1] : nullptr;
         g.lnf_rows = rows;  // (M = rows_g: the padding rows stay out of lnf_stats_out and the range guard)
-        if (!inkernel && fin_site[k & 1]) {
-            g.lnf_stats = lnfS[k & 1];
-        } else if (!inkernel) {
+        if (!inkernel) {
             F5_TRY(timed(p, site, st, [&] {
                 return launch_stats_finalize(p->lnf_partial, (int)p->rows_cap, D / 64, rows, D, pivots, lnfS[k & 1], sat, tag, st, pf);
             }));
@@ -184,7 +182,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         if (lnf1) {
             g.A = p->xres16; g.W = fW; g.bias = nullptr;
             g.lnf_c1 = fc1; g.lnf_c2 = fc2;
-            F5_TRY(lnf_consumer(g, 2 * l - 1, ink_qkv, F5_SITE_LN1, 1 | (l << 4), wpf ? &pf1f_prev : nullptr));
+            F5_TRY(lnf_consumer(g, 2 * l - 1, ink.qkv, F5_SITE_LN1, 1 | (l << 4), wpf ? &pf1f_prev : nullptr));
         }
         // Tile quantisation at small batches: the fused projection has 12 feature tiles per token tile; when the q|k part alone (8 tiles
         // per token tile) fills the CUs a whole number of times but q|k|v does not (M = 8192, 4 utterances x 1024 frames x CFG: 256 + 128
@@ -253,7 +251,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
             g.add2_f16 = 1;
         }
         // partial row sums of the updated stream (site 2l); pivot = the row's previous mean (none yet at site 0: the tables are this evaluation's)
-        if (lnf) lnf_producer(g, 2 * l, 2 | (l << 4), pf2f, ink_ff1);  // (prefetch: the weights of FF1 and FF2)
+        if (lnf) lnf_producer(g, 2 * l, pf2f, ink.ff1);  // (prefetch: the weights of FF1 and FF2)
         F5_TRY(timed(p, F5_SITE_OUT, st, [&] { return run_gemm(p, g, GEMM_DENSE, rmw ? EPI_RESID : EPI_GATE_T, st); }));
         // x += y; n2 = LN(x) * (1 + scale_mlp) + shift_mlp
         if (!lnf) F5_TRY(timed(p, F5_SITE_LN2, st, [&] {
@@ -269,7 +267,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         if (lnf) {
             g.A = p->xres16; g.W = fW + (size_t)3 * inner * D * 2; g.bias = nullptr;
             g.lnf_c1 = fc1 + 3 * inner; g.lnf_c2 = fc2 + 3 * inner;
-            F5_TRY(lnf_consumer(g, 2 * l, ink_ff1, F5_SITE_LN2, 2 | (l << 4), wpf ? &pf2f : nullptr));
+            F5_TRY(lnf_consumer(g, 2 * l, ink.ff1, F5_SITE_LN2, 2 | (l << 4), wpf ? &pf2f : nullptr));
         }
         F5_TRY(timed(p, F5_SITE_FF1, st, [&] { return run_gemm(p, g, GEMM_DENSE, EPI_STORE_T, st); }));
         // y = gate_mlp * ff(n2)  (modules.py:639)
@@ -283,7 +281,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
             g.add2_f16 = 1;
         }
         const bool lnf_next = lnf && l + 1 < c.depth;  // (the final AdaLN pass reads the stream itself)
-        if (lnf_next) lnf_producer(g, 2 * l + 1, 1 | ((l + 1) << 4), pf1f, ink_qkv);  // site 2l + 1 (prefetch: the next block's q|k|v weights and its out-projection)
+        if (lnf_next) lnf_producer(g, 2 * l + 1, pf1f, ink.qkv);  // site 2l + 1 (prefetch: the next block's q|k|v weights and its out-projection)
         F5_TRY(timed(p, F5_SITE_FF2, st, [&] { return run_gemm(p, g, GEMM_DENSE, rmw ? EPI_RESID : EPI_GATE_T, st); }));
         pf1f_prev = pf1f;  // (what a statistics launch in front of the next block's QKV projection prefetches)
     }

@@ -46,8 +46,8 @@ struct GemmParams {
     const float* gate;  // EPI_RESID: gate[b * gate_bstride + n] or null (=1)
     int gate_bstride;
     int rows_per_batch;      // sequence length N_seq: b(m) = m / rows_per_batch, position = m % rows_per_batch
-    int row0;                // tuned kernel: global row index of this launch's row 0 (a launch split into a whole-tile part and a ragged tail: the
-                             // tail's positions / batch indices continue where the first part ended; set by the launcher)
+    int row0;                // tuned kernel: global row index of this launch's row 0 (positions, batch indices and lnf_rows count from it); nothing
+                             // sets it now: every launch starts at row 0
     const uint8_t* rowmask;  // [M] or null
     const uint8_t* rowbits;  // optional transposed form of rowmask for the tuned kernel's epilogue (launch_rowbits): byte [m/128][m%16], bit (m%128)/16
     const float* rope;       // [N_seq][32][2] (cos, sin)
@@ -81,15 +81,8 @@ struct GemmParams {
     float* stats_out;
     int stats_ld;                // rows per 64-feature plane of stats_out
     const float* stats_pivot;    // [M][2]: element 0 of row m is the pivot (the row's previous mean), or null (pivot 0)
-    // ... and, on the non-persistent schedules, the statistics are FINISHED inside the same launch: the workgroup that completes a block of
-    // token rows last (fin_counter[m0 / BM], one ticket per feature tile) adds the row's partial sums in stats_finalize_kernel's order and stores
-    // (mean, rstd) to fin_stats [M][2] -- no statistics launch behind the GEMM.  Hand-off as /opt/skills/guides/cdna_hip_programming.md section 6,
-    // guideline 16 prescribes for a fan-in: write-through (agent-scope) partial stores, every wave drained, workgroup barrier, one relaxed agent-scope
-    // ticket; the last arriver acquires once and reads the partials with agent-scope loads; it also resets the ticket word.  Range guard: lnf_sat / lnf_sat_tag.
-    unsigned* fin_counter;
-    float* fin_stats;
     // rows (global index, as row0) that hold tokens, 0 = all M: a launch over rows padded up to whole tiles (dit_eval: rows_g) computes the padded
-    // rows' statistics for its own epilogue, but stores none of them (lnf_stats_out, fin_stats) and keeps them out of the range guard
+    // rows' statistics for its own epilogue, but stores none of them (lnf_stats_out) and keeps them out of the range guard
     int lnf_rows;
     int tile_group;  // tuned kernel: token tiles per L2 patch (set by the launcher)
     int tile_reverse;  // tuned kernel: walk the tiles in the opposite order (producer / consumer cache experiments)
@@ -105,9 +98,6 @@ bool gemm_fast_supported(const GemmParams& p, int precision, int mode, int epi);
 void gemm_fast_tile(const GemmParams& p, int* bm, int* bn);
 // LayerNorm fold: true when a launch of this shape can take its row statistics from the partial sums inside the kernel (every tile but 256 x 256)
 bool gemm_fast_lnf_inkernel(const GemmParams& p);
-// LayerNorm fold: true when an in-place residual launch with these parameters can finish its row statistics inside the launch
-// (GemmParams::fin_counter): every schedule but the PERSISTENT one, which leaves them to stats_finalize_kernel
-bool gemm_fast_resid_finishes(const GemmParams& p);
 // true when a dense launch with these parameters runs on the one-wave-per-SIMD kernel (gemm_w4.hip): whole tiles, at least one per CU, lean operand forms
 bool gemm_w4_ok(const GemmParams& p, int mode, int epi);
 // LayerNorm fold: a folded projection of this shape finishes the row statistics inside the one-wave-per-SIMD kernel (128-row tiles)

@@ -379,13 +379,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
         float t = a0 + b0, z = 0.0f;
         asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(t), "+v"(z));
         const float tot = t + z;
-        if (fq < 2 && row_ok) {
-            float* dst = p.stats_out + ((size_t)((n0 + wn * WN) >> 6) * p.stats_ld + m) * 2 + fq;
-            if (p.fin_counter)  // read by another workgroup of THIS launch: agent-scope (write-through) store
-                __hip_atomic_store(dst, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else
-                *dst = tot;
-        }
+        if (fq < 2 && row_ok) p.stats_out[((size_t)((n0 + wn * WN) >> 6) * p.stats_ld + m) * 2 + fq] = tot;
     };
     [[maybe_unused]] auto h_round4 = [](const f32x4& v) {  // what the fp16 stream holds after a saturating store of v
         f32x4 r;
@@ -940,65 +934,12 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
     }
 
     epilogue();
-    if constexpr (EPI == EPI_RESID && !PERSIST && !LNF) {
-        if (p.fin_counter) {
-            // LayerNorm fold: finish the row statistics of this block of token rows in the launch (gemm.h: fin_counter).  Every wave has stored
-            // its partial sums write-through; drain them, meet, draw ONE ticket per workgroup; the workgroup that draws the last one owns the block.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            unsigned* flag = reinterpret_cast<unsigned*>(smem);  // (the operand ring is dead: every wave is past its last fragment read)
-            if (tid == 0) *flag = __hip_atomic_fetch_add(p.fin_counter + m0 / BM, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            if (*flag == (unsigned)(tiles_n - 1)) {
-                if (tid == 0) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(p.fin_counter + m0 / BM, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-                }
-                __syncthreads();
-                bool bad = false;
-                float sumsq = 0.f;
-                const int m = m0 + tid;
-                if (tid < BM && m < p.M && (p.lnf_rows == 0 || m + p.row0 < p.lnf_rows)) {  // (padding rows: no statistics, no guard)
-                    const int ncols = p.N >> 6;
-                    float s1 = 0.f, s2 = 0.f;
-                    if (ncols == 16) {
-                        float v1[16], v2[16];
-#pragma unroll
-                        for (int c = 0; c < 16; ++c) {
-                            const float* src = p.stats_out + ((size_t)c * p.stats_ld + m) * 2;
-                            v1[c] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            v2[c] = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-#pragma unroll
-                        for (int c = 0; c < 16; ++c) {
-                            s1 += v1[c];
-                            s2 += v2[c];
-                        }
-                    } else {
-                        for (int c = 0; c < ncols; ++c) {
-                            const float* src = p.stats_out + ((size_t)c * p.stats_ld + m) * 2;
-                            s1 += __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            s2 += __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                    }
-                    const float pv = p.stats_pivot ? p.stats_pivot[(size_t)m * 2] : 0.0f;
-                    float mean, rstd;
-                    lnf_row_stats(s1, s2, pv, p.N, mean, rstd, sumsq);
-                    *reinterpret_cast<f32x2*>(p.fin_stats + (size_t)m * 2) = f32x2{mean, rstd};
-                    bad = !(sumsq < 65504.0f * 65504.0f);
-                }
-                lnf_raise_guard(p.lnf_sat, bad, sumsq, p.lnf_sat_tag, m + p.row0);
-            }
-        }
-    }
     clk_end();
 }
 
 #ifdef F5_LNF_TU
 extern unsigned long long* g_gemm_clk_buf;
-extern int g_gemm_variant, g_gemm_group, g_gemm_persist_grid, g_gemm_persist, g_gemm_reverse_sites, g_gemm_group_sites, g_gemm_tile, g_gemm_bm128, g_gemm_lean,
-    g_gemm_split_tail;
+extern int g_gemm_variant, g_gemm_group, g_gemm_persist_grid, g_gemm_persist, g_gemm_reverse_sites, g_gemm_group_sites, g_gemm_tile, g_gemm_bm128, g_gemm_lean;
 int gemm_persist_grid();
 static int persist_grid() { return gemm_persist_grid(); }
 #else
@@ -1027,7 +968,6 @@ int g_gemm_group_sites = 0;  // diagnostic knob ("gemm_group_sites"): patch heig
 int g_gemm_tile = 0;   // diagnostic knob ("gemm_tile"): bm * 1000 + bn forces the tile of every tuned-GEMM launch that supports it (0 = by shape)
 int g_gemm_bm128 = 1;  // tuning knob ("gemm_bm128"): 128-row token tiles when the 256-row ones leave CUs without a workgroup (single-utterance launches)
 int g_gemm_lean = 1;   // tuning knob ("gemm_lean"): 1 = lean epilogue on whole tiles, 0 = generic epilogue everywhere
-int g_gemm_split_tail = 0;  // tuning knob ("gemm_split_tail"): 1 = M % 256 != 0 launches run as persistent whole tiles + a tail launch.  Measured a LOSS (the tail launch is pure latency: 8 x 1001 346 vs 288 ms); off.  dit_eval rounds the rows up instead ("gemm_pad_rows")
 
 static int persist_grid() { return gemm_persist_grid(); }
 #endif
@@ -1069,34 +1009,6 @@ template <int BN, int WM, int MODE, int EPI, bool LNF = false> static int launch
     const bool resid_ok = EPI == EPI_RESID && p.add2_f16 && p.out_f && (p.ldof & 7) == 0 && p.act == ACT_NONE && (!p.gate || p.gate_bstride == 0) &&
                           (!p.rowmask || p.rowbits);  // in-place update of the fp16 residual stream
     const bool persist_ok = MODE == GEMM_DENSE && (store_ok || resid_ok) && p.M % 256 == 0 && p.K >= 128 && p.N % 256 == 0 && (p.bias || LNF);
-    if constexpr (BN == 256 && MODE == GEMM_DENSE && (EPI == EPI_STORE_T || EPI == EPI_GATE_T || EPI == EPI_ROPE_T || EPI == EPI_RESID)) {
-        // A token count that is not a multiple of the tile height (8 x 1001 frames): the whole tiles go to the persistent schedule like any
-        // other launch, the < 256 tail rows to a launch of their own on 128-wide tiles (generic epilogue).  Every accumulator sums K in the
-        // same order whatever the tile and the lean and generic epilogues round alike, so the values do not depend on the split.  (Round 3
-        // sent the WHOLE launch to the non-persistent schedule, whose QKV + RoPE build spilled: VERDICT round 3, item 3.)
-        if (g_gemm_variant != 0 && g_gemm_persist && g_gemm_split_tail && !persist_ok && p.M > 256 && p.M % 256 != 0 && p.a_row_mod == 0 && p0.row0 == 0 &&
-            MODE == GEMM_DENSE && (store_ok || resid_ok) && p.K >= 128 && p.N % 256 == 0 && (p.bias || LNF)) {
-            const int mw = p.M / 256 * 256;
-            GemmParams pw = p0, pt = p0;
-            pw.M = mw;
-            pt.M = p.M - mw;
-            pt.row0 = mw;
-            pt.A = static_cast<const char*>(p.A) + (size_t)mw * p.lda * 2;
-            if (p.out_t) pt.out_t = static_cast<char*>(p.out_t) + (size_t)mw * p.ldo * 2;
-            if (p.out_f) pt.out_f = reinterpret_cast<float*>(reinterpret_cast<char*>(p.out_f) + (size_t)mw * p.ldof * (p.add2_f16 ? 2 : 4));
-            if (p.rowmask) pt.rowmask = p.rowmask + mw;
-            if (p.rowbits) pt.rowbits = p.rowbits + (size_t)(mw >> 7) * 16;
-            if (p.lnf_stats) pt.lnf_stats = p.lnf_stats + (size_t)mw * 2;
-            if (p.stats_out) pt.stats_out = p.stats_out + (size_t)mw * 2;
-            if (p.stats_pivot) pt.stats_pivot = p.stats_pivot + (size_t)mw * 2;
-            if (p.lnf_partial) pt.lnf_partial = p.lnf_partial + (size_t)mw * 2;
-            if (p.lnf_pivot) pt.lnf_pivot = p.lnf_pivot + (size_t)mw * 2;
-            if (p.lnf_stats_out) pt.lnf_stats_out = p.lnf_stats_out + (size_t)mw * 2;
-            pw.pf_n[0] = pw.pf_n[1] = 0u;
-            F5_TRY((launch_fast<BN, WM, MODE, EPI, LNF>(pw, stream)));
-            return launch_fast<128, 64, MODE, EPI, LNF>(pt, stream);
-        }
-    }
     if constexpr (BN == 256) {
         if (g_gemm_variant == 0)
             hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 0, 4, LNF>), grid, block, 0, stream, p, tiles_n, nblocks);
@@ -1172,15 +1084,6 @@ void gemm_fast_tile(const GemmParams& p, int* pbm, int* pbn) {
     *pbn = bn;
 }
 
-bool gemm_fast_resid_finishes(const GemmParams& p) {
-    int bm, bn;
-    gemm_fast_tile(p, &bm, &bn);
-    const bool resid_ok = p.add2_f16 && p.out_f && (p.ldof & 7) == 0 && p.act == ACT_NONE && (!p.gate || p.gate_bstride == 0) && (!p.rowmask || p.rowbits);
-    const bool persistent = bn == 256 && g_gemm_variant != 0 && g_gemm_persist && resid_ok && p.M % 256 == 0 && p.K >= 128 && p.N % 256 == 0 && p.bias;
-    const bool split = bn == 256 && g_gemm_split_tail && p.M % 256 != 0;  // (whole tiles on the persistent schedule + a tail launch)
-    return !persistent && !split && p.N % 64 == 0 && p.N / 64 <= 64;
-}
-
 bool gemm_fast_lnf_inkernel(const GemmParams& p) {
     int bm, bn;
     gemm_fast_tile(p, &bm, &bn);
@@ -1205,8 +1108,6 @@ int launch_gemm_fast(const GemmParams& p, int mode, int epi, hipStream_t stream)
         if (!p.lnf_c1 || !p.lnf_c2 || (epi != EPI_STORE_T && epi != EPI_ROPE_T)) return f5_fail(F5_EINVAL, "gemm_fast: LayerNorm fold needs c1, c2 and a store / RoPE epilogue");
         return launch_gemm_fast_lnf(p, epi, bm, bn, stream);
     }
-    if (p.fin_counter && (!p.stats_out || !p.fin_stats || epi != EPI_RESID || !gemm_fast_resid_finishes(p)))
-        return f5_fail(F5_ESTATE, "gemm_fast: statistics can be finished inside the launch by the non-persistent in-place residual schedules only");
     if (p.stats_out && (epi != EPI_RESID || !p.add2_f16 || p.N % 64 != 0 || p.stats_ld < p.M))
         return f5_fail(F5_EINVAL, "gemm_fast: row statistics need the in-place fp16 residual epilogue and N % 64 == 0");
 #define F5_FAST_CASE(E)                                                                   \

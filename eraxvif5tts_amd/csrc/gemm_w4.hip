@@ -609,7 +609,6 @@ bool gemm_w4_ok(const GemmParams& p, int mode, int epi) {
     if (p.N % 256 != 0 || p.K % 128 != 0 || p.K < 256 || (p.lda & 7) || (p.ldw & 7) || p.a_row_mod != 0 || p.row0 != 0) return false;
     if (w4_tile_rows(p) == 0) return false;  // small launches: the 8-wave kernel's narrower tiles
     if ((size_t)255 * (size_t)(p.lda > p.ldw ? p.lda : p.ldw) * 2 + 128 > 0x7fffffffull) return false;
-    if (p.fin_counter) return false;  // (weight-prefetch ranges, pf_p: served by the 128-row tile, which is the one small launches take)
     if (p.lnf_partial && !(gemm_w4_lnf_inkernel(p.M, p.N, p.K) != 0 && p.lnf_stats && p.lnf_ncols == 16 && p.lnf_partial_ld >= p.M)) return false;
     const bool lnf = p.lnf_stats != nullptr;
     if (epi == EPI_STORE_T || epi == EPI_ROPE_T) {

@@ -590,23 +590,16 @@ extern "C" int f5_bench_mfma_rate(int random_operands, float* tflops, f5_stream_
     return sync_and_release(a, st, rc);
 }
 
-extern int g_sync_evals, g_attn_persist, g_attn_stagger, g_resid_rmw, g_ln_fold, g_ln_fold_inkernel, g_ln_fold_fin, g_gemm_pad_rows;
+extern int g_sync_evals, g_resid_rmw, g_ln_fold, g_ln_fold_inkernel, g_gemm_pad_rows;
 extern int g_conv31_tok, g_bigvgan_group_frames;
 extern int g_gemm_bm128, g_gemm_tile, g_gemm_group_sites, g_gemm_reverse_sites;
-extern int g_gemm_split_tail, g_gemm_w4, g_gemm_w4_bm, g_gemm_w4_ink;
+extern int g_gemm_w4, g_gemm_w4_bm, g_gemm_w4_ink;
 extern int g_gemm_variant, g_gemm_group, g_gemm_persist_grid, g_gemm_persist, g_gemm_lean, g_ln_defer, g_ln_wide, g_ln_rows, g_ln_rows_min, g_w_prefetch, g_res_f16, g_conv31, g_attn_variant, g_vocos_fft;
 int g_tuning_epoch = 0;
-extern unsigned long long* g_attn_stamp_buf;
 extern unsigned long long* g_gemm_clk_buf;
 // diagnostic: while dev_buf (u64 [workgroups * 4]) is non-null the tuned GEMM writes (s_memtime, s_memrealtime) at workgroup start and end
 extern "C" int f5_debug_gemm_clock(void* dev_buf) {
     g_gemm_clk_buf = reinterpret_cast<unsigned long long*>(dev_buf);
-    return 0;
-}
-// diagnostic: the persistent attention kernel writes shader-clock stamps (wave 0 of every workgroup, first 8 items, 8 stamps each) into
-// `dev_buf` (u64 [workgroups * 64]) while it is non-null
-extern "C" int f5_debug_attn_stamps(void* dev_buf) {
-    g_attn_stamp_buf = reinterpret_cast<unsigned long long*>(dev_buf);
     return 0;
 }
 
@@ -619,14 +612,6 @@ extern "C" int f5_tuning_set(const char* key, int value) {
     }
     if (strcmp(key, "resid_rmw") == 0) {
         g_resid_rmw = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "attn_stagger") == 0) {
-        g_attn_stagger = value;
-        return 0;
-    }
-    if (strcmp(key, "attn_persist") == 0) {
-        g_attn_persist = value != 0;
         return 0;
     }
     if (strcmp(key, "sync_evals") == 0) {
@@ -683,6 +668,7 @@ extern "C" int f5_tuning_set(const char* key, int value) {
         return 0;
     }
     if (strcmp(key, "attn_variant") == 0) {
+        if (value == 6) return f5_fail(F5_EINVAL, "attn_variant 6 (the persistent-grid kernel) was removed: 0 = by grid size, 2 = 64 queries per wave, 5 = pipelined");
         g_attn_variant = value;
         return 0;
     }
@@ -714,16 +700,8 @@ extern "C" int f5_tuning_set(const char* key, int value) {
         g_ln_fold_inkernel = value != 0;
         return 0;
     }
-    if (strcmp(key, "ln_fold_fin") == 0) {
-        g_ln_fold_fin = value != 0;
-        return 0;
-    }
     if (strcmp(key, "ln_fold") == 0) {
         g_ln_fold = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "gemm_split_tail") == 0) {
-        g_gemm_split_tail = value != 0;
         return 0;
     }
     if (strcmp(key, "gemm_w4_ink") == 0) {

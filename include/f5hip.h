@@ -33,7 +33,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: only the entry points declared here are exported */
 #define F5_API __attribute__((visibility("default")))
 
-#define F5HIP_VERSION 400 /* 0.4.0 (round 4; round 5 adds f5_vocoder_decode_ragged, f5_wave_finish and f5_bigvgan_decode_ragged (+ tuning key "bigvgan_group_frames") under the same number, which tests/test_host_logic.py pins: detect them by symbol): + the BigVGAN entry points and mel front-end, f5_op_ln_fold, bounded timing ring; plan options "ln_fold_active", "gemm_w4"; tuning keys "ln_fold", "ln_fold_fin", "gemm_w4"; 0.3.2: + f5_sample_ragged, f5_mmdit_forward, f5_duration_predict_g */
+#define F5HIP_VERSION 400 /* 0.4.0 (round 4; round 5 adds f5_vocoder_decode_ragged, f5_wave_finish and f5_bigvgan_decode_ragged (+ tuning key "bigvgan_group_frames") under the same number, which tests/test_host_logic.py pins: detect them by symbol): + the BigVGAN entry points and mel front-end, f5_op_ln_fold, bounded timing ring; plan options "ln_fold_active", "gemm_w4"; tuning keys "ln_fold", "gemm_w4"; 0.3.2: + f5_sample_ragged, f5_mmdit_forward, f5_duration_predict_g */
 
 /* error codes */
 #define F5_OK 0
@@ -328,9 +328,6 @@ F5_API int f5_bench_attention(int kernel, int B, int N, int H, int iters, float*
 /* Sustained rate of a register-resident v_mfma_f32_16x16x32_bf16 stream on every CU (no memory traffic): random_operands = 0 zeros
  * (clock-limited), 1 pseudo-random bf16 values (power-limited: what a dense bf16 GEMM can approach on this device). */
 F5_API int f5_bench_mfma_rate(int random_operands, float* tflops, f5_stream_t stream);
-/* diagnostic build of the persistent attention kernel: while dev_buf (dev u64 [workgroups * 64]) is non-NULL every launch writes shader-clock
- * stamps of wave 0 (first 8 items of each workgroup: item start, Q prefetch issued, key tiles 0 / 1 / 2 / last done, epilogue done) */
-F5_API int f5_debug_attn_stamps(void* dev_buf);
 /* the clock the chip holds under the tuned GEMM: while dev_buf (dev u64 [workgroups * 4]) is non-NULL every workgroup writes (s_memtime,
  * s_memrealtime) at its start and end; clock = d(s_memtime) / d(s_memrealtime) x 100 MHz */
 F5_API int f5_debug_gemm_clock(void* dev_buf);

@@ -17,7 +17,7 @@ from conftest import rel_l2
 pytestmark = pytest.mark.gpu
 
 DEPTH = 22
-_DEFAULTS = {"gemm_pad_rows": 1, "gemm_w4_ink": 1, "gemm_w4": 1, "ln_fold_inkernel": 0, "ln_fold_fin": 0}
+_DEFAULTS = {"gemm_pad_rows": 1, "gemm_w4_ink": 1, "gemm_w4": 1, "ln_fold_inkernel": 0}
 
 # (B, N) -> (in-kernel statistics on the QKV launch, on the FF1 launch), as measured on the MI355X (256-CU persistent grid) and pinned here through
 # the timing sites.  A folded consumer finishes the statistics itself on the one-wave-per-SIMD kernel's 128-row tiles only where the 8-wave kernel
@@ -154,12 +154,12 @@ def test_padded_launches_equal_every_equivalent_path(models, B, N):
 
 
 def test_padded_launches_with_the_other_statistics_forms(models):
-    """2 x 900 (3600 -> 3840 rows) with the two statistics forms that are off by default: the 8-wave kernel's in-kernel statistics
-    (ln_fold_inkernel = 1) and statistics finished by the producer launch (ln_fold_fin = 1) -- same bits as the default path, no fallback."""
+    """2 x 900 (3600 -> 3840 rows) with the statistics form that is off by default, the 8-wave kernel's in-kernel statistics
+    (ln_fold_inkernel = 1), beside the one-wave-per-SIMD kernel and without it -- same bits as the default path, no fallback."""
     model, cfm = models["bf16"]
     kw = dict(_problem(2, 900, seed=29), steps=3)
     ref = cfm.sample(use_graph=False, **kw)[0].cpu()
-    for kv in ({"ln_fold_inkernel": 1}, {"ln_fold_fin": 1}, {"ln_fold_inkernel": 1, "gemm_w4": 0}, {"ln_fold_fin": 1, "gemm_w4": 0}):
+    for kv in ({"ln_fold_inkernel": 1}, {"ln_fold_inkernel": 1, "gemm_w4": 0}):
         with knobs(**kv):
             out = cfm.sample(use_graph=False, **kw)[0].cpu()
             assert torch.equal(out, ref), kv

@@ -71,6 +71,22 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.f5_version() == 400
 
 
+def test_retired_tuning_keys_are_refused():
+    """The persistent-grid attention kernel, the attention start stagger, the in-launch row statistics of the residual GEMMs and the
+    whole-tiles + tail split were removed with their knobs: f5_tuning_set must say so (F5_EINVAL) instead of accepting a key that selects
+    nothing.  The surviving values of the same families still set."""
+    from eraxvif5tts_amd import _lib
+    lib = _lib.load(build_if_missing=True)
+    F5_EINVAL = -1  # include/f5hip.h
+    for key, value in (("attn_persist", 1), ("attn_stagger", 4), ("ln_fold_fin", 1), ("gemm_split_tail", 1), ("attn_variant", 6)):
+        assert lib.f5_tuning_set(key.encode(), value) == F5_EINVAL, (key, value)
+    try:
+        assert lib.f5_tuning_set(b"attn_variant", 2) == 0
+        assert lib.f5_tuning_set(b"ln_fold_inkernel", 0) == 0
+    finally:
+        assert lib.f5_tuning_set(b"attn_variant", 0) == 0
+
+
 def test_product_path_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
