@@ -107,18 +107,20 @@ __global__ __launch_bounds__(256) void attn_ref_kernel(const T* __restrict__ qkv
     }
 }
 
-int launch_attention_fast(int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride);  // attention_fast.hip
+int launch_attention_fast(int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                          int qscaled);  // attention_fast.hip
 
 int launch_attention(int precision, int kernel_kind, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo,
-                     hipStream_t stream, int bstride) {
+                     hipStream_t stream, int bstride, int qscaled) {
     if (B <= 0 || N <= 0 || H <= 0) return 0;
     if (bstride <= 0) bstride = N;
     if (bstride < N || (bstride != N && mask)) return f5_fail(F5_EINVAL, "attention: batch stride below N, or a key mask with a batch stride");
     if (kernel_kind == 1) {
         if (!attention_fast_supported(precision, N, H)) return f5_fail(F5_EINVAL, "attention: tuned kernel does not support this problem");
-        return launch_attention_fast(B, N, H, qkv, ldq, mask, out, ldo, stream, bstride);
+        return launch_attention_fast(B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
     }
-    const float scale = 0.125f;  // 1/sqrt(64) (SDPA default scale, modules.py:490)
+    // 1/sqrt(64) (SDPA default scale, modules.py:490); pre-scaled q carries 1/sqrt(64) * log2(e): exp(s ln 2) = exp2(s)
+    const float scale = qscaled ? 0.6931471805599453f : 0.125f;
     dim3 grid(cdiv(N, 64), H, B), block(256);
     if (precision == F5_PREC_BF16)
         hipLaunchKernelGGL((attn_ref_kernel<bf16_t>), grid, block, 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, scale);

@@ -15,6 +15,7 @@
 //     is built with -fno-slp-vectorize (packed fp32 VALU beside MFMAs is slower, MI355X_MICROARCH.md cycle constants).
 // K/V staging, fragment reads and the maximum-free softmax are described at the kernel.
 #include "kernels.h"
+#include <type_traits>
 
 typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
@@ -43,13 +44,37 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& s, int base) {
 //     recomputed from the K tile still in LDS, exact running maximum, rescale of O and l.  The first tile of a block sets the reference
 //     to its exact maximum (nothing to rescale yet).  With that the 22-deep max3 chain in front of the exponentials is gone from the
 //     steady state (-8 % on its own).
-template <bool MASKED>
+//   * QS build (q arrives multiplied by softmax_scale * log2 e: the scale sits in the weights that project q): the
+//     reference is ZERO.  P = exp2(s), no first-tile maximum, no fma in front of the exponential.  Two guards keep the range:
+//       high side -- the same per-tile test !(rs < 2^64).  The wave takes the classic step in place (m_run starts at 0, so the new
+//         reference is max(0, row maximum)) and from then on runs the subtracting build of the loop (wave-uniform: a branch, no select);
+//       low side -- a row whose every score is far below zero underflows against reference 0.  Once per item, behind the last tile: any
+//         query whose l is not >= 2^-64 (0 and NaN included) raises one LDS word, one barrier, and the WHOLE workgroup (the four waves
+//         share the DMA ring and its barriers) runs the item again the way the other build does: exact first-tile maximum, subtracting
+//         numerators.  A tile that underflows inside a row whose total is >= 2^-64 holds less than 2^-60 of the row (64 keys x 2^-126
+//         against 2^-64): nothing to do.  A fully masked tile gives rs = 0 legitimately; only the end-of-item test decides.
+//     Bounds (both builds): per-lane tile sums stay below 2^64 or the classic step runs, so l_run < nt * 2^64 (2^68 at N = 1024, 2^71 at
+//     the 128 tiles of the masked build) and |O| < nt * 2^65 * max|v| per element (two half-waves of keys per tile): inside fp32.
+#ifdef F5_ATTN_GUARD_COUNT  // diagnostic build only (tools/attn_guard_count.py): how often the QS build's two guards fire
+__device__ unsigned g_attn_guard_count[3];  // [0] items (workgroups) of the QS build, [1] high-side trips (waves), [2] low-side re-runs (workgroups)
+extern "C" __attribute__((visibility("default"))) int f5_debug_attn_guard_counts(unsigned* out3, int reset) {
+    if (out3 && hipMemcpyFromSymbol(out3, HIP_SYMBOL(g_attn_guard_count), sizeof(g_attn_guard_count)) != hipSuccess) return -1;
+    const unsigned zero[3] = {0u, 0u, 0u};
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_attn_guard_count), zero, sizeof(zero)) != hipSuccess) return -1;
+    return 0;
+}
+#define F5_GUARD_COUNT(i, who) \
+    if (who) atomicAdd(&g_attn_guard_count[i], 1u)
+#else
+#define F5_GUARD_COUNT(i, who)
+#endif
+template <bool MASKED, bool QS>
 __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restrict__ qkv, int ldq, int inner, const uint8_t* __restrict__ mask,
                                                            bf16_t* __restrict__ out, int ldo, int N, int bs /* rows between batch items */, float c) {
     constexpr int KT = 64, QB = 2, TB = KT * 128, NBUF = 3, BUF = 2 * TB, WAVES = 4;
     constexpr int PCS = 8 / WAVES;  // K (and V) pieces per wave per tile
     constexpr int MAXT = 128;  // tiles whose key validity bits fit the LDS table (launcher: N <= 64 * MAXT when masked)
-    __shared__ __attribute__((aligned(1024))) char smem[NBUF * BUF + (MASKED ? MAXT * 8 : 0)];
+    __shared__ __attribute__((aligned(1024))) char smem[NBUF * BUF + (MASKED ? MAXT * 8 : 0) + (QS ? 16 : 0)];
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -68,6 +93,12 @@ __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restr
     const bf16_t* kbase = base + inner;
     const bf16_t* vbase = base + 2 * inner;
     const int nt = (N + KT - 1) / KT;
+    if constexpr (QS) c = 1.0f;  // the scale is in q
+    unsigned* const vote = reinterpret_cast<unsigned*>(smem + NBUF * BUF + (MASKED ? MAXT * 8 : 0));  // QS: the low-side guard's word
+    if constexpr (QS) {
+        if (tid == 0) *vote = 0u;  // (published by the prologue's barrier)
+        F5_GUARD_COUNT(0, tid == 0);
+    }
 
     // ---- key validity bits of every tile (masked build): one 64-bit word per tile in LDS, written before any DMA is in flight
     unsigned long long* mbits = reinterpret_cast<unsigned long long*>(smem + NBUF * BUF);
@@ -145,196 +176,262 @@ __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restr
 
     f32x16 o_acc[QB][2];
     float m_run[QB], l_run[QB];
-#pragma unroll
-    for (int j = 0; j < QB; ++j) {
-        m_run[j] = -1e30f;
-        l_run[j] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o_acc[j][0][i] = o_acc[j][1][i] = 0.f;
-    }
-    // ---- prologue: tiles 0 .. NBUF-2 on their way, tile 0 published
     constexpr int DIST = NBUF - 1;  // tiles requested ahead
-#define F5_VMWAIT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-    dma_tile(0, 0);
-    if (nt > 1) dma_tile(KT, 1);
-    {
-        const int ahead = min(nt, DIST) - 1;  // tiles requested after tile 0
-        if (ahead == 0) F5_VMWAIT(0);
-        else if (ahead == 1) F5_VMWAIT(2 * PCS);
-        else F5_VMWAIT(4 * PCS);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the validity words
-    __builtin_amdgcn_s_barrier();
-
     constexpr float RANGE_GUARD = 18446744073709551616.0f;  // 2^64: per-lane row sums of one tile at or above this take the classic path
+    constexpr float LOW_GUARD = 5.421010862427522e-20f;     // 2^-64 (QS): a query's l below this sends the item through the classic loop
+#define F5_VMWAIT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
+    bool rerun = false;  // QS: the second pass
     int boff = 0, boff2 = DIST * BUF;  // LDS offsets of tile t's buffer and of tile t+DIST's
-    for (int t = 0; t < nt; ++t) {
-        if (t + DIST < nt) dma_tile((t + DIST) * KT, boff2 / BUF);
-        ka[0] = ka_t;
-        ka[1] = ka_t ^ 32u;
-        ka[2] = ka_t ^ 64u;
-        ka[3] = ka_t ^ 96u;
-
-        // ---- S^T = K . Q^T
-        unsigned long long vmv = ~0ull;  // validity of this tile's 64 keys (the same word in every lane)
-        if constexpr (MASKED) {
-            const unsigned ma = lds0 + NBUF * BUF + 8 * t;
-            asm volatile("ds_read_b64 %0, %1" : "=v"(vmv) : "v"(ma));
+    for (;;) {  // QS: at most two passes (the second is the low-side re-run); the other build leaves after the first
+#pragma unroll
+        for (int j = 0; j < QB; ++j) {
+            m_run[j] = (QS && !rerun) ? 0.f : -1e30f;
+            l_run[j] = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o_acc[j][0][i] = o_acc[j][1][i] = 0.f;
         }
-        bf16x8 kf[4];  // fragments 4..7 reuse the registers of 0..3 as soon as those MFMAs are issued
-        F5_KREAD(kf[0], 0); F5_KREAD(kf[1], 1); F5_KREAD(kf[2], 2); F5_KREAD(kf[3], 3);
-        f32x16 s[QB][2];
-        auto qk = [&](auto& kfr, int n) {
-#pragma unroll
-            for (int j = 0; j < QB; ++j)
-                s[j][n >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr, qf[j][n & 3], (n & 3) ? s[j][n >> 2] : f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        };
-        // scheduling fences pin {wait, two MFMAs, next read} groups: left alone the compiler hoists all eight reads (32 registers) above the MFMAs
-#define F5_FENCE() __builtin_amdgcn_sched_barrier(0)
-        F5_FENCE();
-        F5_LWAIT1(3, kf[0]); qk(kf[0], 0); F5_FENCE(); F5_KREAD(kf[0], 4);
-        F5_LWAIT1(3, kf[1]); qk(kf[1], 1); F5_FENCE(); F5_KREAD(kf[1], 5);
-        F5_LWAIT1(3, kf[2]); qk(kf[2], 2); F5_FENCE(); F5_KREAD(kf[2], 6);
-        F5_LWAIT1(3, kf[3]); qk(kf[3], 3); F5_FENCE(); F5_KREAD(kf[3], 7);
-        F5_LWAIT1(3, kf[0]); qk(kf[0], 4); F5_FENCE();
-        F5_LWAIT1(2, kf[1]); qk(kf[1], 5); F5_FENCE();
-        F5_LWAIT1(1, kf[2]); qk(kf[2], 6); F5_FENCE();
-        F5_LWAIT1(0, kf[3]); qk(kf[3], 7); F5_FENCE();
-        if constexpr (MASKED) F5_LWAIT1(0, vmv);  // ties the validity word to the waits above (it was the oldest read)
-        // V^T fragments of the first PV step fly during the softmax
-        bf16x4 vf[2][2];  // [mb][g]; the fragments of step s+1 reuse the registers as soon as the MFMAs of step s are issued
-        F5_VREAD(vf[0][0], 0, 0, 0); F5_VREAD(vf[0][1], 0, 0, 1); F5_VREAD(vf[1][0], 0, 1, 0); F5_VREAD(vf[1][1], 0, 1, 1);
-
-        auto apply_mask = [&]() {
-            if constexpr (MASKED) {
-                if (__builtin_amdgcn_ballot_w64(vmv != ~0ull) != 0ull) {
-                    const unsigned long long vmh = h ? (vmv >> 4) : vmv;
-#pragma unroll
-                    for (int j = 0; j < QB; ++j)
-#pragma unroll
-                        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                            for (int i = 0; i < 16; ++i) {
-                                const int bit = 32 * kb + (i & 3) + 8 * (i >> 2);
-                                if (!((vmh >> bit) & 1ull)) s[j][kb][i] = -INFINITY;
-                            }
-                }
-            }
-        };
-        apply_mask();
-
-        // ---- softmax numerators.  Common path: against the reference the query already has, no maximum.
-        float rs[QB] = {0.f, 0.f};
-        auto exps = [&](int j) {
-            const float nm = -m_run[j];
-            float ra = 0.f, rb = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; i += 2) {
-                    const float x0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[j][kb][i], c, nm));
-                    const float x1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[j][kb][i + 1], c, nm));
-                    s[j][kb][i] = x0;
-                    s[j][kb][i + 1] = x1;
-                    ra += x0;
-                    rb += x1;
-                }
-            rs[j] = ra + rb;
-        };
-        auto row_max = [&](int j) {  // scaled maximum of query block j's 64 scores (both half-waves)
-            float mx0 = max3_asm(s[j][0][0], s[j][0][1], s[j][0][2]), mx1 = max3_asm(s[j][1][0], s[j][1][1], s[j][1][2]);
-#pragma unroll
-            for (int i = 3; i < 15; i += 2) {
-                mx0 = max3_asm(mx0, s[j][0][i], s[j][0][i + 1]);
-                mx1 = max3_asm(mx1, s[j][1][i], s[j][1][i + 1]);
-            }
-            mx0 = max3_asm(mx0, mx1, s[j][0][15]);
-            const float mt = max3_asm(mx0, s[j][1][15], s[j][1][15]);
-            const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-            return fmaxf(__uint_as_float(r2[0]), __uint_as_float(r2[1])) * c;
-        };
-        if (t == 0) {  // first tile of the block: the reference is its exact maximum (O and l are still zero: nothing to rescale);
-                       // -inf (a fully masked tile) leaves the finite start value alone
-            m_run[0] = fmaxf(m_run[0], row_max(0));
-            m_run[1] = fmaxf(m_run[1], row_max(1));
+        // ---- prologue: tiles 0 .. NBUF-2 on their way, tile 0 published
+        int k0z = 0;  // laundered (QS): keeps the prologue's DMA addresses from being hoisted out of the pass loop and held across the tile loops
+        if constexpr (QS) {
+            asm volatile("" : "+s"(k0z));
+            asm volatile("" : "+v"(kco[0]), "+v"(kco[1]), "+v"(vco[0]), "+v"(vco[1]), "+v"(ka_t), "+v"(va[0]), "+v"(va[1]));
         }
-        exps(0);
-        exps(1);
-        if (__builtin_amdgcn_ballot_w64(!(rs[0] < RANGE_GUARD) || !(rs[1] < RANGE_GUARD)) != 0ull) {
-            // some numerator left the guarded range (a score 64 log2 units above its query's reference, inf or NaN): classic step.  The
-            // scores were overwritten by the numerators: recompute them (the K tile is still in LDS), move the references to the exact
-            // running maxima, rescale O and l
-            bf16x8 k2;  // cold path: one fragment at a time
-#define F5_REDO(n) F5_KREAD(k2, n); F5_LWAIT1(0, k2); qk(k2, n);
-            F5_REDO(0) F5_REDO(1) F5_REDO(2) F5_REDO(3) F5_REDO(4) F5_REDO(5) F5_REDO(6) F5_REDO(7)
-#undef F5_REDO
-            apply_mask();
-#pragma unroll
-            for (int j = 0; j < QB; ++j) {
-                const float m_new = fmaxf(m_run[j], row_max(j));
-                const float alpha = __builtin_amdgcn_exp2f(m_run[j] - m_new);
-                m_run[j] = m_new;
-                l_run[j] *= alpha;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    o_acc[j][0][i] *= alpha;
-                    o_acc[j][1][i] *= alpha;
-                }
-                exps(j);
-            }
-        }
-        l_run[0] += rs[0];
-        l_run[1] += rs[1];
-
-        // ---- O^T += V^T . P^T: four 16-key steps; each half (32 dims) of the V^T fragment is re-requested for the next step right after
-        //      its two MFMAs are issued
-        auto pv_half = [&](int st, int mb, const bf16x8 (&pf)[QB]) {
-            const bf16x8 vfr = __builtin_shufflevector(vf[mb][0], vf[mb][1], 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-            for (int j = 0; j < QB; ++j) o_acc[j][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr, pf[j], o_acc[j][mb], 0, 0, 0);
-        };
-#define F5_PV(st, more)                                                                       \
-    {                                                                                         \
-        bf16x8 pf[QB];                                                                        \
-        pf[0] = pack8(s[0][(st) >> 1], 8 * ((st) & 1));                                       \
-        pf[1] = pack8(s[1][(st) >> 1], 8 * ((st) & 1));                                       \
-        F5_FENCE();                                                                           \
-        F5_LWAIT2(2, vf[0][0], vf[0][1]);                                                     \
-        pv_half(st, 0, pf);                                                                   \
-        F5_FENCE();                                                                           \
-        if constexpr (more) {                                                                 \
-            F5_VREAD(vf[0][0], (st) + 1, 0, 0);                                               \
-            F5_VREAD(vf[0][1], (st) + 1, 0, 1);                                               \
-        }                                                                                     \
-        F5_LWAIT2((more) ? 2 : 0, vf[1][0], vf[1][1]);                                        \
-        pv_half(st, 1, pf);                                                                   \
-        F5_FENCE();                                                                           \
-        if constexpr (more) {                                                                 \
-            F5_VREAD(vf[1][0], (st) + 1, 1, 0);                                               \
-            F5_VREAD(vf[1][1], (st) + 1, 1, 1);                                               \
-        }                                                                                     \
-    }
-        F5_PV(0, true)
-        F5_PV(1, true)
-        F5_PV(2, true)
-        F5_PV(3, false)
-#undef F5_PV
-
-        // ---- publish tile t+1 (requested a whole tile ago) and retire this tile's buffer: every LDS read of this wave has been waited for
-        {  // tile t+1 must have landed: the tiles requested after it may stay in flight
-            const int ahead = min(nt - 1, t + DIST) - (t + 1);
-            if (ahead <= 0) F5_VMWAIT(0);
+        dma_tile(k0z, 0);
+        if (nt > 1) dma_tile(KT + k0z, 1);
+        {
+            const int ahead = min(nt, DIST) - 1;  // tiles requested after tile 0
+            if (ahead == 0) F5_VMWAIT(0);
             else if (ahead == 1) F5_VMWAIT(2 * PCS);
             else F5_VMWAIT(4 * PCS);
         }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the validity words
         __builtin_amdgcn_s_barrier();
-        const int step = boff + BUF == NBUF * BUF ? -(NBUF - 1) * BUF : BUF;  // wave-uniform
-        boff += step;
-        ka_t += step;
-        va[0] += step;
-        va[1] += step;
-        boff2 = boff2 + BUF == NBUF * BUF ? 0 : boff2 + BUF;
+
+        // one K/V tile; REFD = the numerators subtract m_run (the only form of the other build).  Returns whether the classic step ran.
+        auto tile = [&](auto refd_c, const int t) -> bool {
+            constexpr bool REFD = decltype(refd_c)::value;
+            bool tripped = false;
+            if (t + DIST < nt) dma_tile((t + DIST) * KT, boff2 / BUF);
+            ka[0] = ka_t;
+            ka[1] = ka_t ^ 32u;
+            ka[2] = ka_t ^ 64u;
+            ka[3] = ka_t ^ 96u;
+
+            // ---- S^T = K . Q^T
+            unsigned long long vmv = ~0ull;  // validity of this tile's 64 keys (the same word in every lane)
+            if constexpr (MASKED) {
+                const unsigned ma = lds0 + NBUF * BUF + 8 * t;
+                asm volatile("ds_read_b64 %0, %1" : "=v"(vmv) : "v"(ma));
+            }
+            bf16x8 kf[4];  // fragments 4..7 reuse the registers of 0..3 as soon as those MFMAs are issued
+            F5_KREAD(kf[0], 0); F5_KREAD(kf[1], 1); F5_KREAD(kf[2], 2); F5_KREAD(kf[3], 3);
+            f32x16 s[QB][2];
+            auto qk = [&](auto& kfr, int n) {
+#pragma unroll
+                for (int j = 0; j < QB; ++j)
+                    s[j][n >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr, qf[j][n & 3], (n & 3) ? s[j][n >> 2] : f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            };
+            // scheduling fences pin {wait, two MFMAs, next read} groups: left alone the compiler hoists all eight reads (32 registers) above the MFMAs
+#define F5_FENCE() __builtin_amdgcn_sched_barrier(0)
+            F5_FENCE();
+            F5_LWAIT1(3, kf[0]); qk(kf[0], 0); F5_FENCE(); F5_KREAD(kf[0], 4);
+            F5_LWAIT1(3, kf[1]); qk(kf[1], 1); F5_FENCE(); F5_KREAD(kf[1], 5);
+            F5_LWAIT1(3, kf[2]); qk(kf[2], 2); F5_FENCE(); F5_KREAD(kf[2], 6);
+            F5_LWAIT1(3, kf[3]); qk(kf[3], 3); F5_FENCE(); F5_KREAD(kf[3], 7);
+            F5_LWAIT1(3, kf[0]); qk(kf[0], 4); F5_FENCE();
+            F5_LWAIT1(2, kf[1]); qk(kf[1], 5); F5_FENCE();
+            F5_LWAIT1(1, kf[2]); qk(kf[2], 6); F5_FENCE();
+            F5_LWAIT1(0, kf[3]); qk(kf[3], 7); F5_FENCE();
+            if constexpr (MASKED) F5_LWAIT1(0, vmv);  // ties the validity word to the waits above (it was the oldest read)
+            // V^T fragments of the first PV step fly during the softmax
+            bf16x4 vf[2][2];  // [mb][g]; the fragments of step s+1 reuse the registers as soon as the MFMAs of step s are issued
+            F5_VREAD(vf[0][0], 0, 0, 0); F5_VREAD(vf[0][1], 0, 0, 1); F5_VREAD(vf[1][0], 0, 1, 0); F5_VREAD(vf[1][1], 0, 1, 1);
+
+            auto apply_mask = [&]() {
+                if constexpr (MASKED) {
+                    if (__builtin_amdgcn_ballot_w64(vmv != ~0ull) != 0ull) {
+                        const unsigned long long vmh = h ? (vmv >> 4) : vmv;
+#pragma unroll
+                        for (int j = 0; j < QB; ++j)
+#pragma unroll
+                            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                                for (int i = 0; i < 16; ++i) {
+                                    const int bit = 32 * kb + (i & 3) + 8 * (i >> 2);
+                                    if (!((vmh >> bit) & 1ull)) s[j][kb][i] = -INFINITY;
+                                }
+                    }
+                }
+            };
+            apply_mask();
+
+            // ---- softmax numerators.  Common path: against the reference the query already has, no maximum.
+            float rs[QB] = {0.f, 0.f};
+            auto exps0 = [&](int j) {  // QS, reference 0
+                float ra = 0.f, rb = 0.f;
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 16; i += 2) {
+                        const float x0 = __builtin_amdgcn_exp2f(s[j][kb][i]);
+                        const float x1 = __builtin_amdgcn_exp2f(s[j][kb][i + 1]);
+                        s[j][kb][i] = x0;
+                        s[j][kb][i + 1] = x1;
+                        ra += x0;
+                        rb += x1;
+                    }
+                rs[j] = ra + rb;
+            };
+            auto exps = [&](int j) {
+                const float nm = -m_run[j];
+                float ra = 0.f, rb = 0.f;
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 16; i += 2) {
+                        const float x0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[j][kb][i], c, nm));
+                        const float x1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[j][kb][i + 1], c, nm));
+                        s[j][kb][i] = x0;
+                        s[j][kb][i + 1] = x1;
+                        ra += x0;
+                        rb += x1;
+                    }
+                rs[j] = ra + rb;
+            };
+            auto row_max = [&](int j) {  // scaled maximum of query block j's 64 scores (both half-waves)
+                float mx0 = max3_asm(s[j][0][0], s[j][0][1], s[j][0][2]), mx1 = max3_asm(s[j][1][0], s[j][1][1], s[j][1][2]);
+#pragma unroll
+                for (int i = 3; i < 15; i += 2) {
+                    mx0 = max3_asm(mx0, s[j][0][i], s[j][0][i + 1]);
+                    mx1 = max3_asm(mx1, s[j][1][i], s[j][1][i + 1]);
+                }
+                mx0 = max3_asm(mx0, mx1, s[j][0][15]);
+                const float mt = max3_asm(mx0, s[j][1][15], s[j][1][15]);
+                const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
+                return fmaxf(__uint_as_float(r2[0]), __uint_as_float(r2[1])) * c;
+            };
+            if constexpr (!REFD) {
+                exps0(0);
+                exps0(1);
+            } else {
+                if (t == 0 && (!QS || rerun)) {  // first tile of the block: the reference is its exact maximum (O and l are still zero: nothing to
+                                                 // rescale); -inf (a fully masked tile) leaves the finite start value alone
+                    m_run[0] = fmaxf(m_run[0], row_max(0));
+                    m_run[1] = fmaxf(m_run[1], row_max(1));
+                }
+                exps(0);
+                exps(1);
+            }
+            if (__builtin_amdgcn_ballot_w64(!(rs[0] < RANGE_GUARD) || !(rs[1] < RANGE_GUARD)) != 0ull) {
+                // some numerator left the guarded range (a score 64 log2 units above its query's reference, inf or NaN): classic step.  The
+                // scores were overwritten by the numerators: recompute them (the K tile is still in LDS), move the references to the exact
+                // running maxima, rescale O and l
+                bf16x8 k2;  // cold path: one fragment at a time
+#define F5_REDO(n) F5_KREAD(k2, n); F5_LWAIT1(0, k2); qk(k2, n);
+                F5_REDO(0) F5_REDO(1) F5_REDO(2) F5_REDO(3) F5_REDO(4) F5_REDO(5) F5_REDO(6) F5_REDO(7)
+#undef F5_REDO
+                apply_mask();
+#pragma unroll
+                for (int j = 0; j < QB; ++j) {
+                    const float m_new = fmaxf(m_run[j], row_max(j));
+                    const float alpha = __builtin_amdgcn_exp2f(m_run[j] - m_new);
+                    m_run[j] = m_new;
+                    l_run[j] *= alpha;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        o_acc[j][0][i] *= alpha;
+                        o_acc[j][1][i] *= alpha;
+                    }
+                    exps(j);
+                }
+                tripped = true;  // (wave-uniform: the ballot decided)
+            }
+            l_run[0] += rs[0];
+            l_run[1] += rs[1];
+
+            // ---- O^T += V^T . P^T: four 16-key steps; each half (32 dims) of the V^T fragment is re-requested for the next step right after
+            //      its two MFMAs are issued
+            auto pv_half = [&](int st, int mb, const bf16x8 (&pf)[QB]) {
+                const bf16x8 vfr = __builtin_shufflevector(vf[mb][0], vf[mb][1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+                for (int j = 0; j < QB; ++j) o_acc[j][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr, pf[j], o_acc[j][mb], 0, 0, 0);
+            };
+#define F5_PV(st, more)                                                                       \
+        {                                                                                         \
+            bf16x8 pf[QB];                                                                        \
+            pf[0] = pack8(s[0][(st) >> 1], 8 * ((st) & 1));                                       \
+            pf[1] = pack8(s[1][(st) >> 1], 8 * ((st) & 1));                                       \
+            F5_FENCE();                                                                           \
+            F5_LWAIT2(2, vf[0][0], vf[0][1]);                                                     \
+            pv_half(st, 0, pf);                                                                   \
+            F5_FENCE();                                                                           \
+            if constexpr (more) {                                                                 \
+                F5_VREAD(vf[0][0], (st) + 1, 0, 0);                                               \
+                F5_VREAD(vf[0][1], (st) + 1, 0, 1);                                               \
+            }                                                                                     \
+            F5_LWAIT2((more) ? 2 : 0, vf[1][0], vf[1][1]);                                        \
+            pv_half(st, 1, pf);                                                                   \
+            F5_FENCE();                                                                           \
+            if constexpr (more) {                                                                 \
+                F5_VREAD(vf[1][0], (st) + 1, 1, 0);                                               \
+                F5_VREAD(vf[1][1], (st) + 1, 1, 1);                                               \
+            }                                                                                     \
+        }
+            F5_PV(0, true)
+            F5_PV(1, true)
+            F5_PV(2, true)
+            F5_PV(3, false)
+#undef F5_PV
+
+            // ---- publish tile t+1 (requested a whole tile ago) and retire this tile's buffer: every LDS read of this wave has been waited for
+            {  // tile t+1 must have landed: the tiles requested after it may stay in flight
+                const int ahead = min(nt - 1, t + DIST) - (t + 1);
+                if (ahead <= 0) F5_VMWAIT(0);
+                else if (ahead == 1) F5_VMWAIT(2 * PCS);
+                else F5_VMWAIT(4 * PCS);
+            }
+            __builtin_amdgcn_s_barrier();
+            const int step = boff + BUF == NBUF * BUF ? -(NBUF - 1) * BUF : BUF;  // wave-uniform
+            boff += step;
+            ka_t += step;
+            va[0] += step;
+            va[1] += step;
+            boff2 = boff2 + BUF == NBUF * BUF ? 0 : boff2 + BUF;
+            return tripped;
+        };
+        // two builds of the loop: reference-free until this wave's first classic step (QS, first pass), subtracting from there on
+        int t = 0;
+        if constexpr (QS) {
+            if (!rerun)
+                while (t < nt)
+                    if (tile(std::false_type{}, t++)) {
+                        F5_GUARD_COUNT(1, lane == 0);
+                        break;
+                    }
+        }
+        for (; t < nt; ++t) tile(std::true_type{}, t);
+        if constexpr (!QS) {
+            break;
+        } else {
+            if (rerun) break;
+            // ---- low-side guard: the loop ended on a barrier with no DMA in flight and every LDS read waited for
+            bool low = false;
+#pragma unroll
+            for (int j = 0; j < QB; ++j) low = low || !(l_run[j] + __shfl_xor(l_run[j], 32, 64) >= LOW_GUARD);
+            if (__builtin_amdgcn_ballot_w64(low) != 0ull && lane == 0) *vote = 1u;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (__builtin_amdgcn_readfirstlane(*vote) == 0u) break;
+            F5_GUARD_COUNT(2, tid == 0);
+            rerun = true;  // the whole item again, classic loop; the ring restarts at buffer 0
+            ka_t -= boff;
+            va[0] -= boff;
+            va[1] -= boff;
+            boff = 0;
+            boff2 = DIST * BUF;
+        }
     }
+#undef F5_GUARD_COUNT
 #undef F5_KREAD
 #undef F5_VREAD
 #undef F5_LWAIT1
@@ -380,10 +477,11 @@ int g_attn_variant = 0;  // tuning knob ("attn_variant"): 0 = by grid size, 2 = 
 
 bool attention_fast_supported(int precision, int N, int H) { return precision == F5_PREC_BF16 && N >= 1 && H >= 1; }
 
-int launch_attention_pipe(int waves, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride);  // attention_pipe.hip
+int launch_attention_pipe(int waves, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                          int qscaled);  // attention_pipe.hip
 
 int launch_attention_pipe_segs(bool masked, int nbr, const AttnSegs& segs, int maxN, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
-                               int bstride);  // attention_pipe.hip
+                               int bstride, int qscaled);  // attention_pipe.hip
 
 static int cu_count_cached() {
     static int cus = 0;
@@ -405,7 +503,7 @@ static bool picks_wide(int B, int N, int H, bool masked, int ldq, int bstride) {
 }
 
 int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& segs, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
-                            int bstride) {
+                            int bstride, int qscaled) {
     if (segs.cnt < 0 || segs.cnt > AttnSegs::MAX || segs.nbr < 1) return f5_fail(F5_EINVAL, "attention_ragged: a table holds at most %d utterances", AttnSegs::MAX);
     const size_t es = precision == F5_PREC_BF16 ? 2 : 4;
     AttnSegs grp[2];  // [0] utterances with n % 64 == 0 (unmasked build), [1] the others -- as each one's own launch would pick
@@ -422,16 +520,16 @@ int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& 
             maxn[masked ? 1 : 0] = std::max(maxn[masked ? 1 : 0], nu);
         } else {  // its own launch: the wide kernel, or the reference kernel
             F5_TRY(launch_attention(precision, kind, segs.nbr, nu, H, (const char*)qkv + (size_t)segs.off[u] * ldq * es, ldq, nullptr,
-                                    (char*)out + (size_t)segs.off[u] * ldo * es, ldo, stream, bstride));
+                                    (char*)out + (size_t)segs.off[u] * ldo * es, ldo, stream, bstride, qscaled));
         }
     }
     for (int k = 0; k < 2; ++k)
-        if (grp[k].cnt > 0) F5_TRY(launch_attention_pipe_segs(k == 1, segs.nbr, grp[k], maxn[k], H, qkv, ldq, out, ldo, stream, bstride));
+        if (grp[k].cnt > 0) F5_TRY(launch_attention_pipe_segs(k == 1, segs.nbr, grp[k], maxn[k], H, qkv, ldq, out, ldo, stream, bstride, qscaled));
     return 0;
 }
 
 int launch_attention_ragged_all(int precision, int attn_kernel_opt, int nbr, int cnt, const int* off, const int* n, int H, const void* qkv, int ldq, void* out,
-                                int ldo, hipStream_t stream, int bstride) {
+                                int ldo, hipStream_t stream, int bstride, int qscaled) {
     for (int u0 = 0; u0 < cnt; u0 += AttnSegs::MAX) {
         AttnSegs sg;
         sg.nbr = nbr;
@@ -439,22 +537,27 @@ int launch_attention_ragged_all(int precision, int attn_kernel_opt, int nbr, int
             sg.off[sg.cnt] = off[u];
             sg.n[sg.cnt++] = n[u];
         }
-        F5_TRY(launch_attention_ragged(precision, attn_kernel_opt, sg, H, qkv, ldq, out, ldo, stream, bstride));
+        F5_TRY(launch_attention_ragged(precision, attn_kernel_opt, sg, H, qkv, ldq, out, ldo, stream, bstride, qscaled));
     }
     return 0;
 }
 
-int launch_attention_fast(int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride) {
+int launch_attention_fast(int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                          int qscaled) {
     if ((ldq & 7) || (ldo & 7)) return f5_fail(F5_EINVAL, "attention_fast: ldq and ldo must be multiples of 8");
     const bool masked = mask != nullptr || (N % 64) != 0;
     const bool wide = picks_wide(B, N, H, masked, ldq, bstride);
-    if (!wide) return launch_attention_pipe(4, B, N, H, qkv, ldq, mask, out, ldo, stream, bstride);
-    const float c = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
+    if (!wide) return launch_attention_pipe(4, B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
+    const float c = qscaled ? 1.0f : F5_ATTN_QSCALE;
     dim3 grid(cdiv(N, 256), H, B);
-    if (masked)
-        hipLaunchKernelGGL((attn_wide_kernel<true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c);
-    else
-        hipLaunchKernelGGL((attn_wide_kernel<false>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c);
+#define F5_WIDE(M_, Q_) \
+    hipLaunchKernelGGL((attn_wide_kernel<M_, Q_>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c)
+    if (masked) {
+        if (qscaled) F5_WIDE(true, true); else F5_WIDE(true, false);
+    } else {
+        if (qscaled) F5_WIDE(false, true); else F5_WIDE(false, false);
+    }
+#undef F5_WIDE
     F5_LAUNCH_CHECK();
     return 0;
 }

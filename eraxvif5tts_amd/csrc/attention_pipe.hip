@@ -439,9 +439,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WPE,
 
 }  // namespace
 
-int launch_attention_pipe(int waves, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride) {
+int launch_attention_pipe(int waves, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                          int qscaled) {
     if (waves != 4) return f5_fail(F5_EINVAL, "attention_pipe: the library instantiates the 4-wave (128 queries per workgroup) build only");
-    const float c = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
+    const float c = qscaled ? 1.0f : F5_ATTN_QSCALE;  // (pre-scaled q: fma(s, 1, -m) is exact)
     const bool masked = mask != nullptr || (N % 64) != 0;
     const dim3 grid(cdiv(N, 128), H, B);
     if (masked)
@@ -454,8 +455,8 @@ int launch_attention_pipe(int waves, int B, int N, int H, const void* qkv, int l
 
 // several utterances (all with N % 64 == 0, or all without) of one ragged batch in ONE launch: grid.z = utterance x branch
 int launch_attention_pipe_segs(bool masked, int nbr, const AttnSegs& segs, int maxN, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
-                               int bstride) {
-    const float c = 0.125f * 1.4426950408889634f;
+                               int bstride, int qscaled) {
+    const float c = qscaled ? 1.0f : F5_ATTN_QSCALE;
     const dim3 grid(cdiv(maxN, 128), H, nbr * segs.cnt);
     if (masked)
         hipLaunchKernelGGL((attn_pipe_kernel<true, 4, 0, 2, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, (const uint8_t*)nullptr, (bf16_t*)out, ldo, maxN,

@@ -98,6 +98,9 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     const FoldTable* ft = p->fold;
     const bool lnf = rmw && g_ln_fold && ft && p->lnf_stats && p->fold_eval >= 0 && p->fold_eval < (int)ft->tv.size() && p->gemm_kernel != 0 &&
                      (p->gemm_kernel == 1 || rows >= 512) && D % 64 == 0 && inner % 64 == 0 && ff % 64 == 0;
+    // pre-scaled q: the table's q rows and block 0's second weight copy carry the softmax scale, the attention kernels apply none
+    const bool qs = lnf && ft->qscaled && plan_attn_prescale(p);
+    if (lnf && ft->qscaled && !qs) return f5_fail(F5_ESTATE, "dit_eval: the fold table holds pre-scaled q rows, the plan runs without them");
     const size_t fR = (size_t)m->fold_R, frow0 = lnf ? ((size_t)p->fold_eval * c.depth) * fR : 0;
     // LayerNorm sites of the folded evaluation, in order: k = 2l is block l's second LayerNorm (statistics: its out-projection), k = 2l - 1 its
     // first (statistics: FF2 of block l - 1).  Site k's (mean, rstd) go to table k & 1; its pivots -- the rows' previous means -- are site k - 1's,
@@ -176,8 +179,10 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         if (l > 0) F5_TRY(tap_f32(p, "blk" + std::to_string(l - 1) + ".out", p->xres, D, rows, D, st));
         F5_TRY(tap_t(p, tn + ".n1", p->hT, D, rows, D, st));
         g = gp_zero();
-        g.A = p->hT; g.lda = D; g.W = b.w_qkv; g.ldw = D; g.M = rows_g; g.N = 3 * inner; g.K = D;
-        g.bias = b.b_qkv; g.out_t = p->qkv; g.ldo = 3 * inner; g.rows_per_batch = N; g.site = 1;
+        const void* const wqkv = (qs && b.w_qkv_qs) ? b.w_qkv_qs : b.w_qkv;  // (block 0: the only unfolded projection of a folded evaluation)
+        const float* const bqkv = (qs && b.w_qkv_qs) ? b.b_qkv_qs : b.b_qkv;
+        g.A = p->hT; g.lda = D; g.W = wqkv; g.ldw = D; g.M = rows_g; g.N = 3 * inner; g.K = D;
+        g.bias = bqkv; g.out_t = p->qkv; g.ldo = 3 * inner; g.rows_per_batch = N; g.site = 1;
         g.rope = rg ? p->rope_exp : p->rope; g.rope_inner = inner; g.rope_heads = m->rope_heads;  // (ragged: row r of a half -> its position in its utterance)
         if (lnf1) {
             g.A = p->xres16; g.W = fW; g.bias = nullptr;
@@ -204,8 +209,8 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
             GemmParams gv = g;
             g.N = 2 * inner;
             gv.N = inner;
-            gv.W = (const char*)b.w_qkv + (size_t)2 * inner * D * f5_elem_size(P);
-            gv.bias = b.b_qkv + 2 * inner;
+            gv.W = (const char*)wqkv + (size_t)2 * inner * D * f5_elem_size(P);
+            gv.bias = bqkv + 2 * inner;
             if (lnf1) {
                 gv.W = fW + (size_t)2 * inner * D * 2;
                 gv.bias = nullptr;
@@ -226,11 +231,11 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         if (rg) {  // every utterance gets the computation of the launch its own batch-1 sample() makes, on its rows of both halves; the ones
                    // that launch would give to the pipelined kernel share launches (grid.z = utterance x branch, 12 utterances per table)
             F5_TRY(launch_attention_ragged_all(P, p->attn_kernel, nb, (int)rg->n.size(), rg->off.data(), rg->n.data(), c.heads, p->qkv, 3 * inner, p->cT, inner,
-                                               st, N));
+                                               st, N, qs));
         } else {
             int kind = 0;
             if (p->attn_kernel != 0 && attention_fast_supported(P, N, c.heads)) kind = 1;
-            F5_TRY(timed(p, F5_SITE_ATTN, st, [&] { return launch_attention(P, kind, nb, N, c.heads, p->qkv, 3 * inner, mask, p->cT, inner, st); }));
+            F5_TRY(timed(p, F5_SITE_ATTN, st, [&] { return launch_attention(P, kind, nb, N, c.heads, p->qkv, 3 * inner, mask, p->cT, inner, st, 0, qs); }));
         }
         if (float* d = tap_dst(p, tn + ".attn")) {  // Attention module output before gating (extra GEMM, debug only)
             g = gp_zero();

@@ -19,6 +19,16 @@ int g_sync_evals = 0;  // diagnostic knob ("sync_evals"): an eager sample() sync
                        // number of dispatches in flight (profiles/r3_rocprof_pmc_sigsegv.md: rocprofv3 --pmc died under ~5 400 queued dispatches)
 
 // fp16 residual storage for this plan's evaluations (bf16 mode without stage taps; the plan option overrides the process-wide knob)
+// Pre-scaled q: bf16 production mode of the DiT backbone on the tuned attention kernels, no qk_norm, no stage taps.  The
+// softmax scale then sits in the weights that project q -- the fold table's q rows and block 0's second copy -- and the attention kernels
+// apply none.  It rides on the LayerNorm fold: an evaluation that runs unfolded keeps q as projected (dit_eval).
+int g_attn_prescale = 1;  // tuning knob ("attn_prescale"); the plan option of the same name overrides it
+bool plan_attn_prescale(const f5_plan_s* p) {
+    const f5_dit_config& c = p->m->cfg;
+    const bool want = p->attn_prescale < 0 ? g_attn_prescale != 0 : p->attn_prescale != 0;
+    return want && c.backbone == F5_BACKBONE_DIT && c.precision == F5_PREC_BF16 && !c.qk_norm && p->attn_kernel != 0 && p->taps.empty() &&
+           p->m->blocks.size() > 0 && p->m->blocks[0].w_qkv_qs != nullptr;
+}
 bool plan_res_f16(const f5_plan_s* p) {
     const bool want = p->res_f16 < 0 ? g_res_f16 != 0 : p->res_f16 != 0;
     if (p->m->cfg.backbone != F5_BACKBONE_DIT || p->m->cfg.long_skip) return false;  // (UNetT, MMDiT and the long-skip DiT keep fp32 streams)

@@ -6,8 +6,11 @@
 // qkv: [B*N, 3*H*64] (q | k | v, token-major), mask u8 [B, N] or null, out [B*N, H*64]; activation dtype by precision.
 // kernel_kind 0: reference kernel (fp32 VALU math, any N); 1: tuned bf16 flash kernel (MFMA, in-register softmax).
 // bstride: token rows between consecutive batch items (0 = N; larger when the items sit in a longer concatenation, mask must then be null)
+// qscaled: q already holds F5_ATTN_QSCALE (the projection's weights carry it, dit_eval.hip): the kernels apply no scale, and the 64-queries-
+// per-wave kernel runs its reference-free build (attention_fast.hip)
+static constexpr float F5_ATTN_QSCALE = 0.125f * 1.4426950408889634f;  // softmax scale 1/sqrt(64) times log2(e)
 int launch_attention(int precision, int kernel_kind, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out,
-                     int ldo, hipStream_t stream, int bstride = 0);
+                     int ldo, hipStream_t stream, int bstride = 0, int qscaled = 0);
 bool attention_fast_supported(int precision, int N, int H);
 // utterances of a ragged batch (f5_sample_ragged): row offset and length of each inside one half of the concatenation
 struct AttnSegs {
@@ -19,10 +22,10 @@ struct AttnSegs {
 // own rows (bstride rows between the branches): utterances whose own launch would take the pipelined kernel share launches, the rest get theirs
 // (F5_EINVAL when the table holds more than AttnSegs::MAX utterances)
 int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& segs, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
-                            int bstride);
+                            int bstride, int qscaled = 0);
 // the same over any number of utterances (host arrays off[cnt], n[cnt]): tables of AttnSegs::MAX, one launch_attention_ragged call each
 int launch_attention_ragged_all(int precision, int attn_kernel_opt, int nbr, int cnt, const int* off, const int* n, int H, const void* qkv, int ldq, void* out,
-                                int ldo, hipStream_t stream, int bstride);
+                                int ldo, hipStream_t stream, int bstride, int qscaled = 0);
 
 // ---- elementwise.hip
 // out[r][c] = LN(x[r][:])[c] * (add_one + mul[b(r)][c]) + add[b(r)][c]; b(r) = r / rows_per_batch; eps 1e-6
@@ -158,9 +161,10 @@ int launch_wave_finish(const float* wave, const WaveTable& tb, int first, int po
 
 // ---- LayerNorm fold (lnfold.hip; gemm.h)
 // per-evaluation-time projection weights W' = fp16(W (1 + scale)) and column constants c1 = rowsum W', c2 = b + W . shift for `evals` times x `depth`
-// blocks x R rows (R = 3 * inner + ff; rows < qkv_rows take the attention norm's shift / scale, the others the FF norm's)
+// blocks x R rows (R = 3 * inner + ff; rows < qkv_rows take the attention norm's shift / scale, the others the FF norm's); the first q_rows rows
+// of every block (the q projection) times qscale (pre-scaled q: F5_ATTN_QSCALE; 1 = as projected)
 int launch_fold_weights(const float* W, const float* bias, const float* mod, int modrow, int evals, int depth, int R, int qkv_rows, int D, void* Wt,
-                        float* c1, float* c2, hipStream_t stream);
+                        float* c1, float* c2, hipStream_t stream, int q_rows = 0, float qscale = 1.0f);
 // partial row sums of an in-place residual GEMM ([ncols][ld] float2 planes) -> stats[row] = (mean, rstd); also the fp16 range guard of the stream
 int launch_stats_finalize(const float* partial, int ld, int ncols, int rows, int D, const float* pivot, float* stats, unsigned* sat, int sat_tag,
                           hipStream_t stream, const PrefetchSet* prefetch = nullptr /* weights of the launches behind it (small launches) */);

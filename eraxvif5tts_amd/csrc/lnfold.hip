@@ -5,6 +5,9 @@
 //                               W'[e][l][n][k] = fp16( W[l][n][k] * (1 + scale[e][l][k]) )
 //                               c1[e][l][n]    = sum_k float(W'[e][l][n][k])            (of the ROUNDED values: what the MFMA multiplies)
 //                               c2[e][l][n]    = b[l][n] + sum_k W[l][n][k] * shift[e][l][k]
+//                           Pre-scaled q (qscale != 1): the first q_rows rows of a block -- the q projection -- carry the
+//                           softmax scale times log2(e): W (1 + scale) and c2 are multiplied by it in fp32 ahead of the rounding / store, c1
+//                           follows as the sum of the rounded values.  qscale = 1 leaves every bit as it was.
 //                           so that  Linear(LN(x) (1 + scale) + shift) = rstd (x . W'^T - mean c1) + c2  with x the fp16 residual stream itself.
 //   stats_finalize_kernel   after every in-place residual GEMM: the per-wave-tile partial sums its epilogue wrote (sum (h - pivot), sum (h - pivot)^2
 //                           per token row and 64-feature tile) -> (mean, rstd) per row, eps = 1e-6 (modules.py:308,624), and the fp16 range guard
@@ -27,7 +30,7 @@ __device__ __forceinline__ float wave_sum_fixed(float v) {  // xor butterfly: ev
 // attention norm (shift_msa at mod + l * 6D, scale_msa at + D), else to the FF norm (shift_mlp at + 3D, scale_mlp at + 4D)  (modules.py:312).
 __global__ __launch_bounds__(256) void fold_weights_kernel(const float* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ mod,
                                                            int modrow, int depth, int R, int qkv_rows, int D, _Float16* __restrict__ Wt,
-                                                           float* __restrict__ c1, float* __restrict__ c2) {
+                                                           float* __restrict__ c1, float* __restrict__ c2, int q_rows, float qscale) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);  // over depth * R
     const int e = blockIdx.y;
@@ -37,6 +40,7 @@ __global__ __launch_bounds__(256) void fold_weights_kernel(const float* __restri
     const float* shift = ml + (r < qkv_rows ? 0 : 3 * D);
     const float* scale = shift + D;
     const float* w = W + (size_t)row * D;
+    const float qs = r < q_rows ? qscale : 1.0f;
     _Float16* wo = Wt + ((size_t)e * depth * R + row) * D;
     float s1 = 0.f, s2 = 0.f;
     for (int c = lane * 4; c < D; c += 256) {
@@ -46,7 +50,7 @@ __global__ __launch_bounds__(256) void fold_weights_kernel(const float* __restri
         f16x4_t h;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            h[k] = (_Float16)(wv[k] * (1.0f + sc[k]));
+            h[k] = (_Float16)(wv[k] * (1.0f + sc[k]) * qs);
             s1 += (float)h[k];
             s2 = __builtin_fmaf(wv[k], sh[k], s2);
         }
@@ -56,15 +60,15 @@ __global__ __launch_bounds__(256) void fold_weights_kernel(const float* __restri
     s2 = wave_sum_fixed(s2);
     if (lane == 0) {
         c1[(size_t)e * depth * R + row] = s1;
-        c2[(size_t)e * depth * R + row] = bias[row] + s2;
+        c2[(size_t)e * depth * R + row] = (bias[row] + s2) * qs;
     }
 }
 
 int launch_fold_weights(const float* W, const float* bias, const float* mod, int modrow, int evals, int depth, int R, int qkv_rows, int D, void* Wt,
-                        float* c1, float* c2, hipStream_t stream) {
+                        float* c1, float* c2, hipStream_t stream, int q_rows, float qscale) {
     if (evals <= 0 || depth <= 0 || R <= 0 || D % 4 != 0) return f5_fail(F5_EINVAL, "fold_weights: bad shape");
     hipLaunchKernelGGL(fold_weights_kernel, dim3((unsigned)((depth * R + 3) / 4), (unsigned)evals), dim3(256), 0, stream, W, bias, mod, modrow, depth, R,
-                       qkv_rows, D, (_Float16*)Wt, c1, c2);
+                       qkv_rows, D, (_Float16*)Wt, c1, c2, q_rows, qscale);
     F5_LAUNCH_CHECK();
     return 0;
 }

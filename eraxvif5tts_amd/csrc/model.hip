@@ -346,7 +346,17 @@ extern "C" int f5_model_finalize(f5_model_t m) {
                 memcpy(&fold_b[(size_t)i * foldR], bias.data(), bias.size() * sizeof(float));
             }
             F5_TRY(f5_upload_t(A, P, w.data(), w.size(), wdst));
-            return f5_upload_f32(A, bias.data(), bias.size(), bdst);
+            F5_TRY(f5_upload_f32(A, bias.data(), bias.size(), bdst));
+            // pre-scaled q: block 0's projection runs unfolded, so it gets a copy whose q rows carry the scale.  The copy is the WHOLE fused
+            // q|k|v weight (the k and v rows are duplicates, 4 MiB at D = 1024, once per model): the projection stays one launch on one weight
+            // pointer, as every tile choice of dit_eval assumes.  (No weight prefetch names it: the prefetch sets only reach blocks 1 and up.)
+            if (fold && sfx.empty() && i == 0) {
+                for (size_t k = 0; k < (size_t)inner * D; ++k) w[k] *= F5_ATTN_QSCALE;
+                for (int k = 0; k < inner; ++k) bias[k] *= F5_ATTN_QSCALE;
+                F5_TRY(f5_upload_t(A, P, w.data(), w.size(), &b.w_qkv_qs));
+                F5_TRY(f5_upload_f32(A, bias.data(), bias.size(), &b.b_qkv_qs));
+            }
+            return 0;
         };
         F5_TRY(fuse_qkv("", &b.w_qkv, &b.b_qkv));
         if (mm) {
@@ -568,6 +578,10 @@ extern "C" int f5_plan_set_option(f5_plan_t p, const char* key, int value) {
     } else if (strcmp(key, "attn_kernel") == 0) {
         rebake = p->attn_kernel != value;
         p->attn_kernel = value;
+    } else if (strcmp(key, "attn_prescale") == 0) {
+        const int v = value < 0 ? -1 : (value != 0);
+        rebake = p->attn_prescale != v;
+        p->attn_prescale = v;
     } else if (strcmp(key, "residual_f16") == 0) {
         const int v = value < 0 ? -1 : (value != 0);
         rebake = p->res_f16 != v;
@@ -596,6 +610,14 @@ extern "C" int f5_plan_get_option(f5_plan_t p, const char* key, int* value) {
         *value = p->gemm_kernel;
     else if (strcmp(key, "attn_kernel") == 0)
         *value = p->attn_kernel;
+    else if (strcmp(key, "attn_prescale") == 0)  // the wish: the plan's option, or the process-wide knob
+        *value = p->attn_prescale < 0 ? (g_attn_prescale != 0) : p->attn_prescale;
+    // "attn_prescale_active": the PLAN's part of the condition -- it wants pre-scaled q and may run it (0 with stage taps, qk_norm, fp32 mode,
+    // the reference kernels, fp32 residual storage, ...).  It does not know the shape: an evaluation uses pre-scaled q only where it also
+    // runs the LayerNorm fold (dit_eval's `lnf`), which under automatic GEMM choice starts at 512 token rows and needs a staged time grid of
+    // at most 64 evaluation times; a smaller call on a plan that reports 1 runs q as projected.
+    else if (strcmp(key, "attn_prescale_active") == 0)
+        *value = (plan_attn_prescale(p) && plan_res_f16(p) && g_ln_fold && p->m->w_fold && p->lnf_stats && p->gemm_kernel != 0) ? 1 : 0;
     else if (strcmp(key, "residual_f16") == 0)
         *value = plan_res_f16(p) ? 1 : 0;  // what the next evaluation will use
     else if (strcmp(key, "residual_guard") == 0)

@@ -19,6 +19,10 @@ static const int MELP = 128;  // mel channels padded to one MFMA k-block multipl
 struct BlockW {
     void *w_qkv = nullptr, *w_o = nullptr, *w_ff1 = nullptr, *w_ff2 = nullptr;
     float *b_qkv = nullptr, *b_o = nullptr, *b_ff1 = nullptr, *b_ff2 = nullptr;
+    // block 0 of a LayerNorm-fold model (its QKV projection runs unfolded): second copy of the fused weight and bias whose q rows carry
+    // F5_ATTN_QSCALE, made from the fp32 master (pre-scaled q, dit_eval.hip)
+    void* w_qkv_qs = nullptr;
+    float* b_qkv_qs = nullptr;
     // UNetT layers (unett.py:139-171): skip projection [D, 2D] of the later half (concat type), RMSNorm gains
     void* w_skip = nullptr;
     float *g_attn = nullptr, *g_ff = nullptr;
@@ -40,6 +44,7 @@ struct FoldTable {
     float *c1 = nullptr, *c2 = nullptr;  // [evals][depth][R]
     hipEvent_t ready = nullptr;          // recorded behind the build; a plan on another stream waits for it once
     uint64_t id = 0;
+    bool qscaled = false;   // the q rows carry F5_ATTN_QSCALE (pre-scaled q)
     int users = 0;          // plans holding it (their captured graphs bake its addresses)
     ~FoldTable() {
         if (ready) (void)hipEventDestroy(ready);
@@ -136,6 +141,7 @@ struct f5_plan_s {
     uint8_t* cmask_in = nullptr;  // staged condition mask of f5_sample_masked, u8 [max_batch, max_seq]
     int rope_n = 0;
     int gemm_kernel = -1, attn_kernel = -1;  // -1 = auto (tuned kernel when it supports the problem)
+    int attn_prescale = -1;  // plan option "attn_prescale": -1 = the process-wide knob, 0 = q as projected, 1 = pre-scaled q where it applies
     // Range guard of the fp16 residual stream (bf16 production mode): the LayerNorm passes raise `sat_flag` (device word) when an element of
     // the stream reaches fp16's largest finite value or is NaN; f5_sample reads it after the loop (the call's one synchronisation) and
     // repeats the loop with fp32 residual storage, which this plan then keeps (`res_f16` = 0).
@@ -225,6 +231,8 @@ int finish_if_pending(f5_plan_s* p);  // completes a deferred sample() before th
 // ---- eval_common.hip
 extern int g_w_prefetch, g_res_f16, g_ln_defer, g_resid_rmw, g_ln_fold, g_ln_fold_inkernel, g_gemm_pad_rows, g_sync_evals, g_gemm_w4;
 bool plan_res_f16(const f5_plan_s* p);
+extern int g_attn_prescale;
+bool plan_attn_prescale(const f5_plan_s* p);  // pre-scaled q wanted and possible for this plan (what its fold table is built for)
 GemmParams gp_zero();
 int run_gemm(f5_plan_s* p, const GemmParams& g, int mode, int epi, hipStream_t st);
 float* tap_dst(f5_plan_s* p, const std::string& name);

@@ -170,6 +170,55 @@ extern "C" int f5_op_attention(int precision, int kernel, int B, int N, int H, c
     return sync_and_release(a, st, rc);
 }
 
+// Attention on PRE-SCALED q (bf16): the q part of `qkv` already holds softmax_scale * log2(e) times the projected q, as the production path's
+// q projection stores it; the kernels apply no scale, the 64-queries-per-wave kernel runs its reference-free build.
+extern "C" int f5_op_attention_prescaled(int kernel, int B, int N, int H, const float* qkv, const uint8_t* mask, float* out, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (B <= 0 || N <= 0 || H <= 0 || !qkv || !out) return f5_fail(F5_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int inner = H * 64, rows = B * N;
+    DevArena a;
+    void *q = nullptr, *o = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&q, (size_t)rows * 3 * inner * 2))) break;
+        if ((rc = a.alloc(&o, (size_t)rows * inner * 2))) break;
+        if ((rc = launch_convert_pad(F5_PREC_BF16, qkv, 3 * inner, rows, 3 * inner, 3 * inner, q, 3 * inner, st))) break;
+        if ((rc = launch_attention(F5_PREC_BF16, kernel, B, N, H, q, 3 * inner, mask, o, inner, st, 0, 1))) break;
+        rc = launch_convert_back(F5_PREC_BF16, o, inner, rows, inner, out, inner, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
+// The fold-table builder (lnfold.hip: fold_weights_kernel) on one block and one evaluation time: W [R, D], bias [R], the two norms' (scale,
+// shift) [D] each -> W' [R, D] (fp16, returned as f32), c1 [R], c2 [R].  Rows below qkv_rows take the attention norm's pair, the others the FF
+// norm's; qscaled: the first q_rows rows carry softmax_scale * log2(e) (pre-scaled q).
+extern "C" int f5_op_fold_weights(int R, int qkv_rows, int q_rows, int D, int qscaled, const float* W, const float* bias, const float* scale_msa,
+                                  const float* shift_msa, const float* scale_mlp, const float* shift_mlp, float* Wt, float* c1, float* c2,
+                                  f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (R <= 0 || D <= 0 || D % 4 != 0 || qkv_rows < 0 || q_rows < 0 || q_rows > R || !W || !bias || !scale_msa || !shift_msa || !scale_mlp || !shift_mlp ||
+        !Wt || !c1 || !c2)
+        return f5_fail(F5_EINVAL, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    DevArena a;
+    void* Wh = nullptr;
+    float* mod = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&Wh, (size_t)R * D * 2))) break;
+        if ((rc = a.alloc_t(&mod, (size_t)6 * D))) break;
+        F5_HIP(hipMemsetAsync(mod, 0, (size_t)6 * D * sizeof(float), st));
+        F5_HIP(hipMemcpyAsync(mod, shift_msa, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));  // slot order of one block: modules.py:312
+        F5_HIP(hipMemcpyAsync(mod + D, scale_msa, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
+        F5_HIP(hipMemcpyAsync(mod + 3 * D, shift_mlp, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
+        F5_HIP(hipMemcpyAsync(mod + 4 * D, scale_mlp, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if ((rc = launch_fold_weights(W, bias, mod, 6 * D, 1, 1, R, qkv_rows, D, Wh, c1, c2, st, qscaled ? q_rows : 0, qscaled ? F5_ATTN_QSCALE : 1.0f))) break;
+        rc = launch_f16_to_f32(Wh, Wt, (size_t)R * D, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
 // The ragged sampler's attention call (dit_eval.hip) on its own: `cnt` utterances at rows off[u] .. off[u] + n[u] of each of the `nbr` branches,
 // the branches `rows` apart (the batch stride).  `out` is staged into the activation dtype first, so rows no launch writes come back as given.
 extern "C" int f5_op_attention_ragged(int precision, int attn_kernel, int nbr, int cnt, const int* off, const int* n, int H, int rows, int ldq_extra,
@@ -590,6 +639,7 @@ extern "C" int f5_bench_mfma_rate(int random_operands, float* tflops, f5_stream_
     return sync_and_release(a, st, rc);
 }
 
+extern int g_attn_prescale;
 extern int g_sync_evals, g_resid_rmw, g_ln_fold, g_ln_fold_inkernel, g_gemm_pad_rows;
 extern int g_conv31_tok, g_bigvgan_group_frames;
 extern int g_gemm_bm128, g_gemm_tile, g_gemm_group_sites, g_gemm_reverse_sites;
@@ -665,6 +715,10 @@ extern "C" int f5_tuning_set(const char* key, int value) {
     if (strcmp(key, "bigvgan_group_frames") == 0) {
         if (value < 1) return f5_fail(F5_EINVAL, "bigvgan_group_frames must be at least 1");
         g_bigvgan_group_frames = value;
+        return 0;
+    }
+    if (strcmp(key, "attn_prescale") == 0) {
+        g_attn_prescale = value != 0;
         return 0;
     }
     if (strcmp(key, "attn_variant") == 0) {

@@ -218,8 +218,9 @@ static int acquire_fold(f5_plan_s* p, const std::vector<float>& tv, hipStream_t 
     const int nev = (int)tv.size();
     FoldTable* want = nullptr;
     if (m->w_fold && g_ln_fold && p->lnf_stats && nev > 0 && nev <= F5_FOLD_MAX_EVALS) {
+        const bool qs = plan_attn_prescale(p);
         for (FoldTable* t : m->folds)
-            if (t->tv == tv) want = t;
+            if (t->tv == tv && t->qscaled == qs) want = t;
         if (!want) {
             for (size_t i = 0; i < m->folds.size() && m->folds.size() >= F5_FOLD_TABLES;) {  // oldest first, never one a plan still points to
                 if (m->folds[i]->users == 0 && m->folds[i] != p->fold) {
@@ -235,13 +236,15 @@ static int acquire_fold(f5_plan_s* p, const std::vector<float>& tv, hipStream_t 
             FoldTable* t = new FoldTable();
             bool ok = t->arena.alloc(&t->Wt, n * c.dim * 2, false) == 0 && t->arena.alloc_t(&t->c1, n, false) == 0 && t->arena.alloc_t(&t->c2, n, false) == 0 &&
                       hipEventCreateWithFlags(&t->ready, hipEventDisableTiming) == hipSuccess;
-            ok = ok && launch_fold_weights(m->w_fold, m->b_fold, p->mod, m->modrow, nev, c.depth, m->fold_R, 3 * m->inner, c.dim, t->Wt, t->c1, t->c2, st) == 0 &&
+            ok = ok && launch_fold_weights(m->w_fold, m->b_fold, p->mod, m->modrow, nev, c.depth, m->fold_R, 3 * m->inner, c.dim, t->Wt, t->c1, t->c2, st, qs ? m->inner : 0,
+                                           qs ? F5_ATTN_QSCALE : 1.0f) == 0 &&
                  hipEventRecord(t->ready, st) == hipSuccess;
             if (!ok) {
                 (void)hipGetLastError();
                 delete t;
             } else {
                 t->tv = tv;
+                t->qscaled = qs;
                 t->id = ++m->fold_seq;
                 m->folds.push_back(t);
                 want = t;

@@ -213,10 +213,16 @@ F5_API int f5_plan_timing_site(f5_plan_t p, int site, float* avg_ms, int* launch
  * knob (default: fp16); key "residual_guard" (default 1): f5_sample reads, after the ODE loop, the flag word the LayerNorm passes raise when
  * an element of the fp16 stream reaches +-65504 or is NaN, repeats the loop with fp32 storage and keeps fp32 storage for this plan
  * (f5_sample then synchronises the stream once per call; 0 = no read, fully asynchronous, clipping goes unnoticed; 2 = the read is
- * deferred to f5_sample_finish). */
+ * deferred to f5_sample_finish).
+ * Key "attn_prescale" (default -1 = the process-wide knob, which is on): 1 = the softmax scale times log2(e) is folded into the weights that
+ * project q and the attention kernels apply none (bf16 DiT on the tuned attention kernels, no qk_norm, no stage taps, LayerNorm-fold
+ * evaluations; everything else keeps q as projected), 0 = q as projected everywhere. */
 F5_API int f5_plan_set_option(f5_plan_t p, const char* key, int value);
 /* reads an option back; besides the keys above: "residual_fallbacks" = f5_sample calls of this plan that were repeated with fp32 residual
- * storage because the range guard fired ("residual_f16" then reads 0). */
+ * storage because the range guard fired ("residual_f16" then reads 0); "attn_prescale_active" = 1 when this plan wants pre-scaled q and may run it (0 e.g.
+ * while a stage tap is set).  That is the plan's part only: an evaluation uses pre-scaled q where it also runs the LayerNorm fold, which
+ * under automatic kernel choice needs at least 512 token rows and a time grid of at most 64 evaluation times -- a smaller call on a plan
+ * that reports 1 still runs q as projected. */
 F5_API int f5_plan_get_option(f5_plan_t p, const char* key, int* value);
 
 /* ------------------------------------------------------------------ duration predictor
@@ -274,6 +280,17 @@ F5_API int f5_op_layernorm_modulate(int rows, int dim, const float* x, const flo
  * -> out f32 [B, N, H*64].  kernel: 0 = reference kernel, 1 = tuned flash kernel (bf16). */
 F5_API int f5_op_attention(int precision, int kernel, int B, int N, int H, const float* qkv, const uint8_t* mask, float* out,
                     f5_stream_t stream);
+/* The same on PRE-SCALED q (bf16 only): the q part of `qkv` already holds softmax_scale * log2(e) = 0.125 * 1.4426950408889634 times the
+ * projected q, the form the production path's q projection stores when the plan option "attn_prescale" is active.  The
+ * kernels apply no scale; the 64-queries-per-wave kernel runs its reference-free build with its two range guards. */
+F5_API int f5_op_attention_prescaled(int kernel, int B, int N, int H, const float* qkv, const uint8_t* mask, float* out, f5_stream_t stream);
+/* The LayerNorm fold's table builder on one block and one evaluation time (parity tests): W f32 [R, D], bias [R], (scale, shift) [D] of the
+ * attention norm (rows < qkv_rows) and of the FF norm (the other rows) -> Wt f32 [R, D] = the fp16 values of W (1 + scale), c1 [R] = their row
+ * sums, c2 [R] = bias + W . shift.  qscaled != 0: the first q_rows rows (the q projection) carry softmax_scale * log2(e), applied in fp32
+ * ahead of the rounding. */
+F5_API int f5_op_fold_weights(int R, int qkv_rows, int q_rows, int D, int qscaled, const float* W, const float* bias, const float* scale_msa,
+                              const float* shift_msa, const float* scale_mlp, const float* shift_mlp, float* Wt, float* c1, float* c2,
+                              f5_stream_t stream);
 /* The attention call of the ragged sampler (f5_sample_ragged) on its own: `cnt` utterances of lengths n[u] at row offsets off[u] (host int
  * arrays) inside each of `nbr` branches that lie `rows` rows apart (the batch stride of every launch).  qkv f32 [nbr * rows, 3*H*64 +
  * ldq_extra], out f32 [nbr * rows, H*64 + ldo_extra] (the extras widen the leading dimensions, normally 0).  attn_kernel 0 = reference
