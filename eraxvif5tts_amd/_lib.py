@@ -79,6 +79,7 @@ _PROTOS = {
     "f5_plan_timing_site": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "f5_plan_set_tap": (_I, [_P, C.c_char_p, _P]),
     "f5_plan_set_option": (_I, [_P, C.c_char_p, _I]),
+    "f5_plan_set_attn_dropout": (_I, [_P, _F, C.c_uint64]),
     "f5_plan_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int)]),
     "f5_duration_predict": (_I, [C.POINTER(DurationWeights), _I, _I, _P, _I, _P, _P, _P, _P]),
     "f5_duration_predict_g": (_I, [C.POINTER(DurationWeights), _I, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
@@ -87,6 +88,7 @@ _PROTOS = {
     "f5_op_ln_fold": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "f5_op_layernorm_modulate": (_I, [_I, _I, _P, _P, _P, _P, _P]),
     "f5_op_attention": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "f5_op_attention_dropout": (_I, [_I, _I, _I, _I, _I, _P, _P, _F, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     "f5_op_attention_prescaled": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "f5_op_fold_weights": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f5_op_attention_ragged": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, _P, _P, _P]),

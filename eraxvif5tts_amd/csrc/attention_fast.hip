@@ -503,9 +503,20 @@ static bool picks_wide(int B, int N, int H, bool masked, int ldq, int bstride) {
 }
 
 int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& segs, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
-                            int bstride, int qscaled) {
+                            int bstride, int qscaled, const AttnDropout* drop) {
     if (segs.cnt < 0 || segs.cnt > AttnSegs::MAX || segs.nbr < 1) return f5_fail(F5_EINVAL, "attention_ragged: a table holds at most %d utterances", AttnSegs::MAX);
     const size_t es = precision == F5_PREC_BF16 ? 2 : 4;
+    if (drop && drop->prob > 0.0) {  // attention dropout: every utterance its own launch (the shared launches have no dropout build)
+        for (int u = 0; u < segs.cnt; ++u) {
+            const int nu = segs.n[u];
+            const int kind = (attn_kernel_opt != 0 && attention_fast_supported(precision, nu, H)) ? 1 : 0;
+            AttnDropout d = *drop;
+            d.bw0 = drop->bw0 + (uint32_t)u;
+            F5_TRY(launch_attention(precision, kind, segs.nbr, nu, H, (const char*)qkv + (size_t)segs.off[u] * ldq * es, ldq, nullptr,
+                                    (char*)out + (size_t)segs.off[u] * ldo * es, ldo, stream, bstride, qscaled, &d));
+        }
+        return 0;
+    }
     AttnSegs grp[2];  // [0] utterances with n % 64 == 0 (unmasked build), [1] the others -- as each one's own launch would pick
     int maxn[2] = {0, 0};
     for (int u = 0; u < segs.cnt; ++u) {
@@ -529,15 +540,18 @@ int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& 
 }
 
 int launch_attention_ragged_all(int precision, int attn_kernel_opt, int nbr, int cnt, const int* off, const int* n, int H, const void* qkv, int ldq, void* out,
-                                int ldo, hipStream_t stream, int bstride, int qscaled) {
+                                int ldo, hipStream_t stream, int bstride, int qscaled, const AttnDropout* drop) {
+    AttnDropout d;
+    if (drop) d = *drop;
     for (int u0 = 0; u0 < cnt; u0 += AttnSegs::MAX) {
+        if (drop) d.bw0 = drop->bw0 + (uint32_t)u0;
         AttnSegs sg;
         sg.nbr = nbr;
         for (int u = u0; u < cnt && u < u0 + AttnSegs::MAX; ++u) {
             sg.off[sg.cnt] = off[u];
             sg.n[sg.cnt++] = n[u];
         }
-        F5_TRY(launch_attention_ragged(precision, attn_kernel_opt, sg, H, qkv, ldq, out, ldo, stream, bstride, qscaled));
+        F5_TRY(launch_attention_ragged(precision, attn_kernel_opt, sg, H, qkv, ldq, out, ldo, stream, bstride, qscaled, drop ? &d : nullptr));
     }
     return 0;
 }

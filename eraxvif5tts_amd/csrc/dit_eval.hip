@@ -230,12 +230,14 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         }
         if (rg) {  // every utterance gets the computation of the launch its own batch-1 sample() makes, on its rows of both halves; the ones
                    // that launch would give to the pipelined kernel share launches (grid.z = utterance x branch, 12 utterances per table)
+            const AttnDropout drop = plan_attn_dropout(p, l, 0, (uint32_t)rg->n.size());  // batch word = branch * B + u
             F5_TRY(launch_attention_ragged_all(P, p->attn_kernel, nb, (int)rg->n.size(), rg->off.data(), rg->n.data(), c.heads, p->qkv, 3 * inner, p->cT, inner,
-                                               st, N, qs));
+                                               st, N, qs, &drop));
         } else {
             int kind = 0;
             if (p->attn_kernel != 0 && attention_fast_supported(P, N, c.heads)) kind = 1;
-            F5_TRY(timed(p, F5_SITE_ATTN, st, [&] { return launch_attention(P, kind, nb, N, c.heads, p->qkv, 3 * inner, mask, p->cT, inner, st, 0, qs); }));
+            const AttnDropout drop = plan_attn_dropout(p, l);  // batch word = row of the (CFG-doubled) batch
+            F5_TRY(timed(p, F5_SITE_ATTN, st, [&] { return launch_attention(P, kind, nb, N, c.heads, p->qkv, 3 * inner, mask, p->cT, inner, st, 0, qs, &drop); }));
         }
         if (float* d = tap_dst(p, tn + ".attn")) {  // Attention module output before gating (extra GEMM, debug only)
             g = gp_zero();

@@ -27,7 +27,22 @@ bool plan_attn_prescale(const f5_plan_s* p) {
     const f5_dit_config& c = p->m->cfg;
     const bool want = p->attn_prescale < 0 ? g_attn_prescale != 0 : p->attn_prescale != 0;
     return want && c.backbone == F5_BACKBONE_DIT && c.precision == F5_PREC_BF16 && !c.qk_norm && p->attn_kernel != 0 && p->taps.empty() &&
-           p->m->blocks.size() > 0 && p->m->blocks[0].w_qkv_qs != nullptr;
+           p->m->blocks.size() > 0 && p->m->blocks[0].w_qkv_qs != nullptr && !(p->drop_p > 0.0) /* the dropout kernels take q as projected */;
+}
+AttnDropout plan_attn_dropout(const f5_plan_s* p, int l, uint32_t bw0, uint32_t bw_step) {
+    AttnDropout d;
+    if (!(p->drop_p > 0.0)) return d;
+    d.prob = p->drop_p;
+    d.seed = p->drop_seed;
+    d.base = p->drop_base;
+    d.offset = (uint32_t)p->drop_eval * (uint32_t)p->m->cfg.depth + (uint32_t)l;
+    d.bw0 = bw0;
+    d.bw_step = bw_step;
+    return d;
+}
+int plan_attn_dropout_advance(f5_plan_s* p, uint32_t by, hipStream_t st) {
+    if (!(p->drop_p > 0.0)) return 0;
+    return launch_attn_dropout_advance(p->drop_base, by, st);
 }
 bool plan_res_f16(const f5_plan_s* p) {
     const bool want = p->res_f16 < 0 ? g_res_f16 != 0 : p->res_f16 != 0;
@@ -129,6 +144,7 @@ int compute_base(f5_plan_s* p, const float* cond, const int32_t* lens, const flo
 // one network evaluation of whichever backbone the model is (plug point A)
 int net_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, int time_row, int per_batch_rows, const uint8_t* mask, hipStream_t st) {
     f5_model_s* m = p->m;
+    p->drop_eval = per_batch_rows ? 0 : time_row;  // (a sample loop's time_row is its evaluation index; a forward is evaluation 0)
     if (m->cfg.backbone == F5_BACKBONE_UNETT)
         return unett_eval(p, x, xrows, nb, N, p->temb + (size_t)time_row * m->cfg.dim, per_batch_rows ? m->cfg.dim : 0, mask, st);
     if (m->cfg.backbone == F5_BACKBONE_MMDIT)
@@ -163,6 +179,8 @@ extern "C" int f5_dit_forward(f5_plan_t p, int B, int N, const float* x, const f
     F5_TRY(compute_modulation(p, time, B, st));
     F5_TRY(compute_base(p, cond, nullptr, text_embed, B, N, drop_audio_cond, 0, st));
     F5_TRY(net_eval(p, x, B * N, B, N, 0, 1, mask, st));
+    F5_TRY(plan_attn_dropout_advance(p, (uint32_t)m->cfg.depth, st));
+    p->drop_base_host += p->drop_p > 0.0 ? (uint32_t)m->cfg.depth : 0u;
     return launch_convert_back(F5_PREC_FP32, p->vout, MELP, B * N, m->cfg.mel_dim, out, m->cfg.mel_dim, st);
 }
 
@@ -182,6 +200,8 @@ extern "C" int f5_mmdit_forward(f5_plan_t p, int B, int N, int nt, const float* 
     p->c_nt = nt;
     p->c_rows_each = B * nt;
     F5_TRY(net_eval(p, x, B * N, B, N, 0, 1, mask, st));
+    F5_TRY(plan_attn_dropout_advance(p, (uint32_t)m->cfg.depth, st));
+    p->drop_base_host += p->drop_p > 0.0 ? (uint32_t)m->cfg.depth : 0u;
     return launch_convert_back(F5_PREC_FP32, p->vout, MELP, B * N, m->cfg.mel_dim, out, m->cfg.mel_dim, st);
 }
 

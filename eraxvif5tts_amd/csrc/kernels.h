@@ -9,8 +9,33 @@
 // qscaled: q already holds F5_ATTN_QSCALE (the projection's weights carry it, dit_eval.hip): the kernels apply no scale, and the 64-queries-
 // per-wave kernel runs its reference-free build (attention_fast.hip)
 static constexpr float F5_ATTN_QSCALE = 0.125f * 1.4426950408889634f;  // softmax scale 1/sqrt(64) times log2(e)
+// Attention dropout (opt-in; philox.h): keep(q, k) of batch item b of a launch is drawn with the batch word
+// bw0 + b * bw_step and the call word *base + offset (base: device word read by the kernel, so a replayed graph sees its current value; null = 0).
+// prob == 0 (or a null descriptor) is the mode off: the launchers then do exactly what they do without one.  With it on, bf16 launches of the
+// tuned kind take attention_dropout.hip's kernel, reference-kind launches the flagged attn_ref_kernel; q must not be pre-scaled.
+struct AttnDropout {
+    double prob = 0.0;  // in [0, 1), as the decimal the caller wrote (attn_dropout_prob_of)
+    uint64_t seed = 0;
+    const uint32_t* base = nullptr;
+    uint32_t offset = 0, bw0 = 0, bw_step = 1;
+};
+double attn_dropout_prob_of(float prob);  // the shortest decimal that rounds to `prob` (0.1f -> 0.1), so T = round(p * 2^32) is the documented word
+// what the kernels take by value
+struct AttnDropArgs {
+    const uint32_t* base;
+    uint64_t seed;
+    uint32_t offset, bw0, bw_step, thresh;
+    float rscale;  // 1 / (1 - p)
+};
+AttnDropArgs attn_drop_args(const AttnDropout& d);
 int launch_attention(int precision, int kernel_kind, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out,
-                     int ldo, hipStream_t stream, int bstride = 0, int qscaled = 0);
+                     int ldo, hipStream_t stream, int bstride = 0, int qscaled = 0, const AttnDropout* drop = nullptr);
+// attention_dropout.hip: the bf16 MFMA flash kernel with dropout (any N >= 1, key mask or not, batch stride, ldq / ldo multiples of 8), and
+// the one-thread kernels that advance / set a plan's call-word base
+int launch_attention_dropout(int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                             const AttnDropout& drop);
+int launch_attn_dropout_advance(uint32_t* base, uint32_t by, hipStream_t stream);
+int launch_attn_dropout_set(uint32_t* base, uint32_t value, hipStream_t stream);
 bool attention_fast_supported(int precision, int N, int H);
 // utterances of a ragged batch (f5_sample_ragged): row offset and length of each inside one half of the concatenation
 struct AttnSegs {
@@ -21,11 +46,12 @@ struct AttnSegs {
 // attention over `cnt` utterances of different lengths, each the computation of launch_attention(precision, kind_u, nbr, n[u], ...) on its
 // own rows (bstride rows between the branches): utterances whose own launch would take the pipelined kernel share launches, the rest get theirs
 // (F5_EINVAL when the table holds more than AttnSegs::MAX utterances)
+// drop (mode on): every utterance gets a launch of its own, utterance u of the table with batch word drop->bw0 + u + branch * drop->bw_step
 int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& segs, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
-                            int bstride, int qscaled = 0);
+                            int bstride, int qscaled = 0, const AttnDropout* drop = nullptr);
 // the same over any number of utterances (host arrays off[cnt], n[cnt]): tables of AttnSegs::MAX, one launch_attention_ragged call each
 int launch_attention_ragged_all(int precision, int attn_kernel_opt, int nbr, int cnt, const int* off, const int* n, int H, const void* qkv, int ldq, void* out,
-                                int ldo, hipStream_t stream, int bstride, int qscaled = 0);
+                                int ldo, hipStream_t stream, int bstride, int qscaled = 0, const AttnDropout* drop = nullptr);
 
 // ---- elementwise.hip
 // out[r][c] = LN(x[r][:])[c] * (add_one + mul[b(r)][c]) + add[b(r)][c]; b(r) = r / rows_per_batch; eps 1e-6

@@ -76,7 +76,8 @@ int mmdit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const flo
         {
             int kind = 0;
             if (p->attn_kernel != 0 && attention_fast_supported(P, S, c.heads)) kind = 1;
-            F5_TRY(launch_attention(P, kind, nb, S, c.heads, p->qkvJ, 3 * inner, maskJ, p->attJ, inner, st));
+            const AttnDropout drop = plan_attn_dropout(p, l);
+            F5_TRY(launch_attention(P, kind, nb, S, c.heads, p->qkvJ, 3 * inner, maskJ, p->attJ, inner, st, 0, 0, &drop));
         }
         // text: c += gate_msa * to_out_c(attn_c); c += gate_mlp * ff_c(norm)   (:697-706; nothing in the context_pre_only block)
         if (!last) {

@@ -535,6 +535,7 @@ extern "C" int f5_plan_create(f5_model_t m, int max_batch, int max_seq, int max_
             if ((rc = A.alloc_t(&p->lnf_stats2, (rows + 256) * 2))) break;
             if ((rc = A.alloc_t(&p->lnf_partial, (D / 64) * rows * 2))) break;
         }
+        if ((rc = A.alloc_t(&p->drop_base, 64))) break;  // attention dropout's call-word base (word 0; the arena zero-fills)
         if ((rc = A.alloc_t(&p->sat_base, 1024))) break;  // the 8 flag words sit in the middle of a 4 KiB block of their own
         p->sat_flag = p->sat_base + 512;
         if (hipHostMalloc((void**)&p->sat_host, 32, hipHostMallocDefault) != hipSuccess) {
@@ -593,21 +594,35 @@ extern "C" int f5_plan_set_option(f5_plan_t p, const char* key, int value) {
     } else {
         return f5_fail(F5_EINVAL, "unknown option '%s'", key);
     }
-    if (rebake) {
-        for (auto& g : p->graphs) {
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
-            if (g.graph) (void)hipGraphDestroy(g.graph);
-        }
-        p->graphs.clear();
-    }
+    if (rebake) plan_drop_graphs(p);
     return 0;
 }
 
+
+// Attention dropout: prob in [0, 1), 0 = off.  The call-word base restarts at 0; captured graphs baked the previous
+// probability and seed (and, across off <-> on, other kernels and another fold table).
+extern "C" int f5_plan_set_attn_dropout(f5_plan_t p, float prob, uint64_t seed) {
+    if (!p) return f5_fail(F5_EINVAL, "null plan");
+    if (!(prob >= 0.f && prob < 1.f)) return f5_fail(F5_EINVAL, "f5_plan_set_attn_dropout: prob must lie in [0, 1)");
+    F5_TRY(finish_if_pending(p));
+    F5_HIP(hipDeviceSynchronize());  // (launches in flight on the caller's streams may still read the word)
+    F5_HIP(hipMemset(p->drop_base, 0, sizeof(uint32_t)));
+    F5_HIP(hipDeviceSynchronize());  // (... and the fill is complete before a non-blocking stream's next launch reads it)
+    p->drop_base_host = p->drop_call_base = 0u;
+    p->drop_p = prob > 0.f ? attn_dropout_prob_of(prob) : 0.0;
+    p->drop_seed = seed;
+    plan_drop_graphs(p);
+    return 0;
+}
 
 extern "C" int f5_plan_get_option(f5_plan_t p, const char* key, int* value) {
     if (!p || !key || !value) return f5_fail(F5_EINVAL, "null argument");
     if (strcmp(key, "gemm_kernel") == 0)
         *value = p->gemm_kernel;
+    else if (strcmp(key, "attn_dropout_on") == 0)
+        *value = p->drop_p > 0.0 ? 1 : 0;
+    else if (strcmp(key, "attn_dropout_base") == 0)  // host mirror of the device word: the call word the next call starts from
+        *value = (int)p->drop_base_host;
     else if (strcmp(key, "attn_kernel") == 0)
         *value = p->attn_kernel;
     else if (strcmp(key, "attn_prescale") == 0)  // the wish: the plan's option, or the process-wide knob

@@ -141,6 +141,15 @@ struct f5_plan_s {
     uint8_t* cmask_in = nullptr;  // staged condition mask of f5_sample_masked, u8 [max_batch, max_seq]
     int rope_n = 0;
     int gemm_kernel = -1, attn_kernel = -1;  // -1 = auto (tuned kernel when it supports the problem)
+    // Attention dropout (f5_plan_set_attn_dropout; philox.h).  Call word of block l in evaluation e of a call = base + e * depth
+    // + l.  `drop_base` is a device word the attention kernels read (a replayed graph sees its current value) and a one-thread kernel
+    // advances as the last node of every sample loop / forward; drop_base_host mirrors it, drop_call_base is the value the last sample loop
+    // started from (the range guard's fp32 rerun starts there again).
+    double drop_p = 0.0;  // 0 = off
+    uint64_t drop_seed = 0;
+    uint32_t* drop_base = nullptr;
+    uint32_t drop_base_host = 0, drop_call_base = 0;
+    int drop_eval = 0;     // evaluation index of the running net_eval
     int attn_prescale = -1;  // plan option "attn_prescale": -1 = the process-wide knob, 0 = q as projected, 1 = pre-scaled q where it applies
     // Range guard of the fp16 residual stream (bf16 production mode): the LayerNorm passes raise `sat_flag` (device word) when an element of
     // the stream reaches fp16's largest finite value or is NaN; f5_sample reads it after the loop (the call's one synchronisation) and
@@ -225,6 +234,7 @@ template <typename F> static int timed(f5_plan_s* p, int site, hipStream_t st, F
     return rc;
 }
 
+void plan_drop_graphs(f5_plan_s* p);  // destroys every captured graph of the plan (sampler.hip)
 int finish_if_pending(f5_plan_s* p);  // completes a deferred sample() before the plan's buffers are reused (sampler.hip)
 
 
@@ -233,6 +243,9 @@ extern int g_w_prefetch, g_res_f16, g_ln_defer, g_resid_rmw, g_ln_fold, g_ln_fol
 bool plan_res_f16(const f5_plan_s* p);
 extern int g_attn_prescale;
 bool plan_attn_prescale(const f5_plan_s* p);  // pre-scaled q wanted and possible for this plan (what its fold table is built for)
+// the dropout descriptor of block l's attention call in the running evaluation (prob 0 when the mode is off)
+AttnDropout plan_attn_dropout(const f5_plan_s* p, int l, uint32_t bw0 = 0, uint32_t bw_step = 1);
+int plan_attn_dropout_advance(f5_plan_s* p, uint32_t by, hipStream_t st);  // no-op when the mode is off
 GemmParams gp_zero();
 int run_gemm(f5_plan_s* p, const GemmParams& g, int mode, int epi, hipStream_t st);
 float* tap_dst(f5_plan_s* p, const std::string& name);

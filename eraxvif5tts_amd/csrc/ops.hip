@@ -170,6 +170,36 @@ extern "C" int f5_op_attention(int precision, int kernel, int B, int N, int H, c
     return sync_and_release(a, st, rc);
 }
 
+// Attention with dropout (philox.h) on its own: the mask of call word `stream_word`, batch item b drawn with batch word
+// batch0 + b.  kernel 0 = the flagged reference kernel, 1 = attention_dropout.hip's MFMA kernel (bf16).  prob == 0 is f5_op_attention.
+extern "C" int f5_op_attention_dropout(int precision, int kernel, int B, int N, int H, const float* qkv, const uint8_t* mask, float prob, uint64_t seed,
+                                       uint32_t stream_word, uint32_t batch0, float* out, f5_stream_t stream) {
+    if (!(prob >= 0.f && prob < 1.f)) return f5_fail(F5_EINVAL, "f5_op_attention_dropout: prob must lie in [0, 1)");
+    if (prob == 0.f) return f5_op_attention(precision, kernel, B, N, H, qkv, mask, out, stream);
+    F5_TRY(f5_check_device());
+    if (B <= 0 || N <= 0 || H <= 0 || !qkv || !out) return f5_fail(F5_EINVAL, "bad argument");
+    if (kernel != 0 && kernel != 1) return f5_fail(F5_EINVAL, "f5_op_attention_dropout: kernel is 0 (reference) or 1 (MFMA, bf16)");
+    hipStream_t st = (hipStream_t)stream;
+    const int inner = H * 64, rows = B * N;
+    const size_t es = f5_elem_size(precision);
+    AttnDropout d;
+    d.prob = attn_dropout_prob_of(prob);
+    d.seed = seed;
+    d.offset = stream_word;
+    d.bw0 = batch0;
+    DevArena a;
+    void *q = nullptr, *o = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&q, (size_t)rows * 3 * inner * es))) break;
+        if ((rc = a.alloc(&o, (size_t)rows * inner * es))) break;
+        if ((rc = launch_convert_pad(precision, qkv, 3 * inner, rows, 3 * inner, 3 * inner, q, 3 * inner, st))) break;
+        if ((rc = launch_attention(precision, kernel, B, N, H, q, 3 * inner, mask, o, inner, st, 0, 0, &d))) break;
+        rc = launch_convert_back(precision, o, inner, rows, inner, out, inner, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
 // Attention on PRE-SCALED q (bf16): the q part of `qkv` already holds softmax_scale * log2(e) times the projected q, as the production path's
 // q projection stores it; the kernels apply no scale, the 64-queries-per-wave kernel runs its reference-free build.
 extern "C" int f5_op_attention_prescaled(int kernel, int B, int N, int H, const float* qkv, const uint8_t* mask, float* out, f5_stream_t stream) {

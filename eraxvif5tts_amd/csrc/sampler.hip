@@ -65,6 +65,10 @@ static int rk_step(f5_plan_s* p, const SampleArgs& a, int s, const float* xs, fl
 
 // everything between the staged inputs and the final state traj[steps]; capturable (no syncs, no allocations)
 static int sample_body_ragged(f5_plan_s* p, const SampleArgs& a, hipStream_t st);
+// attention dropout: call words one sample loop consumes (evaluations x blocks)
+static uint32_t sample_call_words(const f5_plan_s* p, const SampleArgs& a) {
+    return (uint32_t)(ode_method_of(a.method)->evals * a.steps) * (uint32_t)p->m->cfg.depth;
+}
 
 static int sample_body(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
     if (p->rg) return sample_body_ragged(p, a, st);
@@ -120,10 +124,10 @@ static int sample_body(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
             F5_TRY(rk_step(p, a, s, xs, xn, bn, nb, N, mask, st));
         }
     }
-    return 0;
+    return plan_attn_dropout_advance(p, sample_call_words(p, a), st);  // (the loop's last node: a replay advances the base as an eager call does)
 }
 
-static void drop_graphs(f5_plan_s* p) {
+void plan_drop_graphs(f5_plan_s* p) {
     for (auto& g : p->graphs) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
         if (g.graph) (void)hipGraphDestroy(g.graph);
@@ -179,6 +183,10 @@ static int run_sample_loop(f5_plan_s* p, const SampleArgs& a, int use_graph, hip
     } else {
         F5_TRY(sample_body(p, a, st));
     }
+    if (p->drop_p > 0.0) {  // the loop is issued: host mirror of the base word its last node advances on the device
+        p->drop_call_base = p->drop_base_host;
+        p->drop_base_host += sample_call_words(p, a);
+    }
     return 0;
 }
 
@@ -196,7 +204,11 @@ static int guard_check_and_fallback(f5_plan_s* p, const SampleArgs& a, int use_g
         p->sat_row = 0x7fffffffu - p->sat_host[5];
         p->res_f16 = 0;
         ++p->fallbacks;
-        drop_graphs(p);  // they baked the fp16 kernels
+        plan_drop_graphs(p);  // they baked the fp16 kernels
+        if (p->drop_p > 0.0) {  // attention dropout: the rerun draws the masks of the call it repeats
+            F5_TRY(launch_attn_dropout_set(p->drop_base, p->drop_call_base, st));
+            p->drop_base_host = p->drop_call_base;
+        }
         F5_TRY(run_sample_loop(p, a, use_graph, st));
     }
     return 0;
@@ -212,7 +224,6 @@ static int finish_outputs(f5_plan_s* p, const SampleArgs& a, float* out, float* 
 
 // LayerNorm fold: point the plan at the model's table for the evaluation times `tv` (p->mod holds their AdaLN rows, computed on `st`), building it
 // when no plan has sampled on this grid yet.  Never an error: without a table (knob off, grid too long, allocation refused) the unfolded path runs.
-static void drop_graphs(f5_plan_s* p);
 static int acquire_fold(f5_plan_s* p, const std::vector<float>& tv, hipStream_t st) {
     f5_model_s* m = p->m;
     const int nev = (int)tv.size();
@@ -427,7 +438,7 @@ static int sample_body_ragged(f5_plan_s* p, const SampleArgs& a, hipStream_t st)
             F5_TRY(rk_step(p, a, s, xs, xn, T, nb, T, nullptr, st));
         }
     }
-    return 0;
+    return plan_attn_dropout_advance(p, sample_call_words(p, a), st);
 }
 
 extern "C" int f5_sample_ragged(f5_plan_t p, int B, const int32_t* frames_host, const float* cond, const int32_t* text, int nt, const int32_t* lens,

@@ -58,7 +58,8 @@ int unett_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const flo
         {
             int kind = 0;
             if (p->attn_kernel != 0 && attention_fast_supported(P, S, c.heads)) kind = 1;
-            F5_TRY(launch_attention(P, kind, nb, S, c.heads, p->qkv, 3 * inner, mask1, p->cT, inner, st));
+            const AttnDropout drop = plan_attn_dropout(p, l);
+            F5_TRY(launch_attention(P, kind, nb, S, c.heads, p->qkv, 3 * inner, mask1, p->cT, inner, st, 0, 0, &drop));
         }
         g = gp_zero();
         g.A = p->cT; g.lda = inner; g.W = b.w_o; g.ldw = inner; g.M = rows; g.N = D; g.K = inner;

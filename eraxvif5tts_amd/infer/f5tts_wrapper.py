@@ -48,7 +48,7 @@ class F5TTSWrapper:
                  device: Optional[str] = None, hf_cache_dir: Optional[str] = None, target_sample_rate: int = 24000,
                  n_mel_channels: int = 100, hop_length: int = 256, win_length: int = 1024, n_fft: int = 1024,
                  ode_method: str = "euler", use_ema: bool = True, use_duration_predictor: bool = False,
-                 vocoder=None, precision: Optional[str] = None):
+                 vocoder=None, precision: Optional[str] = None, attn_dropout: Optional[float] = None):
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = device
@@ -115,6 +115,12 @@ class F5TTSWrapper:
         # "cpu": draw every chunk's initial noise from torch's CPU generator, in chunk order -- the numbers the reference's CPU path draws after
         # the same torch.manual_seed (reference model/cfm.py:178-183 with device = cpu); None = on the GPU, as the reference's GPU path does
         self.model.noise_device = os.environ.get("F5HIP_NOISE_DEVICE") or None
+        # attention dropout, opt-in (DiT.set_attn_dropout): the reference's attention keeps dropout_p = 0.1 live at inference (modules.py:490);
+        # attn_dropout=0.1 / F5HIP_ATTN_DROPOUT=0.1 runs this side the same way (own mask stream: equal in distribution, not bit for bit)
+        if attn_dropout is None and os.environ.get("F5HIP_ATTN_DROPOUT"):
+            attn_dropout = float(os.environ["F5HIP_ATTN_DROPOUT"])
+        if attn_dropout:
+            self.model.transformer.set_attn_dropout(attn_dropout)
         self.nfe_step = 32
         self.cfg_strength = 2.0
         self.sway_sampling_coef = -1.0

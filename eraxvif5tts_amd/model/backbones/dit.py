@@ -142,6 +142,7 @@ class DiT(nn.Module):
         self._seen_shapes = {}
         self._fallbacks_seen = {}
         self._pending = {}  # plan handle -> stream of a sample() whose range-guard check was deferred (finish_pending)
+        self._attn_dropout = None  # (p, seed, plans numbered so far) while the attention-dropout mode is on (set_attn_dropout)
         self.register_load_state_dict_post_hook(lambda module, _keys: module._drop_native())
 
     # ------------------------------------------------------------------ native handle management
@@ -224,7 +225,38 @@ class DiT(nn.Module):
             lib.f5_plan_destroy(old)
             mine = [i for i, (k, _) in enumerate(self._plans) if k[0] == stream]
         self._plans.append(((stream, batch, seq_cap, max(evals, 1)), h))
+        if self._attn_dropout is not None:
+            self._apply_attn_dropout(h)
         return h
+
+    def set_attn_dropout(self, p, seed=None):
+        """Opt-in attention dropout: the reference's F.scaled_dot_product_attention(dropout_p=0.1) stays live under model.eval()
+        (modules.py:490, :582), so each of its forwards drops 10 % of the attention probabilities; p = 0.1 reproduces that, None or 0
+        turns the mode off (the default: every bit and launch as without it).  The mask stream is this library's own (Philox4x32-10 keyed
+        by `seed`, include/f5hip.h: f5_plan_set_attn_dropout), not torch's: outputs match the reference in distribution, never bit for bit.
+        seed=None draws one int64 from torch's default CPU generator now, so torch.manual_seed governs it as it governs the reference's
+        dropout.  Applies to the live plans and to plans created later; plan i (in creation order, counted from this call) uses seed + i,
+        so chunk streams do not share masks."""
+        if p is None or float(p) == 0.0:
+            self._attn_dropout = None
+            for _, h in self._plans:
+                self._finish_plan(h)
+                _lib.check(_lib.load().f5_plan_set_attn_dropout(h, 0.0, 0), "plan_set_attn_dropout")
+            return
+        p = float(p)
+        if not 0.0 < p < 1.0:
+            raise ValueError(f"attention dropout probability {p} outside [0, 1)")
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        self._attn_dropout = [p, int(seed), 0]
+        for _, h in self._plans:
+            self._apply_attn_dropout(h)
+
+    def _apply_attn_dropout(self, h):
+        p, seed, i = self._attn_dropout
+        self._finish_plan(h)
+        _lib.check(_lib.load().f5_plan_set_attn_dropout(h, p, (seed + i) & 0xFFFFFFFFFFFFFFFF), "plan_set_attn_dropout")
+        self._attn_dropout[2] = i + 1
 
     def set_kernels(self, gemm=None, attn=None):
         """A/B switch between the reference tile kernels (0) and the tuned kernels (1) for existing plans."""

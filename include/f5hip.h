@@ -224,6 +224,20 @@ F5_API int f5_plan_set_option(f5_plan_t p, const char* key, int value);
  * under automatic kernel choice needs at least 512 token rows and a time grid of at most 64 evaluation times -- a smaller call on a plan
  * that reports 1 still runs q as projected. */
 F5_API int f5_plan_get_option(f5_plan_t p, const char* key, int* value);
+/* Attention dropout, opt-in: the reference's F.scaled_dot_product_attention(dropout_p = 0.1) stays live under
+ * model.eval() (modules.py:490, :582).  prob in [0, 1), 0 = off (the default: every output bit and launch as without this call).  With it on,
+ * every attention call of the plan drops probabilities with the mask
+ *   (o0..o3) = Philox4x32-10(counter = (k >> 2, q, bw * H + head, stream), key = (seed & 0xffffffff, seed >> 32)),
+ *   keep(q, k) = o[k & 3] >= T,   out[q] = sum_k keep(q, k) P[q, k] v[k] / (1 - p),   P = softmax over all valid keys;
+ *   T = round(p * 2^32), p = the shortest decimal that rounds to the float `prob` (0.1f -> 0.1, T = 429496730; the same p divides);
+ * q / k: positions in the sequence the softmax runs over (UNetT: the time token is 0; MMDiT: [frames | text]); stream = base + e * depth + l
+ * for block l of evaluation e of the call (solver order); bw = row of the CFG-doubled batch in f5_sample* (branch * B + b, the null half
+ * second; f5_sample_ragged: branch * B + u), b in the forwards.  base is a device word of the plan: a sample advances it by evals * depth, a
+ * forward by depth, a replayed graph too.  The call resets base to 0 and drops captured graphs.  The mask stream is this library's own,
+ * not torch's: a run matches the reference in distribution, never bit for bit.  While it is on, q is never pre-scaled
+ * ("attn_prescale_active" reads 0) and a ragged sample() is not bit-equal to its batch-1 calls.  f5_plan_get_option keys:
+ * "attn_dropout_on", "attn_dropout_base" (host mirror of base). */
+F5_API int f5_plan_set_attn_dropout(f5_plan_t p, float prob, uint64_t seed);
 
 /* ------------------------------------------------------------------ duration predictor
  * Replaces DurationPredictor.forward / .phoneme_forward (reference model/duration_predictor.py:28-46 / :48-68) as called from
@@ -280,6 +294,10 @@ F5_API int f5_op_layernorm_modulate(int rows, int dim, const float* x, const flo
  * -> out f32 [B, N, H*64].  kernel: 0 = reference kernel, 1 = tuned flash kernel (bf16). */
 F5_API int f5_op_attention(int precision, int kernel, int B, int N, int H, const float* qkv, const uint8_t* mask, float* out,
                     f5_stream_t stream);
+/* f5_op_attention with the dropout mask of f5_plan_set_attn_dropout: call word `stream_word`, batch item b drawn with batch word batch0 + b.
+ * kernel 0 = the reference kernel's dropout build, 1 = the MFMA flash kernel with dropout (bf16).  prob == 0 gives f5_op_attention's bits. */
+F5_API int f5_op_attention_dropout(int precision, int kernel, int B, int N, int H, const float* qkv, const uint8_t* mask, float prob,
+                                   uint64_t seed, uint32_t stream_word, uint32_t batch0, float* out, f5_stream_t stream);
 /* The same on PRE-SCALED q (bf16 only): the q part of `qkv` already holds softmax_scale * log2(e) = 0.125 * 1.4426950408889634 times the
  * projected q, the form the production path's q projection stores when the plan option "attn_prescale" is active.  The
  * kernels apply no scale; the 64-queries-per-wave kernel runs its reference-free build with its two range guards. */
