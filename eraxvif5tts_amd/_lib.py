@@ -10,7 +10,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (F5HIP_LIB: developer override, another in-tree build of the library for same-box A/B runs of two builds)
 LIB_PATH = os.environ.get("F5HIP_LIB") or os.path.join(_HERE, "lib", "libf5hip.so")
 
-F5_PREC_BF16, F5_PREC_FP32 = 0, 1
+F5_PREC_BF16, F5_PREC_FP32, F5_PREC_FP16 = 0, 1, 2
+# precision names of DiT(precision=...) / F5TTSWrapper(precision=...) / F5HIP_PRECISION (include/f5hip.h: F5_PREC_*)
+PRECISIONS = {"bf16": F5_PREC_BF16, "fp32": F5_PREC_FP32, "fp16": F5_PREC_FP16}
 F5_ODE_EULER, F5_ODE_MIDPOINT, F5_ODE_RK4, F5_ODE_HEUN2, F5_ODE_HEUN3 = 0, 1, 2, 3, 4
 # odeint_kwargs["method"] -> F5_ODE_* (torchdiffeq's fixed-grid names; f5_ode_evals_per_step gives the evaluations per step)
 ODE_METHODS = {"euler": F5_ODE_EULER, "midpoint": F5_ODE_MIDPOINT, "rk4": F5_ODE_RK4, "heun2": F5_ODE_HEUN2, "heun3": F5_ODE_HEUN3}
@@ -86,6 +88,8 @@ _PROTOS = {
     "f5_op_linear": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "f5_op_linear_fused": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "f5_op_ln_fold": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "f5_op_linear_fused_p": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "f5_op_ln_fold_p": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "f5_op_layernorm_modulate": (_I, [_I, _I, _P, _P, _P, _P, _P]),
     "f5_op_attention": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "f5_op_attention_dropout": (_I, [_I, _I, _I, _I, _I, _P, _P, _F, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),

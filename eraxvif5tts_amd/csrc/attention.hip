@@ -130,8 +130,8 @@ __global__ __launch_bounds__(256) void attn_ref_kernel(const T* __restrict__ qkv
     }
 }
 
-int launch_attention_fast(int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
-                          int qscaled);  // attention_fast.hip
+int launch_attention_fast(int precision, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream,
+                          int bstride, int qscaled);  // attention_fast.hip
 
 double attn_dropout_prob_of(float prob) {
     char buf[32];
@@ -159,6 +159,7 @@ int launch_attention(int precision, int kernel_kind, int B, int N, int H, const 
         }
         const AttnDropArgs da = attn_drop_args(*drop);
         dim3 grid(cdiv(N, 64), H, B), block(256);
+        if (precision == F5_PREC_FP16) return f5_fail(F5_ENOTSUP, "attention: dropout is not built for the fp16 mode");
         if (precision == F5_PREC_BF16)
             hipLaunchKernelGGL((attn_ref_kernel<bf16_t, true>), grid, block, 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, 0.125f, da);
         else
@@ -168,13 +169,16 @@ int launch_attention(int precision, int kernel_kind, int B, int N, int H, const 
     }
     if (kernel_kind == 1) {
         if (!attention_fast_supported(precision, N, H)) return f5_fail(F5_EINVAL, "attention: tuned kernel does not support this problem");
-        return launch_attention_fast(B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
+        if (qscaled && precision == F5_PREC_FP16) return f5_fail(F5_EINVAL, "attention: the fp16 mode takes q as projected");
+        return launch_attention_fast(precision, B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
     }
     // 1/sqrt(64) (SDPA default scale, modules.py:490); pre-scaled q carries 1/sqrt(64) * log2(e): exp(s ln 2) = exp2(s)
     const float scale = qscaled ? 0.6931471805599453f : 0.125f;
     dim3 grid(cdiv(N, 64), H, B), block(256);
     if (precision == F5_PREC_BF16)
         hipLaunchKernelGGL((attn_ref_kernel<bf16_t>), grid, block, 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, scale, AttnNoDrop{});
+    else if (precision == F5_PREC_FP16)
+        hipLaunchKernelGGL((attn_ref_kernel<f16_t>), grid, block, 0, stream, (const f16_t*)qkv, ldq, H * 64, mask, (f16_t*)out, ldo, N, bstride, scale, AttnNoDrop{});
     else
         hipLaunchKernelGGL((attn_ref_kernel<float>), grid, block, 0, stream, (const float*)qkv, ldq, H * 64, mask, (float*)out, ldo, N, bstride, scale, AttnNoDrop{});
     F5_LAUNCH_CHECK();

@@ -1,4 +1,4 @@
-// attention_fast.hip -- flash attention for the DiT blocks on gfx950 (bf16 in/out, head dim 64, non-causal, key-padding mask;
+// attention_fast.hip -- flash attention for the DiT blocks on gfx950 (bf16 in/out, or fp16 with EL = f16_t; head dim 64, non-causal, key-padding mask;
 // reference model/modules.py:483-497): the 64-queries-per-wavefront kernel and the launcher that picks between it and the
 // software-pipelined 32-queries-per-wavefront kernel of attention_pipe.hip.
 //
@@ -25,11 +25,11 @@ __device__ __forceinline__ float max3_asm(float a, float b, float c) {
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
 }
-__device__ __forceinline__ bf16x8 pack8(const f32x16& s, int base) {
-    bf16x8 r;
+template <typename EL> __device__ __forceinline__ bf16x8 pack8(const f32x16& s, int base) {
+    float p[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (bf16_t)s[base + j];
-    return r;
+    for (int j = 0; j < 8; ++j) p[j] = s[base + j];
+    return el_pack_p8<EL>(p);
 }
 
 // attn_wide_kernel:
@@ -55,7 +55,7 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& s, int base) {
 //         against 2^-64): nothing to do.  A fully masked tile gives rs = 0 legitimately; only the end-of-item test decides.
 //     Bounds (both builds): per-lane tile sums stay below 2^64 or the classic step runs, so l_run < nt * 2^64 (2^68 at N = 1024, 2^71 at
 //     the 128 tiles of the masked build) and |O| < nt * 2^65 * max|v| per element (two half-waves of keys per tile): inside fp32.
-#ifdef F5_ATTN_GUARD_COUNT  // diagnostic build only (tools/attn_guard_count.py): how often the QS build's two guards fire
+#if defined(F5_ATTN_GUARD_COUNT) && !defined(F5_F16_TU)  // diagnostic build only (tools/attn_guard_count.py): how often the QS build's two guards fire
 __device__ unsigned g_attn_guard_count[3];  // [0] items (workgroups) of the QS build, [1] high-side trips (waves), [2] low-side re-runs (workgroups)
 extern "C" __attribute__((visibility("default"))) int f5_debug_attn_guard_counts(unsigned* out3, int reset) {
     if (out3 && hipMemcpyFromSymbol(out3, HIP_SYMBOL(g_attn_guard_count), sizeof(g_attn_guard_count)) != hipSuccess) return -1;
@@ -68,7 +68,7 @@ extern "C" __attribute__((visibility("default"))) int f5_debug_attn_guard_counts
 #else
 #define F5_GUARD_COUNT(i, who)
 #endif
-template <bool MASKED, bool QS>
+template <bool MASKED, bool QS, typename EL = bf16_t>
 __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restrict__ qkv, int ldq, int inner, const uint8_t* __restrict__ mask,
                                                            bf16_t* __restrict__ out, int ldo, int N, int bs /* rows between batch items */, float c) {
     constexpr int KT = 64, QB = 2, TB = KT * 128, NBUF = 3, BUF = 2 * TB, WAVES = 4;
@@ -177,7 +177,9 @@ __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restr
     f32x16 o_acc[QB][2];
     float m_run[QB], l_run[QB];
     constexpr int DIST = NBUF - 1;  // tiles requested ahead
-    constexpr float RANGE_GUARD = 18446744073709551616.0f;  // 2^64: per-lane row sums of one tile at or above this take the classic path
+    // 2^64 (bf16) / 2^15 (fp16, whose numerators must stay below 65504): per-lane row sums of one tile at or above this take the classic path
+    static_assert(!(QS && Elem<EL>::F16), "the reference-free build needs bf16's exponent range");
+    constexpr float RANGE_GUARD = Elem<EL>::ATTN_SUM_LOG2 == 64 ? 18446744073709551616.0f : (float)(1u << (Elem<EL>::ATTN_SUM_LOG2 & 31));
     constexpr float LOW_GUARD = 5.421010862427522e-20f;     // 2^-64 (QS): a query's l below this sends the item through the classic loop
 #define F5_VMWAIT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
     bool rerun = false;  // QS: the second pass
@@ -229,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restr
             auto qk = [&](auto& kfr, int n) {
 #pragma unroll
                 for (int j = 0; j < QB; ++j)
-                    s[j][n >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr, qf[j][n & 3], (n & 3) ? s[j][n >> 2] : f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                    s[j][n >> 2] = el_mfma32<EL>(kfr, qf[j][n & 3], (n & 3) ? s[j][n >> 2] : f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
             };
             // scheduling fences pin {wait, two MFMAs, next read} groups: left alone the compiler hoists all eight reads (32 registers) above the MFMAs
 #define F5_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -354,13 +356,13 @@ __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restr
             auto pv_half = [&](int st, int mb, const bf16x8 (&pf)[QB]) {
                 const bf16x8 vfr = __builtin_shufflevector(vf[mb][0], vf[mb][1], 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
-                for (int j = 0; j < QB; ++j) o_acc[j][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr, pf[j], o_acc[j][mb], 0, 0, 0);
+                for (int j = 0; j < QB; ++j) o_acc[j][mb] = el_mfma32<EL>(vfr, pf[j], o_acc[j][mb]);
             };
 #define F5_PV(st, more)                                                                       \
         {                                                                                         \
             bf16x8 pf[QB];                                                                        \
-            pf[0] = pack8(s[0][(st) >> 1], 8 * ((st) & 1));                                       \
-            pf[1] = pack8(s[1][(st) >> 1], 8 * ((st) & 1));                                       \
+            pf[0] = pack8<EL>(s[0][(st) >> 1], 8 * ((st) & 1));                                       \
+            pf[1] = pack8<EL>(s[1][(st) >> 1], 8 * ((st) & 1));                                       \
             F5_FENCE();                                                                           \
             F5_LWAIT2(2, vf[0][0], vf[0][1]);                                                     \
             pv_half(st, 0, pf);                                                                   \
@@ -454,9 +456,7 @@ __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restr
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 v4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(o_acc[j][mb][4 * g + e] * inv);
+                const bf16x4 v4 = el_pack4<EL>(o_acc[j][mb][4 * g] * inv, o_acc[j][mb][4 * g + 1] * inv, o_acc[j][mb][4 * g + 2] * inv, o_acc[j][mb][4 * g + 3] * inv);
                 const int row = 32 * j + r_e, chunk = (4 * mb + g) ^ (row & 7);
                 *reinterpret_cast<bf16x4*>(stage + row * 128 + chunk * 16 + 8 * h_e) = v4;
             }
@@ -473,15 +473,56 @@ __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const bf16_t* __restr
 }
 
 
+// Compiled as two translation units (build time): attention_fast_f16.hip (#define F5_F16_TU + #include of this file) holds the EL = f16_t
+// instantiations of the wide kernel for the fp16 precision mode behind launch_attention_wide_f16(); every host-side rule lives here.
+#ifdef F5_F16_TU
+#define F5_EL f16_t
+#else
+#define F5_EL bf16_t
+#endif
+// the wide kernel's launch for this translation unit's element type
+static int launch_wide(bool masked, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                       int qscaled) {
+    const float c = qscaled ? 1.0f : F5_ATTN_QSCALE;
+    dim3 grid(cdiv(N, 256), H, B);
+#define F5_WIDE(M_, Q_) \
+    hipLaunchKernelGGL((attn_wide_kernel<M_, Q_, F5_EL>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c)
+#ifdef F5_F16_TU
+    if (qscaled) return f5_fail(F5_EINVAL, "attention_fast: the fp16 mode takes q as projected");
+    if (masked) F5_WIDE(true, false); else F5_WIDE(false, false);
+#else
+    if (masked) {
+        if (qscaled) F5_WIDE(true, true); else F5_WIDE(true, false);
+    } else {
+        if (qscaled) F5_WIDE(false, true); else F5_WIDE(false, false);
+    }
+#endif
+#undef F5_WIDE
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+#ifdef F5_F16_TU
+int launch_attention_wide_f16(bool masked, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                              int qscaled) {
+    return launch_wide(masked, B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
+}
+#else
 int g_attn_variant = 0;  // tuning knob ("attn_variant"): 0 = by grid size, 2 = 64 queries per wave, 5 = software-pipelined 32 queries per wave
 
-bool attention_fast_supported(int precision, int N, int H) { return precision == F5_PREC_BF16 && N >= 1 && H >= 1; }
+bool attention_fast_supported(int precision, int N, int H) { return (precision == F5_PREC_BF16 || precision == F5_PREC_FP16) && N >= 1 && H >= 1; }
 
 int launch_attention_pipe(int waves, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
                           int qscaled);  // attention_pipe.hip
 
 int launch_attention_pipe_segs(bool masked, int nbr, const AttnSegs& segs, int maxN, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
                                int bstride, int qscaled);  // attention_pipe.hip
+// the fp16 precision mode's instantiations (attention_pipe_f16.hip, attention_fast_f16.hip)
+int launch_attention_pipe_f16(int waves, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                              int qscaled);
+int launch_attention_pipe_segs_f16(bool masked, int nbr, const AttnSegs& segs, int maxN, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
+                                   int bstride, int qscaled);
+int launch_attention_wide_f16(bool masked, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+                              int qscaled);
 
 static int cu_count_cached() {
     static int cus = 0;
@@ -505,7 +546,7 @@ static bool picks_wide(int B, int N, int H, bool masked, int ldq, int bstride) {
 int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& segs, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
                             int bstride, int qscaled, const AttnDropout* drop) {
     if (segs.cnt < 0 || segs.cnt > AttnSegs::MAX || segs.nbr < 1) return f5_fail(F5_EINVAL, "attention_ragged: a table holds at most %d utterances", AttnSegs::MAX);
-    const size_t es = precision == F5_PREC_BF16 ? 2 : 4;
+    const size_t es = precision == F5_PREC_FP32 ? 4 : 2;
     if (drop && drop->prob > 0.0) {  // attention dropout: every utterance its own launch (the shared launches have no dropout build)
         for (int u = 0; u < segs.cnt; ++u) {
             const int nu = segs.n[u];
@@ -535,7 +576,9 @@ int launch_attention_ragged(int precision, int attn_kernel_opt, const AttnSegs& 
         }
     }
     for (int k = 0; k < 2; ++k)
-        if (grp[k].cnt > 0) F5_TRY(launch_attention_pipe_segs(k == 1, segs.nbr, grp[k], maxn[k], H, qkv, ldq, out, ldo, stream, bstride, qscaled));
+        if (grp[k].cnt > 0)
+            F5_TRY((precision == F5_PREC_FP16 ? launch_attention_pipe_segs_f16 : launch_attention_pipe_segs)(k == 1, segs.nbr, grp[k], maxn[k], H, qkv, ldq, out, ldo,
+                                                                                                             stream, bstride, qscaled));
     return 0;
 }
 
@@ -556,22 +599,13 @@ int launch_attention_ragged_all(int precision, int attn_kernel_opt, int nbr, int
     return 0;
 }
 
-int launch_attention_fast(int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
-                          int qscaled) {
+int launch_attention_fast(int precision, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream,
+                          int bstride, int qscaled) {
     if ((ldq & 7) || (ldo & 7)) return f5_fail(F5_EINVAL, "attention_fast: ldq and ldo must be multiples of 8");
+    const bool h16 = precision == F5_PREC_FP16;
     const bool masked = mask != nullptr || (N % 64) != 0;
     const bool wide = picks_wide(B, N, H, masked, ldq, bstride);
-    if (!wide) return launch_attention_pipe(4, B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
-    const float c = qscaled ? 1.0f : F5_ATTN_QSCALE;
-    dim3 grid(cdiv(N, 256), H, B);
-#define F5_WIDE(M_, Q_) \
-    hipLaunchKernelGGL((attn_wide_kernel<M_, Q_>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c)
-    if (masked) {
-        if (qscaled) F5_WIDE(true, true); else F5_WIDE(true, false);
-    } else {
-        if (qscaled) F5_WIDE(false, true); else F5_WIDE(false, false);
-    }
-#undef F5_WIDE
-    F5_LAUNCH_CHECK();
-    return 0;
+    if (!wide) return (h16 ? launch_attention_pipe_f16 : launch_attention_pipe)(4, B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
+    return (h16 ? launch_attention_wide_f16 : launch_wide)(masked, B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
 }
+#endif

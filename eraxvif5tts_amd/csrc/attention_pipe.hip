@@ -1,4 +1,4 @@
-// attention_pipe.hip -- software-pipelined flash attention for the DiT blocks on gfx950 (bf16 in/out, head dim 64, non-causal,
+// attention_pipe.hip -- software-pipelined flash attention for the DiT blocks on gfx950 (bf16 in/out, or fp16 with EL = f16_t; head dim 64, non-causal,
 // key-padding mask; reference model/modules.py:483-497).  32 queries per wavefront, 128 per workgroup: the launcher
 // (attention_fast.hip) picks it when the 256-query workgroups of the wide kernel would leave CUs idle (single-utterance serving).
 //
@@ -67,7 +67,7 @@ __device__ __forceinline__ float sum_halves(float v) {
 // SEG (ragged sampler): the launch covers several utterances of different lengths that sit at row offsets inside a longer concatenation;
 // batch index = utterance * nbr + branch, N and the row offset come from `segs`, query blocks past an utterance's end leave at once.  Every
 // other block computes exactly what it computes in a launch over its utterance alone (same N, same rows).
-template <bool MASKED, int WAVES, int ABL = 0, int WPE = 2, bool SEG = false>
+template <bool MASKED, int WAVES, int ABL = 0, int WPE = 2, bool SEG = false, typename EL = bf16_t>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void attn_pipe_kernel(const bf16_t* __restrict__ qkv, int ldq, int inner,
                                                                                  const uint8_t* __restrict__ mask, bf16_t* __restrict__ out,
                                                                                  int ldo, int N, int bs /* rows between batch items */, float c /* scale * log2(e) */,
@@ -209,9 +209,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WPE,
             asm volatile("" ::"v"(a), "v"(bq));
         } else if constexpr (ABL & 512) {  // fragment read and waited for, MFMA fed from registers
             asm volatile("" ::"v"(a));
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq, bq, acc, 0, 0, 0);
+            acc = el_mfma32<EL>(bq, bq, acc);
         } else {
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq, acc, 0, 0, 0);
+            acc = el_mfma32<EL>(a, bq, acc);
         }
     };
     auto mma_pv = [&](const bf16x8& a, const bf16x8& bp, f32x16& acc) {
@@ -219,12 +219,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WPE,
             asm volatile("" ::"v"(a), "v"(bp));
         } else if constexpr (ABL & 512) {
             asm volatile("" ::"v"(a));
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bp, bp, acc, 0, 0, 0);
+            acc = el_mfma32<EL>(bp, bp, acc);
         } else {
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bp, acc, 0, 0, 0);
+            acc = el_mfma32<EL>(a, bp, acc);
         }
     };
-    constexpr float ATTN_DEFER_LOG2 = 16.0f;  // a row's exponent reference is moved when its maximum exceeds it by more than this (log2 units)
+    // a row's exponent reference is moved when its maximum exceeds it by more than this (log2 units): 16 for bf16, 14 for fp16, whose numerators
+    // must stay below 65504 (common.h)
+    constexpr float ATTN_DEFER_LOG2 = (float)Elem<EL>::ATTN_DEFER_LOG2;
 
     f32x16 sA[2], sB[2];
     static_for<8>([&](auto nc) {  // S(0) = K(0) . Q^T (no overlap to exploit yet)
@@ -235,7 +237,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WPE,
         }
         bf16x8 kf = k_frag(nc, F5_IC(0));
         lds_wait(F5_IC(0), kf);
-        sA[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ds], sA[kb], 0, 0, 0);
+        sA[kb] = el_mfma32<EL>(kf, qf[ds], sA[kb]);
     });
     __syncthreads();  // every wave has read K(0): the first step may overwrite its buffer with K(2)
 
@@ -379,10 +381,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WPE,
                 rs0 += p[6];
                 rs1 += p[7];
             }
-            bf16x8 pf;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[j] = (bf16_t)p[j];
-            pf_prev = pf;
+            pf_prev = el_pack_p8<EL>(p);
             F5_FENCE();
         };
         slot(F5_IC(0));
@@ -429,40 +428,48 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WPE,
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                bf16x4 v4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(o_acc[mb][4 * g + e] * inv);
-                *reinterpret_cast<bf16x4*>(op + 32 * mb + 8 * g) = v4;
+                *reinterpret_cast<bf16x4*>(op + 32 * mb + 8 * g) =
+                    el_pack4<EL>(o_acc[mb][4 * g] * inv, o_acc[mb][4 * g + 1] * inv, o_acc[mb][4 * g + 2] * inv, o_acc[mb][4 * g + 3] * inv);
             }
     }
 }
 
 }  // namespace
 
-int launch_attention_pipe(int waves, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
+// Compiled as two translation units (build time): attention_pipe_f16.hip (#define F5_F16_TU + #include of this file) holds the EL = f16_t
+// instantiations of the fp16 precision mode behind launch_attention_pipe_f16 / launch_attention_pipe_segs_f16.
+#ifdef F5_F16_TU
+#define F5_EL f16_t
+#define F5_PIPE_FN(name) name##_f16
+#else
+#define F5_EL bf16_t
+#define F5_PIPE_FN(name) name
+#endif
+int F5_PIPE_FN(launch_attention_pipe)(int waves, int B, int N, int H, const void* qkv, int ldq, const uint8_t* mask, void* out, int ldo, hipStream_t stream, int bstride,
                           int qscaled) {
     if (waves != 4) return f5_fail(F5_EINVAL, "attention_pipe: the library instantiates the 4-wave (128 queries per workgroup) build only");
+    if (Elem<F5_EL>::F16 && qscaled) return f5_fail(F5_EINVAL, "attention_pipe: the fp16 mode takes q as projected");
     const float c = qscaled ? 1.0f : F5_ATTN_QSCALE;  // (pre-scaled q: fma(s, 1, -m) is exact)
     const bool masked = mask != nullptr || (N % 64) != 0;
     const dim3 grid(cdiv(N, 128), H, B);
     if (masked)
-        hipLaunchKernelGGL((attn_pipe_kernel<true, 4>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c, AttnSegs{});
+        hipLaunchKernelGGL((attn_pipe_kernel<true, 4, 0, 2, false, F5_EL>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c, AttnSegs{});
     else
-        hipLaunchKernelGGL((attn_pipe_kernel<false, 4>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c, AttnSegs{});
+        hipLaunchKernelGGL((attn_pipe_kernel<false, 4, 0, 2, false, F5_EL>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, mask, (bf16_t*)out, ldo, N, bstride, c, AttnSegs{});
     F5_LAUNCH_CHECK();
     return 0;
 }
 
 // several utterances (all with N % 64 == 0, or all without) of one ragged batch in ONE launch: grid.z = utterance x branch
-int launch_attention_pipe_segs(bool masked, int nbr, const AttnSegs& segs, int maxN, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
+int F5_PIPE_FN(launch_attention_pipe_segs)(bool masked, int nbr, const AttnSegs& segs, int maxN, int H, const void* qkv, int ldq, void* out, int ldo, hipStream_t stream,
                                int bstride, int qscaled) {
     const float c = qscaled ? 1.0f : F5_ATTN_QSCALE;
     const dim3 grid(cdiv(maxN, 128), H, nbr * segs.cnt);
     if (masked)
-        hipLaunchKernelGGL((attn_pipe_kernel<true, 4, 0, 2, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, (const uint8_t*)nullptr, (bf16_t*)out, ldo, maxN,
+        hipLaunchKernelGGL((attn_pipe_kernel<true, 4, 0, 2, true, F5_EL>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, (const uint8_t*)nullptr, (bf16_t*)out, ldo, maxN,
                            bstride, c, segs);
     else
-        hipLaunchKernelGGL((attn_pipe_kernel<false, 4, 0, 2, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, (const uint8_t*)nullptr, (bf16_t*)out, ldo, maxN,
+        hipLaunchKernelGGL((attn_pipe_kernel<false, 4, 0, 2, true, F5_EL>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, ldq, H * 64, (const uint8_t*)nullptr, (bf16_t*)out, ldo, maxN,
                            bstride, c, segs);
     F5_LAUNCH_CHECK();
     return 0;

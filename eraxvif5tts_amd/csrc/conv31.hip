@@ -1,5 +1,5 @@
 // conv31.hip -- ConvPositionEmbedding's grouped Conv1d(dim, dim, k = 31, groups = 16, padding = 15) + Mish for dim = 1024
-// (reference model/modules.py:167-190: two of them per network evaluation), bf16 in / bf16 out, fp32 accumulate.
+// (reference model/modules.py:167-190: two of them per network evaluation), bf16 in / bf16 out (EL = f16_t: fp16 in / out, the fp16 precision mode), fp32 accumulate.
 //
 // The generic path (gemm_fast.hip, GEMM_CONV31) treats the conv as an implicit GEMM and re-fetches the 256-token activation slice
 // for every one of the 31 taps: 20 KiB of LDS-DMA per MFLOP-sized K-step, 2.5x the traffic of the dense tiles (570 TFLOP/s).
@@ -26,7 +26,7 @@ constexpr int WSLOTS = 4, WAHEAD = WSLOTS - 1;  // weight slices in LDS / taps f
 
 // TOK = 256 tokens per workgroup (64 per wave); TOK = 128 (32 per wave) for launches that would otherwise leave CUs without a workgroup
 // (single utterance: 4 token tiles x 16 groups x 2 branches = 128 workgroups of 256 tokens).  Same sums per output either way.
-template <int TOK>
+template <int TOK, typename EL = bf16_t>
 __global__ __launch_bounds__(256, 2) void conv31_kernel(GemmParams p, int tiles_per_seq) {
     constexpr int ROWS = TOK + 2 * HALO;            // 286 / 158 halo rows
     constexpr int A_PIECES = (ROWS + 7) / 8;        // 36 / 20 DMA pieces of 8 rows x 128 B
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void conv31_kernel(GemmParams p, int tiles_
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < TJ; ++j) acc[i][j] = Elem<EL>::mfma16(__builtin_bit_cast(typename Elem<EL>::x8, wf[i]), __builtin_bit_cast(typename Elem<EL>::x8, af[j]), acc[i][j]);
         }
     }
 
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void conv31_kernel(GemmParams p, int tiles_
                     v1[e] = fast_mish(v1[e]);
                 }
             }
-            const u32x4 q = pair_swap(to_bf16x4(v0), to_bf16x4(v1));
+            const u32x4 q = pair_swap(to_el4<EL>(v0), to_el4<EL>(v1));
             if (tok < L) *reinterpret_cast<u32x4*>(out + (size_t)tok * p.ldo + 32 * (i0 / 2)) = q;
         });
     });
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void conv31_kernel(GemmParams p, int tiles_
 int g_conv31 = 1;  // tuning knob ("conv31"): 1 = dedicated halo-tile kernel for the dim-1024 grouped conv, 0 = implicit GEMM (gemm_fast.hip)
 
 bool conv31_supported(const GemmParams& p, int precision, int epi) {
-    if (!g_conv31 || precision != F5_PREC_BF16) return false;
+    if (!g_conv31 || (precision != F5_PREC_BF16 && precision != F5_PREC_FP16)) return false;
     if (p.conv_cg != 64 || p.conv_win != 64 || p.N % 64 != 0 || p.N / 64 > 65535) return false;
     if (p.rows_per_batch <= 0 || p.M % p.rows_per_batch != 0 || (p.lda & 7) || (p.ldo & 7) || !p.bias || !p.out_t) return false;
     if (!(p.act == ACT_MISH || p.act == ACT_NONE)) return false;
@@ -143,18 +143,24 @@ bool conv31_supported(const GemmParams& p, int precision, int epi) {
 }
 
 int g_conv31_tok = 0;  // tuning knob ("conv31_tok"): tokens per workgroup, 0 = by grid size, 128 or 256 forced
-int launch_conv31(const GemmParams& p, hipStream_t stream) {
+int launch_conv31(const GemmParams& p, int precision, hipStream_t stream) {
     const int L = p.rows_per_batch, nb = p.M / L;
     if (nb > 65535) return f5_fail(F5_EINVAL, "conv31: batch %d too large for one launch", nb);
     const bool small = g_conv31_tok == 128 || (g_conv31_tok == 0 && (long)cdiv(L, 256) * (p.N / 64) * nb < 2L * f5_cu_count());
     if (small) {
         const int tiles = cdiv(L, 128);
-        hipLaunchKernelGGL(conv31_kernel<128>, dim3(tiles, p.N / 64, nb), dim3(256), 0, stream, p, tiles);
+        if (precision == F5_PREC_FP16)
+            hipLaunchKernelGGL((conv31_kernel<128, f16_t>), dim3(tiles, p.N / 64, nb), dim3(256), 0, stream, p, tiles);
+        else
+            hipLaunchKernelGGL(conv31_kernel<128>, dim3(tiles, p.N / 64, nb), dim3(256), 0, stream, p, tiles);
         F5_LAUNCH_CHECK();
         return 0;
     }
     const int tiles = cdiv(L, 256);
-    hipLaunchKernelGGL(conv31_kernel<256>, dim3(tiles, p.N / 64, nb), dim3(256), 0, stream, p, tiles);
+    if (precision == F5_PREC_FP16)
+        hipLaunchKernelGGL((conv31_kernel<256, f16_t>), dim3(tiles, p.N / 64, nb), dim3(256), 0, stream, p, tiles);
+    else
+        hipLaunchKernelGGL(conv31_kernel<256>, dim3(tiles, p.N / 64, nb), dim3(256), 0, stream, p, tiles);
     F5_LAUNCH_CHECK();
     return 0;
 }

@@ -15,7 +15,9 @@
 // per vector column (4 per row and pass).
 // XI / XO: storage type of the residual stream read / written (float, or _Float16 in the bf16 production mode: the reference's own GPU
 // path keeps the whole residual stream in fp16, utils_infer.py:184-193; fp32 arithmetic here either way, the fp16 store saturates).
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <typename T> struct Vec4Of { typedef f32x4 type; };
+template <> struct Vec4Of<bf16_t> { typedef bf16x4 type; };
+template <> struct Vec4Of<f16_t> { typedef f16x4 type; };
 template <typename XT> __device__ __forceinline__ f32x4 load_res4(const XT* p) {
     if constexpr (sizeof(XT) == 2) {
         const f16x4 r = *reinterpret_cast<const f16x4*>(p);
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const XI* x, XO* xo /* m
     const XI* xr = x + (size_t)row * ldx;
     [[maybe_unused]] XO* xw = xo + (size_t)row * ldx;
     const int nvec = dim >> 2;  // dim % 4 == 0
-    typedef typename std::conditional<sizeof(TO) == 2, bf16x4, f32x4>::type yvec_t;
+    typedef typename Vec4Of<TO>::type yvec_t;
     auto widen = [](const yvec_t& r) {
         if constexpr (sizeof(TO) == 2)
             return f32x4{(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const XI* x, XO* xo /* m
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * (add_one + m4[i][e]) + a4[i][e];
             if constexpr (sizeof(TO) == 2) {
-                *reinterpret_cast<bf16x4*>(orow + c * 4) = bf16x4{(bf16_t)o[0], (bf16_t)o[1], (bf16_t)o[2], (bf16_t)o[3]};
+                *reinterpret_cast<typename Elem<TO>::x4*>(orow + c * 4) = Elem<TO>::pack4(o[0], o[1], o[2], o[3]);
             } else {
                 *reinterpret_cast<f32x4*>(orow + c * 4) = f32x4{o[0], o[1], o[2], o[3]};
             }
@@ -143,11 +145,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const XI* x, XO* xo /* m
 
 // The production shape of the bf16 mode (dim = 1024, fp16 residual stream, bf16 branches and output) with 16-byte accesses: a lane owns
 // two runs of 8 consecutive features.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-template <int YMODE>
-__global__ __launch_bounds__(256) void layernorm1024_h_kernel(const _Float16* x, _Float16* xo, int ldx, int rows, const bf16_t* __restrict__ y, int ldy,
-                                                              const bf16_t* __restrict__ y2, const float* __restrict__ mul, const float* __restrict__ add,
-                                                              int mod_bstride, int rows_per_batch, float add_one, bf16_t* __restrict__ out, int ldo,
+template <int YMODE, typename TO = bf16_t>
+__global__ __launch_bounds__(256) void layernorm1024_h_kernel(const _Float16* x, _Float16* xo, int ldx, int rows, const TO* __restrict__ y, int ldy,
+                                                              const TO* __restrict__ y2, const float* __restrict__ mul, const float* __restrict__ add,
+                                                              int mod_bstride, int rows_per_batch, float add_one, TO* __restrict__ out, int ldo,
                                                               PrefetchSet pf, unsigned* sat, int sat_tag) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -164,14 +165,14 @@ __global__ __launch_bounds__(256) void layernorm1024_h_kernel(const _Float16* x,
     const size_t moff = (size_t)(row / rows_per_batch) * mod_bstride;
     float v[2][8];
     f16x8 xr[2];
-    [[maybe_unused]] bf16x8 yr[2], yr2[2];
+    [[maybe_unused]] typename Elem<TO>::x8 yr[2], yr2[2];
     f32x4 m4[2][2], a4[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int c = (lane + i * 64) * 8;
         xr[i] = *reinterpret_cast<const f16x8*>(x + (size_t)row * ldx + c);
-        if constexpr (YMODE != 0) yr[i] = *reinterpret_cast<const bf16x8*>(y + (size_t)row * ldy + c);
-        if constexpr (YMODE == 3) yr2[i] = *reinterpret_cast<const bf16x8*>(y2 + (size_t)row * ldy + c);
+        if constexpr (YMODE != 0) yr[i] = *reinterpret_cast<const typename Elem<TO>::x8*>(y + (size_t)row * ldy + c);
+        if constexpr (YMODE == 3) yr2[i] = *reinterpret_cast<const typename Elem<TO>::x8*>(y2 + (size_t)row * ldy + c);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -219,10 +220,10 @@ __global__ __launch_bounds__(256) void layernorm1024_h_kernel(const _Float16* x,
     const float rstd = rsqrtf(wave_sum(q) / 1024.0f + 1e-6f);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        bf16x8 o;
+        typename Elem<TO>::x8 o;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (bf16_t)((v[i][e] - mean) * rstd * (add_one + m4[i][e >> 2][e & 3]) + a4[i][e >> 2][e & 3]);
-        *reinterpret_cast<bf16x8*>(out + (size_t)row * ldo + (lane + i * 64) * 8) = o;
+        for (int e = 0; e < 8; ++e) o[e] = from_f32<TO>((v[i][e] - mean) * rstd * (add_one + m4[i][e >> 2][e & 3]) + a4[i][e >> 2][e & 3]);
+        *reinterpret_cast<typename Elem<TO>::x8*>(out + (size_t)row * ldo + (lane + i * 64) * 8) = o;
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) asm volatile("" ::"v"(pfv[r]));  // keeps the prefetch loads alive
@@ -230,9 +231,9 @@ __global__ __launch_bounds__(256) void layernorm1024_h_kernel(const _Float16* x,
 // The read-only pass of the in-place-residual mode (YMODE 0) with ONE modulation row for every token (the sampler: one time per evaluation):
 // a wave normalises RPW consecutive rows and keeps the 2 x 1024 modulation values in registers across them -- per row the kernel above issues
 // 2 loads of the stream and 8 of the modulation rows (L1 hits, but 4/5 of its load instructions).  Same arithmetic per row, bit for bit.
-template <int RPW>
+template <int RPW, typename TO = bf16_t>
 __global__ __launch_bounds__(256) void layernorm1024_h_rows_kernel(const _Float16* __restrict__ x, int ldx, int rows, const float* __restrict__ mul,
-                                                                   const float* __restrict__ add, float add_one, bf16_t* __restrict__ out, int ldo,
+                                                                   const float* __restrict__ add, float add_one, TO* __restrict__ out, int ldo,
                                                                    PrefetchSet pf, unsigned* sat, int sat_tag) {
     const int lane = threadIdx.x & 63;
     const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
@@ -293,10 +294,10 @@ __global__ __launch_bounds__(256) void layernorm1024_h_rows_kernel(const _Float1
         if (row < rows) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                bf16x8 o;
+                typename Elem<TO>::x8 o;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16_t)((v[i][e] - mean) * rstd * (add_one + m4[i][e >> 2][e & 3]) + a4[i][e >> 2][e & 3]);
-                *reinterpret_cast<bf16x8*>(out + (size_t)row * ldo + (lane + i * 64) * 8) = o;
+                for (int e = 0; e < 8; ++e) o[e] = from_f32<TO>((v[i][e] - mean) * rstd * (add_one + m4[i][e >> 2][e & 3]) + a4[i][e >> 2][e & 3]);
+                *reinterpret_cast<typename Elem<TO>::x8*>(out + (size_t)row * ldo + (lane + i * 64) * 8) = o;
             }
         }
     }
@@ -329,7 +330,7 @@ static void ln_launch(const void* x, void* xo, int ldx, int rows, int dim, const
 
 // ymode (see layernorm_kernel): 1 = x += y (written back), 2 = normalise x + y without writing x, 3 = x = (x + y) + y2 (written back).
 // The residual stream is read from `xin` (fp32, or fp16 when xin_f16) and -- modes 1 and 3 -- written to `xout` (fp32 / fp16 by xout_f16;
-// the same buffer as xin or another one of the same leading dimension).  fp16 residual storage exists for the bf16 output type only.
+// the same buffer as xin or another one of the same leading dimension).  fp16 residual storage exists for the 16-bit output types only.
 int launch_layernorm_res(int precision_out, const void* xin, int xin_f16, void* xout, int xout_f16, int ldx, int rows, int dim, const void* y, int ldy,
                          const void* y2, int ymode, const float* mul, const float* add, int mod_bstride, int rows_per_batch, int add_one, void* out,
                          int ldo, hipStream_t stream, const PrefetchSet* prefetch, unsigned* sat, int sat_tag) {
@@ -338,7 +339,7 @@ int launch_layernorm_res(int precision_out, const void* xin, int xin_f16, void* 
         return f5_fail(F5_EINVAL, "layernorm: dim=%d unsupported", dim);
     if (!y) ymode = 0;
     if (ymode < 0 || ymode > 3 || (ymode == 3 && !y2)) return f5_fail(F5_EINVAL, "layernorm: bad residual mode %d", ymode);
-    if ((xin_f16 || xout_f16) && precision_out != F5_PREC_BF16) return f5_fail(F5_EINVAL, "layernorm: fp16 residual storage needs the bf16 output type");
+    if ((xin_f16 || xout_f16) && precision_out == F5_PREC_FP32) return f5_fail(F5_EINVAL, "layernorm: fp16 residual storage needs a 16-bit output type");
     if (xin_f16 && !xout_f16 && (ymode == 1 || ymode == 3)) return f5_fail(F5_EINVAL, "layernorm: fp16 -> fp32 residual write-back is not built");
     if (rows_per_batch <= 0) rows_per_batch = rows;
     const float one = add_one ? 1.0f : 0.0f;
@@ -349,24 +350,30 @@ int launch_layernorm_res(int precision_out, const void* xin, int xin_f16, void* 
         else                                                                                                                                   \
             ln_launch<TO, 8, XI, XO>(xin, xout, ldx, rows, dim, y, ldy, y2, ymode, mul, add, mod_bstride, rows_per_batch, one, out, ldo, stream, sat, sat_tag); \
     } while (0)
-    if (precision_out == F5_PREC_BF16 && xin_f16 && xout_f16 && dim == 1024 && g_ln_wide && !(ldx & 7) && !(ldo & 7) && !(y && (ldy & 7))) {
+    if (precision_out != F5_PREC_FP32 && xin_f16 && xout_f16 && dim == 1024 && g_ln_wide && !(ldx & 7) && !(ldo & 7) && !(y && (ldy & 7))) {
         dim3 grid(cdiv(rows, 4)), block(256);
         PrefetchSet pfs{{nullptr, nullptr, nullptr, nullptr}, {0u, 0u, 0u, 0u}};
         if (prefetch) pfs = *prefetch;
-#define F5_LN_W(M)                                                                                                                              \
-    hipLaunchKernelGGL((layernorm1024_h_kernel<M>), grid, block, 0, stream, (const _Float16*)xin, (_Float16*)xout, ldx, rows, (const bf16_t*)y, ldy, \
-                       (const bf16_t*)y2, mul, add, mod_bstride, rows_per_batch, one, (bf16_t*)out, ldo, pfs, sat, sat_tag)
-        if (ymode == 0 && mod_bstride == 0 && xin == xout && (g_ln_rows == 2 || g_ln_rows == 4) && rows >= g_ln_rows_min) {
-            if (g_ln_rows == 4)
-                hipLaunchKernelGGL((layernorm1024_h_rows_kernel<4>), dim3(cdiv(rows, 16)), block, 0, stream, (const _Float16*)xin, ldx, rows, mul, add, one,
-                                   (bf16_t*)out, ldo, pfs, sat, sat_tag);
-            else
-                hipLaunchKernelGGL((layernorm1024_h_rows_kernel<2>), dim3(cdiv(rows, 8)), block, 0, stream, (const _Float16*)xin, ldx, rows, mul, add, one,
-                                   (bf16_t*)out, ldo, pfs, sat, sat_tag);
-        } else if (ymode == 0) F5_LN_W(0);
-        else if (ymode == 1) F5_LN_W(1);
-        else if (ymode == 2) F5_LN_W(2);
-        else F5_LN_W(3);
+#define F5_LN_W(M, TO)                                                                                                                      \
+    hipLaunchKernelGGL((layernorm1024_h_kernel<M, TO>), grid, block, 0, stream, (const _Float16*)xin, (_Float16*)xout, ldx, rows, (const TO*)y, ldy, \
+                       (const TO*)y2, mul, add, mod_bstride, rows_per_batch, one, (TO*)out, ldo, pfs, sat, sat_tag)
+#define F5_LN_WIDE(TO)                                                                                                                          \
+    do {                                                                                                                                        \
+        if (ymode == 0 && mod_bstride == 0 && xin == xout && (g_ln_rows == 2 || g_ln_rows == 4) && rows >= g_ln_rows_min) {                     \
+            if (g_ln_rows == 4)                                                                                                                 \
+                hipLaunchKernelGGL((layernorm1024_h_rows_kernel<4, TO>), dim3(cdiv(rows, 16)), block, 0, stream, (const _Float16*)xin, ldx, rows, mul, add, \
+                                   one, (TO*)out, ldo, pfs, sat, sat_tag);                                                                      \
+            else                                                                                                                                \
+                hipLaunchKernelGGL((layernorm1024_h_rows_kernel<2, TO>), dim3(cdiv(rows, 8)), block, 0, stream, (const _Float16*)xin, ldx, rows, mul, add, \
+                                   one, (TO*)out, ldo, pfs, sat, sat_tag);                                                                      \
+        } else if (ymode == 0) F5_LN_W(0, TO);                                                                                                  \
+        else if (ymode == 1) F5_LN_W(1, TO);                                                                                                    \
+        else if (ymode == 2) F5_LN_W(2, TO);                                                                                                    \
+        else F5_LN_W(3, TO);                                                                                                                    \
+    } while (0)
+        if (precision_out == F5_PREC_FP16) F5_LN_WIDE(f16_t);
+        else F5_LN_WIDE(bf16_t);
+#undef F5_LN_WIDE
 #undef F5_LN_W
         F5_LAUNCH_CHECK();
         return 0;
@@ -378,6 +385,13 @@ int launch_layernorm_res(int precision_out, const void* xin, int xin_f16, void* 
             F5_LN_DIM(bf16_t, float, _Float16);
         else
             F5_LN_DIM(bf16_t, float, float);
+    } else if (precision_out == F5_PREC_FP16) {
+        if (xin_f16)
+            F5_LN_DIM(f16_t, _Float16, _Float16);
+        else if (xout_f16)
+            F5_LN_DIM(f16_t, float, _Float16);
+        else
+            F5_LN_DIM(f16_t, float, float);
     } else {
         F5_LN_DIM(float, float, float);
     }
@@ -462,7 +476,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = v[e] * sc * gv[e];
         if constexpr (sizeof(TO) == 2)
-            *reinterpret_cast<bf16x4*>(orow + c) = bf16x4{(bf16_t)o[0], (bf16_t)o[1], (bf16_t)o[2], (bf16_t)o[3]};
+            *reinterpret_cast<typename Elem<TO>::x4*>(orow + c) = Elem<TO>::pack4(o[0], o[1], o[2], o[3]);
         else
             *reinterpret_cast<f32x4*>(orow + c) = f32x4{o[0], o[1], o[2], o[3]};
     }
@@ -473,6 +487,8 @@ int launch_rmsnorm(int precision_out, const float* x, int ldx, int rows, int dim
     dim3 grid(cdiv(rows, 4)), block(256);
     if (precision_out == F5_PREC_BF16)
         hipLaunchKernelGGL((rmsnorm_kernel<bf16_t>), grid, block, 0, stream, x, ldx, rows, dim, g, (bf16_t*)out, ldo);
+    else if (precision_out == F5_PREC_FP16)
+        hipLaunchKernelGGL((rmsnorm_kernel<f16_t>), grid, block, 0, stream, x, ldx, rows, dim, g, (f16_t*)out, ldo);
     else
         hipLaunchKernelGGL((rmsnorm_kernel<float>), grid, block, 0, stream, x, ldx, rows, dim, g, (float*)out, ldo);
     F5_LAUNCH_CHECK();
@@ -499,6 +515,8 @@ int launch_pack_time_token(int precision, const float* h, const void* branch, co
     if (B * (N + 1) <= 0) return 0;
     if (precision == F5_PREC_BF16)
         hipLaunchKernelGGL((pack_time_token_kernel<bf16_t>), dim3(B * (N + 1)), dim3(256), 0, stream, h, (const bf16_t*)branch, temb, temb_bstride, B, N, D, dst);
+    else if (precision == F5_PREC_FP16)
+        hipLaunchKernelGGL((pack_time_token_kernel<f16_t>), dim3(B * (N + 1)), dim3(256), 0, stream, h, (const f16_t*)branch, temb, temb_bstride, B, N, D, dst);
     else
         hipLaunchKernelGGL((pack_time_token_kernel<float>), dim3(B * (N + 1)), dim3(256), 0, stream, h, (const float*)branch, temb, temb_bstride, B, N, D, dst);
     F5_LAUNCH_CHECK();
@@ -593,6 +611,8 @@ int launch_qknorm_rope(int precision, void* qkv, int ldq, int rows, int inner, i
     if (rows <= 0) return 0;
     if (precision == F5_PREC_BF16)
         hipLaunchKernelGGL((qknorm_rope_kernel<bf16_t>), dim3(rows), dim3(256), 0, stream, (bf16_t*)qkv, ldq, inner, heads, rope_heads, wq, wk, rope, rows_per_batch, rows);
+    else if (precision == F5_PREC_FP16)
+        hipLaunchKernelGGL((qknorm_rope_kernel<f16_t>), dim3(rows), dim3(256), 0, stream, (f16_t*)qkv, ldq, inner, heads, rope_heads, wq, wk, rope, rows_per_batch, rows);
     else
         hipLaunchKernelGGL((qknorm_rope_kernel<float>), dim3(rows), dim3(256), 0, stream, (float*)qkv, ldq, inner, heads, rope_heads, wq, wk, rope, rows_per_batch, rows);
     F5_LAUNCH_CHECK();
@@ -692,7 +712,7 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * w4[e] + b4[e];
             if constexpr (sizeof(TO) == 2) {
-                *reinterpret_cast<bf16x4*>(orow + c * 4) = bf16x4{(bf16_t)o[0], (bf16_t)o[1], (bf16_t)o[2], (bf16_t)o[3]};
+                *reinterpret_cast<typename Elem<TO>::x4*>(orow + c * 4) = Elem<TO>::pack4(o[0], o[1], o[2], o[3]);
             } else {
                 *reinterpret_cast<f32x4*>(orow + c * 4) = f32x4{o[0], o[1], o[2], o[3]};
             }
@@ -707,6 +727,8 @@ int launch_dwconv7_ln(int precision_out, const float* x, int B, int N, int C, co
     dim3 grid(cdiv(B * N, 4)), block(256);
     if (precision_out == F5_PREC_BF16)
         hipLaunchKernelGGL((dwconv7_ln_kernel<bf16_t, 4, false>), grid, block, 0, stream, x, B, N, C, wt, cbias, ln_w, ln_b, (bf16_t*)out, ldo, UttExtents{});
+    else if (precision_out == F5_PREC_FP16)
+        hipLaunchKernelGGL((dwconv7_ln_kernel<f16_t, 4, false>), grid, block, 0, stream, x, B, N, C, wt, cbias, ln_w, ln_b, (f16_t*)out, ldo, UttExtents{});
     else
         hipLaunchKernelGGL((dwconv7_ln_kernel<float, 4, false>), grid, block, 0, stream, x, B, N, C, wt, cbias, ln_w, ln_b, (float*)out, ldo, UttExtents{});
     F5_LAUNCH_CHECK();
@@ -771,6 +793,8 @@ int launch_grn(int precision, void* h, int B, int N, int C, const float* gamma, 
     const size_t total = (size_t)B * N * C;
     if (precision == F5_PREC_BF16)
         hipLaunchKernelGGL((grn_sumsq_kernel<bf16_t>), dim3(cdiv(C, 64), B), dim3(256), 0, stream, (const bf16_t*)h, N, C, scratch);
+    else if (precision == F5_PREC_FP16)
+        hipLaunchKernelGGL((grn_sumsq_kernel<f16_t>), dim3(cdiv(C, 64), B), dim3(256), 0, stream, (const f16_t*)h, N, C, scratch);
     else
         hipLaunchKernelGGL((grn_sumsq_kernel<float>), dim3(cdiv(C, 64), B), dim3(256), 0, stream, (const float*)h, N, C, scratch);
     F5_LAUNCH_CHECK();
@@ -778,6 +802,8 @@ int launch_grn(int precision, void* h, int B, int N, int C, const float* gamma, 
     F5_LAUNCH_CHECK();
     if (precision == F5_PREC_BF16)
         hipLaunchKernelGGL((grn_apply_kernel<bf16_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (bf16_t*)h, N, C, scratch, gamma, beta, total);
+    else if (precision == F5_PREC_FP16)
+        hipLaunchKernelGGL((grn_apply_kernel<f16_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (f16_t*)h, N, C, scratch, gamma, beta, total);
     else
         hipLaunchKernelGGL((grn_apply_kernel<float>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (float*)h, N, C, scratch, gamma, beta, total);
     F5_LAUNCH_CHECK();
@@ -902,6 +928,8 @@ int launch_convert_pad(int precision_out, const float* src, int lds, int rows, i
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
     if (precision_out == F5_PREC_BF16)
         hipLaunchKernelGGL((convert_pad_kernel<bf16_t>), grid, block, 0, stream, src, lds, rows, cols, padcols, (bf16_t*)dst, ldo);
+    else if (precision_out == F5_PREC_FP16)
+        hipLaunchKernelGGL((convert_pad_kernel<f16_t>), grid, block, 0, stream, src, lds, rows, cols, padcols, (f16_t*)dst, ldo);
     else
         hipLaunchKernelGGL((convert_pad_kernel<float>), grid, block, 0, stream, src, lds, rows, cols, padcols, (float*)dst, ldo);
     F5_LAUNCH_CHECK();
@@ -920,6 +948,8 @@ int launch_convert_back(int precision_in, const void* src, int lds, int rows, in
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
     if (precision_in == F5_PREC_BF16)
         hipLaunchKernelGGL((convert_back_kernel<bf16_t>), grid, block, 0, stream, (const bf16_t*)src, lds, rows, cols, dst, ldd);
+    else if (precision_in == F5_PREC_FP16)
+        hipLaunchKernelGGL((convert_back_kernel<f16_t>), grid, block, 0, stream, (const f16_t*)src, lds, rows, cols, dst, ldd);
     else
         hipLaunchKernelGGL((convert_back_kernel<float>), grid, block, 0, stream, (const float*)src, lds, rows, cols, dst, ldd);
     F5_LAUNCH_CHECK();
@@ -950,6 +980,9 @@ int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, 
     if (precision_out == F5_PREC_BF16)
         hipLaunchKernelGGL((pack_base_kernel<bf16_t>), dim3(B * N), dim3(256), 0, stream, cond, lens, cmask, text_embed, B, N, mel, melp, td, zero_cond,
                            (bf16_t*)dst, ldd);
+    else if (precision_out == F5_PREC_FP16)
+        hipLaunchKernelGGL((pack_base_kernel<f16_t>), dim3(B * N), dim3(256), 0, stream, cond, lens, cmask, text_embed, B, N, mel, melp, td, zero_cond,
+                           (f16_t*)dst, ldd);
     else
         hipLaunchKernelGGL((pack_base_kernel<float>), dim3(B * N), dim3(256), 0, stream, cond, lens, cmask, text_embed, B, N, mel, melp, td, zero_cond,
                            (float*)dst, ldd);

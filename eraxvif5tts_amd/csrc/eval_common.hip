@@ -47,7 +47,7 @@ int plan_attn_dropout_advance(f5_plan_s* p, uint32_t by, hipStream_t st) {
 bool plan_res_f16(const f5_plan_s* p) {
     const bool want = p->res_f16 < 0 ? g_res_f16 != 0 : p->res_f16 != 0;
     if (p->m->cfg.backbone != F5_BACKBONE_DIT || p->m->cfg.long_skip) return false;  // (UNetT, MMDiT and the long-skip DiT keep fp32 streams)
-    return want && p->taps.empty() && g_ln_defer && p->m->cfg.precision == F5_PREC_BF16 && p->xres16 && p->base16;
+    return want && p->taps.empty() && g_ln_defer && p->m->cfg.precision != F5_PREC_FP32 && p->xres16 && p->base16;  // (both 16-bit modes)
 }
 
 GemmParams gp_zero() {

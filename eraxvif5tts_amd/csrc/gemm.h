@@ -92,7 +92,7 @@ struct GemmParams {
 
 // kernel_kind: 0 = reference tile kernel (any shape), 1 = tuned 256x256 LDS-DMA bf16 kernel
 int launch_gemm(const GemmParams& p, int precision, int mode, int epi, int kernel_kind, hipStream_t stream);
-// true when the tuned kernel can run this problem (bf16, tile-multiple shapes, supported epilogue)
+// true when the tuned kernel can run this problem (bf16 / fp16, tile-multiple shapes, supported epilogue)
 bool gemm_fast_supported(const GemmParams& p, int precision, int mode, int epi);
 // the token x feature tile launch_gemm_fast would pick for this dense problem (by occupancy and the tuning knobs)
 void gemm_fast_tile(const GemmParams& p, int* bm, int* bn);
@@ -104,4 +104,4 @@ bool gemm_w4_ok(const GemmParams& p, int mode, int epi);
 int gemm_w4_lnf_inkernel(int M, int N, int K);  // 0, or the tile height (128) that finishes them
 // dedicated kernel for the dim-1024 grouped Conv1d(k = 31) of ConvPositionEmbedding (conv31.hip); GemmParams as for GEMM_CONV31
 bool conv31_supported(const GemmParams& p, int precision, int epi);
-int launch_conv31(const GemmParams& p, hipStream_t stream);
+int launch_conv31(const GemmParams& p, int precision, hipStream_t stream);

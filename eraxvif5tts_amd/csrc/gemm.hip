@@ -1,25 +1,25 @@
-// gemm.hip -- reference tile kernel (any shape, bf16 or fp32-input MFMA) + dispatch.
+// gemm.hip -- reference tile kernel (any shape, bf16 / fp16 or fp32-input MFMA) + dispatch.
 // The tuned 256x256 LDS-DMA kernel lives in gemm_fast.hip.
 #include "gemm.h"
 #include "gemm_epilogue.h"
 
 // MFMA wrapper: weights on the MFMA row index (operand "A"), tokens on the column index (operand "B").
-template <typename T> struct TileMma;
-template <> struct TileMma<bf16_t> {
-    // v_mfma_f32_16x16x32_bf16: lane l holds rows[l&15][k = 8*(l>>4) .. +7] of both operands
+// the two 16-bit element types share one body: v_mfma_f32_16x16x32_{bf16,f16}, lane l holds rows[l&15][k = 8*(l>>4) .. +7] of both operands
+template <typename T> struct TileMma {
+    typedef typename Elem<T>::x8 x8;
     template <int STRIDE>
-    static __device__ __forceinline__ void step(const bf16_t* w_rows, const bf16_t* a_rows, int lane, f32x4 (&acc)[2][2]) {
+    static __device__ __forceinline__ void step(const T* w_rows, const T* a_rows, int lane, f32x4 (&acc)[2][2]) {
         const int r = lane & 15, kq = (lane >> 4) * 8;
-        bf16x8 wf[2], af[2];
+        x8 wf[2], af[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            wf[i] = *reinterpret_cast<const bf16x8*>(w_rows + (i * 16 + r) * STRIDE + kq);
-            af[i] = *reinterpret_cast<const bf16x8*>(a_rows + (i * 16 + r) * STRIDE + kq);
+            wf[i] = *reinterpret_cast<const x8*>(w_rows + (i * 16 + r) * STRIDE + kq);
+            af[i] = *reinterpret_cast<const x8*>(a_rows + (i * 16 + r) * STRIDE + kq);
         }
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni], af[mi], acc[ni][mi], 0, 0, 0);
+            for (int mi = 0; mi < 2; ++mi) acc[ni][mi] = Elem<T>::mfma16(wf[ni], af[mi], acc[ni][mi]);
     }
 };
 template <> struct TileMma<float> {
@@ -163,7 +163,7 @@ template <typename T> static int dispatch_tile(const GemmParams& p, int mode, in
     return f5_fail(F5_EINVAL, "gemm: unsupported mode/epilogue %d/%d", mode, epi);
 }
 
-int launch_gemm_fast(const GemmParams& p, int mode, int epi, hipStream_t stream);  // gemm_fast.hip
+int launch_gemm_fast(const GemmParams& p, int precision, int mode, int epi, hipStream_t stream);  // gemm_fast.hip
 
 int launch_gemm(const GemmParams& p, int precision, int mode, int epi, int kernel_kind, hipStream_t stream) {
     if (p.M <= 0 || p.N <= 0) return 0;
@@ -178,9 +178,10 @@ int launch_gemm(const GemmParams& p, int precision, int mode, int epi, int kerne
     if ((p.lnf_stats || p.stats_out) && kernel_kind != 1) return f5_fail(F5_ESTATE, "gemm: the LayerNorm fold exists in the tuned kernel only");
     if (kernel_kind == 1) {
         if (!gemm_fast_supported(p, precision, mode, epi)) return f5_fail(F5_EINVAL, "gemm: tuned kernel does not support this problem");
-        return launch_gemm_fast(p, mode, epi, stream);
+        return launch_gemm_fast(p, precision, mode, epi, stream);
     }
     if (precision == F5_PREC_BF16) return dispatch_tile<bf16_t>(p, mode, epi, stream);
+    if (precision == F5_PREC_FP16) return dispatch_tile<f16_t>(p, mode, epi, stream);
     if (precision == F5_PREC_FP32) return dispatch_tile<float>(p, mode, epi, stream);
     return f5_fail(F5_EINVAL, "gemm: bad precision %d", precision);
 }

@@ -30,6 +30,14 @@ template <> __device__ __forceinline__ void store4_t<bf16_t>(bf16_t* dst, const 
     }
 }
 
+template <> __device__ __forceinline__ void store4_t<f16_t>(f16_t* dst, const float v[4], bool vec, int nvalid) {  // saturating (common.h)
+    if (vec) {
+        *reinterpret_cast<f16x4*>(dst) = Elem<f16_t>::pack4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int r = 0; r < nvalid; ++r) dst[r] = from_f32<f16_t>(v[r]);
+    }
+}
+
 template <typename T, int EPI>
 __device__ __forceinline__ void gemm_epilogue4(const GemmParams& p, int m, int n, f32x4 acc) {
     if (m >= p.M || n >= p.N) return;

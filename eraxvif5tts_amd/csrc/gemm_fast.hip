@@ -26,7 +26,14 @@
 
 // This file is compiled as TWO translation units (build time): gemm_fast.hip itself holds every instantiation without the LayerNorm fold,
 // gemm_fast_lnf.hip (#define F5_LNF_TU + #include of this file) the LNF ones behind launch_gemm_fast_lnf().
-#ifdef F5_LNF_TU
+// ... and once more per element type: gemm_fast_f16.hip / gemm_fast_lnf_f16.hip (#define F5_F16_TU) hold the instantiations of the fp16
+// precision mode (EL = f16_t: the f16 MFMA shape and the saturating fp16 pack; data movement is that of the bf16 build, bit for bit).
+#ifdef F5_F16_TU
+#define F5_EL f16_t
+#else
+#define F5_EL bf16_t
+#endif
+#if defined(F5_LNF_TU) || defined(F5_F16_TU)
 static __device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];  // (GEMM_CONV31 only; never read in the LNF instantiations)
 #else
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];  // zero-initialised
@@ -37,7 +44,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // LNF (LayerNorm fold, gemm.h): fp16 operands on v_mfma_f32_16x16x32_f16 (same rate and fragment layout as the bf16 shape), accumulator
 // start 0, epilogue value rstd (acc - mean c1) + c2 in front of the activation / RoPE.  EPI_STORE_T and EPI_ROPE_T only.
-template <int BN, int WM, int MODE, int EPI, int VAR, int NS, bool LNF = false>
+template <int BN, int WM, int MODE, int EPI, int VAR, int NS, bool LNF = false, typename EL = bf16_t>
 __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int tiles_n, int nblocks) {
     static_assert(!LNF || (MODE == GEMM_DENSE && (EPI == EPI_STORE_T || EPI == EPI_ROPE_T)), "LayerNorm fold: QKV (+ RoPE) and FF1 (+ GELU) only");
     constexpr int BK = 32, WN = 64, NSTAGE = NS;
@@ -340,10 +347,8 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
         for (int i = 0; i < NI; ++i)
 #pragma unroll
             for (int j = 0; j < MI; ++j) {
-                if constexpr (LNF)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, wf[i]), __builtin_bit_cast(f16x8_t, af[j]), acc[i][j], 0, 0, 0);
-                else
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], af[j], acc[i][j], 0, 0, 0);
+                typedef Elem<std::conditional_t<LNF, f16_t, EL>> MM;  // the fold's operands are fp16 in both 16-bit modes
+                acc[i][j] = MM::mfma16(__builtin_bit_cast(typename MM::x8, wf[i]), __builtin_bit_cast(typename MM::x8, af[j]), acc[i][j]);
             }
     };
 
@@ -491,13 +496,13 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
                 if (wide_ok) {  // all four feature tiles of this wave in range and 16-byte alignable: pairwise 16-byte stores
                     static_for<NI / 2>([&](auto hc) {
                         constexpr int i = decltype(hc)::value * 2;
-                        const u32x4 q = pair_swap(to_bf16x4(vals[i]), to_bf16x4(vals[i + 1]));
+                        const u32x4 q = pair_swap(to_el4<EL>(vals[i]), to_el4<EL>(vals[i + 1]));
                         if (okm[jj]) *reinterpret_cast<u32x4*>(orow + nwide + 32 * (i / 2)) = q;
                     });
                 } else {
                     static_for<NI>([&](auto ic) {
                         constexpr int i = decltype(ic)::value;
-                        if (okm[jj] && okn[i]) *reinterpret_cast<bf16x4*>(orow + ncol[i]) = to_bf16x4(vals[i]);
+                        if (okm[jj] && okn[i]) *reinterpret_cast<bf16x4*>(orow + ncol[i]) = to_el4<EL>(vals[i]);
                     });
                 }
             } else {
@@ -508,7 +513,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
                         if (ok) *reinterpret_cast<f32x4*>(p.out_f + mr * p.ldof + ncol[i]) = vals[i];
                     } else if constexpr (EPI == EPI_ADD2) {
                         if (ok) {
-                            *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(p.out_t) + mr * p.ldo + ncol[i]) = to_bf16x4(vals[i]);
+                            *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(p.out_t) + mr * p.ldo + ncol[i]) = to_el4<EL>(vals[i]);
                             if (p.add2_f16) {
                                 f16x4_t hv;
 #pragma unroll
@@ -584,8 +589,8 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
                 }
                 vals[i] = v;
             }
-            u32x4 q0 = pair_swap(to_bf16x4(vals[0]), to_bf16x4(vals[1]));
-            u32x4 q1 = pair_swap(to_bf16x4(vals[2]), to_bf16x4(vals[3]));
+            u32x4 q0 = pair_swap(to_el4<EL>(vals[0]), to_el4<EL>(vals[1]));
+            u32x4 q1 = pair_swap(to_el4<EL>(vals[2]), to_el4<EL>(vals[3]));
             if constexpr (EPI == EPI_GATE_T) {
                 const bool keep = (keepbits >> j) & 1u;
                 q0 = keep ? q0 : u32x4{0u, 0u, 0u, 0u};
@@ -646,8 +651,8 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
                 v3 = acc[3][j] + widen_h(s0[1], s1[1]);
             }
             const size_t jo = (size_t)16 * j;
-            *reinterpret_cast<u32x4*>(orow + jo * p.ldo) = pair_swap(to_bf16x4(v0), to_bf16x4(v1));
-            *reinterpret_cast<u32x4*>(orow + jo * p.ldo + 32) = pair_swap(to_bf16x4(v2), to_bf16x4(v3));
+            *reinterpret_cast<u32x4*>(orow + jo * p.ldo) = pair_swap(to_el4<EL>(v0), to_el4<EL>(v1));
+            *reinterpret_cast<u32x4*>(orow + jo * p.ldo + 32) = pair_swap(to_el4<EL>(v2), to_el4<EL>(v3));
             *reinterpret_cast<u32x4*>(hrow + jo * p.ldof) = pair_swap(to_h(v0), to_h(v1));
             *reinterpret_cast<u32x4*>(hrow + jo * p.ldof + 32) = pair_swap(to_h(v2), to_h(v3));
         });
@@ -937,7 +942,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
     clk_end();
 }
 
-#ifdef F5_LNF_TU
+#if defined(F5_LNF_TU) || defined(F5_F16_TU)
 extern unsigned long long* g_gemm_clk_buf;
 extern int g_gemm_variant, g_gemm_group, g_gemm_persist_grid, g_gemm_persist, g_gemm_reverse_sites, g_gemm_group_sites, g_gemm_tile, g_gemm_bm128, g_gemm_lean;
 int gemm_persist_grid();
@@ -1011,28 +1016,60 @@ template <int BN, int WM, int MODE, int EPI, bool LNF = false> static int launch
     const bool persist_ok = MODE == GEMM_DENSE && (store_ok || resid_ok) && p.M % 256 == 0 && p.K >= 128 && p.N % 256 == 0 && (p.bias || LNF);
     if constexpr (BN == 256) {
         if (g_gemm_variant == 0)
-            hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 0, 4, LNF>), grid, block, 0, stream, p, tiles_n, nblocks);
+            hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 0, 4, LNF, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
         else if (g_gemm_persist && persist_ok) {
             if constexpr (EPI == EPI_STORE_T || EPI == EPI_GATE_T || EPI == EPI_ROPE_T || EPI == EPI_RESID)
-                hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, GEMM_DENSE, EPI, 30, 5, LNF>), dim3(nblocks < persist_grid() ? nblocks : persist_grid()), block,
+                hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, GEMM_DENSE, EPI, 30, 5, LNF, F5_EL>), dim3(nblocks < persist_grid() ? nblocks : persist_grid()), block,
                                    0, stream, p, tiles_n, nblocks);
         } else
-            hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 1, 5, LNF>), grid, block, 0, stream, p, tiles_n, nblocks);
+            hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 1, 5, LNF, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     } else if (BN == 128 && g_gemm_variant != 0) {  // staggered wave groups pay on the 128-wide tile too (M = 8192: FF2 44.6 -> 41.5 us, out-projection 26.3 -> 24.4 us)
-        hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 1, 5, LNF>), grid, block, 0, stream, p, tiles_n, nblocks);
+        hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 1, 5, LNF, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     } else {
-        hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 0, 4, LNF>), grid, block, 0, stream, p, tiles_n, nblocks);
+        hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 0, 4, LNF, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     }
     F5_LAUNCH_CHECK();
     return 0;
 }
 
-#ifndef F5_LNF_TU
+#if !defined(F5_LNF_TU)
+// the dense / conv31 instantiations of this translation unit's element type
+static int fast_dispatch(const GemmParams& p, int mode, int epi, int bm, int bn, hipStream_t stream) {
+    if (mode == GEMM_CONV31) {
+        if (epi == EPI_STORE_T) return launch_fast<64, 32, GEMM_CONV31, EPI_STORE_T>(p, stream);
+        if (epi == EPI_GATE_T) return launch_fast<64, 32, GEMM_CONV31, EPI_GATE_T>(p, stream);
+        return f5_fail(F5_EINVAL, "gemm_fast(conv31): unsupported epilogue %d", epi);
+    }
+#define F5_FAST_CASE(E)                                                                   \
+    case E:                                                                               \
+        if (bm == 128 && bn == 128) return launch_fast<128, 32, GEMM_DENSE, E>(p, stream); \
+        if (bm == 128) return launch_fast<64, 16, GEMM_DENSE, E>(p, stream);              \
+        if (bn == 256) return launch_fast<256, 128, GEMM_DENSE, E>(p, stream);            \
+        if (bn == 128) return launch_fast<128, 64, GEMM_DENSE, E>(p, stream);             \
+        return launch_fast<64, 32, GEMM_DENSE, E>(p, stream);
+    switch (epi) {
+        F5_FAST_CASE(EPI_STORE_T)
+        F5_FAST_CASE(EPI_STORE_F32)
+        F5_FAST_CASE(EPI_RESID)
+        F5_FAST_CASE(EPI_ADD2)
+        F5_FAST_CASE(EPI_ROPE_T)
+        F5_FAST_CASE(EPI_GATE_T)
+    }
+#undef F5_FAST_CASE
+    return f5_fail(F5_EINVAL, "gemm_fast: unsupported epilogue %d", epi);
+}
+#endif
+#if defined(F5_F16_TU) && !defined(F5_LNF_TU)
+int launch_gemm_fast_f16(const GemmParams& p, int mode, int epi, int bm, int bn, hipStream_t stream) { return fast_dispatch(p, mode, epi, bm, bn, stream); }
+#endif
+#if !defined(F5_LNF_TU) && !defined(F5_F16_TU)
 int launch_gemm_fast_lnf(const GemmParams& p, int epi, int bm, int bn, hipStream_t stream);  // gemm_fast_lnf.hip
+int launch_gemm_fast_lnf_f16(const GemmParams& p, int epi, int bm, int bn, hipStream_t stream);  // gemm_fast_lnf_f16.hip
+int launch_gemm_fast_f16(const GemmParams& p, int mode, int epi, int bm, int bn, hipStream_t stream);  // gemm_fast_f16.hip
 bool gemm_w4_ok(const GemmParams& p, int mode, int epi);                                     // gemm_w4.hip
-int launch_gemm_w4(const GemmParams& p, int epi, hipStream_t stream);
+int launch_gemm_w4(const GemmParams& p, int precision, int epi, hipStream_t stream);
 bool gemm_fast_supported(const GemmParams& p, int precision, int mode, int epi) {
-    if (precision != F5_PREC_BF16 || p.M <= 0 || p.N <= 0) return false;
+    if ((precision != F5_PREC_BF16 && precision != F5_PREC_FP16) || p.M <= 0 || p.N <= 0) return false;
     if (p.lda & 7) return false;
     if (mode == GEMM_DENSE) {
         if (p.K <= 0 || p.K % 32 != 0 || (p.ldw & 7)) return false;
@@ -1090,46 +1127,34 @@ bool gemm_fast_lnf_inkernel(const GemmParams& p) {
     return bn != 256;  // (the 256-wide tile stages finalized statistics through LDS; every other tile holds them in registers)
 }
 
-int launch_gemm_fast(const GemmParams& p, int mode, int epi, hipStream_t stream) {
+int launch_gemm_fast(const GemmParams& p, int precision, int mode, int epi, hipStream_t stream) {
+    const bool h = precision == F5_PREC_FP16;  // fp16 precision mode: the EL = f16_t instantiations (gemm_fast_f16.hip, gemm_fast_lnf_f16.hip)
     if (mode == GEMM_CONV31) {
-        if (conv31_supported(p, F5_PREC_BF16, epi)) return launch_conv31(p, stream);
-        if (epi == EPI_STORE_T) return launch_fast<64, 32, GEMM_CONV31, EPI_STORE_T>(p, stream);
-        if (epi == EPI_GATE_T) return launch_fast<64, 32, GEMM_CONV31, EPI_GATE_T>(p, stream);
-        return f5_fail(F5_EINVAL, "gemm_fast(conv31): unsupported epilogue %d", epi);
+        if (conv31_supported(p, precision, epi)) return launch_conv31(p, precision, stream);
+        return h ? launch_gemm_fast_f16(p, mode, epi, 0, 0, stream) : fast_dispatch(p, mode, epi, 0, 0, stream);
     }
     if (g_gemm_variant != 0 && g_gemm_persist && gemm_w4_ok(p, mode, epi)) {  // large whole-tile block linears: one wave per SIMD (gemm_w4.hip)
         GemmParams q = p;
         apply_site_knobs(q);
-        return launch_gemm_w4(q, epi, stream);
+        return launch_gemm_w4(q, precision, epi, stream);
     }
     int bn, bm;
     gemm_fast_tile(p, &bm, &bn);
     if (p.lnf_stats) {  // LayerNorm fold: fp16 operands, statistics + column constants in the epilogue (QKV + RoPE, FF1 + GELU)
         if (!p.lnf_c1 || !p.lnf_c2 || (epi != EPI_STORE_T && epi != EPI_ROPE_T)) return f5_fail(F5_EINVAL, "gemm_fast: LayerNorm fold needs c1, c2 and a store / RoPE epilogue");
-        return launch_gemm_fast_lnf(p, epi, bm, bn, stream);
+        return h ? launch_gemm_fast_lnf_f16(p, epi, bm, bn, stream) : launch_gemm_fast_lnf(p, epi, bm, bn, stream);
     }
     if (p.stats_out && (epi != EPI_RESID || !p.add2_f16 || p.N % 64 != 0 || p.stats_ld < p.M))
         return f5_fail(F5_EINVAL, "gemm_fast: row statistics need the in-place fp16 residual epilogue and N % 64 == 0");
-#define F5_FAST_CASE(E)                                                                   \
-    case E:                                                                               \
-        if (bm == 128 && bn == 128) return launch_fast<128, 32, GEMM_DENSE, E>(p, stream); \
-        if (bm == 128) return launch_fast<64, 16, GEMM_DENSE, E>(p, stream);              \
-        if (bn == 256) return launch_fast<256, 128, GEMM_DENSE, E>(p, stream);            \
-        if (bn == 128) return launch_fast<128, 64, GEMM_DENSE, E>(p, stream);             \
-        return launch_fast<64, 32, GEMM_DENSE, E>(p, stream);
-    switch (epi) {
-        F5_FAST_CASE(EPI_STORE_T)
-        F5_FAST_CASE(EPI_STORE_F32)
-        F5_FAST_CASE(EPI_RESID)
-        F5_FAST_CASE(EPI_ADD2)
-        F5_FAST_CASE(EPI_ROPE_T)
-        F5_FAST_CASE(EPI_GATE_T)
-    }
-#undef F5_FAST_CASE
-    return f5_fail(F5_EINVAL, "gemm_fast: unsupported epilogue %d", epi);
+    return h ? launch_gemm_fast_f16(p, mode, epi, bm, bn, stream) : fast_dispatch(p, mode, epi, bm, bn, stream);
 }
-#else  // F5_LNF_TU
+#endif
+#ifdef F5_LNF_TU
+#ifdef F5_F16_TU
+int launch_gemm_fast_lnf_f16(const GemmParams& p, int epi, int bm, int bn, hipStream_t stream) {
+#else
 int launch_gemm_fast_lnf(const GemmParams& p, int epi, int bm, int bn, hipStream_t stream) {
+#endif
     if (bn == 256 && p.lnf_partial) return f5_fail(F5_ESTATE, "gemm_fast: the 256-wide LayerNorm-fold tile takes finalized statistics (gemm_fast_lnf_inkernel)");
 #define F5_FAST_LNF(E)                                                                           \
     if (epi == E) {                                                                              \

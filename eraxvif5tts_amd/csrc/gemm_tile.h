@@ -67,6 +67,13 @@ __device__ __forceinline__ u32x4 pair_swap(bf16x4 a, bf16x4 b) {
     return u32x4{s0[0], s1[0], s0[1], s1[1]};
 }
 __device__ __forceinline__ bf16x4 to_bf16x4(const f32x4& v) { return bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]}; }
+// the RNE pack of four outputs in the element type EL, in the 8-byte container the stores and pair_swap move (fp16: saturating, common.h)
+template <typename EL> __device__ __forceinline__ bf16x4 to_el4(const f32x4& v) {
+    if constexpr (Elem<EL>::F16)
+        return __builtin_bit_cast(bf16x4, Elem<EL>::pack4(v[0], v[1], v[2], v[3]));
+    else
+        return to_bf16x4(v);
+}
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;

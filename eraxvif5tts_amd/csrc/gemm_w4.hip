@@ -38,7 +38,7 @@ constexpr int EPI_LDS_BYTES = 16384;  // behind the stage buffers: the LayerNorm
 
 // MI: token tiles (of 16 rows) per wave.  8: the 256 x 256 tile (128 x 128 per wave, 128 MFMAs per iteration).  4: a 128 x 256 tile (64 x 128 per wave, 128
 // accumulator registers, 64 MFMAs per iteration) for launches that have no 256-row tile for every CU but a 128-row one (batches of 2 - 4 utterances).
-template <int EPI, bool LNF, int MI>
+template <int EPI, bool LNF, int MI, typename EL = bf16_t>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_w4_kernel(GemmParams p, int tiles_n, int nblocks) {
     static_assert(EPI == EPI_STORE_T || EPI == EPI_ROPE_T || EPI == EPI_RESID, "block linears only");
     static_assert(!LNF || EPI != EPI_RESID, "LayerNorm fold: QKV (+ RoPE) and FF1 (+ GELU)");
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             (void)acc; (void)fw; (void)fa; (void)voffA; (void)voffW; (void)baseA; (void)baseW;
             constexpr int n = decltype(nc)::value;
             constexpr int s = n / (8 * MI), i = (n % (8 * MI)) / MI, j = n % MI;
-            if constexpr (LNF)
+            if constexpr (LNF || Elem<EL>::F16)  // (inline asm for the AccVGPR constraint: the mnemonic of Elem<>::mfma16's builtin)
                 asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fw[s][i]), "v"(fa[s][j]));
             else
                 asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fw[s][i]), "v"(fa[s][j]));
@@ -342,8 +342,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 if constexpr (rope_wave) v = epi_rope4(v, rp[j & 1][ii]);  // x_transformers apply_rotary_pos_emb: adjacent pairs, fp32 math
                 vals[ii] = v;
             });
-            const u32x4 q0 = pair_swap(to_bf16x4(vals[0]), to_bf16x4(vals[1]));
-            const u32x4 q1 = pair_swap(to_bf16x4(vals[2]), to_bf16x4(vals[3]));
+            const u32x4 q0 = pair_swap(to_el4<EL>(vals[0]), to_el4<EL>(vals[1]));
+            const u32x4 q1 = pair_swap(to_el4<EL>(vals[2]), to_el4<EL>(vals[3]));
             bf16_t* o = orow + j * jstride;
             *reinterpret_cast<u32x4*>(o) = q0;
             *reinterpret_cast<u32x4*>(o + 32) = q1;
@@ -570,6 +570,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 }  // namespace
 
+// Compiled as two translation units (build time): this file holds the bf16-mode instantiations and every host-side rule, gemm_w4_f16.hip
+// (#define F5_F16_TU + #include of this file) the EL = f16_t instantiations of the fp16 precision mode behind launch_gemm_w4_f16().
+#ifdef F5_F16_TU
+#define F5_EL f16_t
+int gemm_persist_grid();  // gemm_fast.hip
+#else
+#define F5_EL bf16_t
 int g_gemm_w4 = 1;  // tuning knob ("gemm_w4"): 1 = whole-tile block linears with enough tiles for the CUs (w4_tile_rows) run on the one-wave-per-SIMD kernel
 int g_gemm_w4_ink = 1;  // tuning knob ("gemm_w4_ink"): folded projections on the kernel's 128-row tiles finish the row statistics themselves (no statistics launch)
 int g_gemm_w4_bm = 0;  // diagnostic knob ("gemm_w4_bm"): token rows per tile, 0 = by tile count, 128 / 256 forced where the shape allows
@@ -627,27 +634,36 @@ bool gemm_w4_ok(const GemmParams& p, int mode, int epi) {
     return false;
 }
 
+#endif
 template <int MI> static int launch_w4(const GemmParams& p, int epi, hipStream_t stream) {
     const int tiles_n = p.N / 256, nblocks = (p.M / (MI * 32)) * tiles_n;
     const int pg = gemm_persist_grid();
     const dim3 grid(nblocks < pg ? nblocks : pg), block(256);
     const bool lnf = p.lnf_stats != nullptr;
     if (epi == EPI_STORE_T && lnf)
-        hipLaunchKernelGGL((gemm_w4_kernel<EPI_STORE_T, true, MI>), grid, block, 0, stream, p, tiles_n, nblocks);
+        hipLaunchKernelGGL((gemm_w4_kernel<EPI_STORE_T, true, MI, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     else if (epi == EPI_STORE_T)
-        hipLaunchKernelGGL((gemm_w4_kernel<EPI_STORE_T, false, MI>), grid, block, 0, stream, p, tiles_n, nblocks);
+        hipLaunchKernelGGL((gemm_w4_kernel<EPI_STORE_T, false, MI, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     else if (epi == EPI_ROPE_T && lnf)
-        hipLaunchKernelGGL((gemm_w4_kernel<EPI_ROPE_T, true, MI>), grid, block, 0, stream, p, tiles_n, nblocks);
+        hipLaunchKernelGGL((gemm_w4_kernel<EPI_ROPE_T, true, MI, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     else if (epi == EPI_ROPE_T)
-        hipLaunchKernelGGL((gemm_w4_kernel<EPI_ROPE_T, false, MI>), grid, block, 0, stream, p, tiles_n, nblocks);
+        hipLaunchKernelGGL((gemm_w4_kernel<EPI_ROPE_T, false, MI, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     else if (epi == EPI_RESID)
-        hipLaunchKernelGGL((gemm_w4_kernel<EPI_RESID, false, MI>), grid, block, 0, stream, p, tiles_n, nblocks);
+        hipLaunchKernelGGL((gemm_w4_kernel<EPI_RESID, false, MI, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     else
         return f5_fail(F5_EINVAL, "gemm_w4: unsupported epilogue %d", epi);
     F5_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_gemm_w4(const GemmParams& p, int epi, hipStream_t stream) {
+#ifdef F5_F16_TU
+int launch_gemm_w4_f16(const GemmParams& p, int epi, int tile_rows, hipStream_t stream) {
+    return tile_rows == 128 ? launch_w4<4>(p, epi, stream) : launch_w4<8>(p, epi, stream);
+}
+#else
+int launch_gemm_w4_f16(const GemmParams& p, int epi, int tile_rows, hipStream_t stream);  // gemm_w4_f16.hip
+int launch_gemm_w4(const GemmParams& p, int precision, int epi, hipStream_t stream) {
+    if (precision == F5_PREC_FP16) return launch_gemm_w4_f16(p, epi, w4_tile_rows(p), stream);
     return w4_tile_rows(p) == 128 ? launch_w4<4>(p, epi, stream) : launch_w4<8>(p, epi, stream);
 }
+#endif

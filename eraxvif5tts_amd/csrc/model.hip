@@ -40,7 +40,7 @@ extern "C" int f5_model_create(const f5_dit_config* c, f5_model_t* out) {
     if (c->text_dim <= 0 || c->text_dim % 4 != 0 || c->text_dim > 1024 || (c->conv_layers > 0 && c->text_dim % 32 != 0))
         return f5_fail(F5_EINVAL, "text_dim=%d must be a multiple of 4 (of 32 with ConvNeXt text blocks)", c->text_dim);
     if (c->text_num_embeds <= 0 || c->conv_layers < 0) return f5_fail(F5_EINVAL, "bad text config");
-    if (c->precision != F5_PREC_BF16 && c->precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision");
+    if (c->precision != F5_PREC_BF16 && c->precision != F5_PREC_FP32 && c->precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "bad precision");
     if (c->rope_layout != F5_ROPE_ADJACENT && c->rope_layout != F5_ROPE_HALF_SPLIT) return f5_fail(F5_EINVAL, "bad rope_layout");
     f5_model_s* m = new f5_model_s();
     m->cfg = *c;
@@ -180,7 +180,26 @@ extern "C" int f5_model_set_tensor(f5_model_t m, const char* name, const float* 
     return f5_slot_set(m->slots, name, host, shape, ndim);
 }
 
-static const std::vector<float>& H(f5_model_s* m, const std::string& name) { return m->slots[name].host; }
+static const std::vector<float>& H(f5_model_s* m, const std::string& name) {
+    m->read_names.push_back(name);  // (what up_t names when a weight does not survive the rounding to fp16)
+    return m->slots[name].host;
+}
+// f5_upload_t of a weight matrix built from the host tensors read since the previous upload.  fp16 mode: an element that is not finite after the
+// rounding (|w| >= 65520, inf, NaN) fails with F5_EINVAL and the name of the tensor it came from.  Only what is uploaded in the precision's type
+// is tested: vectors, the embedding tables and the time MLP stay fp32.
+static int up_t(f5_model_s* m, DevArena& a, int precision, const float* host, size_t count, void** out) {
+    const int rc = f5_upload_t(a, precision, host, count, out);
+    if (rc == F5_EINVAL && precision == F5_PREC_FP16) {
+        for (const std::string& name : m->read_names) {
+            const TensorSlot& t = m->slots[name];
+            if (t.shape.size() < 2) continue;
+            for (float v : t.host)
+                if (!(fabsf(v) < 65520.0f)) return f5_fail(F5_EINVAL, "tensor '%s' holds %g, which is not finite in fp16", name.c_str(), (double)v);
+        }
+    }
+    m->read_names.clear();
+    return rc;
+}
 
 extern "C" int f5_model_finalize(f5_model_t m) {
     if (!m) return f5_fail(F5_EINVAL, "null model");
@@ -257,11 +276,11 @@ extern "C" int f5_model_finalize(f5_model_t m) {
         F5_TRY(f5_upload_f32(A, H(m, p + "dwconv.bias").data(), td, &t.dw_b));
         F5_TRY(f5_upload_f32(A, H(m, p + "norm.weight").data(), td, &t.ln_w));
         F5_TRY(f5_upload_f32(A, H(m, p + "norm.bias").data(), td, &t.ln_b));
-        F5_TRY(f5_upload_t(A, P, H(m, p + "pwconv1.weight").data(), 2 * td * td, &t.w1));
+        F5_TRY(up_t(m, A, P, H(m, p + "pwconv1.weight").data(), 2 * td * td, &t.w1));
         F5_TRY(f5_upload_f32(A, H(m, p + "pwconv1.bias").data(), 2 * td, &t.b1));
         F5_TRY(f5_upload_f32(A, H(m, p + "grn.gamma").data(), 2 * td, &t.gamma));
         F5_TRY(f5_upload_f32(A, H(m, p + "grn.beta").data(), 2 * td, &t.beta));
-        F5_TRY(f5_upload_t(A, P, H(m, p + "pwconv2.weight").data(), 2 * td * td, &t.w2));
+        F5_TRY(up_t(m, A, P, H(m, p + "pwconv2.weight").data(), 2 * td * td, &t.w2));
         F5_TRY(f5_upload_f32(A, H(m, p + "pwconv2.bias").data(), td, &t.b2));
     }
     // input projection split: columns [x | cond | text]  (dit.py:88,95 concat order)
@@ -274,8 +293,8 @@ extern "C" int f5_model_finalize(f5_model_t m) {
             for (size_t k = 0; k < mel; ++k) wct[n * kct + k] = w[n * kin + mel + k];
             for (size_t k = 0; k < itd; ++k) wct[n * kct + MELP + k] = w[n * kin + 2 * mel + k];
         }
-        F5_TRY(f5_upload_t(A, P, wx.data(), wx.size(), &m->w_x));
-        F5_TRY(f5_upload_t(A, P, wct.data(), wct.size(), &m->w_ct));
+        F5_TRY(up_t(m, A, P, wx.data(), wx.size(), &m->w_x));
+        F5_TRY(up_t(m, A, P, wct.data(), wct.size(), &m->w_ct));
         F5_TRY(f5_upload_f32(A, H(m, mm ? "audio_embed.linear.bias" : "input_embed.proj.bias").data(), D, &m->b_in));
     }
     // grouped conv (k=31, groups=16) -> tap-major [31][D][win], zero outside each output row's own group
@@ -300,7 +319,7 @@ extern "C" int f5_model_finalize(f5_model_t m) {
                     for (int tap = 0; tap < 31; ++tap) r[((size_t)tap * D + n) * win + j] = w[((size_t)n * cg + ci) * 31 + tap];
                 }
             }
-            F5_TRY(f5_upload_t(A, P, r.data(), r.size(), &m->w_conv[li]));
+            F5_TRY(up_t(m, A, P, r.data(), r.size(), &m->w_conv[li]));
             F5_TRY(f5_upload_f32(A, H(m, p + "bias").data(), D, &m->b_conv[li]));
         }
     }
@@ -308,7 +327,7 @@ extern "C" int f5_model_finalize(f5_model_t m) {
     m->blocks.resize(c.depth);
     const bool un = c.backbone == F5_BACKBONE_UNETT;
     // LayerNorm fold: fp32 masters of the fused q|k|v and the first FF projection of every block, as the kernels see them (RoPE row order)
-    const bool fold = c.backbone == F5_BACKBONE_DIT && P == F5_PREC_BF16 && !c.qk_norm && !c.long_skip && D % 128 == 0;
+    const bool fold = c.backbone == F5_BACKBONE_DIT && P != F5_PREC_FP32 && !c.qk_norm && !c.long_skip && D % 128 == 0;
     const size_t foldR = 3 * inner + ff;
     std::vector<float> fold_w(fold ? (size_t)c.depth * foldR * D : 0), fold_b(fold ? (size_t)c.depth * foldR : 0);
     for (int i = 0; i < c.depth; ++i) {
@@ -345,15 +364,15 @@ extern "C" int f5_model_finalize(f5_model_t m) {
                 memcpy(&fold_w[(size_t)i * foldR * D], w.data(), w.size() * sizeof(float));
                 memcpy(&fold_b[(size_t)i * foldR], bias.data(), bias.size() * sizeof(float));
             }
-            F5_TRY(f5_upload_t(A, P, w.data(), w.size(), wdst));
+            F5_TRY(up_t(m, A, P, w.data(), w.size(), wdst));
             F5_TRY(f5_upload_f32(A, bias.data(), bias.size(), bdst));
             // pre-scaled q: block 0's projection runs unfolded, so it gets a copy whose q rows carry the scale.  The copy is the WHOLE fused
             // q|k|v weight (the k and v rows are duplicates, 4 MiB at D = 1024, once per model): the projection stays one launch on one weight
             // pointer, as every tile choice of dit_eval assumes.  (No weight prefetch names it: the prefetch sets only reach blocks 1 and up.)
-            if (fold && sfx.empty() && i == 0) {
+            if (fold && sfx.empty() && i == 0 && P == F5_PREC_BF16) {  // (the fp16 mode never pre-scales q)
                 for (size_t k = 0; k < (size_t)inner * D; ++k) w[k] *= F5_ATTN_QSCALE;
                 for (int k = 0; k < inner; ++k) bias[k] *= F5_ATTN_QSCALE;
-                F5_TRY(f5_upload_t(A, P, w.data(), w.size(), &b.w_qkv_qs));
+                F5_TRY(up_t(m, A, P, w.data(), w.size(), &b.w_qkv_qs));
                 F5_TRY(f5_upload_f32(A, bias.data(), bias.size(), &b.b_qkv_qs));
             }
             return 0;
@@ -362,23 +381,23 @@ extern "C" int f5_model_finalize(f5_model_t m) {
         if (mm) {
             F5_TRY(fuse_qkv("_c", &b.w_qkv_c, &b.b_qkv_c));
             if (i != c.depth - 1) {
-                F5_TRY(f5_upload_t(A, P, H(m, pa + "to_out_c.weight").data(), D * inner, &b.w_o_c));
+                F5_TRY(up_t(m, A, P, H(m, pa + "to_out_c.weight").data(), D * inner, &b.w_o_c));
                 F5_TRY(f5_upload_f32(A, H(m, pa + "to_out_c.bias").data(), D, &b.b_o_c));
-                F5_TRY(f5_upload_t(A, P, H(m, p + "ff_c.ff.0.0.weight").data(), ff * D, &b.w_ff1_c));
+                F5_TRY(up_t(m, A, P, H(m, p + "ff_c.ff.0.0.weight").data(), ff * D, &b.w_ff1_c));
                 F5_TRY(f5_upload_f32(A, H(m, p + "ff_c.ff.0.0.bias").data(), ff, &b.b_ff1_c));
-                F5_TRY(f5_upload_t(A, P, H(m, p + "ff_c.ff.2.weight").data(), D * ff, &b.w_ff2_c));
+                F5_TRY(up_t(m, A, P, H(m, p + "ff_c.ff.2.weight").data(), D * ff, &b.w_ff2_c));
                 F5_TRY(f5_upload_f32(A, H(m, p + "ff_c.ff.2.bias").data(), D, &b.b_ff2_c));
             }
         }
-        F5_TRY(f5_upload_t(A, P, H(m, pa + "to_out.0.weight").data(), D * inner, &b.w_o));
+        F5_TRY(up_t(m, A, P, H(m, pa + "to_out.0.weight").data(), D * inner, &b.w_o));
         F5_TRY(f5_upload_f32(A, H(m, pa + "to_out.0.bias").data(), D, &b.b_o));
-        F5_TRY(f5_upload_t(A, P, H(m, pf + "ff.0.0.weight").data(), ff * D, &b.w_ff1));
+        F5_TRY(up_t(m, A, P, H(m, pf + "ff.0.0.weight").data(), ff * D, &b.w_ff1));
         F5_TRY(f5_upload_f32(A, H(m, pf + "ff.0.0.bias").data(), ff, &b.b_ff1));
         if (fold) {
             memcpy(&fold_w[((size_t)i * foldR + 3 * inner) * D], H(m, pf + "ff.0.0.weight").data(), ff * D * sizeof(float));
             memcpy(&fold_b[(size_t)i * foldR + 3 * inner], H(m, pf + "ff.0.0.bias").data(), ff * sizeof(float));
         }
-        F5_TRY(f5_upload_t(A, P, H(m, pf + "ff.2.weight").data(), D * ff, &b.w_ff2));
+        F5_TRY(up_t(m, A, P, H(m, pf + "ff.2.weight").data(), D * ff, &b.w_ff2));
         F5_TRY(f5_upload_f32(A, H(m, pf + "ff.2.bias").data(), D, &b.b_ff2));
         if (c.qk_norm) {  // (half-split rotary layout: the features of the rope heads were re-ordered above, their norm weights follow)
             for (int part = 0; part < 2; ++part) {
@@ -398,7 +417,7 @@ extern "C" int f5_model_finalize(f5_model_t m) {
         if (un) {
             F5_TRY(f5_upload_f32(A, H(m, p + "1.g").data(), D, &b.g_attn));
             F5_TRY(f5_upload_f32(A, H(m, p + "3.g").data(), D, &b.g_ff));
-            if (i >= c.depth / 2 && c.skip_connect == F5_SKIP_CONCAT) F5_TRY(f5_upload_t(A, P, H(m, p + "0.weight").data(), D * 2 * D, &b.w_skip));
+            if (i >= c.depth / 2 && c.skip_connect == F5_SKIP_CONCAT) F5_TRY(up_t(m, A, P, H(m, p + "0.weight").data(), D * 2 * D, &b.w_skip));
         }
     }
     if (fold) {
@@ -408,13 +427,13 @@ extern "C" int f5_model_finalize(f5_model_t m) {
         std::vector<float>().swap(fold_w);
     }
     if (un) F5_TRY(f5_upload_f32(A, H(m, "norm_out.g").data(), D, &m->g_out));
-    if (c.long_skip) F5_TRY(f5_upload_t(A, P, H(m, "long_skip_connection.weight").data(), D * 2 * D, &m->w_lskip));
+    if (c.long_skip) F5_TRY(up_t(m, A, P, H(m, "long_skip_connection.weight").data(), D * 2 * D, &m->w_lskip));
     {
         // proj_out rows padded to MELP so the tuned kernel can run it too (rows >= mel are zero)
         std::vector<float> w((size_t)MELP * D, 0.f), b(MELP, 0.f);
         memcpy(w.data(), H(m, "proj_out.weight").data(), mel * D * sizeof(float));
         memcpy(b.data(), H(m, "proj_out.bias").data(), mel * sizeof(float));
-        F5_TRY(f5_upload_t(A, P, w.data(), w.size(), &m->w_out));
+        F5_TRY(up_t(m, A, P, w.data(), w.size(), &m->w_out));
         F5_TRY(f5_upload_f32(A, b.data(), b.size(), &m->b_out));
     }
     for (auto& kv : m->slots) {  // host copies are no longer needed
@@ -455,7 +474,7 @@ extern "C" int f5_plan_create(f5_model_t m, int max_batch, int max_seq, int max_
     int rc = 0;
     do {
         if ((rc = A.alloc_t(&p->xres, rows * D))) break;
-        if (c.precision == F5_PREC_BF16) {
+        if (c.precision != F5_PREC_FP32) {
             uint16_t* h16 = nullptr;
             if ((rc = A.alloc_t(&h16, rows * D))) break;
             p->xres16 = h16;
@@ -604,6 +623,8 @@ extern "C" int f5_plan_set_option(f5_plan_t p, const char* key, int value) {
 extern "C" int f5_plan_set_attn_dropout(f5_plan_t p, float prob, uint64_t seed) {
     if (!p) return f5_fail(F5_EINVAL, "null plan");
     if (!(prob >= 0.f && prob < 1.f)) return f5_fail(F5_EINVAL, "f5_plan_set_attn_dropout: prob must lie in [0, 1)");
+    if (prob > 0.f && p->m->cfg.precision == F5_PREC_FP16)
+        return f5_fail(F5_ENOTSUP, "attention dropout is not built for the fp16 precision mode (the dropout kernels are bf16 / fp32)");
     F5_TRY(finish_if_pending(p));
     F5_HIP(hipDeviceSynchronize());  // (launches in flight on the caller's streams may still read the word)
     F5_HIP(hipMemset(p->drop_base, 0, sizeof(uint32_t)));

@@ -84,6 +84,7 @@ struct f5_model_s {
     int fold_R = 0;
     std::vector<FoldTable*> folds;  // at most F5_FOLD_TABLES time grids, oldest dropped first (never one a plan still points to)
     uint64_t fold_seq = 0;
+    std::vector<std::string> read_names;  // f5_model_finalize: host tensors read since the last weight upload (model.hip: up_t)
     ~f5_model_s();
 };
 

@@ -42,10 +42,11 @@ extern "C" int f5_op_linear(int precision, int kernel, int M, int N, int K, cons
 //   epi 0 (EPI_STORE_T): out = act(A W^T + b)                         FF1 (modules.py:258-264)
 //   epi 5 (EPI_GATE_T):  out = gate[n] * act(A W^T + b), 0 where rowmask[m] == 0   attention out / FF2 with the AdaLN gate (modules.py:499-501,635,639)
 //   epi 4 (EPI_ROPE_T):  out = rope(A W^T + b) on the q/k columns of the first rope_heads heads (N = 3 * inner, modules.py:452-461)
-extern "C" int f5_op_linear_fused(int kernel, int epi, int M, int N, int K, const float* A, const float* W, const float* bias, int act,
+extern "C" int f5_op_linear_fused_p(int precision, int kernel, int epi, int M, int N, int K, const float* A, const float* W, const float* bias, int act,
                                   const float* gate, const uint8_t* rowmask, const float* rope, int rope_heads, int seq, float* out,
                                   f5_stream_t stream) {
     F5_TRY(f5_check_device());
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "f5_op_linear_fused_p: a 16-bit precision mode (bf16 0, fp16 2), got %d", precision);
     if (M <= 0 || N <= 0 || K <= 0 || !A || !W || !out) return f5_fail(F5_EINVAL, "bad argument");
     if (!(epi == EPI_STORE_T || epi == EPI_GATE_T || epi == EPI_ROPE_T || epi == EPI_RESID)) return f5_fail(F5_EINVAL, "f5_op_linear_fused: epilogue %d", epi);
     if (epi == EPI_RESID && ((size_t)M * N) % 4 != 0) return f5_fail(F5_EINVAL, "f5_op_linear_fused: M * N must be a multiple of 4 for the in-place form");
@@ -59,10 +60,10 @@ extern "C" int f5_op_linear_fused(int kernel, int epi, int M, int N, int K, cons
     do {
         if ((rc = a.alloc(&At, (size_t)Mp * Kp * 2))) break;
         if ((rc = a.alloc(&Wt, (size_t)Np * Kp * 2))) break;
-        if ((rc = a.alloc(&Ot, (size_t)Mp * N * 2))) break;  // bf16 output, or the fp16 stream of the in-place form
+        if ((rc = a.alloc(&Ot, (size_t)Mp * N * 2))) break;  // 16-bit output, or the fp16 stream of the in-place form
         if ((rc = a.alloc_t(&bits, (size_t)(Mp / 128 + 1) * 16))) break;
-        if ((rc = launch_convert_pad(F5_PREC_BF16, A, K, M, K, Kp, At, Kp, st))) break;
-        if ((rc = launch_convert_pad(F5_PREC_BF16, W, K, N, K, Kp, Wt, Kp, st))) break;
+        if ((rc = launch_convert_pad(precision, A, K, M, K, Kp, At, Kp, st))) break;
+        if ((rc = launch_convert_pad(precision, W, K, N, K, Kp, Wt, Kp, st))) break;
         GemmParams g;
         memset(&g, 0, sizeof(g));
         g.A = At; g.lda = Kp; g.W = Wt; g.ldw = Kp; g.M = M; g.N = N; g.K = Kp;
@@ -83,20 +84,27 @@ extern "C" int f5_op_linear_fused(int kernel, int epi, int M, int N, int K, cons
             }
         }
         if (epi == EPI_ROPE_T) { g.rope = rope; g.rope_inner = N / 3; g.rope_heads = rope_heads; }
-        if ((rc = launch_gemm(g, F5_PREC_BF16, GEMM_DENSE, epi, kernel, st))) break;
-        rc = epi == EPI_RESID ? launch_f16_to_f32(Ot, out, (size_t)M * N, st) : launch_convert_back(F5_PREC_BF16, Ot, N, M, N, out, N, st);
+        if ((rc = launch_gemm(g, precision, GEMM_DENSE, epi, kernel, st))) break;
+        rc = epi == EPI_RESID ? launch_f16_to_f32(Ot, out, (size_t)M * N, st) : launch_convert_back(precision, Ot, N, M, N, out, N, st);
     } while (0);
     return sync_and_release(a, st, rc);
+}
+
+extern "C" int f5_op_linear_fused(int kernel, int epi, int M, int N, int K, const float* A, const float* W, const float* bias, int act,
+                                  const float* gate, const uint8_t* rowmask, const float* rope, int rope_heads, int seq, float* out,
+                                  f5_stream_t stream) {
+    return f5_op_linear_fused_p(F5_PREC_BF16, kernel, epi, M, N, K, A, W, bias, act, gate, rowmask, rope, rope_heads, seq, out, stream);
 }
 
 // The LayerNorm fold of one call site end to end (parity tests; gemm.h, lnfold.hip).  `x` [M, D] is the fp16 residual stream, handed over and
 // returned as f32: (1) x += gate * (A . Wo^T + bo) in place with partial row statistics (EPI_RESID + stats_out; pivots = column 0 of `pivot`
 // [M][2] or none), (2) stats_finalize -> `stats` [M][2] = (mean, rstd), (3) W' / c1 / c2 from W [N, D], bias, scale, shift (fold_weights_kernel),
 // (4) out [M, N] = epilogue(rstd (x . W'^T - mean c1) + c2): epi 0 = store with `act` (FF1: GELU tanh), epi 4 = RoPE (fused QKV, N = 3 * inner).
-extern "C" int f5_op_ln_fold(int epi, int M, int D, int N, int Kb, float* x, const float* A, const float* Wo, const float* bo, const float* gate,
+extern "C" int f5_op_ln_fold_p(int precision, int epi, int M, int D, int N, int Kb, float* x, const float* A, const float* Wo, const float* bo, const float* gate,
                              const float* pivot, const float* W, const float* bias, const float* scale, const float* shift, int act,
                              const float* rope, int rope_heads, int seq, float* stats, float* out, f5_stream_t stream) {
     F5_TRY(f5_check_device());
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "f5_op_ln_fold_p: a 16-bit precision mode (bf16 0, fp16 2), got %d", precision);
     if (M <= 0 || D <= 0 || N <= 0 || Kb <= 0 || !x || !A || !Wo || !bo || !W || !bias || !scale || !shift || !stats || !out) return f5_fail(F5_EINVAL, "bad argument");
     if (D % 128 != 0 || Kb % 32 != 0 || N % 64 != 0 || (epi != EPI_STORE_T && epi != EPI_ROPE_T)) return f5_fail(F5_EINVAL, "f5_op_ln_fold: D % 128, Kb % 32, N % 64, epi 0 | 4");
     if (epi == EPI_ROPE_T && (!rope || seq <= 0 || M % seq != 0 || N % 3 != 0 || (N / 3) % 64 != 0)) return f5_fail(F5_EINVAL, "bad RoPE arguments");
@@ -117,8 +125,8 @@ extern "C" int f5_op_ln_fold(int epi, int M, int D, int N, int Kb, float* x, con
         if ((rc = a.alloc_t(&mod, (size_t)6 * D))) break;
         if ((rc = a.alloc_t(&c1, (size_t)N))) break;
         if ((rc = a.alloc_t(&c2, (size_t)N))) break;
-        if ((rc = launch_convert_pad(F5_PREC_BF16, A, Kb, M, Kb, Kb, At, Kb, st))) break;
-        if ((rc = launch_convert_pad(F5_PREC_BF16, Wo, Kb, D, Kb, Kb, Wot, Kb, st))) break;
+        if ((rc = launch_convert_pad(precision, A, Kb, M, Kb, Kb, At, Kb, st))) break;
+        if ((rc = launch_convert_pad(precision, Wo, Kb, D, Kb, Kb, Wot, Kb, st))) break;
         if ((rc = launch_f32_to_f16(x, xs, (size_t)M * D, st))) break;
         if (pivot) F5_HIP(hipMemcpyAsync(st2, pivot, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
         F5_HIP(hipMemcpyAsync(mod, shift, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));      // (shift_msa, scale_msa) slots of one block
@@ -128,19 +136,25 @@ extern "C" int f5_op_ln_fold(int epi, int M, int D, int N, int Kb, float* x, con
         g.A = At; g.lda = Kb; g.W = Wot; g.ldw = Kb; g.M = M; g.N = D; g.K = Kb; g.bias = bo; g.rows_per_batch = seq > 0 ? seq : M;
         g.out_f = reinterpret_cast<float*>(xs); g.ldof = D; g.add2_f16 = 1; g.gate = gate;
         g.stats_out = partial; g.stats_ld = (int)Mp; g.stats_pivot = pivot ? st2 : nullptr;
-        if ((rc = launch_gemm(g, F5_PREC_BF16, GEMM_DENSE, EPI_RESID, 1, st))) break;
+        if ((rc = launch_gemm(g, precision, GEMM_DENSE, EPI_RESID, 1, st))) break;
         if ((rc = launch_stats_finalize(partial, (int)Mp, D / 64, M, D, pivot ? st2 : nullptr, st2, nullptr, 0, st))) break;
         if ((rc = launch_fold_weights(W, bias, mod, 6 * D, 1, 1, N, N, D, Wt, c1, c2, st))) break;
         memset(&g, 0, sizeof(g));
         g.A = xs; g.lda = D; g.W = Wt; g.ldw = D; g.M = M; g.N = N; g.K = D; g.act = act; g.out_t = Ot; g.ldo = N; g.rows_per_batch = seq > 0 ? seq : M;
         g.lnf_stats = st2; g.lnf_c1 = c1; g.lnf_c2 = c2;
         if (epi == EPI_ROPE_T) { g.rope = rope; g.rope_inner = N / 3; g.rope_heads = rope_heads; }
-        if ((rc = launch_gemm(g, F5_PREC_BF16, GEMM_DENSE, epi, 1, st))) break;
+        if ((rc = launch_gemm(g, precision, GEMM_DENSE, epi, 1, st))) break;
         if ((rc = launch_f16_to_f32(xs, x, (size_t)M * D, st))) break;
         F5_HIP(hipMemcpyAsync(stats, st2, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        rc = launch_convert_back(F5_PREC_BF16, Ot, N, M, N, out, N, st);
+        rc = launch_convert_back(precision, Ot, N, M, N, out, N, st);
     } while (0);
     return sync_and_release(a, st, rc);
+}
+
+extern "C" int f5_op_ln_fold(int epi, int M, int D, int N, int Kb, float* x, const float* A, const float* Wo, const float* bo, const float* gate,
+                             const float* pivot, const float* W, const float* bias, const float* scale, const float* shift, int act,
+                             const float* rope, int rope_heads, int seq, float* stats, float* out, f5_stream_t stream) {
+    return f5_op_ln_fold_p(F5_PREC_BF16, epi, M, D, N, Kb, x, A, Wo, bo, gate, pivot, W, bias, scale, shift, act, rope, rope_heads, seq, stats, out, stream);
 }
 
 extern "C" int f5_op_layernorm_modulate(int rows, int dim, const float* x, const float* scale, const float* shift, float* out,
@@ -321,8 +335,8 @@ extern "C" int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const 
         memset(&g, 0, sizeof(g));
         g.A = xt; g.lda = dim; g.W = wr[0]; g.M = rows; g.N = dim; g.K = 31 * win; g.bias = b0; g.act = ACT_MISH;
         g.rows_per_batch = N; g.conv_cg = cg; g.conv_win = win; g.out_t = c1; g.ldo = dim;
-        // tuning knob "op_conv_kernel" = 1: the tuned kernels exactly as dit_eval launches them (store-only second conv, bf16 only)
-        const int kind = (g_op_conv_kernel && precision == F5_PREC_BF16 && gemm_fast_supported(g, precision, GEMM_CONV31, EPI_STORE_T)) ? 1 : 0;
+        // tuning knob "op_conv_kernel" = 1: the tuned kernels exactly as dit_eval launches them (store-only second conv, the 16-bit modes)
+        const int kind = (g_op_conv_kernel && precision != F5_PREC_FP32 && gemm_fast_supported(g, precision, GEMM_CONV31, EPI_STORE_T)) ? 1 : 0;
         if ((rc = launch_gemm(g, precision, GEMM_CONV31, EPI_STORE_T, kind, st))) break;
         if (kind) {
             void* c2 = nullptr;
@@ -359,7 +373,7 @@ extern "C" int f5_op_layernorm_res(int precision, int xin_f16, int xout_f16, int
                                    f5_stream_t stream) {
     F5_TRY(f5_check_device());
     if (rows <= 0 || dim <= 0 || !x || !mul || !add || !out || !xback) return f5_fail(F5_EINVAL, "bad argument");
-    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "bad precision %d", precision);
     if (ldx < dim || ldo < dim || (ldx & 3) || (ldo & 3) || (y && (ldy < dim || (ldy & 3)))) return f5_fail(F5_EINVAL, "leading dimensions below dim");
     if ((ymode != 0 && !y) || (ymode == 3 && !y2)) return f5_fail(F5_EINVAL, "residual mode %d needs its branches", ymode);
     if (inplace && xin_f16 != xout_f16) return f5_fail(F5_EINVAL, "in place needs one storage type");
@@ -417,7 +431,7 @@ extern "C" int f5_op_qknorm_rope(int precision, int rows, int heads, int rope_he
     F5_TRY(f5_check_device());
     if (rows <= 0 || heads <= 0 || rope_heads < 0 || rope_heads > heads || rows_per_batch <= 0 || !qkv || !wq || !wk || !out || (rope_heads && !rope))
         return f5_fail(F5_EINVAL, "bad argument");
-    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "bad precision %d", precision);
     hipStream_t st = (hipStream_t)stream;
     const int inner = heads * 64, ld = 3 * inner;
     DevArena a;
@@ -436,7 +450,7 @@ extern "C" int f5_op_dwconv7_ln(int precision, int B, int N, int C, const float*
                                 const float* ln_b, float* out, f5_stream_t stream) {
     F5_TRY(f5_check_device());
     if (B <= 0 || N <= 0 || C <= 0 || !x || !wt || !cbias || !ln_w || !ln_b || !out) return f5_fail(F5_EINVAL, "bad argument");
-    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "bad precision %d", precision);
     hipStream_t st = (hipStream_t)stream;
     const int rows = B * N;
     DevArena a;
@@ -453,7 +467,7 @@ extern "C" int f5_op_dwconv7_ln(int precision, int B, int N, int C, const float*
 extern "C" int f5_op_grn(int precision, int B, int N, int C, const float* h, const float* gamma, const float* beta, float* out, f5_stream_t stream) {
     F5_TRY(f5_check_device());
     if (B <= 0 || N <= 0 || C <= 0 || !h || !gamma || !beta || !out) return f5_fail(F5_EINVAL, "bad argument");
-    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "bad precision %d", precision);
     hipStream_t st = (hipStream_t)stream;
     const int rows = B * N;
     DevArena a;
@@ -473,7 +487,7 @@ extern "C" int f5_op_grn(int precision, int B, int N, int C, const float* h, con
 extern "C" int f5_op_rmsnorm(int precision, int rows, int dim, const float* x, const float* g, float* out, f5_stream_t stream) {
     F5_TRY(f5_check_device());
     if (rows <= 0 || dim <= 0 || !x || !g || !out) return f5_fail(F5_EINVAL, "bad argument");
-    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32) return f5_fail(F5_EINVAL, "bad precision %d", precision);
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP32 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "bad precision %d", precision);
     hipStream_t st = (hipStream_t)stream;
     DevArena a;
     void* o = nullptr;

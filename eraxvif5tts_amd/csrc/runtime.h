@@ -24,8 +24,10 @@ struct DevArena {
 int f5_check_device();                       // F5_ENODEVICE unless a gfx950 device is current
 int f5_cu_count();                           // compute units of the current device (cached; 256 on MI355X)
 uint16_t f5_f32_to_bf16_bits(float f);       // round-to-nearest-even, NaN preserved
-size_t f5_elem_size(int precision);          // 2 (bf16) / 4 (fp32)
-// upload host fp32 -> device in the activation dtype of `precision` (bf16 RNE on the host) / as fp32
+uint16_t f5_f32_to_f16_bits(float f);        // round-to-nearest-even, overflow -> inf
+size_t f5_elem_size(int precision);          // 2 (bf16, fp16) / 4 (fp32)
+// upload host fp32 -> device in the activation dtype of `precision` (bf16 / fp16 RNE on the host; fp16: F5_EINVAL when an element does not stay
+// finite) / as fp32
 int f5_upload_t(DevArena& a, int precision, const float* host, size_t count, void** out);
 int f5_upload_f32(DevArena& a, const float* host, size_t count, float** out);
 

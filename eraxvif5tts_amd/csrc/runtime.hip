@@ -101,7 +101,25 @@ uint16_t f5_f32_to_bf16_bits(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
 }
-size_t f5_elem_size(int precision) { return precision == F5_PREC_BF16 ? 2 : 4; }
+// fp32 -> fp16 bits, round to nearest even (overflow -> inf, NaN stays NaN, subnormals exact)
+uint16_t f5_f32_to_f16_bits(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    const uint32_t a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
+    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);  // >= 65520 rounds to inf (inf itself included)
+    if (a < 0x33000001u) return sign;                          // <= 2^-25 rounds to zero (the tie goes to the even 0)
+    const int e = (int)(a >> 23) - 127;
+    uint32_t man = (a & 0x7fffffu) | 0x800000u;
+    const int shift = e < -14 ? 13 + (-14 - e) : 13;  // subnormal results lose more bits
+    const uint32_t kept = man >> shift, rem = man & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    uint32_t r = kept + ((rem > half || (rem == half && (kept & 1u))) ? 1u : 0u);
+    // normal: r has the implicit bit at position 10 (a carry into bit 11 bumps the exponent through the addition below)
+    const uint32_t bits = e < -14 ? r : (uint32_t)((e + 15 - 1) << 10) + r;
+    return (uint16_t)(sign | bits);
+}
+size_t f5_elem_size(int precision) { return (precision == F5_PREC_BF16 || precision == F5_PREC_FP16) ? 2 : 4; }
 
 int f5_upload_f32(DevArena& a, const float* host, size_t count, float** out) {
     F5_TRY(a.alloc_t(out, count, false));
@@ -111,7 +129,14 @@ int f5_upload_f32(DevArena& a, const float* host, size_t count, float** out) {
 int f5_upload_t(DevArena& a, int precision, const float* host, size_t count, void** out) {
     if (precision == F5_PREC_FP32) return f5_upload_f32(a, host, count, (float**)out);
     std::vector<uint16_t> tmp(count);
-    for (size_t i = 0; i < count; ++i) tmp[i] = f5_f32_to_bf16_bits(host[i]);
+    if (precision == F5_PREC_FP16) {
+        for (size_t i = 0; i < count; ++i) {
+            tmp[i] = f5_f32_to_f16_bits(host[i]);
+            if ((tmp[i] & 0x7c00u) == 0x7c00u) return f5_fail(F5_EINVAL, "a weight is not finite in fp16 (element %zu = %g)", i, (double)host[i]);
+        }
+    } else {
+        for (size_t i = 0; i < count; ++i) tmp[i] = f5_f32_to_bf16_bits(host[i]);
+    }
     F5_TRY(a.alloc(out, count * 2, false));
     F5_HIP(hipMemcpy(*out, tmp.data(), count * 2, hipMemcpyHostToDevice));
     return 0;

@@ -86,8 +86,9 @@ def load_vocoder(vocoder_name="vocos", is_local=False, local_path="", device=dev
 
 
 def load_checkpoint(model, ckpt_path, device: str, dtype=None, use_ema=True):
-    """Reference :184-226.  The checkpoint dtype policy of the reference (fp16 on CUDA) does not apply: the HIP backbone keeps
-    fp32 master weights and converts them once to its own bf16 kernel layouts."""
+    """Reference :184-226.  The reference casts the model to fp16 on CUDA here; the HIP backbone keeps fp32 master weights in the module and
+    converts them once to the kernel layouts of its precision mode: bf16 (default), fp32, or fp16 -- the reference's own GPU dtype -- as
+    chosen by ``precision=`` / ``F5HIP_PRECISION``.  ``dtype`` is accepted for the reference's signature."""
     ckpt_type = ckpt_path.split(".")[-1]
     if ckpt_type == "safetensors":
         from safetensors.torch import load_file

@@ -111,7 +111,7 @@ class DiT(nn.Module):
         self.text_mask_padding, self.conv_layers, self.pe_attn_head = bool(text_mask_padding), conv_layers, pe_attn_head
         self.skip_connect_type = skip_connect_type
         prec = precision or os.environ.get("F5HIP_PRECISION", "bf16")
-        self.precision = {"bf16": _lib.F5_PREC_BF16, "fp32": _lib.F5_PREC_FP32}[prec]
+        self.precision = _lib.PRECISIONS[prec]  # "bf16" (production), "fp32" (parity), "fp16" (the reference's own GPU dtype)
         # x_transformers (dit.py:16,134) is not vendored in the reference tree: "adjacent" rotates feature pairs (2j, 2j+1), the form the
         # pinned >= 1.31 releases publish (default); "half_split" rotates (j, j+32).  ONE switch, also settable as F5HIP_ROPE_LAYOUT.
         layout = rope_layout or os.environ.get("F5HIP_ROPE_LAYOUT", "adjacent")
@@ -237,6 +237,8 @@ class DiT(nn.Module):
         seed=None draws one int64 from torch's default CPU generator now, so torch.manual_seed governs it as it governs the reference's
         dropout.  Applies to the live plans and to plans created later; plan i (in creation order, counted from this call) uses seed + i,
         so chunk streams do not share masks."""
+        if p is not None and float(p) != 0.0 and self.precision == _lib.F5_PREC_FP16:
+            raise NotImplementedError("attention dropout is not built for the fp16 precision mode (the dropout kernels are bf16 / fp32)")
         if p is None or float(p) == 0.0:
             self._attn_dropout = None
             for _, h in self._plans:
@@ -417,7 +419,7 @@ class DiT(nn.Module):
         return len(pending)
 
     def _report_fallback(self, lib, plan):
-        if self.precision == _lib.F5_PREC_BF16:
+        if self.precision != _lib.F5_PREC_FP32:  # both 16-bit modes keep the residual stream in fp16
             # fp16 residual-stream range guard (include/f5hip.h, plan option "residual_guard"): the library repeated the loop with fp32
             # residual storage when an activation reached fp16's range, and keeps fp32 storage for this plan; say so once per event
             n = C.c_int(0)

@@ -47,6 +47,16 @@ extern "C" {
 /* arithmetic of the dense kernels */
 #define F5_PREC_BF16 0 /* bf16 MFMA inputs, fp32 accumulate and arithmetic, fp32 ODE state, residual stream stored as fp16 (production) */
 #define F5_PREC_FP32 1 /* fp32-input MFMA everywhere (debug / parity mode, ~1/16 of the bf16 rate) */
+/* fp16 weights, activations and MFMA inputs (v_mfma_f32_*_f16: the bf16 rate and fragment layouts), fp32 accumulate and arithmetic, fp32 ODE
+ * state, and the fp16 residual stream with its range guard exactly as in the bf16 mode: the dtype the reference casts its model to on a GPU
+ * (infer/utils_infer.py:184-193).  Weights are rounded to nearest even on the host; a tensor that holds a non-finite value after the rounding
+ * fails f5_model_finalize with F5_EINVAL and its name.  Every fp32 -> fp16 ACTIVATION store saturates at +-65504: an out-of-range activation
+ * clips silently (the residual stream is the one buffer whose clipping is guarded).  The attention kernels keep their un-normalised softmax
+ * numerators inside fp16: the exponent reference is always a score of the row (q is never pre-scaled: "attn_prescale_active" reads 0 and the
+ * LayerNorm-fold tables carry plain q rows), and a tile whose row sums reach 2^15 against a stale reference is redone against the row maxima.
+ * f5_plan_set_attn_dropout(prob > 0) answers F5_ENOTSUP on an fp16 plan; the vocoders, the front-end and the duration predictor keep their own
+ * precisions. */
+#define F5_PREC_FP16 2
 
 /* ODE solvers of torchdiffeq's fixed-grid family used by cfm.py:197 (odeint_kwargs["method"]): euler, midpoint, and the explicit
  * Runge-Kutta methods rk4 (rk4_alt_step_func, the 3/8 rule), heun2 and heun3.  Network evaluations per step: 1 / 2 / 4 / 2 / 3
@@ -216,7 +226,8 @@ F5_API int f5_plan_timing_site(f5_plan_t p, int site, float* avg_ms, int* launch
  * deferred to f5_sample_finish).
  * Key "attn_prescale" (default -1 = the process-wide knob, which is on): 1 = the softmax scale times log2(e) is folded into the weights that
  * project q and the attention kernels apply none (bf16 DiT on the tuned attention kernels, no qk_norm, no stage taps, LayerNorm-fold
- * evaluations; everything else keeps q as projected), 0 = q as projected everywhere. */
+ * evaluations; everything else keeps q as projected), 0 = q as projected everywhere.  An F5_PREC_FP16 plan never pre-scales q, whatever the key says:
+ * the reference-free attention build needs bf16's exponent range. */
 F5_API int f5_plan_set_option(f5_plan_t p, const char* key, int value);
 /* reads an option back; besides the keys above: "residual_fallbacks" = f5_sample calls of this plan that were repeated with fp32 residual
  * storage because the range guard fired ("residual_f16" then reads 0); "attn_prescale_active" = 1 when this plan wants pre-scaled q and may run it (0 e.g.
@@ -236,7 +247,7 @@ F5_API int f5_plan_get_option(f5_plan_t p, const char* key, int* value);
  * forward by depth, a replayed graph too.  The call resets base to 0 and drops captured graphs.  The mask stream is this library's own,
  * not torch's: a run matches the reference in distribution, never bit for bit.  While it is on, q is never pre-scaled
  * ("attn_prescale_active" reads 0) and a ragged sample() is not bit-equal to its batch-1 calls.  f5_plan_get_option keys:
- * "attn_dropout_on", "attn_dropout_base" (host mirror of base). */
+ * "attn_dropout_on", "attn_dropout_base" (host mirror of base).  prob > 0 on an F5_PREC_FP16 plan: F5_ENOTSUP (the dropout kernel is bf16 / fp32). */
 F5_API int f5_plan_set_attn_dropout(f5_plan_t p, float prob, uint64_t seed);
 
 /* ------------------------------------------------------------------ duration predictor
@@ -262,8 +273,8 @@ F5_API int f5_duration_predict_g(const f5_duration_weights* w, int batch, int nt
 
 /* ------------------------------------------------------------------ per-op entry points (parity tests, micro-benchmarks) */
 /* out[M,N] = A[M,K] @ W[N,K]^T + bias ; A/W/out f32 dev; computed through the precision's GEMM kernel
- * (bf16: inputs rounded to bf16 on device, MFMA, f32 accumulate).  act: 0 none, 1 gelu-tanh, 2 gelu-erf, 3 mish.
- * kernel: 0 = reference tile kernel, 1 = tuned 256x256 LDS-DMA kernel (bf16 only; shapes must be tile multiples). */
+ * (bf16 / fp16: inputs rounded to the 16-bit type on device, MFMA, f32 accumulate).  act: 0 none, 1 gelu-tanh, 2 gelu-erf, 3 mish.
+ * kernel: 0 = reference tile kernel, 1 = tuned 256x256 LDS-DMA kernel (bf16 / fp16; shapes must be tile multiples). */
 F5_API int f5_op_linear(int precision, int kernel, int M, int N, int K, const float* A, const float* W, const float* bias, int act,
                  float* out, f5_stream_t stream);
 /* One DiT block linear with the fused store epilogue the sampler uses for it (bf16 path; output converted back to f32):
@@ -279,6 +290,10 @@ F5_API int f5_op_linear(int precision, int kernel, int M, int N, int K, const fl
 F5_API int f5_op_linear_fused(int kernel, int epi, int M, int N, int K, const float* A, const float* W, const float* bias, int act,
                        const float* gate, const uint8_t* rowmask, const float* rope, int rope_heads, int seq, float* out,
                        f5_stream_t stream);
+/* f5_op_linear_fused in the 16-bit mode `precision` (F5_PREC_BF16 = f5_op_linear_fused itself, F5_PREC_FP16) */
+F5_API int f5_op_linear_fused_p(int precision, int kernel, int epi, int M, int N, int K, const float* A, const float* W, const float* bias, int act,
+                         const float* gate, const uint8_t* rowmask, const float* rope, int rope_heads, int seq, float* out,
+                         f5_stream_t stream);
 /* The LayerNorm fold of one call site end to end (round 4; parity tests).  x [M, D]: the fp16 residual stream, handed over and returned as f32.
  * (1) x += gate * (A . Wo^T + bo) in place by the tuned GEMM's EPI_RESID epilogue, which also writes partial row sums of the values it stores
  * (pivot = column 0 of `pivot` [M][2], or NULL); (2) stats [M][2] = (mean, rstd) of every row, eps 1e-6 (modules.py:308,624); (3) W' = fp16(W (1 +
@@ -287,6 +302,10 @@ F5_API int f5_op_linear_fused(int kernel, int epi, int M, int N, int K, const fl
 F5_API int f5_op_ln_fold(int epi, int M, int D, int N, int Kb, float* x, const float* A, const float* Wo, const float* bo, const float* gate,
                          const float* pivot, const float* W, const float* bias, const float* scale, const float* shift, int act, const float* rope,
                          int rope_heads, int seq, float* stats, float* out, f5_stream_t stream);
+/* f5_op_ln_fold in the 16-bit mode `precision`: the stream, the statistics and W' are fp16 in both; A, Wo and the output take the mode's type */
+F5_API int f5_op_ln_fold_p(int precision, int epi, int M, int D, int N, int Kb, float* x, const float* A, const float* Wo, const float* bo,
+                           const float* gate, const float* pivot, const float* W, const float* bias, const float* scale, const float* shift, int act,
+                           const float* rope, int rope_heads, int seq, float* stats, float* out, f5_stream_t stream);
 /* LayerNorm(eps 1e-6, no affine) * (1 + scale) + shift ; x f32 [rows, dim]; scale/shift f32 [dim] */
 F5_API int f5_op_layernorm_modulate(int rows, int dim, const float* x, const float* scale, const float* shift, float* out,
                              f5_stream_t stream);
