@@ -52,9 +52,10 @@ __device__ __forceinline__ float to_f32(bf16_t v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }  // v_cvt_pk_bf16_f32 (RNE, NaN-safe)
-// fp16 activation stores SATURATE: an out-of-range value clips to +-65504 instead of becoming inf (and NaN in the next softmax)
+// fp16 activation stores SATURATE: an out-of-range value clips to +-65504 instead of becoming inf (and NaN in the next softmax).  A NaN
+// stays a NaN: v_med3_f32 alone answers a NaN operand with the minimum of the other two, which would turn it into a large finite number.
 __device__ __forceinline__ float to_f32(f16_t v) { return (float)v; }
-__device__ __forceinline__ float f16_sat(float v) { return __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f); }
+__device__ __forceinline__ float f16_sat(float v) { return v != v ? v : __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f); }
 template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float v) { return (f16_t)f16_sat(v); }  // clamp, then v_cvt_pk_f16_f32 (RNE)
 
 // The 16-bit element type of a production mode as a template parameter (Elem<bf16_t> is the default everywhere, Elem<f16_t> the fp16 mode):

@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
         q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
     }
     const float nrm = sqrtf(wave_sum(q));
-    const float sc = sqrtf((float)dim) / fmaxf(nrm, 1e-12f);
+    const float sc = sqrtf((float)dim) / (nrm < 1e-12f ? 1e-12f : nrm);  // clamp_min as torch does it: a NaN norm stays NaN (fmaxf would answer 1e-12)
     TO* orow = out + (size_t)row * ldo;
     for (int c = lane * 4; c < dim; c += 256) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c);

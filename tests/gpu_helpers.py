@@ -257,17 +257,24 @@ def bf16_ulp(ref):
     return torch.pow(2.0, (e - 8).clamp(min=-133).double())
 
 
+def fp16_ulp(ref):
+    """Spacing of fp16 at |ref| (fp64): 2^(floor(log2 |ref|) - 10), at least the subnormal spacing 2^-24."""
+    _, e = torch.frexp(ref.abs().double())
+    return torch.pow(2.0, (e - 11).clamp(min=-24).double())
+
+
 def check_rounded(name, out, ref, scale, precision):
     """Element-wise bound of a kernel output against its fp64 reference.  `scale` [same shape]: the magnitude of the largest term the kernel
-    evaluates in fp32 for that element; the slack is 8 fp32 ulps of it.  bf16 outputs: |out - ref| <= 1 bf16 ulp of ref + slack per element;
-    fp32 outputs: <= 1e-5 |ref| + slack.  Returns (worst error in the bound's units, signed error sum in bf16 ulps, count) for the bias check."""
+    evaluates in fp32 for that element; the slack is 8 fp32 ulps of it.  bf16 / fp16 outputs (precision 0 / 2): |out - ref| <= 1 ulp of ref in
+    the stored type + slack per element; fp32 outputs: <= 1e-5 |ref| + slack.  Returns (worst error in the bound's units, (signed error sum in
+    ulps of the stored type, count)) for the bias check: the sum runs over the elements whose slack is below 0.05 ulp."""
     ref = ref.double()
     err = out.double() - ref
     slack = 8 * 2.0 ** -23 * scale.double().abs()
-    if precision == 0:
-        ulp = bf16_ulp(ref)
+    if precision in (0, 2):
+        ulp = bf16_ulp(ref) if precision == 0 else fp16_ulp(ref)
         bound = ulp + slack
-        keep = slack < 0.05 * ulp  # the rounding bias is read where fp32 evaluation error is negligible next to a bf16 ulp
+        keep = slack < 0.05 * ulp  # the rounding bias is read where fp32 evaluation error is negligible next to an ulp of the stored type
         signed = (err * torch.sign(ref) / ulp)[keep]
         sums = (float(signed.sum()), int(signed.numel()))
     else:
@@ -276,9 +283,9 @@ def check_rounded(name, out, ref, scale, precision):
     ratio = (err.abs() / bound)
     worst = float(ratio.max())
     bad = ratio > 1
-    if precision == 0:  # (in ulps where the fp32 slack is negligible; the bound's share everywhere)
+    if precision in (0, 2):  # (in ulps where the fp32 slack is negligible; the bound's share everywhere)
         in_ulp = float((err.abs() / ulp)[keep].max()) if keep.any() else float("nan")
-        print(f"  {name}: worst {in_ulp:.3f} bf16 ulp, {worst:.3f} of the bound")
+        print(f"  {name}: worst {in_ulp:.3f} {'bf16' if precision == 0 else 'fp16'} ulp, {worst:.3f} of the bound")
     else:
         print(f"  {name}: worst {float((err.abs() / ref.abs().clamp(min=1e-30)).max()):.3e} relative, {worst:.3f} of the bound")
     assert not bad.any(), (f"{name}: {int(bad.sum())} elements out of bound, first at {bad.nonzero()[0].tolist()}: "

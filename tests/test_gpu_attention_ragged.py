@@ -12,7 +12,9 @@ Every result-checking test asserts, for every utterance and branch,
       utterance alone").  The own launch has B = nbr, as launch_attention_ragged states it and as the batch-1 sample() makes it: by grid size
       (attn_variant 0) the kernel choice depends on B;
   (b) accuracy against the fp64 softmax of that utterance, with the bounds the packed-form tests of test_gpu_ops.py use at this input scale
-      (tuned bf16 kernels: rel-L2 < 6e-3, max-abs < 0.05, all finite; reference kernels: rel-L2 < 3e-6 in fp32, < 4e-3 in bf16);
+      (tuned bf16 kernels: rel-L2 < 6e-3, max-abs < 0.05, all finite; reference kernels: rel-L2 < 3e-6 in fp32, < 4e-3 in bf16); in the
+      fp16 mode (P_FP16: utterances rounded to fp16, a cache entry of their own) the ELEMENT-WISE fp64 bound of test_gpu_fp16_ops.py
+      (1 fp16 ulp + 8 fp32 ulps of the sums of magnitudes + the numerator-rounding terms) per utterance and branch, no rel-L2 number;
   (c) no stray write: every element of `out` outside the utterances' rows and head columns, in every branch, still holds 776.0."""
 import functools
 
@@ -22,8 +24,8 @@ import torch
 from conftest import rel_l2
 
 pytestmark = pytest.mark.gpu
-P_BF16, P_FP32 = 0, 1
-SENTINEL, POISON = 776.0, 50.0  # both exact in bf16
+P_BF16, P_FP32, P_FP16 = 0, 1, 2
+SENTINEL, POISON = 776.0, 50.0  # both exact in bf16 and in fp16
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -49,15 +51,21 @@ def _layout(lens, first=0):
 
 
 @functools.lru_cache(maxsize=2)
-def _case(lens, nbr, H, first, ref_heads):
-    """Seeded utterances [nbr, n, 3, H, 64], their layout, and the fp64 reference of each over the heads `ref_heads` (None: all).  Shared by
-    the parametrisations that differ only in the schedule; nobody modifies it."""
+def _case(lens, nbr, H, first, ref_heads, fp16=False):
+    """Seeded utterances [nbr, n, 3, H, 64] (rounded to bf16, or to fp16 for the fp16 mode), their layout, and the fp64 reference of each over
+    the heads `ref_heads` (None: all) -- for fp16 the triple (reference, fp32 magnitude, numerator-rounding allowance) of
+    test_gpu_fp16_ops._attn_ref.  Shared by the parametrisations that differ only in the schedule; nobody modifies it."""
     import gpu_helpers as G
     g = torch.Generator().manual_seed(sum(lens) + 131 * nbr + 7 * H + first)
-    utts = [G.bf16_round(torch.randn(nbr, n, 3, H, 64, generator=g) * 1.5) for n in lens]
+    rnd = (lambda t: t.half().float()) if fp16 else G.bf16_round
+    utts = [rnd(torch.randn(nbr, n, 3, H, 64, generator=g) * 1.5) for n in lens]
     off, rows = _layout(lens, first)
     heads = list(range(H)) if ref_heads is None else list(ref_heads)
-    refs = [_attn_ref(u[:, :, :, heads]) for u in utts]
+    if fp16:
+        from test_gpu_fp16_ops import _attn_ref as attn_ref_f16
+        refs = [attn_ref_f16(u[:, :, :, heads], None) for u in utts]
+    else:
+        refs = [_attn_ref(u[:, :, :, heads]) for u in utts]
     return utts, off, rows, heads, refs
 
 
@@ -75,11 +83,11 @@ def _run(prec, attn_kernel, variant, lens, nbr, H, first=0, ldq_extra=0, ldo_ext
     import gpu_helpers as G
     from eraxvif5tts_amd import _lib
     lib = _lib.load()
-    utts, off, rows, heads, refs = _case(tuple(lens), nbr, H, first, None if ref_heads is None else tuple(ref_heads))
+    utts, off, rows, heads, refs = _case(tuple(lens), nbr, H, first, None if ref_heads is None else tuple(ref_heads), prec == P_FP16)
     inner, ldo = H * 64, H * 64 + ldo_extra
     qkv = _pack(utts, off, rows, nbr, H, ldq_extra)
     out0 = torch.full((nbr * rows, ldo), SENTINEL)
-    kind = 1 if (prec == P_BF16 and attn_kernel != 0) else 0
+    kind = 1 if (prec in (P_BF16, P_FP16) and attn_kernel != 0) else 0  # the tuned kernels exist for both 16-bit modes
     _lib.check(lib.f5_tuning_set(b"attn_variant", variant))
     try:
         out = G.op_attention_ragged(prec, attn_kernel, nbr, off, list(lens), H, rows, qkv, out0, ldq_extra, ldo_extra).view(nbr, rows, ldo)
@@ -94,6 +102,12 @@ def _run(prec, attn_kernel, variant, lens, nbr, H, first=0, ldq_extra=0, ldo_ext
         assert torch.isfinite(got).all(), f"utterance {u} (n = {n})"
         bad = (got != own[u]).any(dim=-1).nonzero()
         assert torch.equal(got, own[u]), f"(a) utterance {u} (n = {n}) differs from its own launch, first at (branch, row) {bad[0].tolist()} of {len(bad)} rows"
+        if prec == P_FP16:
+            from test_gpu_fp16_ops import check_f16
+            ref, mag, extra = refs[u]
+            for br in range(nbr):
+                check_f16(f"(b) utterance {u} n={n} branch {br}", got[br][:, cols], ref[br], mag[br], extra[br])
+            continue
         for br in range(nbr):
             g, r = got[br][:, cols], refs[u][br]
             rl, ma = rel_l2(g, r), float((g - r).abs().max())
@@ -195,3 +209,40 @@ def test_ragged_refusals():
     assert "has no rows" in _refused(P_BF16, 1, [0, 272], [256, 0], 528)
     assert "has no rows" in _refused(P_FP32, 0, [0], [0], 16)
     assert "attention_fast: ldq and ldo must be multiples of 8" in _refused(P_BF16, 1, [0, 272], [256, 257], 544, ldq_extra=4)
+
+
+# ----------------------------------------------------------------------------- the fp16 mode: launch_attention_pipe_segs_f16 (both SEG builds),
+# launch_attention_wide_f16 with bstride != N and attn_ref_kernel<f16_t>, with assertions (a), (b) element-wise, (c)
+@pytest.mark.parametrize("lens,nbr,H,first", [
+    ((256, 320, 1024), 2, 2, 0),      # unmasked SEG build alone
+    ((257, 411, 300), 2, 2, 0),       # masked SEG build alone
+    ((256, 257, 320, 333), 2, 4, 48),  # both in one call, BH = 16 each: XCD remap taken; the first utterance starts at row 48
+], ids=["unmasked", "masked", "mixed_remap_first_offset"])
+def test_ragged_fp16_pipelined_seg_builds(lens, nbr, H, first):
+    _run(P_FP16, 1, 5, lens, nbr, H, first)
+
+
+@pytest.mark.parametrize("variant", [5, 0], ids=["pipelined", "by_grid_size"])
+def test_ragged_fp16_short_utterance_next_to_long(variant):
+    _run(P_FP16, 1, variant, (1, 31, 64, 127, 129, 1500), 2, 2)
+
+
+def test_ragged_fp16_wide_kernel_with_batch_stride():
+    """attn_variant 2: launch_attention_wide_f16 per utterance with bstride = rows != n, unmasked (256, 1024) and masked (300) builds."""
+    _run(P_FP16, 1, 2, (256, 300, 1024), 2, 2)
+
+
+def test_ragged_fp16_more_utterances_than_one_table():
+    lens = tuple([256, 257, 320, 300][i % 4] for i in range(13))
+    _run(P_FP16, 1, 5, lens, 2, 2)
+
+
+def test_ragged_fp16_reference_kernel_with_batch_stride():
+    """attn_kernel 0: attn_ref_kernel<f16_t>, one launch per utterance with bstride = rows."""
+    _run(P_FP16, 0, 0, (41, 200, 64), 2, 2)
+
+
+@pytest.mark.parametrize("variant", [5, 2], ids=["pipelined", "64_queries_per_wave"])
+def test_ragged_fp16_padded_leading_dimensions(variant):
+    out = _run(P_FP16, 1, variant, (256, 300), 2, 2, ldq_extra=64, ldo_extra=8)
+    assert (out[:, :, 2 * 64:] == SENTINEL).all()

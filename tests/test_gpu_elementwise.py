@@ -17,7 +17,7 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-P_BF16, P_FP32 = 0, 1
+P_BF16, P_FP32, P_FP16 = 0, 1, 2
 F16_MAX = 65504.0
 
 
@@ -96,6 +96,8 @@ def _run_ln_case(name, prec, xin_f16, xout_f16, rows, dim, ymode, add_one, per_b
     y2 = torch.randn(rows, dim, generator=g) * 0.7
     if prec == P_BF16:
         y, y2 = _bf16(y), _bf16(y2)
+    elif prec == P_FP16:
+        y, y2 = _f16(y), _f16(y2)
     rpb = max(1, rows // 3) if per_batch else 0
     mbs = dim + 8 if per_batch else 0
     mul, add = _mods(rows, dim, mbs, rpb, g)
@@ -152,16 +154,16 @@ def test_layernorm_res_generic_kernel_against_fp64(dim, pair):
     _bias_check(f"dim {dim} {pair}", total)
 
 
-def _rows_case(rows, seed, ln_rows, ln_rows_min, add_one=1):
+def _rows_case(rows, seed, ln_rows, ln_rows_min, add_one=1, prec=P_BF16):
     """In-place read-only pass (ymode 0, one modulation row): the multi-row kernel's form.  Returns (out, reference run of the one-row kernel)."""
     import gpu_helpers as G
     g = torch.Generator().manual_seed(seed)
     x = _stream(rows, 1024, 40 * (seed % 2), g)
     mul, add = _mods(rows, 1024, 0, 0, g)
     with G.knobs(ln_rows=ln_rows, ln_rows_min=ln_rows_min):
-        out, xb, guard = G.op_layernorm_res(P_BF16, x, None, None, 0, mul, add, 0, 0, add_one, 1)
+        out, xb, guard = G.op_layernorm_res(prec, x, None, None, 0, mul, add, 0, 0, add_one, 1)
     with G.knobs(ln_rows=1):
-        one, _, _ = G.op_layernorm_res(P_BF16, x, None, None, 0, mul, add, 0, 0, add_one, 1)
+        one, _, _ = G.op_layernorm_res(prec, x, None, None, 0, mul, add, 0, 0, add_one, 1)
     assert torch.equal(xb, x) and guard == [0] * 6
     ref, scale = _ln_ref(x, mul, add, 0, rows, add_one)
     return out, one, ref, scale
@@ -221,7 +223,7 @@ _GUARD_CASES = {"65504": (F16_MAX, True), "-65504": (-F16_MAX, True), "65472": (
 _TAG = 2 | (5 << 4)  # the second LayerNorm of block 5
 
 
-def _guard_run(kernel, rows, offenders, value):
+def _guard_run(kernel, rows, offenders, value, prec=P_BF16):
     """Rows of an in-range stream with `value` formed at one element of each offending row.  Write-back kernels form it as x + y (or
     (x + y) + y2: generic), x = 65440 in the same place of every row; the read-only kernels read it from the stream itself."""
     import gpu_helpers as G
@@ -240,9 +242,10 @@ def _guard_run(kernel, rows, offenders, value):
         br = y2 if ymode == 3 else y
         for r in offenders:
             br[r, col] = value - x[r, col] if math.isfinite(value) else value
-        assert torch.equal(_bf16(br).nan_to_num(), br.nan_to_num())  # the branch values are exact in bf16
+        rnd = _bf16 if prec == P_BF16 else _f16
+        assert torch.equal(rnd(br).nan_to_num(), br.nan_to_num())  # the branch values are exact in the branch type
     with G.knobs(**kn):
-        out, xb, guard = G.op_layernorm_res(P_BF16, x, y, y2, ymode, mul, add, 0, 0, 1, 1, 1, 1, sat_tag=_TAG)
+        out, xb, guard = G.op_layernorm_res(prec, x, y, y2, ymode, mul, add, 0, 0, 1, 1, 1, 1, sat_tag=_TAG)
     return x, y, y2, ymode, out, xb, guard
 
 
@@ -341,6 +344,25 @@ def _rope_table(seq, g):
     return torch.stack([ang.cos(), ang.sin()], dim=-1).float()  # [seq][32][2]
 
 
+def _qknorm_ref(qkv, wq, wk, rope, heads, rope_heads, rpb):
+    """fp64 qk_norm + RoPE of the q and k thirds [rows, 2, heads, 64] and the scale of the fp32 slack."""
+    rows, inner = qkv.shape[0], heads * 64
+    x = qkv[:, :2 * inner].double().reshape(rows, 2, heads, 64)
+    w = torch.stack([wq, wk]).double()[None, :, None, :]
+    rs = 1.0 / torch.sqrt((x * x).mean(-1, keepdim=True) + 1e-6)
+    y = x * rs * w
+    scale = (x.abs().amax(-1, keepdim=True) * rs * w.abs()).expand_as(y).clone()
+    cs = rope.double()[torch.arange(rows) % rpb]  # [rows, 32, 2]
+    c, s = cs[..., 0][:, None, None, :], cs[..., 1][:, None, None, :]
+    yr = y.reshape(rows, 2, heads, 32, 2)
+    a0, a1 = yr[..., 0], yr[..., 1]
+    rot = torch.stack([a0 * c - a1 * s, a1 * c + a0 * s], dim=-1).reshape(rows, 2, heads, 64)
+    ref = y.clone()
+    ref[:, :, :rope_heads] = rot[:, :, :rope_heads]
+    sc = scale.reshape(rows, 2, heads, 32, 2).amax(-1, keepdim=True).expand(rows, 2, heads, 32, 2).reshape(rows, 2, heads, 64) * 2
+    return ref, sc
+
+
 @pytest.mark.parametrize("prec", [P_BF16, P_FP32])
 @pytest.mark.parametrize("heads,rope_heads", [(1, 0), (1, 1), (12, 0), (12, 1), (12, 12), (16, 1), (16, 16)])
 def test_qknorm_rope_against_fp64(heads, rope_heads, prec):
@@ -357,19 +379,7 @@ def test_qknorm_rope_against_fp64(heads, rope_heads, prec):
         qkv = _bf16(qkv)
     out = G.op_qknorm_rope(prec, qkv, heads, rope_heads, rpb, wq, wk, rope)
     assert torch.equal(out[:, 2 * inner:], qkv[:, 2 * inner:]), "the v third changed"
-    x = qkv[:, :2 * inner].double().reshape(rows, 2, heads, 64)
-    w = torch.stack([wq, wk]).double()[None, :, None, :]
-    rs = 1.0 / torch.sqrt((x * x).mean(-1, keepdim=True) + 1e-6)
-    y = x * rs * w
-    scale = (x.abs().amax(-1, keepdim=True) * rs * w.abs()).expand_as(y).clone()
-    cs = rope.double()[torch.arange(rows) % rpb]  # [rows, 32, 2]
-    c, s = cs[..., 0][:, None, None, :], cs[..., 1][:, None, None, :]
-    yr = y.reshape(rows, 2, heads, 32, 2)
-    a0, a1 = yr[..., 0], yr[..., 1]
-    rot = torch.stack([a0 * c - a1 * s, a1 * c + a0 * s], dim=-1).reshape(rows, 2, heads, 64)
-    ref = y.clone()
-    ref[:, :, :rope_heads] = rot[:, :, :rope_heads]
-    sc = scale.reshape(rows, 2, heads, 32, 2).amax(-1, keepdim=True).expand(rows, 2, heads, 32, 2).reshape(rows, 2, heads, 64) * 2
+    ref, sc = _qknorm_ref(qkv, wq, wk, rope, heads, rope_heads, rpb)
     name = f"qknorm {'bf16' if prec == P_BF16 else 'fp32'} heads {heads} rope_heads {rope_heads}"
     _, sums = G.check_rounded(name, out[:, :2 * inner].reshape(rows, 2, heads, 64), ref, sc, prec)
     _bias_check(name, sums)
@@ -381,6 +391,20 @@ def _utterances(B, N, C, g):
     lvl = torch.tensor([0.0, 6.0, -3.0])[:B, None, None]
     sd = torch.tensor([0.5, 2.0, 4.0])[:B, None, None]
     return lvl + sd * torch.randn(B, N, C, generator=g)
+
+
+def _dwconv7_ln_ref(x, wt, cb, lw, lb):
+    """fp64 depthwise conv (7 taps, zero padding inside each utterance) + bias + LayerNorm(eps 1e-6, affine), and the scale of the fp32 slack."""
+    N = x.shape[1]
+    xp = torch.nn.functional.pad(x.double(), (0, 0, 3, 3))  # [B, N + 6, C]: zeros past both ends of each utterance
+    a = cb.double() + sum(xp[:, t:t + N] * wt.double()[t] for t in range(7))
+    mag = cb.double().abs() + sum(xp[:, t:t + N].abs() * wt.double()[t].abs() for t in range(7))
+    mean = a.mean(-1, keepdim=True)
+    d = a - mean
+    rstd = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + 1e-6)
+    ref = d * rstd * lw.double() + lb.double()
+    scale = mag.amax(-1, keepdim=True) * rstd * lw.double().abs() + lb.double().abs()
+    return ref, scale
 
 
 @pytest.mark.parametrize("prec", [P_BF16, P_FP32])
@@ -396,17 +420,20 @@ def test_dwconv7_ln_against_fp64(N, C, prec):
     wt, cb = torch.randn(7, C, generator=g) * 0.4, torch.randn(C, generator=g)
     lw, lb = 1 + 0.3 * torch.randn(C, generator=g), torch.randn(C, generator=g) * 0.5
     out = G.op_dwconv7_ln(prec, x, wt, cb, lw, lb)
-    xp = torch.nn.functional.pad(x.double(), (0, 0, 3, 3))  # [B, N + 6, C]: zeros past both ends of each utterance
-    a = cb.double() + sum(xp[:, t:t + N] * wt.double()[t] for t in range(7))
-    mag = cb.double().abs() + sum(xp[:, t:t + N].abs() * wt.double()[t].abs() for t in range(7))
-    mean = a.mean(-1, keepdim=True)
-    d = a - mean
-    rstd = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + 1e-6)
-    ref = d * rstd * lw.double() + lb.double()
-    scale = mag.amax(-1, keepdim=True) * rstd * lw.double().abs() + lb.double().abs()
+    ref, scale = _dwconv7_ln_ref(x, wt, cb, lw, lb)
     name = f"dwconv7_ln {'bf16' if prec == P_BF16 else 'fp32'} N {N} C {C}"
     _, sums = G.check_rounded(name, out, ref, scale, prec)
     _bias_check(name, sums)
+
+
+def _grn_ref(h, gamma, beta):
+    """fp64 GRN over each utterance's own tokens and the sum of the magnitudes of its terms."""
+    hd = h.double()
+    Gx = torch.sqrt((hd * hd).sum(1, keepdim=True))
+    nx = Gx / (Gx.mean(-1, keepdim=True) + 1e-6)
+    ref = gamma.double() * (hd * nx) + beta.double() + hd
+    scale = (gamma.double() * hd * nx).abs() + beta.double().abs() + hd.abs()
+    return ref, scale
 
 
 @pytest.mark.parametrize("prec", [P_BF16, P_FP32])
@@ -422,17 +449,19 @@ def test_grn_against_fp64(N, C, prec):
         h = _bf16(h)
     gamma, beta = torch.randn(C, generator=g) * 0.5, torch.randn(C, generator=g) * 0.5
     out = G.op_grn(prec, h, gamma, beta)
-    hd = h.double()
-    Gx = torch.sqrt((hd * hd).sum(1, keepdim=True))
-    nx = Gx / (Gx.mean(-1, keepdim=True) + 1e-6)
-    ref = gamma.double() * (hd * nx) + beta.double() + hd
-    scale = (gamma.double() * hd * nx).abs() + beta.double().abs() + hd.abs()
+    ref, scale = _grn_ref(h, gamma, beta)
     name = f"grn {'bf16' if prec == P_BF16 else 'fp32'} N {N} C {C}"
     _, sums = G.check_rounded(name, out, ref, scale * 4, prec)
     _bias_check(name, sums)
 
 
 # ----------------------------------------------------------------------------- RMSNorm (UNetT)
+def _rmsnorm_ref(x, gw):
+    xd = x.double()
+    sc = math.sqrt(x.shape[1]) / torch.sqrt((xd * xd).sum(-1, keepdim=True)).clamp(min=1e-12)
+    return xd * sc * gw.double()
+
+
 @pytest.mark.parametrize("prec", [P_BF16, P_FP32])
 @pytest.mark.parametrize("rows,dim", [(1, 1024), (6, 512), (37, 1024), (7, 100)])
 def test_rmsnorm_against_fp64(rows, dim, prec):
@@ -444,9 +473,7 @@ def test_rmsnorm_against_fp64(rows, dim, prec):
     gw = 1 + 0.3 * torch.randn(dim, generator=g)
     out = G.op_rmsnorm(prec, x, gw)
     assert torch.equal(out[rows // 2], torch.zeros(dim)), "an all-zero row must stay zero"
-    xd = x.double()
-    sc = math.sqrt(dim) / torch.sqrt((xd * xd).sum(-1, keepdim=True)).clamp(min=1e-12)
-    ref = xd * sc * gw.double()
+    ref = _rmsnorm_ref(x, gw)
     name = f"rmsnorm {'bf16' if prec == P_BF16 else 'fp32'} rows {rows} dim {dim}"
     _, sums = G.check_rounded(name, out, ref, ref.abs(), prec)
     _bias_check(name, sums)

@@ -15,6 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_helpers import fp16_ulp
 from oracle import cpu_ref
 
 pytestmark = pytest.mark.gpu
@@ -30,12 +31,6 @@ def _gpu():
 
 def f16r(t):
     return t.half().float()
-
-
-def fp16_ulp(ref):
-    """Spacing of fp16 at |ref| (fp64): 2^(floor(log2 |ref|) - 10), at least the subnormal spacing 2^-24."""
-    _, e = torch.frexp(ref.abs().double())
-    return torch.pow(2.0, (e - 11).clamp(min=-24).double())
 
 
 def check_f16(name, out, ref, scale, extra=None):
@@ -267,13 +262,9 @@ def test_layernorm_fold_site(M, D, N, Kb, epi):
 
 
 # ----------------------------------------------------------------------------- 5. position conv
-@pytest.mark.parametrize("conv31", [1, 0], ids=["halo_tile_kernel", "implicit_gemm"])
-@pytest.mark.parametrize("dim,B,N", [(1024, 2, 70), (1024, 1, 700)])
-def test_position_conv(conv31, dim, B, N):
-    """mish(conv(mish(conv(x)))) with the tuned kernels as dit_eval launches them (the second conv stores its branch): the intermediate
-    activation is an fp16 buffer, so the second conv's reference is taken from the first conv's fp64 result ROUNDED to fp16 -- the bound
-    allows the first conv one ulp of its own: a one-ulp change of an intermediate element moves the output by |w| ulp(c1) (mish' < 1.1)."""
-    import gpu_helpers as G
+def position_conv_case(dim, B, N):
+    """Inputs of mish(conv(mish(conv(x)))) rounded to fp16, its fp64 reference with the intermediate ROUNDED to fp16, the magnitude of the
+    second sum and the propagated term of the intermediate's own ulp (test_position_conv)."""
     g = torch.Generator().manual_seed(dim + N)
     x = f16r(torch.randn(B, N, dim, generator=g))
     cg = dim // 16
@@ -293,9 +284,32 @@ def test_position_conv(conv31, dim, B, N):
     # an intermediate element off by one fp16 ulp (+ its own fp32 slack) moves the second sum by |w1| times that
     d1 = fp16_ulp(m1) + 1.1 * F32_ULPS * s1
     prop, _ = conv(d1, w1.abs(), torch.zeros_like(b1))
+    return (x, w0, b0, w1, b1), ref, 1.1 * s2, 1.1 * prop
+
+
+@pytest.mark.parametrize("conv31", [1, 0], ids=["halo_tile_kernel", "implicit_gemm"])
+@pytest.mark.parametrize("dim,B,N", [(1024, 2, 70), (1024, 1, 700)])
+def test_position_conv(conv31, dim, B, N):
+    """mish(conv(mish(conv(x)))) with the tuned kernels as dit_eval launches them (the second conv stores its branch): the intermediate
+    activation is an fp16 buffer, so the second conv's reference is taken from the first conv's fp64 result ROUNDED to fp16 -- the bound
+    allows the first conv one ulp of its own: a one-ulp change of an intermediate element moves the output by |w| ulp(c1) (mish' < 1.1)."""
+    import gpu_helpers as G
+    args, ref, scale, prop = position_conv_case(dim, B, N)
     with knobs(op_conv_kernel=1, conv31=conv31):
-        out = G.op_conv_pos(P_FP16, x, w0, b0, w1, b1)
-    check_f16(f"conv31={conv31} {(dim, B, N)}", out, ref, 1.1 * s2, extra=1.1 * prop)
+        out = G.op_conv_pos(P_FP16, *args)
+    check_f16(f"conv31={conv31} {(dim, B, N)}", out, ref, scale, extra=prop)
+
+
+@pytest.mark.parametrize("dim,B,N", [(128, 2, 70), (1024, 1, 40)])
+def test_position_conv_untuned(dim, B, N):
+    """op_conv_kernel = 0 (the entry point's default): the GEMM_CONV31 path of the generic tile kernel in fp16 -- the first conv stores its fp16
+    intermediate, the second accumulates into an fp32 buffer, so the output's own fp16 ulp in the bound is an allowance here.  Reference and
+    bound of test_position_conv, its propagated term for the fp16 intermediate included."""
+    import gpu_helpers as G
+    args, ref, scale, prop = position_conv_case(dim, B, N)
+    with knobs(op_conv_kernel=0):
+        out = G.op_conv_pos(P_FP16, *args)
+    check_f16(f"untuned position conv {(dim, B, N)}", out, ref, scale, extra=prop)
 
 
 # ----------------------------------------------------------------------------- 6. / 7. attention
@@ -338,6 +352,23 @@ def test_attention(B, N, H, masked, variant):
     valid = slice(None) if mask is None else mask
     assert torch.isfinite(out).all()
     check_f16(f"attention {(B, N, H, masked)} variant {variant}", out[valid], ref[valid], mag[valid], extra[valid])
+
+
+@pytest.mark.parametrize("B,N,H,masked", [(2, 70, 2, True), (1, 200, 3, False)])
+def test_attention_reference_kernel(B, N, H, masked):
+    """attn_ref_kernel<f16_t> (attention kernel 0 in fp16 mode) against the same element-wise bound.  The reference kernel keeps its
+    numerators in fp32, so the bound's numerator-rounding term is an allowance here, not a requirement."""
+    import gpu_helpers as G
+    g = torch.Generator().manual_seed(N + H)
+    qkv = f16r(torch.randn(B, N, 3, H, 64, generator=g) * 1.5)
+    mask = None
+    if masked:
+        lens = torch.tensor([N, max(1, N - 13)][:B])
+        mask = torch.arange(N)[None, :] < lens[:, None]
+    ref, mag, extra = _attn_ref(qkv, mask)
+    out = G.op_attention(P_FP16, 0, qkv, mask)
+    valid = slice(None) if mask is None else mask
+    check_f16(f"attention reference kernel {(B, N, H, masked)}", out[valid], ref[valid], mag[valid], extra[valid])
 
 
 @pytest.mark.parametrize("variant", [2, 5], ids=["64_queries_per_wave", "pipelined_32_queries_per_wave"])
