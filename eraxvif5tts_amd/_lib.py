@@ -118,6 +118,9 @@ _PROTOS = {
     "f5_vocoder_decode_ragged": (_I, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _I, _P, C.POINTER(C.c_int64), _P]),
     "f5_wave_finish": (_I, [_I, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), _P, C.c_float, _I, _I, _P, _P, _P, _P, _P,
                             C.POINTER(C.c_int64), _P]),
+    "f5_wave_stream_create": (_I, [_I, _I, _P, _P, _P, C.c_float, _I, C.POINTER(_P)]),
+    "f5_wave_stream_push": (_I, [_P, _I, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), _P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "f5_wave_stream_destroy": (_I, [_P]),
     "f5_bigvgan_create": (_I, [C.POINTER(BigVGANConfig), C.POINTER(_P)]),
     "f5_bigvgan_set_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
     "f5_bigvgan_has_tensor": (_I, [_P, C.c_char_p, C.POINTER(C.c_int64)]),

@@ -184,6 +184,12 @@ struct WaveTable {
 // product is taken in double; otherwise fp32.  rms_dev (or null): device scalar, gain applied to every utterance when *rms_dev < target.
 int launch_wave_finish(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n, const double* w_down, const double* w_up,
                        const float* rms_dev, float target, int gain_div, bool f64, float* out_f32, double* out_f64, int16_t* out_pcm, hipStream_t stream);
+// One push of a wave stream (f5_wave_stream_push): the same arithmetic with positions local to the push.  carry_in (or null): n gained fp32 samples,
+// the tail of the utterance before the table's utterance 0, which that utterance's first n samples are cross-faded with; carry_out (or null): receives
+// the last n samples of the table's last utterance, gained, from n extra threads behind pos_end -- another buffer than carry_in.
+int launch_wave_stream(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n, const double* w_down, const double* w_up,
+                       const float* rms_dev, float target, int gain_div, bool f64, const float* carry_in, float* carry_out, float* out_f32,
+                       double* out_f64, int16_t* out_pcm, hipStream_t stream);
 
 // ---- LayerNorm fold (lnfold.hip; gemm.h)
 // per-evaluation-time projection weights W' = fp16(W (1 + scale)) and column constants c1 = rowsum W', c2 = b + W . shift for `evals` times x `depth`

@@ -368,3 +368,111 @@ extern "C" int f5_wave_finish(int B, const float* wave, const int32_t* samples_h
     }
     return 0;
 }
+
+// ---- f5_wave_finish in consecutive pushes (see f5hip.h).  The session holds what one call's wave buffer held for the next joint: the last n samples
+// of the utterance to the left, with their gain applied, in one of two buffers used in alternation (a push reads one and writes the other in the
+// same launch).  Whether the signal is float64 is decided by the whole list (total_utterances, n), so every push of a stream answers in one dtype.
+struct f5_wave_stream_s {
+    int total = 0, n = 0, done = 0, cur = 0;  // utterances of the whole list / taken so far; carry[cur] holds the tail of utterance done - 1
+    int64_t in_total = 0;                     // input samples taken so far (the 2^31 bound is the one-shot call's, over the whole list)
+    bool f64 = false;
+    const double *w_down = nullptr, *w_up = nullptr;
+    const float* rms_dev = nullptr;
+    float target = 0.f;
+    int gain_div = 0;
+    float* carry[2] = {nullptr, nullptr};
+    DevArena arena;
+};
+
+extern "C" int f5_wave_stream_create(int total_utterances, int xfade_samples, const double* w_down, const double* w_up, const float* rms_dev,
+                                     float target_rms, int gain_div, f5_wave_stream_t* out) {
+    if (!out) return f5_fail(F5_EINVAL, "null argument");
+    *out = nullptr;
+    if (total_utterances <= 0 || xfade_samples < 0) return f5_fail(F5_EINVAL, "need total_utterances >= 1 and xfade_samples >= 0");
+    if (rms_dev && !(target_rms > 0.f)) return f5_fail(F5_EINVAL, "target_rms must be positive");
+    F5_TRY(f5_check_device());
+    const int n = (total_utterances >= 2 && xfade_samples > 0) ? xfade_samples : 0;
+    if (n > 0 && (!w_down || !w_up)) return f5_fail(F5_EINVAL, "a cross-fade needs the w_down / w_up tables");
+    f5_wave_stream_s* s = new f5_wave_stream_s();
+    s->total = total_utterances;
+    s->n = n;
+    s->f64 = n > 0;
+    s->w_down = w_down;
+    s->w_up = w_up;
+    s->rms_dev = rms_dev;
+    s->target = target_rms;
+    s->gain_div = gain_div;
+    if (n > 0) {
+        float* both = nullptr;
+        const int rc = s->arena.alloc_t(&both, (size_t)2 * n);
+        if (rc != 0) {
+            delete s;
+            return rc;
+        }
+        s->carry[0] = both;
+        s->carry[1] = both + n;
+    }
+    *out = s;
+    return 0;
+}
+
+extern "C" int f5_wave_stream_destroy(f5_wave_stream_t s) {
+    delete s;  // (the arena's hipFree waits for the pushes still in flight)
+    return 0;
+}
+
+extern "C" int f5_wave_stream_push(f5_wave_stream_t s, int B, const float* wave, const int32_t* samples_host, const float* gain_host,
+                                   const uint8_t* apply_host, float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* emitted,
+                                   f5_stream_t stream) {
+    if (!s || !samples_host || B <= 0) return f5_fail(F5_EINVAL, "null argument or B <= 0");
+    if (B > s->total - s->done) return f5_fail(F5_EINVAL, "%d utterances pushed where %d of the stream's %d are left", B, s->total - s->done, s->total);
+    if (gain_host && !apply_host) return f5_fail(F5_EINVAL, "gain_host needs apply_host");
+    if (gain_host && s->rms_dev) return f5_fail(F5_EINVAL, "give the rms either as host gains or as a device scalar");
+    if (gain_host && !(s->target > 0.f)) return f5_fail(F5_EINVAL, "target_rms must be positive");
+    const int n = s->n;
+    const bool joins = n > 0 && s->done > 0, last = s->done + B == s->total;
+    int64_t in0 = 0, out0 = 0;
+    std::vector<int> vin(B), vout(B);
+    for (int u = 0; u < B; ++u) {
+        const int len = samples_host[u], g = s->done + u;
+        if (len <= 0) return f5_fail(F5_EINVAL, "utterance %d: no samples", g);
+        if (n > 0 && len < ((g == 0 || g == s->total - 1) ? n : 2 * n))
+            return f5_fail(F5_ENOTSUP, "utterance %d (%d samples) is shorter than its cross-fades (%d samples each): the joints chain", g, len, n);
+        vin[u] = (int)in0;
+        vout[u] = (int)out0;
+        in0 += len;
+        out0 += len - ((u + 1 < B || !last) ? n : 0);
+        if (s->in_total + in0 >= (int64_t)1 << 31) return f5_fail(F5_EINVAL, "more than 2^31 samples");
+    }
+    if (emitted) *emitted = out0;
+    if (!out_f32 && !out_f64 && !out_pcm16) return 0;  // "how many would this push emit": nothing is enqueued, the session stays as it is
+    if (!wave) return f5_fail(F5_EINVAL, "null wave");
+    if (s->f64 ? out_f32 != nullptr : out_f64 != nullptr)
+        return f5_fail(F5_EINVAL, "the float result is float64 exactly when the stream cross-fades (out_f32 / out_f64)");
+    F5_TRY(f5_check_device());
+    hipStream_t st = (hipStream_t)stream;
+    const float* carry_in = joins ? s->carry[s->cur] : nullptr;
+    float* carry_out = (n > 0 && !last) ? s->carry[s->cur ^ 1] : nullptr;
+    for (int a = 0; a < B; a += WaveTable::MAXU - 1) {
+        WaveTable tb;
+        const int b = a + WaveTable::MAXU < B ? a + WaveTable::MAXU : B;
+        tb.cnt = b - a;
+        for (int k = a; k < b; ++k) {
+            tb.in0[k - a] = vin[k];
+            tb.len[k - a] = samples_host[k];
+            tb.out0[k - a] = vout[k];
+            tb.gain[k - a] = gain_host ? gain_host[k] : 0.f;
+            tb.apply[k - a] = gain_host ? (apply_host[k] != 0) : 0;
+        }
+        const int first = a == 0 ? 0 : 1;
+        if (first >= tb.cnt) break;
+        const int pos0 = vout[a + first], pos_end = b < B ? vout[b] : (int)out0;
+        F5_TRY(launch_wave_stream(wave, tb, first, pos0, pos_end, n, s->w_down, s->w_up, s->rms_dev, s->target, s->gain_div, s->f64,
+                                  a == 0 ? carry_in : nullptr, b == B ? carry_out : nullptr, out_f32, out_f64, out_pcm16, st));
+        if (b == B) break;
+    }
+    s->done += B;
+    s->in_total += in0;
+    if (carry_out) s->cur ^= 1;
+    return 0;
+}

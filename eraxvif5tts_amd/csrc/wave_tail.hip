@@ -73,3 +73,65 @@ int launch_wave_finish(const float* wave, const WaveTable& tb, int first, int po
     F5_LAUNCH_CHECK();
     return 0;
 }
+
+// The same tail, one push of a stream at a time (f5_wave_stream_push): positions are those of THIS push's output.  Utterance 0 of the push (table
+// with first = 0) joins the session's carry -- the previous push's last n samples, stored with their gain applied, fp32 as wave_gain gives them,
+// so the joint's left operand has the bits the one-shot kernel reads from its wave buffer -- where carry_in is given; the threads behind pos_end
+// (carry_out given: a later push follows) store the last n samples of the table's last utterance into the OTHER carry buffer for that push.
+template <bool F64>
+__global__ __launch_bounds__(256) void wave_stream_kernel(const float* __restrict__ wave, const WaveTable tb, int first, int pos0, int pos_end, int n,
+                                                          const double* __restrict__ w_down, const double* __restrict__ w_up,
+                                                          const float* __restrict__ rms_dev, float target, float inv_target, int gain_div,
+                                                          const float* __restrict__ carry_in, float* __restrict__ carry_out,
+                                                          float* __restrict__ out_f32, double* __restrict__ out_f64, int16_t* __restrict__ out_pcm) {
+#pragma clang fp contract(off)
+    const int pos = pos0 + blockIdx.x * 256 + threadIdx.x;
+    if (pos >= pos_end + (carry_out ? n : 0)) return;
+    const bool dev = rms_dev != nullptr;
+    const float gd = dev ? *rms_dev : 0.f;
+    if (pos >= pos_end) {  // the carry of the next push
+        const int kl = tb.cnt - 1, j = pos - pos_end;
+        carry_out[j] = wave_gain(wave[(size_t)tb.in0[kl] + tb.len[kl] - n + j], dev ? gd : tb.gain[kl], dev ? gd < target : tb.apply[kl] != 0, target,
+                                 inv_target, gain_div);
+        return;
+    }
+    int lo = first, hi = tb.cnt - 1;
+    while (lo < hi) {  // last utterance whose first output sample is at or before pos
+        const int mid = (lo + hi + 1) >> 1;
+        if (tb.out0[mid] <= pos) lo = mid; else hi = mid - 1;
+    }
+    const int k = lo, j = pos - tb.out0[k];
+    const float b = wave_gain(wave[(size_t)tb.in0[k] + j], dev ? gd : tb.gain[k], dev ? gd < target : tb.apply[k] != 0, target, inv_target, gain_div);
+    if constexpr (F64) {
+        double v = (double)b;
+        if (j < n && (k > 0 || carry_in)) {
+            const float a = k > 0 ? wave_gain(wave[(size_t)tb.in0[k - 1] + tb.len[k - 1] - n + j], dev ? gd : tb.gain[k - 1],
+                                              dev ? gd < target : tb.apply[k - 1] != 0, target, inv_target, gain_div)
+                                  : carry_in[j];
+            const double pa = (double)a * w_down[j], pb = (double)b * w_up[j];
+            v = pa + pb;
+        }
+        if (out_f64) out_f64[pos] = v;
+        if (out_pcm) out_pcm[pos] = pcm_sat(v * 32767.0);
+    } else {
+        if (out_f32) out_f32[pos] = b;
+        if (out_pcm) out_pcm[pos] = pcm_sat((double)(b * 32767.0f));
+    }
+}
+
+int launch_wave_stream(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n, const double* w_down, const double* w_up,
+                       const float* rms_dev, float target, int gain_div, bool f64, const float* carry_in, float* carry_out, float* out_f32,
+                       double* out_f64, int16_t* out_pcm, hipStream_t stream) {
+    const int count = pos_end - pos0 + (carry_out ? n : 0);
+    if (count <= 0 || tb.cnt <= 0) return 0;
+    const dim3 grid(cdiv(count, 256));
+    const float inv_target = 1.0f / target;
+    if (f64)
+        hipLaunchKernelGGL(wave_stream_kernel<true>, grid, dim3(256), 0, stream, wave, tb, first, pos0, pos_end, n, w_down, w_up, rms_dev, target, inv_target,
+                           gain_div, carry_in, carry_out, out_f32, out_f64, out_pcm);
+    else
+        hipLaunchKernelGGL(wave_stream_kernel<false>, grid, dim3(256), 0, stream, wave, tb, first, pos0, pos_end, n, w_down, w_up, rms_dev, target, inv_target,
+                           gain_div, carry_in, carry_out, out_f32, out_f64, out_pcm);
+    F5_LAUNCH_CHECK();
+    return 0;
+}

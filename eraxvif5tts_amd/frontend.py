@@ -47,6 +47,11 @@ def _destroy_handles():
     _handles.clear()
 
 
+def mel_frame_count(nw, n_fft=1024, hop_length=256, mel_type="vocos") -> int:
+    """frames `mel_spectrogram` returns for nw samples (no GPU needed: callers plan with it)"""
+    return nw // hop_length + 1 if mel_type == "vocos" else (nw + 2 * ((n_fft - hop_length) // 2) - n_fft) // hop_length + 1
+
+
 @torch.no_grad()
 def mel_spectrogram(wave: torch.Tensor, n_fft=1024, hop_length=256, win_length=1024, n_mel_channels=100, target_sample_rate=24000,
                     mel_type="vocos") -> torch.Tensor:
@@ -58,7 +63,7 @@ def mel_spectrogram(wave: torch.Tensor, n_fft=1024, hop_length=256, win_length=1
     b, nw = w.shape
     dev = _device_index(w)
     mt = {"vocos": _lib.F5_MEL_VOCOS, "bigvgan": _lib.F5_MEL_BIGVGAN}[mel_type]
-    frames = nw // hop_length + 1 if mt == _lib.F5_MEL_VOCOS else (nw + 2 * ((n_fft - hop_length) // 2) - n_fft) // hop_length + 1
+    frames = mel_frame_count(nw, n_fft, hop_length, mel_type)
     out = torch.empty(b, n_mel_channels, frames, device=w.device, dtype=torch.float32)
     with torch.cuda.device(dev):
         _lib.check(lib.f5_frontend_mel(_handle(dev, n_fft, hop_length, win_length, n_mel_channels, target_sample_rate, mt), b, nw, _lib.ptr(w),

@@ -31,8 +31,8 @@ from ..model import CFM
 from ..model import backbones as _backbones
 from ..model.utils import convert_char_to_pinyin, get_tokenizer, list_str_to_idx
 from . import audio as _audio
-from .utils_infer import (DEFAULT_VOCAB, chunk_text, cross_fade_concat, decode_utterances, device_tail_kind, finish_waves, load_checkpoint, load_vocoder,
-                          mel_rows_of)
+from .utils_infer import (DEFAULT_VOCAB, WaveStream, chunk_groups, chunk_text, cross_fade_concat, decode_utterances, device_tail_kind, finish_waves,
+                          load_checkpoint, load_vocoder, mel_rows_of)
 
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs")
 
@@ -112,6 +112,9 @@ class F5TTSWrapper:
         # (0 = off: chunks run one per stream as above).  Applies when every chunk has at least 256 frames (the row count from which a batch-1
         # call takes the tuned kernels too, so both paths compute bit-identical mels).
         self.ragged_chunks = int(os.environ.get("F5HIP_RAGGED_CHUNKS", "8"))
+        # generate_stream(): the first `stream_first_chunks` text chunks form the first piece (1: the first audio waits for one utterance only);
+        # the rest follows in groups of up to `ragged_chunks`.  Not a constructor argument either; set the attribute or F5HIP_STREAM_FIRST
+        self.stream_first_chunks = int(os.environ.get("F5HIP_STREAM_FIRST", "1"))
         # "cpu": draw every chunk's initial noise from torch's CPU generator, in chunk order -- the numbers the reference's CPU path draws after
         # the same torch.manual_seed (reference model/cfm.py:178-183 with device = cpu); None = on the GPU, as the reference's GPU path does
         self.model.noise_device = os.environ.get("F5HIP_NOISE_DEVICE") or None
@@ -181,6 +184,14 @@ class F5TTSWrapper:
                  return_numpy: bool = False, return_spectrogram: bool = False, return_pcm16: bool = False):
         """``return_pcm16``: the wave comes back as the int16 PCM the streaming server sends (``streaming.wire.pcm16_bytes`` of the float
         result, bit for bit), converted on the device where the device tail runs -- one int16 copy instead of a float copy and a host pass."""
+        (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs = self._plan_jobs(
+            text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
+        return self._generate_jobs(jobs, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration, return_numpy,
+                                   return_spectrogram, return_pcm16)
+
+    def _plan_jobs(self, text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor):
+        """The host work of generate() / generate_stream() before any sampling: the arguments' defaults, the text cut into chunks, and per chunk
+        the token list and the frames asked for (duration rule or predictor) -- the ``jobs`` list."""
         if self.ref_audio_processed is None or self.ref_text is None:
             raise ValueError("Reference audio not preprocessed. Call preprocess_reference() first.")
         nfe_step = nfe_step if nfe_step is not None else self.nfe_step
@@ -199,12 +210,6 @@ class F5TTSWrapper:
             print(f"Text batch {i}: {text_batch}")
         print("\n")
 
-        generated_waves, spectrograms = [], []
-        # The text chunks of one call are independent (the reference samples them one after the other, :476-533).  Here up to `chunk_streams`
-        # of them are in flight at once, each on a HIP stream (and a libf5hip plan) of its own: a single-utterance sample() fills a fraction
-        # of the 256 CUs, so the streams overlap.  Every chunk runs exactly the launches of the serial path -- same shapes, same kernels --
-        # so its mel is bit-identical to the serial result; noise is drawn in chunk order either way.
-        transformer = getattr(self.model, "transformer", None)
         jobs = []  # (token list, frames asked for) per chunk -- host work of the reference's loop (:476-510), before any sampling
         for i, text_batch in enumerate(text_batches):
             local_speed = 0.3 if len(text_batch.encode("utf-8")) < 10 else speed
@@ -225,7 +230,16 @@ class F5TTSWrapper:
                 duration = self.ref_audio_len + int(self.ref_audio_len / ref_text_len * gen_text_len / local_speed)
                 print(f"Calculated duration based on text ratio: {duration} frames")
             jobs.append((final_text_list, int(duration)))
+        return (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs
 
+    def _sample_jobs(self, jobs, nfe_step, cfg_strength, sway_sampling_coef):
+        """The mels of these jobs, in order, by the sampler their list calls for: ragged when the backbone is the DiT and there are at least 2 jobs,
+        all of at least 256 and at most 4096 frames; otherwise sample() per job, up to `chunk_streams` of them in flight."""
+        transformer = getattr(self.model, "transformer", None)
+        # The text chunks of one call are independent (the reference samples them one after the other, :476-533).  Here up to `chunk_streams`
+        # of them are in flight at once, each on a HIP stream (and a libf5hip plan) of its own: a single-utterance sample() fills a fraction
+        # of the 256 CUs, so the streams overlap.  Every chunk runs exactly the launches of the serial path -- same shapes, same kernels --
+        # so its mel is bit-identical to the serial result; noise is drawn in chunk order either way.
         # Several chunks, each long enough for the tuned kernels: ONE ragged batch per group of chunks -- the utterances concatenated along the
         # token axis, no padding to a common length, every chunk with the arithmetic of its own batch-1 call (bit-identical mels, same noise
         # order).  A single-utterance sample() fills a fraction of the 256 CUs; the concatenation fills them.
@@ -233,23 +247,15 @@ class F5TTSWrapper:
                   and getattr(transformer, "BACKBONE", None) == 0 and min(d for _, d in jobs) >= 256 and max(d for _, d in jobs) <= 4096)
         n_streams = 1
         if not ragged and torch.cuda.is_available() and hasattr(transformer, "finish_pending"):
-            n_streams = max(1, min(len(text_batches), int(self.chunk_streams)))
+            n_streams = max(1, min(len(jobs), int(self.chunk_streams)))
         main = torch.cuda.current_stream() if n_streams > 1 else None
         streams = self._chunk_stream_pool(n_streams) if n_streams > 1 else []
         for st in streams:
             st.wait_stream(main)  # the preprocessed prompt was produced on the caller's stream
         mels = []
         if ragged:
-            group, rows = [], 0
-            groups = [group]
-            for job in jobs:
-                if group and (len(group) >= int(self.ragged_chunks) or rows + job[1] > 16384):
-                    group, rows = [], 0
-                    groups.append(group)
-                group.append(job)
-                rows += job[1]
             with torch.inference_mode():
-                for group in groups:
+                for group in ([jobs[i] for i in idx] for idx in chunk_groups([d for _, d in jobs], 0, int(self.ragged_chunks))):
                     mels += self.model.sample_ragged(self.ref_audio_processed, [j[0][0] for j in group], [j[1] for j in group], steps=nfe_step,
                                                      cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
         for i, (final_text_list, duration) in enumerate(jobs if not ragged else []):
@@ -270,13 +276,19 @@ class F5TTSWrapper:
             # decoded mels that were still being written -- found by test_generate_end_to_end_matches_the_oracle_chain[fp32-False])
             for st in streams:
                 main.wait_stream(st)
+            with torch.inference_mode():
+                for generated in mels:
+                    generated.record_stream(main)
+        return mels
+
+    def _generate_jobs(self, jobs, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration, return_numpy, return_spectrogram,
+                       return_pcm16):
+        generated_waves, spectrograms = [], []
+        mels = self._sample_jobs(jobs, nfe_step, cfg_strength, sway_sampling_coef)
         want_spec = return_spectrogram or output_path is not None
         want_float = not return_pcm16 or output_path is not None
         final_wave = final_pcm = None
         with torch.inference_mode():
-            if n_streams > 1:
-                for generated in mels:
-                    generated.record_stream(main)
             # The tail on the device where the vocoder is one of ours: the mels of all chunks go to ONE ragged vocoder call (the prompt frames
             # skipped by a row offset, no permute copy), then one wave_finish (rms rule decided on the device from the device-resident prompt,
             # cross-fade, PCM) and one copy to the host.  Byte-identical to the per-chunk loop below, which foreign vocoder objects keep.
@@ -332,6 +344,61 @@ class F5TTSWrapper:
         if return_spectrogram:
             return final_wave, self.target_sample_rate, combined_spectrogram
         return final_wave, self.target_sample_rate
+
+    def generate_stream(self, text: str, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
+                        sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
+                        cross_fade_duration: Optional[float] = None, use_duration_predictor: Optional[bool] = None,
+                        return_numpy: bool = True, return_spectrogram: bool = False, return_pcm16: bool = False):
+        """generate() as a generator of ``(piece, sample_rate)``: the audio of each group of text chunks as soon as it is final, cross-fades
+        included.  The pieces, concatenated, are byte for byte what ``generate()`` returns for the same arguments after the same
+        ``torch.manual_seed`` (float of the same dtype -- float64 in EVERY piece when chunks are cross-faded -- or int16 with ``return_pcm16``).
+        The first ``stream_first_chunks`` chunks form the first piece, the rest follows in groups of up to ``ragged_chunks`` chunks and 16384
+        frames (`utils_infer.chunk_groups`); per group one sampler call, one ragged vocoder call, one push into the wave tail's stream session
+        (``f5_wave_stream_push``: the joint's left side is carried from the previous group) and one copy to the host.  Nothing of group g + 1
+        starts before group g has been handed out.
+
+        The streamed tail applies when the vocoder is one of the HIP vocoders, the prompt is on the GPU, every chunk has at least 2 generated
+        frames and no cross-fade reaches into another (`plan_wave_tail`'s ``device_ok``); this is decided before any sampling, and otherwise
+        the generator yields exactly once, with what ``generate()`` returns.  With attention dropout on, a ragged sampler call does not promise
+        the bits of its batch-1 calls, so the byte-equality with ``generate()`` holds for dropout off only.  ``return_numpy`` and
+        ``return_spectrogram`` are accepted for the signature's sake: a piece is always an array, and no spectrogram is streamed.  Closing the
+        generator early frees the session and leaves the wrapper as it was."""
+        (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs = self._plan_jobs(
+            text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
+        frames = self._generated_frames(jobs)
+        kind = device_tail_kind(self.vocoder, self.ref_audio_processed)
+        session = None
+        if kind is not None and kind == self.mel_spec_type and frames and min(frames) >= 2:
+            samples = [(t - 1) * self.hop_length for t in frames] if kind == "vocos" else [t * self.vocoder._total_up() for t in frames]
+            with torch.inference_mode():
+                rms = torch.sqrt(torch.mean(torch.square(self.ref_audio_processed)))  # of the stored, already boosted prompt (:529-531)
+                session = WaveStream(samples, cross_fade_duration, self.target_sample_rate, rms=rms.to(torch.float32), target_rms=self.target_rms,
+                                     want_float=not return_pcm16, want_pcm16=return_pcm16)
+        if session is None or not session.ok:
+            wave, rate = self._generate_jobs(jobs, None, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration, True, False, return_pcm16)
+            yield wave, rate
+            return
+        try:
+            first = 0
+            for group in chunk_groups([d for _, d in jobs], int(self.stream_first_chunks), int(self.ragged_chunks)):
+                mels = self._sample_jobs([jobs[i] for i in group], nfe_step, cfg_strength, sway_sampling_coef)
+                with torch.inference_mode():
+                    rows, row_start, got = mel_rows_of(mels, self.ref_audio_len)
+                    if got != frames[first: first + len(group)]:
+                        raise RuntimeError(f"the sampler returned {got} generated frames where {frames[first: first + len(group)]} were planned")
+                    wave_buf, counts = decode_utterances(self.vocoder, kind, rows, row_start, got)
+                    signal, pcm = session.push(wave_buf, counts)
+                    piece = (pcm if return_pcm16 else signal).cpu().numpy()
+                first += len(group)
+                yield piece, self.target_sample_rate
+        finally:
+            session.close()
+
+    def _generated_frames(self, jobs):
+        """Frames each job's sample() call generates behind the prompt, from the host values alone: the sampler raises the frames asked for to
+        one more than the longer of the text and the prompt's mel, and caps them at 4096 (model/cfm.py)."""
+        cond_frames = self.model.mel_spec.frame_count(self.ref_audio_processed.shape[-1])
+        return [min(max(max(len(tokens[0]), cond_frames) + 1, duration), 4096) - self.ref_audio_len for tokens, duration in jobs]
 
     def _chunk_stream_pool(self, n):
         pool = getattr(self, "_chunk_streams_pool", None) or []

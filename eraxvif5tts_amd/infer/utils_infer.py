@@ -218,25 +218,10 @@ def _xfade_weights(n, dev):
     return _xfade_tables[key]
 
 
-def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_sample_rate, rms=None, target_rms=target_rms, want_float=True,
-                 want_pcm16=False, gain_divide=False):
-    """``f5_wave_finish`` over the utterances held back to back in ``wave`` (fp32, on the GPU; ``samples[i]`` each): the rms rule, the linear
-    cross-fade of `cross_fade_concat` and the int16 PCM of ``streaming.wire.pcm16_bytes`` in one kernel.  Returns ``(signal, pcm16)`` as device
-    tensors (None where not asked for) -- ``signal`` float64 when a joint mixed, float32 otherwise, as numpy's promotion gives -- or ``None`` when
-    the library answers F5_ENOTSUP (utterances shorter than their cross-fades: take the host functions for that call).
-    ``rms``: None (no gain); a 0-dim fp32 tensor on the GPU (the gain applies when ``rms < target_rms``, decided on the device: no host wait);
-    or host values -- one number / 0-dim CPU tensor for all utterances, or one per utterance -- with the decision ``rms_i < target_rms`` taken
-    here exactly as the host loop takes it.  The gain is ``w * rms / target_rms`` as torch evaluates it on a GPU tensor (fp32 product, then the
-    fp32 reciprocal of the host scalar), or with a true fp32 divide (``gain_divide``: torch on CPU tensors)."""
+def _rms_forms(rms, B, target_rms):
+    """The rms rule in the forms the library takes (`finish_waves` documents ``rms``): ``(gain_host, apply_host, rms_dev)``, ctypes arrays of B
+    host gains with the decision ``rms_i < target_rms`` taken here exactly as the host loop takes it, or the device scalar; all None: no gain."""
     import ctypes as C
-
-    from .. import _lib
-    lib = _lib.load()
-    B = len(samples)
-    assert wave.is_cuda and wave.dtype == torch.float32 and wave.is_contiguous() and wave.numel() == sum(samples) and B >= 1
-    plan = plan_wave_tail(samples, cross_fade_duration, sample_rate)
-    n, mixed = plan["n"], plan["n"] > 0
-    total = sum(samples) - (B - 1) * n
     gain_host = apply_host = rms_dev = None
     if torch.is_tensor(rms) and rms.is_cuda:
         assert rms.dtype == torch.float32 and rms.numel() == 1
@@ -256,6 +241,29 @@ def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_samp
             return bool(r < target_rms)
         gain_host = (C.c_float * B)(*vals)
         apply_host = (C.c_uint8 * B)(*[1 if below_target(r, v) else 0 for r, v in zip(per_utt, vals)])
+    return gain_host, apply_host, rms_dev
+
+
+def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_sample_rate, rms=None, target_rms=target_rms, want_float=True,
+                 want_pcm16=False, gain_divide=False):
+    """``f5_wave_finish`` over the utterances held back to back in ``wave`` (fp32, on the GPU; ``samples[i]`` each): the rms rule, the linear
+    cross-fade of `cross_fade_concat` and the int16 PCM of ``streaming.wire.pcm16_bytes`` in one kernel.  Returns ``(signal, pcm16)`` as device
+    tensors (None where not asked for) -- ``signal`` float64 when a joint mixed, float32 otherwise, as numpy's promotion gives -- or ``None`` when
+    the library answers F5_ENOTSUP (utterances shorter than their cross-fades: take the host functions for that call).
+    ``rms``: None (no gain); a 0-dim fp32 tensor on the GPU (the gain applies when ``rms < target_rms``, decided on the device: no host wait);
+    or host values -- one number / 0-dim CPU tensor for all utterances, or one per utterance -- with the decision ``rms_i < target_rms`` taken
+    here exactly as the host loop takes it.  The gain is ``w * rms / target_rms`` as torch evaluates it on a GPU tensor (fp32 product, then the
+    fp32 reciprocal of the host scalar), or with a true fp32 divide (``gain_divide``: torch on CPU tensors)."""
+    import ctypes as C
+
+    from .. import _lib
+    lib = _lib.load()
+    B = len(samples)
+    assert wave.is_cuda and wave.dtype == torch.float32 and wave.is_contiguous() and wave.numel() == sum(samples) and B >= 1
+    plan = plan_wave_tail(samples, cross_fade_duration, sample_rate)
+    n, mixed = plan["n"], plan["n"] > 0
+    total = sum(samples) - (B - 1) * n
+    gain_host, apply_host, rms_dev = _rms_forms(rms, B, target_rms)
     w_down, w_up = _xfade_weights(n, wave.device) if mixed else (None, None)
     if total <= 0 or not plan["device_ok"]:
         out = pcm = None  # the library decides (and says why); nothing is allocated for a call it will refuse
@@ -271,6 +279,110 @@ def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_samp
     _lib.check(rc, "wave_finish")
     assert got.value == total
     return out, pcm
+
+
+# ---------------------------------------------------------------------------- the same tail, group by group (generate_stream)
+def chunk_groups(durations, first=0, group_max=8, max_rows=16384):
+    """Cut chunks of these frame counts, in order, into groups of consecutive indices: the first ``first`` chunks form group 0 (``first`` <= 0: no
+    such group), the rest goes into groups of at most ``group_max`` chunks and ``max_rows`` frames (a chunk longer than that stands alone) --
+    with ``first = 0`` the groups one ragged sampler call each takes in `F5TTSWrapper.generate`.  A pure function of the durations."""
+    durations = [int(d) for d in durations]
+    group_max = max(1, int(group_max))
+    head = min(max(int(first), 0), len(durations))
+    groups = [list(range(head))] if head else []
+    group, rows = [], 0
+    for i in range(head, len(durations)):
+        if group and (len(group) >= group_max or rows + durations[i] > max_rows):
+            groups.append(group)
+            group, rows = [], 0
+        group.append(i)
+        rows += durations[i]
+    if group:
+        groups.append(group)
+    return groups
+
+
+def stream_emitted_counts(lengths, group_sizes, cross_fade_duration, sample_rate=target_sample_rate):
+    """Output samples each push of a `WaveStream` over waves of these ``lengths`` emits when the list is pushed in consecutive groups of
+    ``group_sizes`` utterances: a push that ends before the last utterance emits up to where the next utterance's first sample lands
+    (`plan_wave_tail`'s ``out_offsets``), the last push the rest.  Returns ``(counts, dtype)``; the counts sum to the plan's ``total`` and the
+    dtype is the whole result's -- float64 when any joint mixes, for EVERY piece, float32 otherwise."""
+    plan = plan_wave_tail(lengths, cross_fade_duration, sample_rate)
+    assert sum(group_sizes) == len(lengths) and all(g >= 1 for g in group_sizes)
+    bounds = plan["out_offsets"] + [plan["total"]]
+    counts, k = [], 0
+    for g in group_sizes:
+        counts.append(bounds[k + g] - bounds[k])
+        k += g
+    return counts, plan["dtype"]
+
+
+class WaveStream:
+    """`finish_waves` in consecutive pushes (``f5_wave_stream_*``): ``samples`` lists the sample counts of ALL utterances up front -- they follow
+    from the frame counts, before any sampling -- and ``push(wave, samples)`` hands over the next few, back to back in one fp32 GPU buffer.  The
+    pieces, concatenated, are byte-identical to ``finish_waves`` over the whole list; every piece has the whole result's dtype.  ``rms``: None, a
+    0-dim fp32 GPU tensor, one host value, or one host value per utterance of the whole list.  ``ok`` is False when the library would refuse
+    the list (`plan_wave_tail`'s ``device_ok``): then nothing is created and the caller keeps its one-shot route.  ``close()`` frees the session."""
+
+    def __init__(self, samples, cross_fade_duration=0.0, sample_rate=target_sample_rate, rms=None, target_rms=target_rms, want_float=True,
+                 want_pcm16=False, gain_divide=False):
+        import ctypes as C
+
+        from .. import _lib
+        self.samples = [int(x) for x in samples]
+        self.plan = plan_wave_tail(self.samples, cross_fade_duration, sample_rate)
+        self.n, self.mixed = self.plan["n"], self.plan["n"] > 0
+        self.ok = bool(self.plan["device_ok"]) and min(self.samples) > 0
+        assert want_float or want_pcm16
+        self.want_float, self.want_pcm16, self.done, self._handle = want_float, want_pcm16, 0, None
+        self._gain_host, self._apply_host, self._rms_dev = _rms_forms(rms, len(self.samples), target_rms)
+        if not self.ok:
+            return
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self._tables = _xfade_weights(self.n, dev) if self.mixed else (None, None)  # (kept alive with the session, which reads them in every push)
+        handle = C.c_void_p()
+        _lib.check(_lib.load().f5_wave_stream_create(len(self.samples), int(self.n), _lib.ptr(self._tables[0]), _lib.ptr(self._tables[1]),
+                                                    _lib.ptr(self._rms_dev), float(target_rms), 1 if gain_divide else 0, C.byref(handle)),
+                   "wave_stream_create")
+        self._handle = handle
+
+    def push(self, wave, samples):
+        """The next ``len(samples)`` utterances -> ``(signal_or_None, pcm_or_None)`` device tensors holding what has become final."""
+        import ctypes as C
+
+        from .. import _lib
+        lib = _lib.load()
+        B, k = len(samples), self.done
+        samples = [int(x) for x in samples]
+        assert self._handle is not None, "the stream is closed, or its utterances chain (ok is False)"
+        assert B >= 1 and samples == self.samples[k: k + B], "a push takes the next utterances of the list given at construction"
+        assert wave.is_cuda and wave.dtype == torch.float32 and wave.is_contiguous() and wave.numel() == sum(samples)
+        arr = (C.c_int32 * B)(*samples)
+        gains = (C.c_float * B)(*self._gain_host[k: k + B]) if self._gain_host is not None else None
+        applies = (C.c_uint8 * B)(*self._apply_host[k: k + B]) if self._apply_host is not None else None
+        got = C.c_int64(0)
+        _lib.check(lib.f5_wave_stream_push(self._handle, B, None, arr, gains, applies, None, None, None, C.byref(got), None), "wave_stream_push")
+        count = got.value
+        # (a zero-sized tensor has no address, and a push without outputs is the question above: one element at least, cut off below)
+        out = torch.empty(max(count, 1), device=wave.device, dtype=torch.float64 if self.mixed else torch.float32) if self.want_float else None
+        pcm = torch.empty(max(count, 1), device=wave.device, dtype=torch.int16) if self.want_pcm16 else None
+        _lib.check(lib.f5_wave_stream_push(self._handle, B, _lib.ptr(wave), arr, gains, applies, _lib.ptr(out) if not self.mixed else None,
+                                           _lib.ptr(out) if self.mixed else None, _lib.ptr(pcm), C.byref(got), _lib.stream_ptr()), "wave_stream_push")
+        assert got.value == count
+        self.done += B
+        return (out[:count] if out is not None else None), (pcm[:count] if pcm is not None else None)
+
+    def close(self):
+        if self._handle is not None:
+            from .. import _lib
+            _lib.load().f5_wave_stream_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
 
 
 def device_tail_kind(vocoder, *tensors):

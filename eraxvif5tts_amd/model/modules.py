@@ -50,6 +50,11 @@ class MelSpec(nn.Module):
         self.n_mel_channels, self.target_sample_rate = n_mel_channels, target_sample_rate
         self.register_buffer("dummy", torch.tensor(0), persistent=False)
 
+    def frame_count(self, nw):
+        """frames `forward` returns for a wave of nw samples"""
+        from ..frontend import mel_frame_count
+        return mel_frame_count(int(nw), self.n_fft, self.hop_length, "vocos" if self.extractor is get_vocos_mel_spectrogram else "bigvgan")
+
     def forward(self, wav):
         return self.extractor(wav, n_fft=self.n_fft, n_mel_channels=self.n_mel_channels, target_sample_rate=self.target_sample_rate,
                               hop_length=self.hop_length, win_length=self.win_length)

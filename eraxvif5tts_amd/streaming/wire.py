@@ -98,12 +98,39 @@ def _offers_pcm16(model) -> bool:
         return False
 
 
-def stream_audio(model, cache: ReferenceCache, speaker: str, text_chunks: Iterable[str], **gen_kwargs) -> Iterator[bytes]:
-    """WAV header (unknown size) then one PCM block per synthesised chunk; the wrapper's reference state is always cleared."""
+def _clean_chunk(chunk_text: str) -> str:
+    chunk_text = chunk_text.strip()
+    if chunk_text.endswith(".."):
+        chunk_text = chunk_text[:-1].strip()
+    return chunk_text
+
+
+def process_chunk_pieces(chunk_text: str, model, **gen_kwargs) -> Iterator[bytes]:
+    """`process_chunk` over ``model.generate_stream``: the same bytes, handed out group by group as the model finishes them."""
+    chunk_text = _clean_chunk(chunk_text)
+    if not chunk_text:
+        return
+    pieces = model.generate_stream(text=chunk_text, return_pcm16=True, **gen_kwargs)
+    try:
+        for pcm, _sr in pieces:
+            if pcm is not None and np.size(pcm):
+                yield np.ascontiguousarray(pcm, dtype=np.int16).tobytes()
+    finally:
+        pieces.close()
+
+
+def stream_audio(model, cache: ReferenceCache, speaker: str, text_chunks: Iterable[str], stream_groups: bool = False, **gen_kwargs) -> Iterator[bytes]:
+    """WAV header (unknown size) then one PCM block per synthesised chunk; the wrapper's reference state is always cleared.
+    ``stream_groups=True`` with a model that has ``generate_stream`` (duck-typed): each text chunk's pieces are sent as they come -- the same
+    bytes in more blocks, the first of them after one utterance's work.  Any other model keeps the one block per text chunk."""
     cache.install(model, speaker)
     try:
         yield create_wave_header(sample_rate=model.target_sample_rate, data_size=0)
+        grouped = stream_groups and callable(getattr(model, "generate_stream", None))
         for chunk in text_chunks:
+            if grouped:
+                yield from process_chunk_pieces(chunk, model, **gen_kwargs)
+                continue
             data = process_chunk(chunk, model, **gen_kwargs)
             if data:
                 yield data

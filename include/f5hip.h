@@ -432,6 +432,37 @@ F5_API int f5_vocoder_decode_ragged(f5_vocoder_t v, int B, const int32_t* row_st
 F5_API int f5_wave_finish(int B, const float* wave, const int32_t* samples_host, const float* gain_host, const uint8_t* apply_host,
                           const float* rms_dev, float target_rms, int gain_div, int xfade_samples, const double* w_down, const double* w_up,
                           float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* total_samples_out, f5_stream_t stream);
+/* f5_wave_finish in consecutive pushes: a caller that decodes its utterances group by group gets every output sample as soon as it is final.
+ * For EVERY way of cutting an utterance list into consecutive pushes, the emitted pieces, concatenated, are byte-identical to one f5_wave_finish
+ * over the whole list (float and PCM): the same kernel arithmetic, tables and saturation rule.
+ *   create   total_utterances = length of the whole list, known up front; xfade_samples, w_down / w_up, rms_dev, target_rms, gain_div as for
+ *            f5_wave_finish.  The device arrays (w_down, w_up, rms_dev) are read by every push and stay the caller's: keep them alive until destroy.
+ *            n = xfade_samples when total_utterances >= 2, else 0.  float64 or float32 is a property of the WHOLE STREAM, not of a push: with
+ *            n > 0 every push emits float64 and forms its PCM from the fp64 product -- also a first push of one utterance that mixes nothing
+ *            itself (in the one-shot result that utterance is float64 too) -- and with n = 0 everything is float32 and nothing is carried.
+ *   push     the next B utterances of the list, back to back in wave (dev f32), samples_host[B]; gain_host / apply_host as for f5_wave_finish
+ *            (per utterance of this push; not together with a rms_dev given at create).  Emits the joint with the carried tail of the previous
+ *            push, then everything of these B utterances except the last n samples of the last one, which are carried (with their gain applied)
+ *            for the next push; the push that completes total_utterances emits its own tail too.  *emitted (host) = sum samples - (B - 1) n,
+ *            minus n unless this push is the last: computed from the extents alone.  out_f32 / out_f64 / out_pcm16 [*emitted]: which float output
+ *            must be NULL follows f5_wave_finish (out_f32 when n > 0, out_f64 when n = 0).  With ALL THREE outputs NULL a push only answers
+ *            *emitted (and judges the extents): nothing is enqueued and the session does not advance, so a caller can size its buffers and push
+ *            the same utterances again.  A push of one utterance of exactly n samples emits 0 samples and still carries: give it a non-NULL
+ *            output pointer.
+ *            The carry belongs to the session: once a push is enqueued the caller may overwrite or free its wave buffer, in stream order; the
+ *            next push does not read it.  All pushes of a session go to one stream (or are ordered by the caller).
+ *   extents  the chaining rule of f5_wave_finish over the WHOLE list: the first and the last utterance hold at least n samples, every other 2 n;
+ *            a push that breaks it answers F5_ENOTSUP.  F5_EINVAL: more utterances than the stream has left, samples <= 0, a total (over all
+ *            pushes) reaching 2^31 samples.  A refused push leaves the session unchanged.
+ * More utterances than one kernel table holds are split into tables that overlap by one utterance, as in f5_wave_finish.  Nothing synchronises;
+ * destroy frees the carry (and thereby waits for the device). */
+typedef struct f5_wave_stream_s* f5_wave_stream_t;
+F5_API int f5_wave_stream_create(int total_utterances, int xfade_samples, const double* w_down, const double* w_up, const float* rms_dev,
+                                 float target_rms, int gain_div, f5_wave_stream_t* out);
+F5_API int f5_wave_stream_push(f5_wave_stream_t s, int B, const float* wave, const int32_t* samples_host, const float* gain_host,
+                               const uint8_t* apply_host, float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* emitted,
+                               f5_stream_t stream);
+F5_API int f5_wave_stream_destroy(f5_wave_stream_t s);
 /* ISTFT head alone (for the roofline measurement): spec dev f32 [B, T, n_fft+2] (head.out activations:
  * log-magnitude | phase) -> wave dev f32 [B, (T-1)*hop] */
 F5_API int f5_vocoder_istft_head(f5_vocoder_t v, int B, int T, const float* head_out, float* wave, f5_stream_t stream);
