@@ -128,6 +128,8 @@ _PROTOS = {
     "f5_bigvgan_destroy": (_I, [_P]),
     "f5_bigvgan_forward": (_I, [_P, _I, _I, _P, _P, _P]),
     "f5_bigvgan_decode_ragged": (_I, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _I, _P, C.POINTER(C.c_int64), _P]),
+    "f5_op_bigvgan_snake": (_I, [_I, _I, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
+    "f5_op_bigvgan_snake_ragged": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
     "f5_frontend_create": (_I, [C.POINTER(MelConfig), C.POINTER(_P)]),
     "f5_frontend_destroy": (_I, [_P]),
     "f5_frontend_mel": (_I, [_P, _I, _I, _P, _P, _P]),

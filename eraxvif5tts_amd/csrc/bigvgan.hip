@@ -2,7 +2,8 @@
 // third-party checkout (`third_party.BigVGAN.bigvgan.BigVGAN.from_pretrained("nvidia/bigvgan_v2_24khz_100band_256x")`, remove_weight_norm()) and
 // infer/f5tts_wrapper.py:526 / eval/eval_infer_batch.py:189 call `vocoder(mel)`.
 //
-// PARITY UNPINNED: that checkout is ABSENT from the reference tree, no checkpoint exists offline and no reference test covers it.  The architecture
+// PARITY UNPINNED: that checkout is ABSENT from the reference tree, no checkpoint exists offline and no reference test covers it.  (Pinned instead:
+// every kernel against the oracle's restatement at every width of the published model, tests/test_gpu_bigvgan_widths.py.)  The architecture
 // is restated from the published BigVGAN-v2 source as recalled (oracle: oracle/cpu_ref.py bigvgan_forward, which the tests compare this file with):
 //   conv_pre Conv1d(mels -> C0, k 7)
 //   per stage i:  ConvTranspose1d(C -> C / 2, k_i, stride u_i, padding (k_i - u_i) / 2), then the MEAN of num_kernels AMPBlock1(C / 2, kernel, dilations):
@@ -12,7 +13,8 @@
 //   AA-snake -> conv_post Conv1d(C -> 1, k 7, optional bias) -> clamp(-1, 1) or tanh.
 //
 // MI355X form: activations are TIME-major [T, C] fp32 (rows = time: every Conv1d is an im2col + GEMM on the fp32-input MFMA tile kernel, exact fp32
-// products; the transposed convolution is a polyphase GEMM: k = R u, so every output sample takes R input frames, one GEMM of N = u x C_out);
+// products; the transposed convolution is a polyphase GEMM: k = R u, so every output sample takes R input frames, one GEMM of N = u x C_out;
+// R <= 3 so that T + 1 gather rows suffice, f5_bigvgan_create refuses a longer kernel);
 // the anti-aliased activation is ONE kernel (a 32-step x 32/64-channel tile staged in LDS: up-sampling, snake and down-sampling never touch HBM);
 // the residual add of a block's second convolution rides in the GEMM epilogue (EPI_RESID).
 //
@@ -273,6 +275,9 @@ extern "C" int f5_bigvgan_create(const f5_bigvgan_config* c, f5_bigvgan_t* out) 
     for (int i = 0; i < c->num_upsamples; ++i) {
         const int u = c->upsample_rates[i], k = c->upsample_kernel_sizes[i];
         if (u <= 0 || k < u || k % u != 0 || ((k - u) & 1)) return f5_fail(F5_ENOTSUP, "upsample stage %d: kernel %d / rate %d (kernel must be a multiple of the rate, k - u even)", i, k, u);
+        // the scatter reads tmp row (p + pad) / u <= T + (pad - 1) / u; the gather, the GEMM and the workspace provide rows 0 .. T only, which covers
+        // pad = (k - u) / 2 <= u, that is k <= 3u (every published config has k = 2u)
+        if (k > 3 * u) return f5_fail(F5_ENOTSUP, "upsample stage %d: kernel %d > 3 x rate %d (the transposed convolution keeps one gather row past the utterance's end)", i, k, u);
     }
     for (int j = 0; j < c->num_kernels; ++j)
         if (c->resblock_kernel_sizes[j] <= 0 || c->resblock_kernel_sizes[j] % 2 == 0) return f5_fail(F5_EINVAL, "resblock kernel sizes must be odd");
@@ -438,10 +443,11 @@ static int bv_conv(f5_bigvgan_s* v, const BvConv& cv, const float* x, int T, int
     g.rows_per_batch = T;
     return launch_gemm(g, F5_PREC_FP32, GEMM_DENSE, residual ? EPI_RESID : EPI_STORE_F32, 0, st);
 }
-static int bv_snake(f5_bigvgan_s* v, const BvSnake& s, const float* x, int T, int C, float* out, const BvRagged* rg, int up, hipStream_t st) {
+// the one place that chooses the anti-aliased snake's instantiation (the generator and the f5_op_bigvgan_snake* entries)
+static int bv_snake(const float* up_f, const float* dn_f, const BvSnake& s, const float* x, int T, int C, float* out, const BvRagged* rg, int up, hipStream_t st) {
     BvFilters f;
-    memcpy(f.up, v->up_f, sizeof(f.up));
-    memcpy(f.dn, v->dn_f, sizeof(f.dn));
+    memcpy(f.up, up_f, sizeof(f.up));
+    memcpy(f.dn, dn_f, sizeof(f.dn));
     if (rg) {
         for (const UttExtents& e : rg->tabs) {
             const unsigned tiles = (unsigned)(((size_t)e.max_frames * up + 31) / 32);
@@ -557,9 +563,9 @@ static int bv_generate(f5_bigvgan_s* v, const BvRagged* rg, int T, const float* 
             const BvBlock& blk = v->blocks[(size_t)i * c.num_kernels + j];
             F5_HIP(hipMemcpyAsync(v->y, v->x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
             for (int t = 0; t < 3; ++t) {
-                F5_TRY(bv_snake(v, blk.act[2 * t], v->y, Ti, ch, v->xt, rg, U, st));
+                F5_TRY(bv_snake(v->up_f, v->dn_f, blk.act[2 * t], v->y, Ti, ch, v->xt, rg, U, st));
                 F5_TRY(bv_conv(v, blk.c1[t], v->xt, Ti, blk.dil[t], 0, v->xt2, false, rg, U, 0, st));
-                F5_TRY(bv_snake(v, blk.act[2 * t + 1], v->xt2, Ti, ch, v->xt, rg, U, st));
+                F5_TRY(bv_snake(v->up_f, v->dn_f, blk.act[2 * t + 1], v->xt2, Ti, ch, v->xt, rg, U, st));
                 F5_TRY(bv_conv(v, blk.c2[t], v->xt, Ti, 1, 0, v->y, true, rg, U, 0, st));  // y += conv2(...)
             }
             if (j == 0)
@@ -572,7 +578,7 @@ static int bv_generate(f5_bigvgan_s* v, const BvRagged* rg, int T, const float* 
         hipLaunchKernelGGL(bv_axpby_kernel, dim3(bv_blocks(n)), dim3(256), 0, st, v->x, v->xs, 0.0f, 1.0f / (float)c.num_kernels, n);
         F5_LAUNCH_CHECK();
     }
-    F5_TRY(bv_snake(v, v->act_post, v->x, Ti, ch, v->xt, rg, U, st));
+    F5_TRY(bv_snake(v->up_f, v->dn_f, v->act_post, v->x, Ti, ch, v->xt, rg, U, st));
     F5_TRY(bv_conv(v, v->conv_post, v->xt, Ti, 1, 0, v->y, false, rg, U, 0, st));
     hipLaunchKernelGGL(bv_final_kernel, dim3(bv_blocks((size_t)Ti)), dim3(256), 0, st, v->y, c.use_tanh_at_final, wave, (size_t)Ti);
     F5_LAUNCH_CHECK();
@@ -598,8 +604,6 @@ extern "C" int f5_bigvgan_decode_ragged(f5_bigvgan_t v, int B, const int32_t* ro
     if (!v || !row_start_host || !frames_host || !mel || !wave) return f5_fail(F5_EINVAL, "null argument");
     if (!v->finalized) return f5_fail(F5_ESTATE, "f5_bigvgan_finalize must be called first");
     if (B <= 0 || ld < v->cfg.num_mels) return f5_fail(F5_EINVAL, "need B >= 1 and ld >= num_mels");
-    for (const BvUp& up : v->ups)
-        if (up.pad > up.u) return f5_fail(F5_ENOTSUP, "ragged decode: a transposed convolution with kernel > 3 x rate reads past its T + 1 gather rows");
     F5_TRY(f5_check_device());
     hipStream_t st = (hipStream_t)stream;
     const int64_t total_up = (int64_t)bv_total_up(v->cfg);
@@ -636,4 +640,46 @@ extern "C" int f5_bigvgan_decode_ragged(f5_bigvgan_t v, int B, const int32_t* ro
     F5_TRY(bv_ensure_work(v, max_frames, max_cnt, st));
     for (size_t k = 0; k < sets.size(); ++k) F5_TRY(bv_generate(v, &sets[k], sets[k].frames, mel, ld, wave + (size_t)(set_frame0[k] * total_up), st));
     return 0;
+}
+
+// ----------------------------------------------------------------------------- test-only ops (f5hip.h)
+static void bv_op_filters(const float* up_f, const float* dn_f, float* up, float* dn) {
+    if (up_f) memcpy(up, up_f, 12 * sizeof(float)); else kaiser_sinc_filter(0.25, 0.3, 12, up);
+    if (dn_f) memcpy(dn, dn_f, 12 * sizeof(float)); else kaiser_sinc_filter(0.25, 0.3, 12, dn);
+}
+extern "C" int f5_op_bigvgan_snake(int T, int C, const float* x, const float* a, const float* invb, const float* up_f, const float* dn_f, float* out,
+                                   f5_stream_t stream) {
+    if (T <= 0 || C <= 0 || !x || !a || !invb || !out) return f5_fail(F5_EINVAL, "bad argument");
+    F5_TRY(f5_check_device());
+    float up[12], dn[12];
+    bv_op_filters(up_f, dn_f, up, dn);
+    BvSnake s;
+    s.a = const_cast<float*>(a);
+    s.invb = const_cast<float*>(invb);
+    return bv_snake(up, dn, s, x, T, C, out, nullptr, 1, (hipStream_t)stream);
+}
+extern "C" int f5_op_bigvgan_snake_ragged(int cnt, const int32_t* frames_host, int up, int C, const float* x, const float* a, const float* invb,
+                                          const float* up_f, const float* dn_f, float* out, f5_stream_t stream) {
+    if (cnt <= 0 || up <= 0 || C <= 0 || !frames_host || !x || !a || !invb || !out) return f5_fail(F5_EINVAL, "bad argument");
+    F5_TRY(f5_check_device());
+    BvRagged rg;
+    for (int u = 0; u < cnt; ++u) {
+        const int t = frames_host[u];
+        if (t < 1 || ((int64_t)rg.frames + t) * up > (int64_t)INT_MAX) return f5_fail(F5_EINVAL, "utterance %d: need 1 <= frames and 32-bit rows", u);
+        if (rg.tabs.empty() || rg.tabs.back().cnt == UttExtents::MAXU) rg.tabs.emplace_back();
+        UttExtents& e = rg.tabs.back();
+        e.row0[e.cnt] = rg.frames;
+        e.frames[e.cnt] = t;
+        e.src0[e.cnt] = e.out0[e.cnt] = 0;  // (the snake reads neither)
+        if (t > e.max_frames) e.max_frames = t;
+        ++e.cnt;
+        ++rg.cnt;
+        rg.frames += t;
+    }
+    float fu[12], fd[12];
+    bv_op_filters(up_f, dn_f, fu, fd);
+    BvSnake s;
+    s.a = const_cast<float*>(a);
+    s.invb = const_cast<float*>(invb);
+    return bv_snake(fu, fd, s, x, rg.frames * up, C, out, &rg, up, (hipStream_t)stream);
 }

@@ -479,7 +479,7 @@ typedef struct f5_bigvgan_config {
     int32_t upsample_initial_channel; /* 1536 */
     int32_t num_upsamples;            /* 6 (<= 8) */
     int32_t upsample_rates[8];        /* 4 4 2 2 2 2 */
-    int32_t upsample_kernel_sizes[8]; /* 8 8 4 4 4 4 (a multiple of the rate, k - u even) */
+    int32_t upsample_kernel_sizes[8]; /* 8 8 4 4 4 4 (a multiple of the rate, k - u even, k <= 3u: else F5_ENOTSUP) */
     int32_t num_kernels;              /* 3 (<= 4) AMP blocks per stage */
     int32_t resblock_kernel_sizes[4]; /* 3 7 11 */
     int32_t resblock_dilations[4][3]; /* 1 3 5 each */
@@ -505,6 +505,16 @@ F5_API int f5_bigvgan_forward(f5_bigvgan_t v, int B, int T, const float* mel, fl
  * rows or samples beyond 32-bit indexing.  Nothing synchronises (workspace growth aside, as for f5_bigvgan_forward). */
 F5_API int f5_bigvgan_decode_ragged(f5_bigvgan_t v, int B, const int32_t* row_start_host, const int32_t* frames_host, const float* mel, int ld,
                                     float* wave, int64_t* total_samples, f5_stream_t stream);
+/* Test-only: the anti-aliased SnakeBeta kernel alone, launched exactly as the generator launches it for one utterance (the 64-channel tile when
+ * C % 64 == 0, else the 32-channel one).  x, out: dev f32 [T, C] (time-major); a, invb: dev f32 [C], the kernel's own parameters exp(alpha) and
+ * 1 / (beta + 1e-9f); up_f, dn_f: 12 HOST floats each, NULL = the library's Kaiser-windowed sinc.  out[t][c] = sum_j dn_f[j] z[clamp(2t + j - 5)],
+ * z[n] = w + invb sin^2(a w), w = 2 sum_m xpad[m] up_f[n + 15 - 2m], xpad = x replicate-padded by 5, both clamps at the utterance's own ends. */
+F5_API int f5_op_bigvgan_snake(int T, int C, const float* x, const float* a, const float* invb, const float* up_f, const float* dn_f, float* out,
+                               f5_stream_t stream);
+/* The same through the generator's ragged path: cnt utterances back to back, frames_host[u] * up rows each (host array; more than 64
+ * utterances take several launches).  Every utterance gets the bits of the one-utterance op on its own rows. */
+F5_API int f5_op_bigvgan_snake_ragged(int cnt, const int32_t* frames_host, int up, int C, const float* x, const float* a, const float* invb,
+                                      const float* up_f, const float* dn_f, float* out, f5_stream_t stream);
 
 /* ------------------------------------------------------------------ reference-audio front-end on the device
  * Replaces the two torchaudio transforms of the path:

@@ -758,15 +758,16 @@ BIGVGAN_V2_24K_100BAND_256X = dict(num_mels=100, upsample_initial_channel=1536, 
                                    use_tanh_at_final=False, use_bias_at_final=False)
 
 
-def kaiser_sinc_filter1d(cutoff, half_width, kernel_size):
-    """alias_free_activation/torch/filter.py: Kaiser-windowed sinc low-pass, normalised to unit sum -> [kernel_size]."""
+def kaiser_sinc_filter1d(cutoff, half_width, kernel_size, dtype=None):
+    """alias_free_activation/torch/filter.py: Kaiser-windowed sinc low-pass, normalised to unit sum -> [kernel_size] (dtype: torch's default, or
+    float64 for a reference)."""
     even = kernel_size % 2 == 0
     half_size = kernel_size // 2
     delta_f = 4 * half_width
     A = 2.285 * (half_size - 1) * math.pi * delta_f + 7.95
     beta = 0.1102 * (A - 8.7) if A > 50.0 else (0.5842 * (A - 21) ** 0.4 + 0.07886 * (A - 21.0) if A >= 21.0 else 0.0)
-    window = torch.kaiser_window(kernel_size, beta=beta, periodic=False)
-    time = (torch.arange(-half_size, half_size) + 0.5) if even else (torch.arange(kernel_size) - half_size)
+    window = torch.kaiser_window(kernel_size, beta=beta, periodic=False, dtype=dtype)
+    time = (torch.arange(-half_size, half_size, dtype=dtype) + 0.5) if even else (torch.arange(kernel_size, dtype=dtype) - half_size)
     filt = 2 * cutoff * window * torch.sinc(2 * cutoff * time)
     return filt / filt.sum()
 
@@ -789,12 +790,14 @@ def _aa_snake(x, alpha, beta, up_f, dn_f, logscale):
 
 
 def bigvgan_forward(W, hp, mel):
-    """mel [b, num_mels, T] -> wave [b, 1, T * prod(upsample_rates)].  W: state dict with weight norm REMOVED (`...weight`, `...bias`)."""
-    up_f = W.get("aa_up_filter", kaiser_sinc_filter1d(0.25, 0.3, 12))
-    dn_f = W.get("aa_down_filter", kaiser_sinc_filter1d(0.25, 0.3, 12))
+    """mel [b, num_mels, T] -> wave [b, 1, T * prod(upsample_rates)].  W: state dict with weight norm REMOVED (`...weight`, `...bias`).  Runs in
+    the dtype of the weights: float32, or float64 (every tensor of W cast to double) as the reference of the width probes."""
+    dt = W["conv_pre.weight"].dtype
+    up_f = W.get("aa_up_filter", kaiser_sinc_filter1d(0.25, 0.3, 12).to(dt))
+    dn_f = W.get("aa_down_filter", kaiser_sinc_filter1d(0.25, 0.3, 12).to(dt))
     ls = bool(hp.get("snake_logscale", True))
     nk = len(hp["resblock_kernel_sizes"])
-    x = F.conv1d(mel.float(), W["conv_pre.weight"], W["conv_pre.bias"], padding=3)
+    x = F.conv1d(mel.to(dt), W["conv_pre.weight"], W["conv_pre.bias"], padding=3)
     for i, (u, k) in enumerate(zip(hp["upsample_rates"], hp["upsample_kernel_sizes"])):
         x = F.conv_transpose1d(x, W[f"ups.{i}.0.weight"], W[f"ups.{i}.0.bias"], stride=u, padding=(k - u) // 2)
         xs = None
