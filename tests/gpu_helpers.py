@@ -7,8 +7,8 @@ from eraxvif5tts_amd import _lib
 from eraxvif5tts_amd.model import CFM, DiT
 
 
-def make_dit(arch, vocab, weights, precision):
-    m = DiT(**arch, text_num_embeds=vocab, mel_dim=100, precision=precision)
+def make_dit(arch, vocab, weights, precision, mel_dim=100):
+    m = DiT(**arch, text_num_embeds=vocab, mel_dim=mel_dim, precision=precision)
     sd = m.state_dict()
     missing = [k for k in sd if k not in weights and k != "rotary_embed.inv_freq"]
     assert not missing, missing
@@ -16,9 +16,9 @@ def make_dit(arch, vocab, weights, precision):
     return m.cuda()
 
 
-def make_cfm(arch, vocab, weights, precision, method="euler"):
-    m = make_dit(arch, vocab, weights, precision)
-    return CFM(transformer=m, mel_spec_kwargs={"mel_spec_type": "vocos"}, odeint_kwargs={"method": method}).cuda()
+def make_cfm(arch, vocab, weights, precision, method="euler", mel_dim=100):
+    m = make_dit(arch, vocab, weights, precision, mel_dim=mel_dim)
+    return CFM(transformer=m, num_channels=mel_dim, mel_spec_kwargs={"mel_spec_type": "vocos"}, odeint_kwargs={"method": method}).cuda()
 
 
 def op_linear(precision, kernel, A, W, bias=None, act="none"):

@@ -88,7 +88,9 @@ def _fused_ref(epi, A, W, b, act, gate, rowmask, rope, rope_heads, seq):
                          ids=["default_persistent_grid", "one_tile_per_workgroup", "generic_epilogue", "plain_ring"])
 @pytest.mark.parametrize("epi_name,shape,seq", [("store", (512, 1024, 256), 0), ("store", (10240, 1024, 128), 0), ("store", (10300, 2048, 192), 0),
                                                 ("gate", (768, 512, 128), 0), ("gate", (10240, 1024, 256), 0), ("gate", (10301, 1024, 128), 0),
-                                                ("rope", (1024, 768, 128), 256), ("rope", (4096, 3072, 128), 1024), ("rope", (4120, 3072, 128), 1030)])
+                                                ("rope", (1024, 768, 128), 256), ("rope", (4096, 3072, 128), 1024), ("rope", (4120, 3072, 128), 1030),
+                                                # the Small configs' widths (dim 768: N = 768 / 2304 = 3 / 9 tiles of 256), M no multiple of 256
+                                                ("gate", (1100, 768, 768), 0), ("rope", (2002, 2304, 768), 1001)])
 def test_linear_fused_epilogues(knobs, epi_name, shape, seq):
     import gpu_helpers as G
     from eraxvif5tts_amd import _lib
@@ -122,7 +124,8 @@ def test_linear_fused_epilogues(knobs, epi_name, shape, seq):
 
 @pytest.mark.parametrize("knobs", [{}, {"gemm_persist": 0}, {"gemm_persist": 0, "gemm_lean": 0}, {"gemm_variant": 0}],
                          ids=["default_persistent_grid", "one_tile_per_workgroup", "generic_epilogue", "plain_ring"])
-@pytest.mark.parametrize("shape", [(768, 512, 128), (10240, 1024, 1024), (10240, 1024, 2048), (10301, 1024, 128), (1000, 100, 256)])
+@pytest.mark.parametrize("shape", [(768, 512, 128), (10240, 1024, 1024), (10240, 1024, 2048), (10301, 1024, 128), (1000, 100, 256),
+                                   (4004, 768, 1536), (1100, 2304, 768)])  # (dim 768: out-projection / FF2 shaped, and a 9-tile-wide stream; M % 256 != 0)
 @pytest.mark.parametrize("masked", [False, True], ids=["all_rows", "row_mask"])
 def test_linear_in_place_residual_epilogue(knobs, shape, masked):
     """x += gate * (A W^T + b) IN PLACE on the fp16 residual stream (how the attention out-projection and the second FF linear update the
@@ -177,7 +180,9 @@ def test_attention_reference_kernel(prec, B, N, H, masked):
 
 
 @pytest.mark.parametrize("prec", [P_FP32, P_BF16])
-@pytest.mark.parametrize("dim,B,N", [(128, 2, 50), (1024, 2, 70), (768, 1, 40)])
+@pytest.mark.parametrize("dim,B,N", [(128, 2, 50), (1024, 2, 70), (768, 1, 40),
+                                     # channels per group that do not divide the 64-channel output tile (dim / 16 = 48, 24, 40, 72) and the cap (128)
+                                     (768, 2, 70), (768, 1, 700), (384, 2, 300), (640, 2, 129), (1152, 1, 256), (2048, 1, 64)])
 def test_conv_pos_embed(prec, dim, B, N):
     import gpu_helpers as G
     g = torch.Generator().manual_seed(dim + N)
@@ -196,7 +201,10 @@ def test_conv_pos_embed(prec, dim, B, N):
 
 
 @pytest.mark.parametrize("conv31", [1, 0], ids=["halo_tile_kernel", "implicit_gemm"])
-@pytest.mark.parametrize("dim,B,N", [(1024, 2, 70), (1024, 3, 256), (1024, 1, 700), (1024, 2, 1000), (128, 2, 300)])
+@pytest.mark.parametrize("dim,B,N", [(1024, 2, 70), (1024, 3, 256), (1024, 1, 700), (1024, 2, 1000), (128, 2, 300),
+                                     # groups that straddle output tiles: the window of a tile is 96 .. 160 channels, padded to 128 / 192 (conv31.hip refuses
+                                     # every group size but 64, so both settings take the implicit GEMM there)
+                                     (768, 2, 70), (768, 1, 700), (384, 2, 300), (640, 2, 129), (1152, 1, 256), (2048, 1, 64)])
 def test_conv_pos_embed_tuned_kernels(conv31, dim, B, N):
     """The two tuned forms of the grouped Conv1d(k=31)+Mish pair: conv31.hip (dim 1024: 64 channels per group) and the implicit GEMM of
     gemm_fast.hip, against the oracle and against the reference tile kernel.  Ragged last tiles, utterance edges (zero padding) and
@@ -242,7 +250,7 @@ def test_linear_tuned_kernel(shape, act):
 
 
 @pytest.mark.parametrize("B,N,H,masked", [(2, 56, 2, True), (1, 41, 2, False), (2, 200, 3, True), (1, 128, 16, False), (2, 1024, 4, True),
-                                          (1, 1024, 2, False), (3, 333, 1, True)])
+                                          (1, 1024, 2, False), (3, 333, 1, True), (2, 333, 12, True), (1, 1024, 12, False)])  # (12 heads: dim 768)
 @pytest.mark.parametrize("variant", [0, 2, 5], ids=["by_grid_size", "64_queries_per_wave", "pipelined_32_queries_per_wave"])
 def test_attention_tuned_kernel(B, N, H, masked, variant):
     import gpu_helpers as G
@@ -453,6 +461,12 @@ def test_attention_tuned_kernel_spiked_scores():
     (1100, 1024, 2048, 1024, 0),  # M % 256 != 0: whole tiles on the persistent schedule + a tail launch
     (512, 1024, 3072, 1024, 4),   # fewer tiles than CUs
     (4096, 1024, 3072, 1024, -16),  # persistent 256 x 256 tiles with RoPE on ALL 16 heads (F5TTS_v1_Base: pe_attn_head = null)
+    (300, 768, 2304, 768, 4),       # F5TTS_Small QKV (D / 64 = 12 partial planes, 9 feature tiles of 256): ragged token tile
+    (1024, 768, 2304, 768, 4),      # ... whole tiles: 4 x 9
+    (1100, 768, 1536, 1536, 0),     # F5TTS_Small FF1 behind an FF2-shaped producer, M % 256 != 0
+    (4096, 768, 2304, 768, -12),    # RoPE on all 12 heads
+    (1024, 1280, 3840, 1280, 4),    # 20 partial planes
+    (512, 2048, 4096, 2048, 0),     # the widest model create() accepts: 32 partial planes
 ])
 @pytest.mark.parametrize("offset", [0.0, 40.0])
 def test_layernorm_fold_site_against_fp64(M, D, N, Kb, epi, offset):
@@ -522,7 +536,8 @@ def _with_knob(lib, key, value, fn):
 
 
 @pytest.mark.parametrize("epi_name,shape,seq", [("rope", (2048, 3072, 1024), 1024), ("store", (2048, 2048, 1024), 0), ("resid", (6144, 1024, 2048), 0),
-                                                ("store", (6144, 2048, 1024), 0)])
+                                                ("store", (6144, 2048, 1024), 0),
+                                                ("rope", (2048, 2304, 768), 1024), ("resid", (8192, 768, 1536), 0)])  # dim 768: 144 / 192 short tiles
 def test_w4_kernel_on_partly_filled_grids(epi_name, shape, seq):
     """Small batches: the launcher gives a launch to the one-wave-per-SIMD kernel from three quarters of the CUs on (256-row tiles) or from half
     (128-row tiles) -- single-utterance projections (192 / 128 short tiles), three utterances' FF1 (192 tall tiles) and FF2 (192 short ones).  A
@@ -552,7 +567,11 @@ def test_w4_kernel_on_partly_filled_grids(epi_name, shape, seq):
 @pytest.mark.parametrize("bm", [256, 128], ids=["256_row_tiles", "128_row_tiles"])
 @pytest.mark.parametrize("epi_name,shape,seq", [("store", (8192, 2048, 256), 0), ("store", (8192, 2048, 1024), 0), ("rope", (8192, 3072, 384), 1024),
                                                 ("rope", (16384, 1536, 1024), 2048), ("resid", (16384, 1024, 512), 0), ("resid_masked", (16384, 1024, 2048), 0),
-                                                ("resid_masked", (8320, 1024, 256), 0)])
+                                                ("resid_masked", (8320, 1024, 256), 0),
+                                                # dim 768 (K = 768 = 12 stages of 64; N = 2304 / 1536 / 3072 / 768 = 9 / 6 / 12 / 3 tiles of 256); M = 22528 gives
+                                                # 88 x 3 = 264 tall tiles, so the 256-row form of an N = 768 launch really runs
+                                                ("rope", (8192, 2304, 768), 1024), ("store", (8192, 1536, 768), 0), ("store", (8192, 3072, 768), 0),
+                                                ("resid", (22528, 768, 768), 0), ("resid_masked", (22528, 768, 1536), 0)])
 def test_w4_kernel_equals_the_8_wave_kernel(bm, epi_name, shape, seq):
     """Round 4, late: whole-tile block linears with at least one 256 x 256 tile per CU run on the one-wave-per-SIMD kernel (csrc/gemm_w4.hip: four
     waves, 128 x 128 outputs per wave, 64-deep stages refilled in place, hand-placed main loop).  Same MFMA, K order, start value and epilogue
@@ -581,7 +600,7 @@ def test_w4_kernel_equals_the_8_wave_kernel(bm, epi_name, shape, seq):
         rope, heads = None, 0
         if epi_name == "rope":
             ang = torch.rand(seq, 32, generator=g) * 6.28
-            rope, heads = torch.stack([ang.cos(), ang.sin()], dim=-1), (1 if N == 3072 else N // 3 // 64)
+            rope, heads = torch.stack([ang.cos(), ang.sin()], dim=-1), (1 if N in (3072, 2304) else N // 3 // 64)
         run = lambda: G.op_linear_fused(1, epi, A, W, b, act, None, None, rope, heads, seq)
         ref, tol = _fused_ref(epi, A, W, b, act, None, None, rope, heads, seq), 3e-3
     _lib.check(lib.f5_tuning_set(b"gemm_w4_bm", bm))
@@ -595,15 +614,19 @@ def test_w4_kernel_equals_the_8_wave_kernel(bm, epi_name, shape, seq):
 
 
 @pytest.mark.parametrize("bm", [256, 128], ids=["256_row_tiles", "128_row_tiles"])
-@pytest.mark.parametrize("N,Kb,epi", [(3072, 1024, 4), (2048, 2048, 0), (3072, 1024, -16)])
-def test_w4_kernel_layernorm_fold_site_equals_the_8_wave_kernel(bm, N, Kb, epi):
+@pytest.mark.parametrize("D,N,Kb,epi", [pytest.param(1024, 3072, 1024, 4, id="3072-1024-4"), pytest.param(1024, 2048, 2048, 0, id="2048-2048-0"),
+                                        pytest.param(1024, 3072, 1024, -16, id="3072-1024--16"),
+                                        # dim 768: K = 768, so the consumer runs on this kernel with FINALIZED statistics (12 partial planes through
+                                        # stats_finalize), not with the in-kernel form, which needs K = 1024
+                                        pytest.param(768, 2304, 768, 4, id="d768-2304-768-4"), pytest.param(768, 1536, 1536, 0, id="d768-1536-1536-0")])
+def test_w4_kernel_layernorm_fold_site_equals_the_8_wave_kernel(bm, D, N, Kb, epi):
     """The LayerNorm fold of one call site at a size the one-wave-per-SIMD kernel takes (M = 16 384 token rows: producer 64 x 4, consumer 64 x 8 / 12
     tiles): in-place residual epilogue with partial row statistics -> statistics -> fp16-operand projection with the fold epilogue (+ RoPE / GELU).
     Stream, statistics and output bit for bit against the 8-wave kernel (gemm_w4 = 0)."""
     import gpu_helpers as G
     from eraxvif5tts_amd import _lib
     lib = _lib.load()
-    M, D = 16384, 1024
+    M = 16384
     rope_heads = 1
     if epi < 0:
         rope_heads, epi = -epi, 4
