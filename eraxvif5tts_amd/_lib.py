@@ -121,6 +121,9 @@ _PROTOS = {
     "f5_wave_stream_create": (_I, [_I, _I, _P, _P, _P, C.c_float, _I, C.POINTER(_P)]),
     "f5_wave_stream_push": (_I, [_P, _I, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), _P, _P, _P, C.POINTER(C.c_int64), _P]),
     "f5_wave_stream_destroy": (_I, [_P]),
+    "f5_wave_remove_silence_workspace": (C.c_int64, [C.c_int64, _I, _I, _I]),
+    "f5_wave_remove_silence": (_I, [_P, _I, C.c_int64, _I, C.c_int64, _I, _I, _I, _I, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "f5_op_silence_ranges": (_I, [_P, _I, C.c_int64, _I, C.c_int64, _I, _I, _I, _I, _P, C.c_int64, _P, _P, _P, _P]),
     "f5_bigvgan_create": (_I, [C.POINTER(BigVGANConfig), C.POINTER(_P)]),
     "f5_bigvgan_set_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
     "f5_bigvgan_has_tensor": (_I, [_P, C.c_char_p, C.POINTER(C.c_int64)]),

@@ -64,7 +64,12 @@ def write_wav(path, wave, sample_rate):
     """float waveform [n] or [1, n] in [-1, 1] -> 16-bit PCM WAV (what torchaudio.save writes for float input by default is
     32-bit float; 16-bit keeps the files small and is what the streaming front-ends of the reference send)."""
     x = np.asarray(wave, dtype=np.float64).reshape(-1)
-    pcm = np.clip(np.round(x * 32767.0), -32768, 32767).astype("<i2").tobytes()
+    write_wav_pcm16(path, np.clip(np.round(x * 32767.0), -32768, 32767), sample_rate)
+
+
+def write_wav_pcm16(path, samples, sample_rate):
+    """integer samples [n] inside int16 -> the same 16-bit mono PCM WAV (a file rewritten from its own samples, with no float in between)"""
+    pcm = np.asarray(samples).reshape(-1).astype("<i2").tobytes()
     with open(path, "wb") as f:
         f.write(b"RIFF" + struct.pack("<I", 36 + len(pcm)) + b"WAVE")
         f.write(b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, sample_rate * 2, 2, 16))
@@ -164,14 +169,38 @@ def detect_nonsilent(seg, min_silence_len=1000, silence_thresh=-16, seek_step=1)
     return out
 
 
-def split_on_silence(seg, min_silence_len=1000, silence_thresh=-16, keep_silence=100, seek_step=1):
+def _padded_ranges(seg, min_silence_len, silence_thresh, keep_silence, seek_step):
+    """the non-silent ranges in milliseconds, padded by keep_silence; overlapping neighbours meet at the midpoint (not yet clamped)"""
     ranges = [[s - keep_silence, e + keep_silence] for s, e in detect_nonsilent(seg, min_silence_len, silence_thresh, seek_step)]
     for a, b in zip(ranges, ranges[1:]):
         if b[0] < a[1]:
             a[1] = (a[1] + b[0]) // 2
             b[0] = a[1]
+    return ranges
+
+
+def split_on_silence(seg, min_silence_len=1000, silence_thresh=-16, keep_silence=100, seek_step=1):
     n = len(seg)
-    return [seg.slice_ms(max(s, 0), min(e, n)) for s, e in ranges]
+    return [seg.slice_ms(max(s, 0), min(e, n)) for s, e in _padded_ranges(seg, min_silence_len, silence_thresh, keep_silence, seek_step)]
+
+
+def split_sample_ranges(seg, min_silence_len=1000, silence_thresh=-16, keep_silence=100, seek_step=1):
+    """The parts of `split_on_silence` as ``(first sample, end sample)`` pairs instead of segments, for a caller that cuts something else at
+    the same places (the float wave the PCM came from).  tests/test_silence_host.py holds the two together."""
+    n, count = len(seg), seg.samples.shape[0]
+    out = []
+    for s, e in _padded_ranges(seg, min_silence_len, silence_thresh, keep_silence, seek_step):
+        first, end = min(seg._frame(min(max(s, 0), n)), count), min(seg._frame(min(max(e, 0), n)), count)
+        out.append((first, max(first, end)))
+    return out
+
+
+def silence_threshold_floor(silence_thresh, max_possible_amplitude=32768.0):
+    """R = floor(10^(dB / 20) * amplitude), the integer the device decision takes: ``Segment.rms <= thresh`` compares an integer, so it is
+    ``rms <= R``, and over n < 2^22 samples with the sum of squares S that is ``S < (R + 1)^2 * n``.  An rms never exceeds the
+    amplitude, so R stops there."""
+    thresh = (10 ** (silence_thresh / 20.0)) * max_possible_amplitude
+    return int(min(math.floor(thresh), int(max_possible_amplitude)))
 
 
 def detect_leading_silence(seg, silence_threshold=-50.0, chunk_size=10):

@@ -181,13 +181,17 @@ class F5TTSWrapper:
     def generate(self, text: str, output_path: Optional[str] = None, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
                  sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
                  cross_fade_duration: Optional[float] = None, use_duration_predictor: Optional[bool] = None,
-                 return_numpy: bool = False, return_spectrogram: bool = False, return_pcm16: bool = False):
+                 return_numpy: bool = False, return_spectrogram: bool = False, return_pcm16: bool = False, remove_silence: bool = False):
         """``return_pcm16``: the wave comes back as the int16 PCM the streaming server sends (``streaming.wire.pcm16_bytes`` of the float
-        result, bit for bit), converted on the device where the device tail runs -- one int16 copy instead of a float copy and a host pass."""
+        result, bit for bit), converted on the device where the device tail runs -- one int16 copy instead of a float copy and a host pass.
+        ``remove_silence``: the reference's option (infer_cli --remove_silence, api.py) -- the written file is byte for byte the file without
+        the option after `utils_infer.remove_silence_for_generated_wav`; the returned wave (float, or the truncating PCM with
+        ``return_pcm16``) holds the same kept samples, and the spectrogram is untouched.  Where the device tail runs the decision is taken
+        there (`utils_infer.remove_silence`) and only the kept samples are copied; an all-silent result is empty."""
         (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs = self._plan_jobs(
             text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
         return self._generate_jobs(jobs, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration, return_numpy,
-                                   return_spectrogram, return_pcm16)
+                                   return_spectrogram, return_pcm16, remove_silence)
 
     def _plan_jobs(self, text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor):
         """The host work of generate() / generate_stream() before any sampling: the arguments' defaults, the text cut into chunks, and per chunk
@@ -281,8 +285,15 @@ class F5TTSWrapper:
                     generated.record_stream(main)
         return mels
 
+    def _silence_step(self, signal, pcm16=None):
+        """The step behind the tail when ``remove_silence`` is on: ``(kept signal, kept pcm16 or None)`` at the reference's four values
+        (`utils_infer.SILENCE_DEFAULTS`), on the device for device tensors (the `finish_waves` outputs), by the host functions for arrays."""
+        from .utils_infer import SILENCE_DEFAULTS, remove_silence
+        kept = remove_silence(signal, self.target_sample_rate, pcm16=pcm16, **SILENCE_DEFAULTS)
+        return kept if pcm16 is not None else (kept, None)
+
     def _generate_jobs(self, jobs, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration, return_numpy, return_spectrogram,
-                       return_pcm16):
+                       return_pcm16, remove_silence=False):
         generated_waves, spectrograms = [], []
         mels = self._sample_jobs(jobs, nfe_step, cfg_strength, sway_sampling_coef)
         want_spec = return_spectrogram or output_path is not None
@@ -298,10 +309,12 @@ class F5TTSWrapper:
                 wave_buf, samples = decode_utterances(self.vocoder, kind, rows, row_start, frames)
                 rms = torch.sqrt(torch.mean(torch.square(self.ref_audio_processed)))  # of the stored, already boosted prompt (:529-531)
                 done = finish_waves(wave_buf, samples, cross_fade_duration, self.target_sample_rate, rms=rms.to(torch.float32), target_rms=self.target_rms,
-                                    want_float=want_float, want_pcm16=return_pcm16)
+                                    want_float=want_float or remove_silence, want_pcm16=return_pcm16)  # (the float wave is what is judged)
                 if want_spec:
                     spectrograms = [rows[r: r + t].t().cpu().numpy() for r, t in zip(row_start, frames)]
                 if done is not None:
+                    if remove_silence:
+                        done, remove_silence = self._silence_step(*done), False
                     final_wave = done[0].cpu().numpy() if want_float else None
                     final_pcm = done[1].cpu().numpy() if return_pcm16 else None
                 else:  # utterances shorter than their cross-fades (F5_ENOTSUP): the decoded waves take the host functions
@@ -329,6 +342,8 @@ class F5TTSWrapper:
         if return_pcm16 and final_pcm is None:
             from ..streaming.wire import pcm16_bytes
             final_pcm = np.frombuffer(pcm16_bytes(final_wave), dtype=np.int16)
+        if remove_silence:  # the host tails (a foreign vocoder, or joints that chain): the same rule by the host functions
+            final_wave, final_pcm = self._silence_step(final_wave, final_pcm)
         combined_spectrogram = np.concatenate(spectrograms, axis=1) if spectrograms else None
         if output_path is not None:
             output_dir = os.path.dirname(output_path)

@@ -385,6 +385,115 @@ class WaveStream:
             pass
 
 
+# ---------------------------------------------------------------------------- remove silence (reference :569-578)
+# The reference runs pydub's split_on_silence(min_silence_len=1000, silence_thresh=-50, keep_silence=500, seek_step=10) on the exported 16-bit file
+# and rewrites the file from the kept parts.  The rule here is `audio.split_on_silence`, this package's stand-in for pydub; the PCM that is judged
+# is the one `audio.write_wav` puts into the file (rounded, never the truncating streaming PCM).  On the device (csrc/silence.hip) the same
+# integer arithmetic gives the same parts, so only the kept samples cross to the host.
+SILENCE_DEFAULTS = dict(min_silence_len=1000, silence_thresh=-50, keep_silence=500, seek_step=10)
+
+
+def remove_silence_for_generated_wav(filename):
+    """The reference's name, at file level: the 16-bit file is read, split at the reference's four values and rewritten from the kept parts."""
+    aseg = _audio.Segment.from_file(filename)
+    kept = aseg.silent_like(0)
+    for part in _audio.split_on_silence(aseg, **SILENCE_DEFAULTS):
+        kept = kept + part
+    _audio.write_wav_pcm16(filename, kept.samples[:, 0], aseg.frame_rate)
+
+
+def rounded_pcm16(wave):
+    """the int16 samples `audio.write_wav` stores for this float wave (product in float64, round half to even, clipped)"""
+    x = np.asarray(wave, dtype=np.float64).reshape(-1)
+    return np.clip(np.round(x * 32767.0), -32768, 32767).astype(np.int16)
+
+
+def _silence_windows(n_samples, sample_rate, min_silence_len, seek_step):
+    """(n_ms, window starts, table entries) the library derives from the same four numbers (f5hip.h)"""
+    n_ms = int(round(1000.0 * n_samples / sample_rate))
+    windows = 0
+    if n_ms >= min_silence_len:
+        last = n_ms - min_silence_len
+        windows = last // seek_step + 1 + (1 if last % seek_step else 0)
+    return n_ms, windows, n_ms // max(min_silence_len, 1) + 2
+
+
+def silence_ranges(wave, sample_rate=target_sample_rate, *, min_silence_len=1000, silence_thresh=-50, keep_silence=500, seek_step=10):
+    """``f5_op_silence_ranges``: the decision alone for a 1-D fp32 / fp64 wave on the GPU -> ``(flags, table, kept, parts)``: one byte per window
+    start (1 = silent), the parts as rows ``(first sample, end sample, position in the output)``, the kept samples and the number of parts
+    (host numbers: this copies)."""
+    from .. import _lib
+    lib = _lib.load()
+    assert wave.is_cuda and wave.dim() == 1 and wave.is_contiguous() and wave.dtype in (torch.float32, torch.float64)
+    n = wave.numel()
+    n_ms, windows, cap = _silence_windows(n, sample_rate, min_silence_len, seek_step)
+    need = lib.f5_wave_remove_silence_workspace(n, int(sample_rate), int(min_silence_len), int(seek_step))
+    ws = torch.empty(max(int(need), 16), device=wave.device, dtype=torch.uint8)
+    flags = torch.zeros(max(windows, 1), device=wave.device, dtype=torch.uint8)
+    table = torch.zeros(cap, 3, device=wave.device, dtype=torch.int32)
+    counts = torch.zeros(2, device=wave.device, dtype=torch.int64)
+    rc = lib.f5_op_silence_ranges(_lib.ptr(wave) if n else None, int(wave.dtype == torch.float64), n, int(sample_rate), n_ms, int(min_silence_len),
+                                  _audio.silence_threshold_floor(silence_thresh), int(keep_silence), int(seek_step), _lib.ptr(ws), ws.numel(),
+                                  _lib.ptr(flags), _lib.ptr(table), _lib.ptr(counts), _lib.stream_ptr())
+    _lib.check(rc, "op_silence_ranges")
+    kept, parts = (int(v) for v in counts.cpu().tolist())
+    return flags[:windows].cpu().numpy(), table[:parts].cpu().numpy(), kept, parts
+
+
+def remove_silence_device(wave, sample_rate=target_sample_rate, *, min_silence_len=1000, silence_thresh=-50, keep_silence=500, seek_step=10,
+                          pcm16=None, want_wave=True, want_rounded=False):
+    """``f5_wave_remove_silence`` on a 1-D fp32 / fp64 wave on the GPU -> ``(kept wave, kept rounded PCM, kept pcm16, parts)`` as device tensors
+    (None where not asked for).  One small copy (the two counts) comes to the host to size the results; the samples stay on the device."""
+    from .. import _lib
+    lib = _lib.load()
+    assert wave.is_cuda and wave.dim() == 1 and wave.is_contiguous() and wave.dtype in (torch.float32, torch.float64)
+    n, dev = wave.numel(), wave.device
+    if pcm16 is not None:
+        assert pcm16.is_cuda and pcm16.dtype == torch.int16 and pcm16.is_contiguous() and pcm16.numel() == n
+    assert want_wave or want_rounded or pcm16 is not None
+    if n == 0:  # (nothing to judge: the host functions answer one empty part)
+        empty = lambda dtype: torch.empty(0, device=dev, dtype=dtype)  # noqa: E731
+        return (empty(wave.dtype) if want_wave else None, empty(torch.int16) if want_rounded else None,
+                empty(torch.int16) if pcm16 is not None else None, 1)
+    n_ms, _, _ = _silence_windows(n, sample_rate, min_silence_len, seek_step)
+    need = lib.f5_wave_remove_silence_workspace(n, int(sample_rate), int(min_silence_len), int(seek_step))
+    ws = torch.empty(max(int(need), 16), device=dev, dtype=torch.uint8)
+    out = torch.empty(max(n, 1), device=dev, dtype=wave.dtype) if want_wave else None
+    rounded = torch.empty(max(n, 1), device=dev, dtype=torch.int16) if want_rounded else None
+    kept_pcm = torch.empty(max(n, 1), device=dev, dtype=torch.int16) if pcm16 is not None else None
+    counts = torch.zeros(2, device=dev, dtype=torch.int64)
+    rc = lib.f5_wave_remove_silence(_lib.ptr(wave) if n else None, int(wave.dtype == torch.float64), n, int(sample_rate), n_ms, int(min_silence_len),
+                                    _audio.silence_threshold_floor(silence_thresh), int(keep_silence), int(seek_step),
+                                    _lib.ptr(pcm16) if n else None, _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.ptr(rounded),
+                                    _lib.ptr(kept_pcm) if n else None, _lib.ptr(counts), _lib.stream_ptr())
+    _lib.check(rc, "wave_remove_silence")
+    kept, parts = (int(v) for v in counts.cpu().tolist())
+    cut = lambda t: t[:kept] if t is not None else None  # noqa: E731
+    return cut(out), cut(rounded), cut(kept_pcm), parts
+
+
+def remove_silence(wave, sample_rate=target_sample_rate, *, min_silence_len=1000, silence_thresh=-50, keep_silence=500, seek_step=10, pcm16=None):
+    """The kept samples of a finished mono wave: what `remove_silence_for_generated_wav` leaves of the file `audio.write_wav` makes of it, taken
+    from the float wave itself (and, with ``pcm16``, from a second array of the same length: the truncating PCM of `finish_waves`).  A tensor on
+    the GPU (fp32 / fp64) takes the device route and device tensors come back; a numpy array or CPU tensor takes the host functions, with the same
+    result byte for byte.  Returns the kept wave, or ``(kept wave, kept pcm16)`` when ``pcm16`` is given.  NaN samples count as 0."""
+    rule = dict(min_silence_len=min_silence_len, silence_thresh=silence_thresh, keep_silence=keep_silence, seek_step=seek_step)
+    if torch.is_tensor(wave) and wave.is_cuda:
+        flat = wave.reshape(-1).contiguous()
+        kept, _, kept_pcm, _ = remove_silence_device(flat, sample_rate, pcm16=pcm16.reshape(-1).contiguous() if pcm16 is not None else None, **rule)
+        return kept if pcm16 is None else (kept, kept_pcm)
+    as_tensor = torch.is_tensor(wave)
+    x = (wave.numpy() if as_tensor else np.asarray(wave)).reshape(-1)
+    ranges = _audio.split_sample_ranges(_audio.Segment(rounded_pcm16(x), sample_rate, 2), **rule)
+    kept = np.concatenate([x[a:b] for a, b in ranges]) if ranges else x[:0]
+    if pcm16 is None:
+        return torch.from_numpy(kept) if as_tensor else kept
+    p = (pcm16.numpy() if torch.is_tensor(pcm16) else np.asarray(pcm16)).reshape(-1)
+    assert len(p) == len(x)
+    kept_pcm = np.concatenate([p[a:b] for a, b in ranges]) if ranges else p[:0]
+    return (torch.from_numpy(kept), torch.from_numpy(kept_pcm)) if as_tensor else (kept, kept_pcm)
+
+
 def device_tail_kind(vocoder, *tensors):
     """Which device tail applies to this vocoder object and these mels: "bigvgan" (the HIP BigVGAN: ``T * up`` samples per utterance), "vocos"
     (the HIP Vocos, or an object with its ``decode_ragged_buffer``: ``(T - 1) * hop`` samples) or None (a foreign object at plug point B, or

@@ -463,6 +463,42 @@ F5_API int f5_wave_stream_push(f5_wave_stream_t s, int B, const float* wave, con
                                const uint8_t* apply_host, float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* emitted,
                                f5_stream_t stream);
 F5_API int f5_wave_stream_destroy(f5_wave_stream_t s);
+/* "Remove silence" on the finished wave, on the device: the reference's remove_silence_for_generated_wav (infer/utils_infer.py:569-578: pydub's
+ * split_on_silence on the exported 16-bit file, the kept parts written back), detected by symbol like the round-5 entries.
+ *   rule       this package's stand-in for pydub, infer/audio.py split_on_silence / detect_nonsilent / detect_silence / Segment.slice_ms /
+ *              Segment.__len__, bit for bit: n_ms = round(1000 n_samples / sample_rate) half to even (the caller passes it; it is checked);
+ *              millisecond m is sample F(m) = min(int(m * (sample_rate / 1000.0)), n_samples), a double product, truncated; window starts 0,
+ *              seek_step, .. <= last = n_ms - min_silence_len, and last itself once more when last % seek_step != 0; a window covers
+ *              [i, i + min_silence_len); a silent start i opens a new silent range only when i != prev + seek_step and i > prev + min_silence_len;
+ *              the silent ranges are inverted (a leading [0, 0] dropped; all silent: no part; no silent window, or n_ms < min_silence_len: the one
+ *              part [0, n_ms]), each part is padded by keep_silence, overlapping neighbours meet at (a_end + b_start) / 2, all is clamped to
+ *              [0, n_ms]; samples behind F(n_ms) belong to no part
+ *   PCM judged clip(rint(double(x) * 32767.0), -32768, 32767): the product in fp64, rint half to even -- what audio.write_wav puts into the file.
+ *              It is formed in registers; it is never the truncating PCM of f5_wave_finish.  NaN counts as 0 (numpy leaves that cast undefined)
+ *   decision   a window of n samples with the sum of squares S is silent when S < (R + 1)^2 n, R = threshold_floor = floor(10^(dB / 20) * 32768),
+ *              taken by the caller: equal to the host's int(sqrt(S / n)) <= threshold while n < 2^22; 64-bit integers throughout, no
+ *              sqrt, pow or division on the device
+ *   wave       dev f32 (is_f64 = 0) or f64 (1), n_samples mono samples, aligned to its element
+ *   workspace  dev, 16-byte aligned, at least the bytes the _workspace entry answers for the same n_samples, sample_rate, min_silence_len and
+ *              seek_step (a negative F5_* code for arguments it refuses).  Nothing is allocated here
+ *   outputs    each may be NULL, each with room for n_samples elements: out_wave (the kept samples, in the input's dtype), out_pcm16 (their
+ *              rounded PCM, as above), out_pcm_in (the kept samples of pcm_in, dev int16 [n_samples]: the caller's truncating PCM; both or
+ *              neither).  counts_dev: dev int64 [2] = (kept samples, parts); copy it before, or together with, the data
+ *   refusals   F5_EINVAL with the argument's name, before any launch, the outputs untouched: a window of 2^22 samples or more
+ *              (min_silence_len * sample_rate / 1000 + 1), n_samples < 0 or >= 2^31, min_silence_len < 1, seek_step < 1, keep_silence < 0,
+ *              sample_rate < 1000, threshold_floor < 0, an n_ms other than the rule's, a short or misaligned workspace
+ * Nothing synchronises.
+ * The op-level entry stops behind the decision (for tests): flags_out dev u8 [W], W = the number of window starts above (0 when
+ * n_ms < min_silence_len; give one byte at least), 1 = silent; table_out dev i32 [3 (n_ms / min_silence_len + 2)]: per part (first sample, end
+ * sample, position of its first sample in the output); counts_dev as above. */
+F5_API int64_t f5_wave_remove_silence_workspace(int64_t n_samples, int sample_rate, int min_silence_len, int seek_step);
+F5_API int f5_wave_remove_silence(const void* wave, int is_f64, int64_t n_samples, int sample_rate, int64_t n_ms, int min_silence_len,
+                                  int threshold_floor, int keep_silence, int seek_step, const int16_t* pcm_in, void* workspace,
+                                  int64_t workspace_bytes, void* out_wave, int16_t* out_pcm16, int16_t* out_pcm_in, int64_t* counts_dev,
+                                  f5_stream_t stream);
+F5_API int f5_op_silence_ranges(const void* wave, int is_f64, int64_t n_samples, int sample_rate, int64_t n_ms, int min_silence_len,
+                                int threshold_floor, int keep_silence, int seek_step, void* workspace, int64_t workspace_bytes,
+                                uint8_t* flags_out, int32_t* table_out, int64_t* counts_dev, f5_stream_t stream);
 /* ISTFT head alone (for the roofline measurement): spec dev f32 [B, T, n_fft+2] (head.out activations:
  * log-magnitude | phase) -> wave dev f32 [B, (T-1)*hop] */
 F5_API int f5_vocoder_istft_head(f5_vocoder_t v, int B, int T, const float* head_out, float* wave, f5_stream_t stream);
