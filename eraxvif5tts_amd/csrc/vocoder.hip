@@ -99,6 +99,20 @@ extern "C" int f5_vocoder_finalize(f5_vocoder_t v) {
     F5_TRY(f5_slots_all_set(v->slots));
     const f5_vocos_config& c = v->cfg;
     const size_t C = c.n_mels, D = c.dim, I = c.inter_dim, NF = c.n_fft, F = NF / 2 + 1;
+    {
+        // torch.istft's NOLA check on the final window (default or head.istft.window): the overlap-add divides every sample by the overlap-added
+        // squared window, whose steady-state value at sample j of a hop is sum_m w^2[j + m hop].  Periodic Hann at hop = n_fft has w[0] = 0 and no
+        // other frame over that sample: 0 / 0.  (Not covered: zeros that only a custom window under fewer frames than one full overlap produces.)
+        double env_min = INFINITY;
+        for (size_t j = 0; j < (size_t)c.hop; ++j) {
+            double e = 0.0;
+            for (size_t n = j; n < NF; n += c.hop) e += (double)v->window[n] * (double)v->window[n];
+            if (std::isnan(e) || e < env_min) env_min = e;  // (a NaN in the window sticks: no later e compares below it)
+        }
+        if (!(env_min >= 1e-11))
+            return f5_fail(F5_EINVAL, "vocos: the window of n_fft %d at hop %d violates the NOLA condition (min over a hop of the overlap-added "
+                                      "squared window is %g, below 1e-11): the ISTFT would divide by zero", c.n_fft, c.hop, env_min);
+    }
     v->F = (int)F;
     DevArena& A = v->arena;
     auto Hs = [&](const std::string& n) -> const std::vector<float>& { return v->slots[n].host; };

@@ -400,6 +400,10 @@ typedef struct f5_vocos_config {
 F5_API int f5_vocoder_create(const f5_vocos_config* cfg, f5_vocoder_t* out);
 F5_API int f5_vocoder_set_tensor(f5_vocoder_t v, const char* name, const float* host_data, const int64_t* shape, int ndim);
 F5_API int f5_vocoder_has_tensor(f5_vocoder_t v, const char* name, int64_t* numel);
+/* Uploads the tensors.  F5_EINVAL when the final ISTFT window (periodic Hann, or the caller's "head.istft.window") violates the NOLA condition
+ * at (n_fft, hop): min over j < hop of sum_m w^2[j + m * hop] below 1e-11, torch.istft's own threshold -- the overlap-add would divide by
+ * zero and write NaN (e.g. Hann at hop == n_fft).  Only this steady-state envelope is judged: zeros that a custom window produces under
+ * fewer frames than one full overlap are not detected. */
 F5_API int f5_vocoder_finalize(f5_vocoder_t v);
 F5_API int f5_vocoder_destroy(f5_vocoder_t v);
 /* Vocos.decode: mel dev f32 [B, n_mels, T] -> wave dev f32 [B, (T-1)*hop] */

@@ -615,6 +615,79 @@ def bigvgan_mel_spectrogram(wave, n_fft=1024, n_mels=100, sr=24000, hop=256, win
     return torch.log(torch.clamp(torch.matmul(mel_basis, spec), min=1e-5))
 
 
+# ----------------------------------------------------------------------------- both mel front-ends in float64, as a direct DFT
+# (no torch.stft: shares no code with mel_spectrogram / bigvgan_mel_spectrogram above, so the two agree only if both are right).  The pieces are
+# separate functions so that tests/test_audio_oracles_host.py can put a deliberately wrong one in and show that the test inputs see it.
+def mel_frame_geometry(nw, n_fft, hop, mel_type="vocos"):
+    """(pad, T): samples reflected in on either side, and the frame count.  "vocos" = torch.stft(center=True): pad n_fft / 2, T = nw // hop + 1;
+    "bigvgan" = explicit padding of (n_fft - hop) // 2 with center=False: T = (nw + 2 pad - n_fft) // hop + 1."""
+    if mel_type == "vocos":
+        return n_fft // 2, nw // hop + 1
+    pad = (n_fft - hop) // 2
+    return pad, (nw + 2 * pad - n_fft) // hop + 1
+
+
+def reflect_index(s, nw):
+    """index into the waveform of padded position s (s = 0 is the first true sample): the edge sample is the mirror and is not repeated"""
+    import numpy as np
+    s = np.where(s < 0, -s, s)
+    return np.where(s >= nw, 2 * (nw - 1) - s, s)
+
+
+def mel_frames_f64(wave, n_fft, hop, pad, T, index=reflect_index):
+    """[b, nw] -> float64 frames [b, T, n_fft]: frame t starts at true sample t * hop - pad"""
+    import numpy as np
+    x = wave.detach().cpu().to(torch.float64).numpy()
+    s = np.arange(T)[:, None] * hop + np.arange(n_fft)[None, :] - pad
+    return x[:, index(s, x.shape[-1])]
+
+
+def hann_in_frame_f64(win, n_fft):
+    """periodic Hann window of `win` samples, centred inside n_fft (torch.stft pads a shorter window on both sides)"""
+    import numpy as np
+    w = np.zeros(n_fft, dtype=np.float64)
+    off = (n_fft - win) // 2
+    w[off: off + win] = 0.5 - 0.5 * np.cos(2.0 * math.pi * np.arange(win) / win)
+    return w
+
+
+def dft_matrices_f64(n_fft):
+    """cos, sin of 2 pi k n / n_fft for the one-sided bins k <= n_fft / 2: [F, n_fft] each (the angle reduced exactly, in integers)"""
+    import numpy as np
+    kn = (np.arange(n_fft // 2 + 1)[:, None] * np.arange(n_fft)[None, :]) % n_fft
+    ang = 2.0 * math.pi * kn / n_fft
+    return np.cos(ang), np.sin(ang)
+
+
+def mel_filterbank_f64(n_fft, n_mels, sr, mel_type="vocos"):
+    """the float32 filterbank of either front-end (data here, not the thing under test), as float64 [n_mels, F]"""
+    if mel_type == "vocos":
+        return mel_filterbank(n_fft // 2 + 1, n_mels, sr).double().numpy().T
+    return librosa_mel_filterbank(sr, n_fft, n_mels).astype("float64")
+
+
+def log_mel_from_frames_f64(frames, window, fb, eps):
+    """frames [b, T, n_fft] -> log(max(fb @ sqrt(re^2 + im^2 + eps), 1e-5)) [b, n_mels, T]"""
+    import numpy as np
+    cos, sin = dft_matrices_f64(frames.shape[-1])
+    xw = frames * window
+    re, im = xw @ cos.T, -(xw @ sin.T)
+    mag = np.sqrt(re * re + im * im + eps)  # [b, T, F]
+    return np.log(np.maximum(mag @ fb.T, 1e-5)).transpose(0, 2, 1)
+
+
+def mel_spectrogram_f64(wave, n_fft=1024, hop=256, win=1024, n_mels=100, sr=24000, mel_type="vocos"):
+    """modules.py:75-101 ("vocos") and modules.py:29-72 ("bigvgan": padding (n_fft - hop) // 2, no centring, 1e-9 under the root, the Slaney
+    filterbank) in float64: explicit reflect index map, periodic Hann of `win` centred in n_fft, dense cos / sin DFT over the one-sided bins,
+    magnitude, filterbank, log(max(., 1e-5)).  wave [b, nw] -> float64 tensor [b, n_mels, T]."""
+    assert mel_type in ("vocos", "bigvgan")
+    pad, T = mel_frame_geometry(wave.shape[-1], n_fft, hop, mel_type)
+    frames = mel_frames_f64(wave, n_fft, hop, pad, T)
+    out = log_mel_from_frames_f64(frames, hann_in_frame_f64(win, n_fft), mel_filterbank_f64(n_fft, n_mels, sr, mel_type),
+                                  1e-9 if mel_type == "bigvgan" else 0.0)
+    return torch.from_numpy(out.copy())
+
+
 # ----------------------------------------------------------------------------- f3: sample-rate conversion (unpinned: torchaudio absent)
 def resample(wave, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
     """torchaudio.transforms.Resample(orig, new) with its defaults (resampling_method "sinc_interp_hann", width 6, rolloff 0.99), the call
@@ -696,12 +769,50 @@ def istft_center(spec_re, spec_im, n_fft=1024, hop=256):
     return y[:, half: out_len - half] / env[half: out_len - half]
 
 
-def vocos_decode(V, mel):
-    """vocos Vocos.decode (wrapper.py:524): backbone -> Linear(512->1026) -> exp/clip(1e2), cos/sin -> ISTFT."""
+def istft_f64(spec_re, spec_im, n_fft=1024, hop=256, window=None):
+    """istft_center in float64 with a window argument (None: periodic Hann), the inverse real DFT written out as a dense cos / sin sum instead of
+    torch.fft.irfft: frame[n] = w[n] / n_fft * sum_k c_k (Re_k cos(2 pi k n / n_fft) - Im_k sin(2 pi k n / n_fft)), c = 1 at DC and Nyquist (whose
+    imaginary parts drop out: sin = 0 there) and 2 between.  spec [b, n_fft / 2 + 1, T] -> float64 tensor [b, (T - 1) * hop]."""
+    import numpy as np
+    re = spec_re.detach().cpu().to(torch.float64).numpy()
+    im = spec_im.detach().cpu().to(torch.float64).numpy()
+    b, F_, T = re.shape
+    assert F_ == n_fft // 2 + 1
+    w = (0.5 - 0.5 * np.cos(2.0 * math.pi * np.arange(n_fft) / n_fft)) if window is None else window.detach().cpu().to(torch.float64).numpy()
+    assert w.shape == (n_fft,)
+    cos, sin = dft_matrices_f64(n_fft)  # [F, n_fft]
+    ck = np.full(F_, 2.0)
+    ck[0] = ck[-1] = 1.0
+    sin = sin.copy()
+    sin[0] = sin[-1] = 0.0  # exactly: the imaginary parts of DC and Nyquist are ignored
+    frames = (np.einsum("bkt,kn->btn", re * ck[None, :, None], cos) - np.einsum("bkt,kn->btn", im * ck[None, :, None], sin)) * (w / n_fft)
+    out_len = n_fft + hop * (T - 1)
+    y = np.zeros((b, out_len))
+    env = np.zeros(out_len)
+    for t in range(T):
+        y[:, t * hop: t * hop + n_fft] += frames[:, t]
+        env[t * hop: t * hop + n_fft] += w * w
+    half = n_fft // 2
+    return torch.from_numpy(y[:, half: out_len - half] / env[half: out_len - half])
+
+
+def head_to_wave_f64(head, n_fft=1024, hop=256, window=None):
+    """the ISTFT head alone in float64: head.out activations [b, T, n_fft + 2] (log-magnitude | phase) -> exp, clamp(max=1e2), cos / sin -> ISTFT"""
+    F_ = n_fft // 2 + 1
+    h = head.detach().cpu().to(torch.float64).transpose(1, 2)  # [b, 2F, T]
+    mag = torch.exp(h[:, :F_]).clamp(max=1e2)
+    return istft_f64(mag * torch.cos(h[:, F_:]), mag * torch.sin(h[:, F_:]), n_fft, hop, window)
+
+
+def vocos_decode(V, mel, n_fft=1024, hop=256, window=None):
+    """vocos Vocos.decode (wrapper.py:524): backbone -> Linear(512->1026) -> exp/clip(1e2), cos/sin -> ISTFT.  window None: the periodic Hann
+    window of istft_center; a given head.istft.window goes through istft_f64 (float32 result)."""
     h = _lin(vocos_backbone(V, mel), V["head.out.weight"], V["head.out.bias"]).transpose(1, 2)
     mag, ph = h.chunk(2, dim=1)
     mag = torch.exp(mag).clamp(max=1e2)
-    return istft_center(mag * torch.cos(ph), mag * torch.sin(ph))
+    if window is None:
+        return istft_center(mag * torch.cos(ph), mag * torch.sin(ph), n_fft, hop)
+    return istft_f64(mag * torch.cos(ph), mag * torch.sin(ph), n_fft, hop, window).float()
 
 
 # ----------------------------------------------------------------------------- a1: the composed generate() chain
