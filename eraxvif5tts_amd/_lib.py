@@ -118,6 +118,10 @@ _PROTOS = {
     "f5_vocoder_decode_ragged": (_I, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _I, _P, C.POINTER(C.c_int64), _P]),
     "f5_wave_finish": (_I, [_I, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), _P, C.c_float, _I, _I, _P, _P, _P, _P, _P,
                             C.POINTER(C.c_int64), _P]),
+    "f5_wave_finish_segments": (_I, [_I, _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_uint8), _P, _I,
+                                     C.POINTER(C.c_int32), C.c_float, _I, _I, _P, _P, C.POINTER(C.c_uint8), _P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "f5_wave_stream_create_segments": (_I, [_I, C.POINTER(C.c_uint8), _I, _P, _P, _P, _I, C.POINTER(C.c_int32), C.c_float, _I, C.POINTER(C.c_uint8),
+                                            C.POINTER(_P)]),
     "f5_wave_stream_create": (_I, [_I, _I, _P, _P, _P, C.c_float, _I, C.POINTER(_P)]),
     "f5_wave_stream_push": (_I, [_P, _I, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8), _P, _P, _P, C.POINTER(C.c_int64), _P]),
     "f5_wave_stream_destroy": (_I, [_P]),

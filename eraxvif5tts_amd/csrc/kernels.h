@@ -171,23 +171,28 @@ int launch_vocos_ola_ragged(const float* frames, const UttExtents& ext, int n_ff
 
 // ---- wave_tail.hip: what follows the vocoder (rms gain, linear cross-fade, int16 PCM) in one kernel
 // Utterances k = 0 .. cnt-1 of the launch: in0 / len = extent in the concatenated fp32 wave, out0 = position of its first sample in the output
-// (out0[k] = out0[k-1] + len[k-1] - n: consecutive utterances overlap by the n cross-faded samples), gain / apply = the host form of the rms rule.
+// (out0[k] = out0[k-1] + len[k-1] - nj[k]: consecutive utterances overlap by the cross-faded samples), nj = samples of the joint BEFORE utterance k
+// (xfade_samples where k continues a segment, 0 where it begins one: plain concatenation), gain / apply = the host form of the rms rule, ridx = the
+// utterance's entry of the device rms vector (the device form), pcm32 = this utterance's PCM product is taken in fp32 although the signal is
+// double (a one-utterance segment that keeps the PCM of a call of its own).
 struct WaveTable {
     static constexpr int MAXU = 64;
     int cnt = 0;
-    int in0[MAXU], len[MAXU], out0[MAXU];
+    int in0[MAXU], len[MAXU], out0[MAXU], nj[MAXU], ridx[MAXU];
     float gain[MAXU];
-    unsigned char apply[MAXU];
+    unsigned char apply[MAXU], pcm32[MAXU];
 };
-// Output samples pos0 .. pos_end-1; sample pos belongs to the last utterance k >= first with out0[k] <= pos and, when k > 0 and it is one of k's
-// first n samples, is the cross-fade with utterance k-1's tail.  f64: a joint mixed, so the whole signal is double (numpy's promotion) and the PCM
-// product is taken in double; otherwise fp32.  rms_dev (or null): device scalar, gain applied to every utterance when *rms_dev < target.
-int launch_wave_finish(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n, const double* w_down, const double* w_up,
+// Output samples pos0 .. pos_end-1; sample pos belongs to the last utterance k >= first with out0[k] <= pos and, when it is one of k's first
+// nj[k] samples, is the cross-fade with utterance k-1's tail (nj[0] = 0 in a table that starts the list).  f64: a joint mixed, so the whole signal
+// is double (numpy's promotion) and the PCM product is taken in double; otherwise fp32.  rms_dev (or null): device vector, utterance k takes
+// g = rms_dev[ridx[k]] and the gain applies when g < target.
+int launch_wave_finish(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, const double* w_down, const double* w_up,
                        const float* rms_dev, float target, int gain_div, bool f64, float* out_f32, double* out_f64, int16_t* out_pcm, hipStream_t stream);
-// One push of a wave stream (f5_wave_stream_push): the same arithmetic with positions local to the push.  carry_in (or null): n gained fp32 samples,
-// the tail of the utterance before the table's utterance 0, which that utterance's first n samples are cross-faded with; carry_out (or null): receives
-// the last n samples of the table's last utterance, gained, from n extra threads behind pos_end -- another buffer than carry_in.
-int launch_wave_stream(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n, const double* w_down, const double* w_up,
+// One push of a wave stream (f5_wave_stream_push): the same arithmetic with positions local to the push.  carry_in (given exactly when nj[0] > 0 in
+// the push's first table): nj[0] gained fp32 samples, the tail of the utterance before the table's utterance 0, which that utterance's first samples
+// are cross-faded with; carry_out (or null): receives the last n_carry samples of the table's last utterance, gained, from n_carry extra threads
+// behind pos_end -- another buffer than carry_in.
+int launch_wave_stream(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n_carry, const double* w_down, const double* w_up,
                        const float* rms_dev, float target, int gain_div, bool f64, const float* carry_in, float* carry_out, float* out_f32,
                        double* out_f64, int16_t* out_pcm, hipStream_t stream);
 

@@ -20,7 +20,10 @@ when the loaded model carries one; otherwise the reference's own fallback branch
 """
 from __future__ import annotations
 
+import contextlib
 import os
+import re
+import types
 from typing import Optional
 
 import numpy as np
@@ -32,7 +35,7 @@ from ..model import backbones as _backbones
 from ..model.utils import convert_char_to_pinyin, get_tokenizer, list_str_to_idx
 from . import audio as _audio
 from .utils_infer import (DEFAULT_VOCAB, WaveStream, chunk_groups, chunk_text, cross_fade_concat, decode_utterances, device_tail_kind, finish_waves,
-                          load_checkpoint, load_vocoder, mel_rows_of)
+                          load_checkpoint, load_vocoder, mel_rows_of, split_voice_script)
 
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs")
 
@@ -103,6 +106,7 @@ class F5TTSWrapper:
         self.ref_audio_processed = None
         self.ref_text = None
         self.ref_audio_len = None
+        self._voices = {}  # add_voice(): name -> the fields of one more reference voice ("main" is the three fields above)
         self.target_rms = 0.1
         self.cross_fade_duration = 0.15
         # text chunks of one generate() call sampled concurrently (HIP streams); 1 = one after the other as the reference does.  Not a
@@ -135,6 +139,14 @@ class F5TTSWrapper:
 
     # ------------------------------------------------------------------ reference voice
     def preprocess_reference(self, ref_audio_path: str, ref_text: str = "", clip_short: bool = True):
+        audio, ref_text = self._preprocess_voice(ref_audio_path, ref_text, clip_short)
+        self.ref_audio_processed = audio
+        self.ref_text = ref_text
+        self.ref_audio_len = audio.shape[-1] // self.hop_length
+        return audio, ref_text
+
+    def _preprocess_voice(self, ref_audio_path, ref_text, clip_short):
+        """The steps of preprocess_reference() / add_voice(): ``(audio on the device, ref_text as it is used)``."""
         print("Converting audio...")
         aseg = _audio.Segment.from_file(ref_audio_path)
         if clip_short:
@@ -157,10 +169,57 @@ class F5TTSWrapper:
         audio = audio.to(self.device)
         if sr != self.target_sample_rate:
             audio = _audio.resample(audio, sr, self.target_sample_rate)  # on the device (f5_frontend_resample)
-        self.ref_audio_processed = audio
-        self.ref_text = ref_text
-        self.ref_audio_len = audio.shape[-1] // self.hop_length
         return audio, ref_text
+
+    # ------------------------------------------------------------------ further voices (generate_multi)
+    def add_voice(self, name: str, ref_audio_path: str, ref_text: str = "", clip_short: bool = True):
+        """One more reference voice for `generate_multi`, under ``name`` (a ``\\w+`` word other than "main", which is the voice
+        `preprocess_reference` stored): exactly the steps of `preprocess_reference`, with the prompt's mel and its rms computed once.  The main
+        fields are not touched.  Returns ``(audio, ref_text)`` as `preprocess_reference` does."""
+        if not isinstance(name, str) or not re.fullmatch(r"\w+", name) or name == "main":
+            raise ValueError(f"voice name {name!r}: a name is one \\w+ word (what a [name] tag can hold) and \"main\" is the voice of preprocess_reference()")
+        audio, ref_text = self._preprocess_voice(ref_audio_path, ref_text, clip_short)
+        self._voices[name] = self._voice_fields(audio, ref_text)
+        return audio, ref_text
+
+    def remove_voice(self, name: str):
+        if name == "main":
+            raise ValueError("\"main\" is the voice of preprocess_reference(): store another one with it")
+        del self._voices[name]
+
+    def _voice_fields(self, audio, ref_text):
+        with torch.inference_mode():
+            mel = self.model.mel_spec(audio).permute(0, 2, 1)  # what sample() makes of the raw prompt, once
+            rms = torch.sqrt(torch.mean(torch.square(audio))).to(torch.float32)  # of the stored, already boosted prompt (:529-531)
+        return dict(audio=audio, ref_text=ref_text, ref_audio_len=audio.shape[-1] // self.hop_length, mel=mel, rms=rms)
+
+    def _main_voice(self):
+        if self.ref_audio_processed is None or self.ref_text is None:
+            return None
+        cached = getattr(self, "_main_voice_cache", None)
+        if (cached is None or cached["audio"] is not self.ref_audio_processed or cached["ref_text"] != self.ref_text
+                or cached["ref_audio_len"] != self.ref_audio_len):  # (the main fields are public: a caller may have installed another prompt)
+            cached = self._voice_fields(self.ref_audio_processed, self.ref_text)
+            cached["ref_audio_len"] = self.ref_audio_len
+            self._main_voice_cache = cached
+        return cached
+
+    @property
+    def voices(self):
+        """Read-only view: name -> fields (``audio``, ``ref_text``, ``ref_audio_len``, ``mel``, ``rms``) of every stored voice, "main" included
+        once `preprocess_reference` has run."""
+        main = self._main_voice()
+        return types.MappingProxyType({**({"main": main} if main is not None else {}), **self._voices})
+
+    @contextlib.contextmanager
+    def _voice_installed(self, voice):
+        """The main fields hold ``voice``'s inside the block (the planning of generate() reads them) and are put back behind it."""
+        kept = self.ref_audio_processed, self.ref_text, self.ref_audio_len
+        self.ref_audio_processed, self.ref_text, self.ref_audio_len = voice["audio"], voice["ref_text"], voice["ref_audio_len"]
+        try:
+            yield
+        finally:
+            self.ref_audio_processed, self.ref_text, self.ref_audio_len = kept
 
     def _remove_silence_edges(self, audio, silence_threshold=-42):
         return _audio.remove_silence_edges(audio, silence_threshold)
@@ -236,9 +295,11 @@ class F5TTSWrapper:
             jobs.append((final_text_list, int(duration)))
         return (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs
 
-    def _sample_jobs(self, jobs, nfe_step, cfg_strength, sway_sampling_coef):
+    def _sample_jobs(self, jobs, nfe_step, cfg_strength, sway_sampling_coef, voices=None):
         """The mels of these jobs, in order, by the sampler their list calls for: ragged when the backbone is the DiT and there are at least 2 jobs,
-        all of at least 256 and at most 4096 frames; otherwise sample() per job, up to `chunk_streams` of them in flight."""
+        all of at least 256 and at most 4096 frames; otherwise sample() per job, up to `chunk_streams` of them in flight.  ``voices`` (one field
+        dict per job, generate_multi): every job takes its own voice's prompt mel -- in a ragged call one prompt per utterance, zero-padded
+        to the longest, with ``lens``; None: the main prompt for all."""
         transformer = getattr(self.model, "transformer", None)
         # The text chunks of one call are independent (the reference samples them one after the other, :476-533).  Here up to `chunk_streams`
         # of them are in flight at once, each on a HIP stream (and a libf5hip plan) of its own: a single-utterance sample() fills a fraction
@@ -259,18 +320,25 @@ class F5TTSWrapper:
         mels = []
         if ragged:
             with torch.inference_mode():
-                for group in ([jobs[i] for i in idx] for idx in chunk_groups([d for _, d in jobs], 0, int(self.ragged_chunks))):
-                    mels += self.model.sample_ragged(self.ref_audio_processed, [j[0][0] for j in group], [j[1] for j in group], steps=nfe_step,
+                for idx in chunk_groups([d for _, d in jobs], 0, int(self.ragged_chunks)):
+                    group = [jobs[i] for i in idx]
+                    cond, lens = self.ref_audio_processed, None
+                    if voices is not None:
+                        prompts = [voices[i]["mel"][0] for i in idx]
+                        lens = torch.tensor([int(m.shape[0]) for m in prompts], device=prompts[0].device, dtype=torch.long)
+                        cond = torch.nn.utils.rnn.pad_sequence(prompts, batch_first=True, padding_value=0.0)
+                    mels += self.model.sample_ragged(cond, [j[0][0] for j in group], [j[1] for j in group], lens=lens, steps=nfe_step,
                                                      cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
         for i, (final_text_list, duration) in enumerate(jobs if not ragged else []):
+            prompt = self.ref_audio_processed if voices is None else voices[i]["mel"]
             with torch.inference_mode():
                 if n_streams > 1:
                     with torch.cuda.stream(streams[i % n_streams]):
-                        generated, _ = self.model.sample(cond=self.ref_audio_processed, text=final_text_list, duration=duration, steps=nfe_step,
+                        generated, _ = self.model.sample(cond=prompt, text=final_text_list, duration=duration, steps=nfe_step,
                                                          cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, return_trajectory=False,
                                                          defer_guard=True)
                 else:
-                    generated, _ = self.model.sample(cond=self.ref_audio_processed, text=final_text_list, duration=duration, steps=nfe_step,
+                    generated, _ = self.model.sample(cond=prompt, text=final_text_list, duration=duration, steps=nfe_step,
                                                      cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, return_trajectory=False)
                 mels.append(generated)
         if n_streams > 1:
@@ -399,6 +467,174 @@ class F5TTSWrapper:
                 mels = self._sample_jobs([jobs[i] for i in group], nfe_step, cfg_strength, sway_sampling_coef)
                 with torch.inference_mode():
                     rows, row_start, got = mel_rows_of(mels, self.ref_audio_len)
+                    if got != frames[first: first + len(group)]:
+                        raise RuntimeError(f"the sampler returned {got} generated frames where {frames[first: first + len(group)]} were planned")
+                    wave_buf, counts = decode_utterances(self.vocoder, kind, rows, row_start, got)
+                    signal, pcm = session.push(wave_buf, counts)
+                    piece = (pcm if return_pcm16 else signal).cpu().numpy()
+                first += len(group)
+                yield piece, self.target_sample_rate
+        finally:
+            session.close()
+
+    # ------------------------------------------------------------------ one script in several voices
+    def _plan_multi(self, text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor):
+        """`_plan_jobs` per piece of the script, each with its voice's fields: the arguments' defaults, the flat job list, the voice (field
+        dict) of every job and the jobs per segment (one segment per piece, in order)."""
+        voices = self.voices
+        if "main" not in voices:
+            raise ValueError("Reference audio not preprocessed. Call preprocess_reference() first.")
+        settings, jobs, job_voices, seg_sizes = None, [], [], []
+        for name, piece in split_voice_script(text, voices):
+            print(f"Voice: {name}")
+            with self._voice_installed(voices[name]):
+                settings, piece_jobs = self._plan_jobs(piece, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration,
+                                                       use_duration_predictor)
+            if piece_jobs:
+                jobs += piece_jobs
+                job_voices += [voices[name]] * len(piece_jobs)
+                seg_sizes.append(len(piece_jobs))
+        if not jobs:
+            raise RuntimeError("No audio generated")
+        return settings, jobs, job_voices, seg_sizes
+
+    @staticmethod
+    def _voice_rms_table(job_voices):
+        """``(rms vector on the device: one value per distinct voice, index of every job's voice in it)``"""
+        distinct, index = [], []
+        for v in job_voices:
+            at = next((i for i, d in enumerate(distinct) if d is v), None)
+            if at is None:
+                at = len(distinct)
+                distinct.append(v)
+            index.append(at)
+        return torch.stack([v["rms"].reshape(()) for v in distinct]), index
+
+    @staticmethod
+    def _own_pcm_flags(seg_sizes):
+        """per job: it is a segment of its own, whose generate() call forms its int16 from the fp32 product (`finish_waves`'s ``pcm_f32``)"""
+        return [g == 1 for g in seg_sizes for _ in range(g)]
+
+    def generate_multi(self, text: str, output_path: Optional[str] = None, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
+                       sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
+                       cross_fade_duration: Optional[float] = None, use_duration_predictor: Optional[bool] = None,
+                       return_numpy: bool = False, return_spectrogram: bool = False, return_pcm16: bool = False, remove_silence: bool = False):
+        """One script in several voices (the reference's infer_cli.py:290-354): ``text`` is cut at its ``[name]`` tags
+        (`utils_infer.split_voice_script`; voices come from `preprocess_reference` -- "main" -- and `add_voice`), every piece is planned as
+        ``generate()`` plans it with that voice's prompt, and ALL chunks of ALL pieces are sampled as ragged batches with one prompt per
+        utterance, decoded by one ragged vocoder call and finished by one segmented wave tail: cross-fades inside a piece, plain
+        concatenation between pieces, each utterance's gain by its own voice's prompt rms.  After one ``torch.manual_seed`` and with
+        attention dropout off the result is byte for byte ``np.concatenate([generate(piece, ...) with that voice installed for voice, piece
+        in split_voice_script(text, voices)])`` -- float (float64 as soon as one piece cross-faded), ``return_pcm16`` and the written file;
+        ``remove_silence`` applies to the whole result (infer_cli.py:360-363).  Same arguments and return shapes as ``generate()``."""
+        (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs, job_voices, seg_sizes = self._plan_multi(
+            text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
+        return self._generate_multi_jobs(jobs, job_voices, seg_sizes, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration,
+                                         return_numpy, return_spectrogram, return_pcm16, remove_silence)
+
+    def _generate_multi_jobs(self, jobs, job_voices, seg_sizes, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration,
+                             return_numpy, return_spectrogram, return_pcm16, remove_silence=False):
+        """`_generate_jobs` for a flat job list over several voices: ``job_voices[i]`` is job i's voice, ``seg_sizes`` the jobs per piece."""
+        mels = self._sample_jobs(jobs, nfe_step, cfg_strength, sway_sampling_coef, voices=job_voices)
+        want_spec = return_spectrogram or output_path is not None
+        want_float = not return_pcm16 or output_path is not None
+        final_wave = final_pcm = None
+        generated_waves, spectrograms = [], []
+        skips = [v["ref_audio_len"] for v in job_voices]
+        with torch.inference_mode():
+            kind = device_tail_kind(self.vocoder, *[v["audio"] for v in job_voices], *mels)
+            if kind is not None and kind == self.mel_spec_type and min(int(m.shape[1]) - k for m, k in zip(mels, skips)) >= 2:
+                rows, row_start, frames = mel_rows_of(mels, skips)
+                wave_buf, samples = decode_utterances(self.vocoder, kind, rows, row_start, frames)
+                rms, rms_index = self._voice_rms_table(job_voices)
+                done = finish_waves(wave_buf, samples, cross_fade_duration, self.target_sample_rate, rms=rms, target_rms=self.target_rms,
+                                    want_float=want_float or remove_silence, want_pcm16=return_pcm16, segments=seg_sizes, rms_index=rms_index,
+                                    pcm_f32=self._own_pcm_flags(seg_sizes))
+                if want_spec:
+                    spectrograms = [rows[r: r + t].t().cpu().numpy() for r, t in zip(row_start, frames)]
+                if done is not None:
+                    if remove_silence:
+                        done, remove_silence = self._silence_step(*done), False
+                    final_wave = done[0].cpu().numpy() if want_float else None
+                    final_pcm = done[1].cpu().numpy() if return_pcm16 else None
+                else:  # utterances shorter than their cross-fades (F5_ENOTSUP): the decoded waves take the host functions
+                    for w, v in zip(torch.split(wave_buf, samples), job_voices):
+                        generated_waves.append((w * v["rms"] / self.target_rms if bool(v["rms"] < self.target_rms) else w).cpu().numpy())
+            else:
+                for generated, v in zip(mels, job_voices):
+                    generated = generated.to(torch.float32)[:, v["ref_audio_len"]:, :].permute(0, 2, 1)
+                    if self.mel_spec_type == "vocos":
+                        generated_wave = self.vocoder.decode(generated)
+                    elif self.mel_spec_type == "bigvgan":
+                        generated_wave = self.vocoder(generated)
+                    rms = torch.sqrt(torch.mean(torch.square(v["audio"])))  # of the stored, already boosted prompt (:529-531)
+                    if rms < self.target_rms:
+                        generated_wave = generated_wave * rms / self.target_rms
+                    generated_waves.append(generated_wave.squeeze().cpu().numpy())
+                    if want_spec:
+                        spectrograms.append(generated.squeeze().cpu().numpy())
+
+        if final_wave is None and final_pcm is None:  # the host tail: cross_fade_concat per piece, np.concatenate of the pieces
+            from ..streaming.wire import pcm16_bytes
+            pieces, k = [], 0
+            for g in seg_sizes:
+                pieces.append(cross_fade_concat(generated_waves[k: k + g], cross_fade_duration, self.target_sample_rate))
+                k += g
+            final_wave = np.concatenate(pieces)
+            if return_pcm16:  # (each piece's int16 from its own dtype, as its generate() call forms it)
+                final_pcm = np.concatenate([np.frombuffer(pcm16_bytes(p), dtype=np.int16) for p in pieces])
+        if remove_silence:  # the host tails (a foreign vocoder, or joints that chain): the same rule by the host functions
+            final_wave, final_pcm = self._silence_step(final_wave, final_pcm)
+        combined_spectrogram = np.concatenate(spectrograms, axis=1) if spectrograms else None
+        if output_path is not None:
+            output_dir = os.path.dirname(output_path)
+            if output_dir and not os.path.exists(output_dir):
+                os.makedirs(output_dir)
+            _audio.write_wav(output_path, final_wave, self.target_sample_rate)
+            if return_spectrogram:
+                np.save(os.path.splitext(output_path)[0] + "_spec.npy", combined_spectrogram)
+            if not return_numpy:
+                return output_path
+        if return_pcm16:
+            final_wave = final_pcm
+        if return_spectrogram:
+            return final_wave, self.target_sample_rate, combined_spectrogram
+        return final_wave, self.target_sample_rate
+
+    def generate_multi_stream(self, text: str, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
+                              sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
+                              cross_fade_duration: Optional[float] = None, use_duration_predictor: Optional[bool] = None,
+                              return_numpy: bool = True, return_spectrogram: bool = False, return_pcm16: bool = False):
+        """`generate_multi` as a generator of ``(piece, sample_rate)``, as `generate_stream` is to `generate`: groups of consecutive chunks of
+        the flat list (`utils_infer.chunk_groups`, the first ``stream_first_chunks`` on their own), per group one sampler call, one ragged
+        decode and one push into a segmented `WaveStream`; a group that ends a voice's piece emits all of it.  The pieces, concatenated,
+        are byte for byte what ``generate_multi()`` returns (attention dropout off).  When the streamed tail does not apply -- decided
+        before any sampling, by `generate_stream`'s conditions -- the generator yields exactly once, with ``generate_multi()``'s result."""
+        (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs, job_voices, seg_sizes = self._plan_multi(
+            text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
+        skips = [v["ref_audio_len"] for v in job_voices]
+        frames = [min(max(max(len(tokens[0]), int(v["mel"].shape[1])) + 1, duration), 4096) - v["ref_audio_len"]
+                  for (tokens, duration), v in zip(jobs, job_voices)]  # (`_generated_frames` with each job's own prompt)
+        kind = device_tail_kind(self.vocoder, *[v["audio"] for v in job_voices])
+        session = None
+        if kind is not None and kind == self.mel_spec_type and min(frames) >= 2:
+            samples = [(t - 1) * self.hop_length for t in frames] if kind == "vocos" else [t * self.vocoder._total_up() for t in frames]
+            with torch.inference_mode():
+                rms, rms_index = self._voice_rms_table(job_voices)
+                session = WaveStream(samples, cross_fade_duration, self.target_sample_rate, rms=rms, target_rms=self.target_rms,
+                                     want_float=not return_pcm16, want_pcm16=return_pcm16, segments=seg_sizes, rms_index=rms_index,
+                                     pcm_f32=self._own_pcm_flags(seg_sizes))
+        if session is None or not session.ok:
+            wave, rate = self._generate_multi_jobs(jobs, job_voices, seg_sizes, None, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration,
+                                                   True, False, return_pcm16)
+            yield wave, rate
+            return
+        try:
+            first = 0
+            for group in chunk_groups([d for _, d in jobs], int(self.stream_first_chunks), int(self.ragged_chunks)):
+                mels = self._sample_jobs([jobs[i] for i in group], nfe_step, cfg_strength, sway_sampling_coef, voices=[job_voices[i] for i in group])
+                with torch.inference_mode():
+                    rows, row_start, got = mel_rows_of(mels, [skips[i] for i in group])
                     if got != frames[first: first + len(group)]:
                         raise RuntimeError(f"the sampler returned {got} generated frames where {frames[first: first + len(group)]} were planned")
                     wave_buf, counts = decode_utterances(self.vocoder, kind, rows, row_start, got)

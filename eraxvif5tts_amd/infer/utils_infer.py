@@ -207,6 +207,58 @@ def plan_wave_tail(lengths, cross_fade_duration, sample_rate=target_sample_rate)
                 device_ok=device_ok)
 
 
+def plan_wave_tail_segments(lengths, seg_sizes, cross_fade_duration, sample_rate=target_sample_rate):
+    """`plan_wave_tail` for ``np.concatenate([cross_fade_concat(seg) for seg in segments])`` -- a script in several voices: cross-fades inside
+    a segment, plain concatenation between segments -- from the lengths alone.  ``seg_sizes`` lists the utterances per segment, in order
+    (they sum to ``len(lengths)``).  ``joints`` holds the n of every joint of the flat list (0 between segments), ``out_offsets`` / ``total`` /
+    ``mixed`` / ``dtype`` describe the concatenated result (float64 throughout once ANY joint mixed: np.concatenate promotes the segments
+    that mixed nothing too), ``n`` is the cross-fade length the device kernel takes at in-segment joints, ``seg_start`` the 0/1 array
+    ``f5_wave_finish_segments`` takes, and ``device_ok`` its chaining rule per segment: in a segment of two or more utterances the first and
+    the last hold at least n samples, every inner one 2 n; a one-utterance segment has no constraint."""
+    lengths, seg_sizes = [int(x) for x in lengths], [int(x) for x in seg_sizes]
+    assert sum(seg_sizes) == len(lengths) and all(g >= 1 for g in seg_sizes)
+    joints, offsets, seg_start, total, mixed, device_ok, k = [], [], [], 0, False, True, 0
+    for g in seg_sizes:
+        plan = plan_wave_tail(lengths[k: k + g], cross_fade_duration, sample_rate)
+        if k:
+            joints.append(0)
+        joints += plan["joints"]
+        offsets += [total + o for o in plan["out_offsets"]]
+        seg_start += [1] + [0] * (g - 1)
+        total += plan["total"]
+        mixed = mixed or plan["mixed"]
+        device_ok = device_ok and plan["device_ok"]
+        k += g
+    nx = max(int(cross_fade_duration * sample_rate), 0) if cross_fade_duration > 0 else 0
+    return dict(joints=joints, out_offsets=offsets, total=total, mixed=mixed, dtype=np.float64 if mixed else np.float32,
+                n=nx if max(seg_sizes) >= 2 else 0, device_ok=device_ok, seg_start=seg_start)
+
+
+def split_voice_script(text, voices, show_info=print):
+    """A script with ``[name]`` tags -> ``[(voice, text)]``, by the reference's rule (infer_cli.py:306-324): the text is cut in front of every
+    ``[word]`` tag, blank pieces are skipped, a piece's voice is the tag it starts with -- "main" when it starts with none or the name is not in
+    ``voices`` (with the reference's two messages) -- and every tag is removed from the piece's text, which is stripped.  One deviation: a piece
+    whose text is empty after that is dropped (the reference hands "" on and fails inside infer_batch_process)."""
+    tag = r"\[(\w+)\]"
+    pieces = []
+    for chunk in re.split(r"(?=\[\w+\])", text):
+        if not chunk.strip():
+            continue
+        match = re.match(tag, chunk)
+        if match:
+            voice = match[1]
+        else:
+            show_info("No voice tag found, using main.")
+            voice = "main"
+        if voice not in voices:
+            show_info(f"Voice {voice} not found, using main.")
+            voice = "main"
+        piece = re.sub(tag, "", chunk).strip()
+        if piece:
+            pieces.append((voice, piece))
+    return pieces
+
+
 _xfade_tables = {}
 
 
@@ -218,15 +270,18 @@ def _xfade_weights(n, dev):
     return _xfade_tables[key]
 
 
-def _rms_forms(rms, B, target_rms):
+def _rms_forms(rms, B, target_rms, rms_index=None):
     """The rms rule in the forms the library takes (`finish_waves` documents ``rms``): ``(gain_host, apply_host, rms_dev)``, ctypes arrays of B
-    host gains with the decision ``rms_i < target_rms`` taken here exactly as the host loop takes it, or the device scalar; all None: no gain."""
+    host gains with the decision ``rms_i < target_rms`` taken here exactly as the host loop takes it, or the device scalar -- with ``rms_index``
+    (one entry per utterance) the device vector of one value per voice; all None: no gain."""
     import ctypes as C
     gain_host = apply_host = rms_dev = None
     if torch.is_tensor(rms) and rms.is_cuda:
-        assert rms.dtype == torch.float32 and rms.numel() == 1
-        rms_dev = rms.reshape(1).contiguous()
+        assert rms.dtype == torch.float32 and (rms.numel() == 1 if rms_index is None else rms.ndim == 1 and rms.numel() >= 1)
+        assert rms_index is None or (len(rms_index) == B and all(0 <= int(i) < rms.numel() for i in rms_index))
+        rms_dev = rms.reshape(-1).contiguous()
     elif rms is not None:
+        assert rms_index is None, "rms_index goes with a device vector of rms values"
         per_utt = list(rms) if isinstance(rms, (list, tuple)) else [rms] * B
         assert len(per_utt) == B
         on_dev = [i for i, r in enumerate(per_utt) if torch.is_tensor(r) and r.is_cuda]
@@ -245,7 +300,7 @@ def _rms_forms(rms, B, target_rms):
 
 
 def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_sample_rate, rms=None, target_rms=target_rms, want_float=True,
-                 want_pcm16=False, gain_divide=False):
+                 want_pcm16=False, gain_divide=False, segments=None, rms_index=None, pcm_f32=None):
     """``f5_wave_finish`` over the utterances held back to back in ``wave`` (fp32, on the GPU; ``samples[i]`` each): the rms rule, the linear
     cross-fade of `cross_fade_concat` and the int16 PCM of ``streaming.wire.pcm16_bytes`` in one kernel.  Returns ``(signal, pcm16)`` as device
     tensors (None where not asked for) -- ``signal`` float64 when a joint mixed, float32 otherwise, as numpy's promotion gives -- or ``None`` when
@@ -253,17 +308,23 @@ def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_samp
     ``rms``: None (no gain); a 0-dim fp32 tensor on the GPU (the gain applies when ``rms < target_rms``, decided on the device: no host wait);
     or host values -- one number / 0-dim CPU tensor for all utterances, or one per utterance -- with the decision ``rms_i < target_rms`` taken
     here exactly as the host loop takes it.  The gain is ``w * rms / target_rms`` as torch evaluates it on a GPU tensor (fp32 product, then the
-    fp32 reciprocal of the host scalar), or with a true fp32 divide (``gain_divide``: torch on CPU tensors)."""
+    fp32 reciprocal of the host scalar), or with a true fp32 divide (``gain_divide``: torch on CPU tensors).
+    ``segments`` (utterances per segment, in order; ``f5_wave_finish_segments``): the cross-fade runs inside each segment and the segments are
+    joined without one -- ``np.concatenate([cross_fade_concat(seg) for seg in segments])``, see `plan_wave_tail_segments`.  ``rms_index`` (one
+    entry per utterance): ``rms`` is then a 1-D fp32 GPU tensor with one value per voice and utterance k takes ``rms[rms_index[k]]``.
+    ``pcm_f32`` (one flag per utterance, only for one-utterance segments): that utterance's int16 is the one a call over it alone gives -- the
+    product in fp32 -- although the whole result is float64; without it ``pcm16`` is ``pcm16_bytes`` of the returned signal."""
     import ctypes as C
 
     from .. import _lib
     lib = _lib.load()
     B = len(samples)
     assert wave.is_cuda and wave.dtype == torch.float32 and wave.is_contiguous() and wave.numel() == sum(samples) and B >= 1
-    plan = plan_wave_tail(samples, cross_fade_duration, sample_rate)
+    segmented = segments is not None or rms_index is not None or pcm_f32 is not None
+    plan = plan_wave_tail_segments(samples, [B] if segments is None else segments, cross_fade_duration, sample_rate)
     n, mixed = plan["n"], plan["n"] > 0
-    total = sum(samples) - (B - 1) * n
-    gain_host, apply_host, rms_dev = _rms_forms(rms, B, target_rms)
+    total = sum(samples) - n * (B - sum(plan["seg_start"]))
+    gain_host, apply_host, rms_dev = _rms_forms(rms, B, target_rms, rms_index)
     w_down, w_up = _xfade_weights(n, wave.device) if mixed else (None, None)
     if total <= 0 or not plan["device_ok"]:
         out = pcm = None  # the library decides (and says why); nothing is allocated for a call it will refuse
@@ -271,9 +332,16 @@ def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_samp
         out = torch.empty(total, device=wave.device, dtype=torch.float64 if mixed else torch.float32) if want_float else None
         pcm = torch.empty(total, device=wave.device, dtype=torch.int16) if want_pcm16 else None
     got = C.c_int64(0)
-    rc = lib.f5_wave_finish(B, _lib.ptr(wave), (C.c_int32 * B)(*[int(x) for x in samples]), gain_host, apply_host, _lib.ptr(rms_dev),
-                            float(target_rms), 1 if gain_divide else 0, int(n), _lib.ptr(w_down), _lib.ptr(w_up),
-                            _lib.ptr(out) if not mixed else None, _lib.ptr(out) if mixed else None, _lib.ptr(pcm), C.byref(got), _lib.stream_ptr())
+    head = (float(target_rms), 1 if gain_divide else 0, int(n), _lib.ptr(w_down), _lib.ptr(w_up))
+    tail = (_lib.ptr(out) if not mixed else None, _lib.ptr(out) if mixed else None, _lib.ptr(pcm), C.byref(got), _lib.stream_ptr())
+    arr = (C.c_int32 * B)(*[int(x) for x in samples])
+    if segmented:
+        index = (C.c_int32 * B)(*[int(i) for i in rms_index]) if rms_index is not None and rms_dev is not None else None
+        rc = lib.f5_wave_finish_segments(B, _lib.ptr(wave), arr, (C.c_uint8 * B)(*plan["seg_start"]), gain_host, apply_host, _lib.ptr(rms_dev),
+                                         int(rms_dev.numel()) if rms_dev is not None else 0, index, *head,
+                                         (C.c_uint8 * B)(*[1 if f else 0 for f in pcm_f32]) if pcm_f32 is not None else None, *tail)
+    else:
+        rc = lib.f5_wave_finish(B, _lib.ptr(wave), arr, gain_host, apply_host, _lib.ptr(rms_dev), *head, *tail)
     if rc == _lib.F5_ENOTSUP:
         return None
     _lib.check(rc, "wave_finish")
@@ -302,12 +370,14 @@ def chunk_groups(durations, first=0, group_max=8, max_rows=16384):
     return groups
 
 
-def stream_emitted_counts(lengths, group_sizes, cross_fade_duration, sample_rate=target_sample_rate):
+def stream_emitted_counts(lengths, group_sizes, cross_fade_duration, sample_rate=target_sample_rate, segments=None):
     """Output samples each push of a `WaveStream` over waves of these ``lengths`` emits when the list is pushed in consecutive groups of
     ``group_sizes`` utterances: a push that ends before the last utterance emits up to where the next utterance's first sample lands
     (`plan_wave_tail`'s ``out_offsets``), the last push the rest.  Returns ``(counts, dtype)``; the counts sum to the plan's ``total`` and the
-    dtype is the whole result's -- float64 when any joint mixes, for EVERY piece, float32 otherwise."""
-    plan = plan_wave_tail(lengths, cross_fade_duration, sample_rate)
+    dtype is the whole result's -- float64 when any joint mixes, for EVERY piece, float32 otherwise.  ``segments``: the utterances per segment
+    of a segmented stream (`plan_wave_tail_segments`); a push that ends a segment emits all of it."""
+    plan = (plan_wave_tail(lengths, cross_fade_duration, sample_rate) if segments is None
+            else plan_wave_tail_segments(lengths, segments, cross_fade_duration, sample_rate))
     assert sum(group_sizes) == len(lengths) and all(g >= 1 for g in group_sizes)
     bounds = plan["out_offsets"] + [plan["total"]]
     counts, k = [], 0
@@ -322,28 +392,40 @@ class WaveStream:
     from the frame counts, before any sampling -- and ``push(wave, samples)`` hands over the next few, back to back in one fp32 GPU buffer.  The
     pieces, concatenated, are byte-identical to ``finish_waves`` over the whole list; every piece has the whole result's dtype.  ``rms``: None, a
     0-dim fp32 GPU tensor, one host value, or one host value per utterance of the whole list.  ``ok`` is False when the library would refuse
-    the list (`plan_wave_tail`'s ``device_ok``): then nothing is created and the caller keeps its one-shot route.  ``close()`` frees the session."""
+    the list (`plan_wave_tail`'s ``device_ok``): then nothing is created and the caller keeps its one-shot route.  ``close()`` frees the session.
+    ``segments`` / ``rms_index`` / ``pcm_f32`` as for `finish_waves`, over the whole list (``f5_wave_stream_create_segments``)."""
 
     def __init__(self, samples, cross_fade_duration=0.0, sample_rate=target_sample_rate, rms=None, target_rms=target_rms, want_float=True,
-                 want_pcm16=False, gain_divide=False):
+                 want_pcm16=False, gain_divide=False, segments=None, rms_index=None, pcm_f32=None):
         import ctypes as C
 
         from .. import _lib
         self.samples = [int(x) for x in samples]
-        self.plan = plan_wave_tail(self.samples, cross_fade_duration, sample_rate)
+        segmented = segments is not None or rms_index is not None or pcm_f32 is not None
+        self.plan = plan_wave_tail_segments(self.samples, [len(self.samples)] if segments is None else segments, cross_fade_duration, sample_rate)
         self.n, self.mixed = self.plan["n"], self.plan["n"] > 0
         self.ok = bool(self.plan["device_ok"]) and min(self.samples) > 0
         assert want_float or want_pcm16
         self.want_float, self.want_pcm16, self.done, self._handle = want_float, want_pcm16, 0, None
-        self._gain_host, self._apply_host, self._rms_dev = _rms_forms(rms, len(self.samples), target_rms)
+        self._gain_host, self._apply_host, self._rms_dev = _rms_forms(rms, len(self.samples), target_rms, rms_index)
         if not self.ok:
             return
         dev = torch.device("cuda", torch.cuda.current_device())
         self._tables = _xfade_weights(self.n, dev) if self.mixed else (None, None)  # (kept alive with the session, which reads them in every push)
         handle = C.c_void_p()
-        _lib.check(_lib.load().f5_wave_stream_create(len(self.samples), int(self.n), _lib.ptr(self._tables[0]), _lib.ptr(self._tables[1]),
-                                                    _lib.ptr(self._rms_dev), float(target_rms), 1 if gain_divide else 0, C.byref(handle)),
-                   "wave_stream_create")
+        B = len(self.samples)
+        if segmented:
+            index = (C.c_int32 * B)(*[int(i) for i in rms_index]) if rms_index is not None and self._rms_dev is not None else None
+            rc = _lib.load().f5_wave_stream_create_segments(B, (C.c_uint8 * B)(*self.plan["seg_start"]), int(self.n), _lib.ptr(self._tables[0]),
+                                                            _lib.ptr(self._tables[1]), _lib.ptr(self._rms_dev),
+                                                            int(self._rms_dev.numel()) if self._rms_dev is not None else 0, index,
+                                                            float(target_rms), 1 if gain_divide else 0,
+                                                            (C.c_uint8 * B)(*[1 if f else 0 for f in pcm_f32]) if pcm_f32 is not None else None,
+                                                            C.byref(handle))
+        else:
+            rc = _lib.load().f5_wave_stream_create(B, int(self.n), _lib.ptr(self._tables[0]), _lib.ptr(self._tables[1]), _lib.ptr(self._rms_dev),
+                                                   float(target_rms), 1 if gain_divide else 0, C.byref(handle))
+        _lib.check(rc, "wave_stream_create")
         self._handle = handle
 
     def push(self, wave, samples):
@@ -508,15 +590,18 @@ def device_tail_kind(vocoder, *tensors):
 
 def mel_rows_of(mels, skip):
     """[1, N_i, mel] sampler outputs -> (rows [R, mel] fp32 contiguous, row_start, frames) with the first ``skip`` frames of each left out by the
-    offset.  The ragged sampler hands back views of ONE buffer: that buffer is taken as it is (no copy); anything else is concatenated once."""
+    offset (``skip``: one int, or one per utterance -- prompts of several voices).  The ragged sampler hands back views of ONE buffer: that buffer
+    is taken as it is (no copy); anything else is concatenated once."""
     mel = mels[0].shape[-1]
-    frames = [int(m.shape[1]) - skip for m in mels]
+    skips = [int(x) for x in skip] if isinstance(skip, (list, tuple)) else [int(skip)] * len(mels)
+    assert len(skips) == len(mels)
+    frames = [int(m.shape[1]) - k for m, k in zip(mels, skips)]
     st = mels[0].untyped_storage()
     if all(m.dtype == torch.float32 and m.is_contiguous() and m.untyped_storage().data_ptr() == st.data_ptr() and m.storage_offset() % mel == 0
            for m in mels):
         rows = torch.empty(0, dtype=torch.float32, device=mels[0].device).set_(st, 0, (st.nbytes() // (4 * mel), mel), (mel, 1))
-        return rows, [m.storage_offset() // mel + skip for m in mels], frames
-    rows = torch.cat([m[0, skip:].to(torch.float32) for m in mels])
+        return rows, [m.storage_offset() // mel + k for m, k in zip(mels, skips)], frames
+    rows = torch.cat([m[0, k:].to(torch.float32) for m, k in zip(mels, skips)])
     starts, r = [], 0
     for t in frames:
         starts.append(r)

@@ -467,6 +467,37 @@ F5_API int f5_wave_stream_push(f5_wave_stream_t s, int B, const float* wave, con
                                const uint8_t* apply_host, float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* emitted,
                                f5_stream_t stream);
 F5_API int f5_wave_stream_destroy(f5_wave_stream_t s);
+/* The same tail over SEGMENTS, for a script spoken in several voices (the reference's infer_cli.py:290-354 runs each tagged piece on its own and
+ * joins the pieces with np.concatenate): cross-fades inside a segment, plain concatenation between segments, and the rms rule per voice.  Detected
+ * by symbol like the entries above.  f5_wave_finish / f5_wave_stream_create ARE these calls with one segment and rms index 0: one kernel, the same
+ * arithmetic (wave_gain, two fp64 products and one fp64 sum without contraction, saturating PCM), the same bytes.
+ *   segments    seg_start_host[B] (host; NULL: one segment): a non-zero entry means utterance k begins a new segment; entry 0 always begins one.
+ *               The joint before utterance k has n_k = xfade_samples when k continues a segment and n_k = 0 when it begins one: no table read, no
+ *               left operand, no carry
+ *   chaining    per segment: in a segment of two or more utterances the first and the last hold at least n samples and every inner one 2 n; a
+ *               one-utterance segment has no constraint.  A violation answers F5_ENOTSUP naming the utterance
+ *   dtype       the result is float64 exactly when xfade_samples > 0 and at least one utterance continues a segment (np.concatenate then promotes
+ *               everything, segments that mixed nothing included, and the PCM product is taken in fp64 for every sample); otherwise fp32.  For a
+ *               stream this is a property of the whole list.  *total_samples_out = sum samples - n * (number of in-segment joints)
+ *   rms         rms_dev is an array of n_rms >= 1 dev f32 values, one per voice, and rms_index_host[B] (host; NULL: all 0; each in [0, n_rms)) names
+ *               each utterance's entry: utterance k takes g = rms_dev[rms_index[k]] and the gain applies when g < target_rms, decided in the kernel;
+ *               at a joint the left operand uses utterance k - 1's own entry.  gain_host / apply_host stay available, exclusive with rms_dev
+ *   stream      seg_start_host and rms_index_host cover the WHOLE list (total_utterances entries, copied at create); the session is pushed with
+ *               f5_wave_stream_push and freed with f5_wave_stream_destroy.  A push whose last utterance ends a segment emits all of it and carries
+ *               nothing, and the next push's first utterance reads no carry; so does a push that ends the list.  For every way of cutting the list
+ *               into consecutive pushes the pieces, concatenated, are byte-identical to the one-shot call.  The query form of a push (all outputs
+ *               NULL) answers the emitted count and does not advance the session
+ *   pcm_f32     pcm_f32_host[B] (host; NULL: none): a non-zero entry keeps utterance k's PCM product in fp32 inside a float64 result -- the int16
+ *               that a call over this utterance alone gives (trunc(fp32(x * 32767)) can differ from trunc(double(x) * 32767) by one).  Only for an
+ *               utterance that is a segment of its own (F5_EINVAL otherwise); without it the PCM follows the dtype rule above for every sample
+ * Lists longer than one kernel table are split into tables that overlap by one utterance; a segment boundary may fall on the overlap. */
+F5_API int f5_wave_finish_segments(int B, const float* wave, const int32_t* samples_host, const uint8_t* seg_start_host, const float* gain_host,
+                                   const uint8_t* apply_host, const float* rms_dev, int n_rms, const int32_t* rms_index_host, float target_rms,
+                                   int gain_div, int xfade_samples, const double* w_down, const double* w_up, const uint8_t* pcm_f32_host,
+                                   float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* total_samples_out, f5_stream_t stream);
+F5_API int f5_wave_stream_create_segments(int total_utterances, const uint8_t* seg_start_host, int xfade_samples, const double* w_down,
+                                          const double* w_up, const float* rms_dev, int n_rms, const int32_t* rms_index_host, float target_rms,
+                                          int gain_div, const uint8_t* pcm_f32_host, f5_wave_stream_t* out);
 /* "Remove silence" on the finished wave, on the device: the reference's remove_silence_for_generated_wav (infer/utils_infer.py:569-578: pydub's
  * split_on_silence on the exported 16-bit file, the kept parts written back), detected by symbol like the round-5 entries.
  *   rule       this package's stand-in for pydub, infer/audio.py split_on_silence / detect_nonsilent / detect_silence / Segment.slice_ms /
