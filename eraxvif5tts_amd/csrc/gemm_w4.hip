@@ -18,9 +18,17 @@
 //     boundaries, so a tile's first two stages land before / under the previous tile's epilogue;
 //   * LDS image: row r (128 bytes), logical 16-byte chunk c at physical chunk c ^ ((r >> 1) & 7) -- applied on the DMA source address and on the
 //     read address -- every 16-lane group of a ds_read_b128 covers the 16 slots of the 256-byte bank row once (SQ_LDS_BANK_CONFLICT = 0);
-//   * same MFMA (weights on the row index), same K order, same start value (bias, or 0 under the LayerNorm fold) and the same epilogue arithmetic
-//     as gemm_fast.hip's persistent build: a wave's 128 features are treated as two 64-feature halves = two "waves" of that kernel, so the output
-//     bits do not depend on which of the two kernels a launch takes (tests/test_gpu_ops.py::test_w4_kernel_equals_the_8_wave_kernel).
+//   * same MFMA (weights on the row index; tokens in the whole-line store builds below), same K order, same start value (bias, or 0 under the
+//     LayerNorm fold) and the same epilogue arithmetic as gemm_fast.hip's persistent build: a wave's 128 features are treated as two 64-feature
+//     halves = two "waves" of that kernel, so the output bits do not depend on which of the two kernels a launch takes
+//     (tests/test_gpu_ops.py::test_w4_kernel_equals_the_8_wave_kernel).
+//   * the store builds on 256-row tiles (QKV + RoPE, FF1 + GELU; WL below) swap the MFMA's operand roles -- tokens on its row index -- and permute the
+//     weight rows on their way into LDS (row 16 i + c of a wave's 128 <- weight row 8 c + i; only the eight per-lane constants voffW[] differ), so that a
+//     lane's eight accumulators over the feature fragments are eight consecutive features of one token: one 16-byte store, 16 adjacent lanes write 256
+//     contiguous bytes, an instruction 8 whole lines instead of 64 separate 16-byte pieces (store_wave_impl; no cross-lane instruction).  Same products,
+//     same K order, same epilogue operations per element: same bits.  Probe (tools/gemm_w4_probe.hip schedules 70 - 73,
+//     profiles/w4_whole_line_epilogue_probe.txt): - 15 .. - 20 us at the QKV and FF1 shapes; the in-place residual epilogue gained less than a third
+//     of its read-modify-write cost there and keeps the map above, as do the 128-row tiles (not measured);
 //   * a second tile height (template parameter MI = 4: 128 x 256, 64 x 128 per wave) for small batches; there the folded projections also finish the
 //     LayerNorm fold's row statistics themselves (finish_stats) and the kernel touches the weights of the launches behind it.
 // Launch conditions (gemm_w4_ok): bf16 / fp16-fold operands, M % 128 == 0, N % 256 == 0, K % 128 == 0, K >= 256, the lean operand forms of the
@@ -49,6 +57,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int NP = MI + 8, NR = MI + 8, NMF = 16 * MI;       // requests per wave, fragment reads per sub-step, MFMAs per iteration
     constexpr int LNF_AREA = MI == 4 ? 11264 : 2048;  // per wave: c1[128] | c2[128] | (mean, rstd)[128 rows] (| 16 partial planes x 64 rows | pivots of 64 rows)
     constexpr int EPI_BYTES = 4 * LNF_AREA > EPI_LDS_BYTES ? 4 * LNF_AREA : EPI_LDS_BYTES;
+    // WL: the whole-line store epilogue of the 256-row store builds (QKV, FF1).  The MFMA's operand roles are swapped -- tokens on its row index -- and
+    // the weight rows are permuted on their way into LDS (row 16 i + c of a wave's 128 <- weight row 8 c + i), so that lane (fq, fc) holds tokens
+    // 16 j + 4 fq + r of feature 8 fc + i in acc[i][j][r]: for a fixed (j, r) its eight accumulators over i are 16 consecutive output bytes, and
+    // the 16 lanes of a row write 256 contiguous bytes.  Same products in the same K order: the same bits as the other operand order.
+    constexpr bool WL = MI == 8 && EPI != EPI_RESID;
     __shared__ __attribute__((aligned(1024))) char smem[EPI_LDS + EPI_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -92,8 +105,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
         const int row = (wave * 8 + jj) * 8 + (lane >> 3);
-        const int logical = (lane & 7) ^ ((row >> 1) & 7);
-        voffW[jj] = (unsigned)(row * p.ldw * 2 + logical * 16);
+        const int logical = (lane & 7) ^ ((row >> 1) & 7);  // (keyed on the LDS row, also under WL)
+        const int wrow = WL ? (row & ~127) + 8 * (row & 15) + ((row & 127) >> 4) : row;
+        voffW[jj] = (unsigned)(wrow * p.ldw * 2 + logical * 16);
     }
 #pragma unroll
     for (int jj = 0; jj < MI; ++jj) {
@@ -177,7 +191,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             (void)acc; (void)fw; (void)fa; (void)voffA; (void)voffW; (void)baseA; (void)baseW;
             constexpr int n = decltype(nc)::value;
             constexpr int s = n / (8 * MI), i = (n % (8 * MI)) / MI, j = n % MI;
-            if constexpr (LNF || Elem<EL>::F16)  // (inline asm for the AccVGPR constraint: the mnemonic of Elem<>::mfma16's builtin)
+            if constexpr (WL) {  // tokens on the row index
+                if constexpr (LNF || Elem<EL>::F16)
+                    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fa[s][j]), "v"(fw[s][i]));
+                else
+                    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fa[s][j]), "v"(fw[s][i]));
+            } else if constexpr (LNF || Elem<EL>::F16)  // (inline asm for the AccVGPR constraint: the mnemonic of Elem<>::mfma16's builtin)
                 asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fw[s][i]), "v"(fa[s][j]));
             else
                 asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fw[s][i]), "v"(fa[s][j]));
@@ -266,13 +285,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         }
     };
-    auto load_bias = [&](int tn0, f32x4 (&dst)[8]) {
+    constexpr int NBS = WL ? 2 : 8;  // registers of a tile's accumulator start.  WL: the lane's eight features' bias, 8 fc .. 8 fc + 7
+    auto load_bias = [&](int tn0, f32x4 (&dst)[NBS]) {
+        if constexpr (WL) {
+            dst[0] = *reinterpret_cast<const f32x4*>(p.bias + tn0 + wn * 128 + 8 * fr);
+            dst[1] = *reinterpret_cast<const f32x4*>(p.bias + tn0 + wn * 128 + 8 * fr + 4);
+        } else {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) dst[i] = *reinterpret_cast<const f32x4*>(p.bias + tn0 + wn * 128 + i * 16 + 4 * fq);
+            for (int i = 0; i < NBS; ++i) dst[i] = *reinterpret_cast<const f32x4*>(p.bias + tn0 + wn * 128 + i * 16 + 4 * fq);
+        }
     };
-    auto acc_from = [&](const f32x4 (&b4)[8]) {  // every accumulator starts from its feature's bias (gemm_fast.hip: init_acc)
+    auto acc_from = [&](const f32x4 (&b4)[NBS]) {  // every accumulator starts from its feature's bias (gemm_fast.hip: init_acc)
         static_for<8>([&](auto ic) {
-            static_for<MI>([&](auto jc) { acc[decltype(ic)::value][decltype(jc)::value] = b4[decltype(ic)::value]; });
+            static_for<MI>([&](auto jc) {
+                constexpr int i = decltype(ic)::value;
+                if constexpr (WL) {
+                    const float b = b4[i >> 2][i & 3];  // (one feature per fragment i, four tokens)
+                    acc[i][decltype(jc)::value] = f32x4{b, b, b, b};
+                } else {
+                    acc[i][decltype(jc)::value] = b4[i];
+                }
+            });
         });
     };
     // An accumulator reaches the vector ALU through four volatile v_accvgpr_read_b32 statements AT ITS USE.  Left to the compiler, the AGPR -> VGPR
@@ -348,6 +381,92 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             *reinterpret_cast<u32x4*>(o) = q0;
             *reinterpret_cast<u32x4*>(o + 32) = q1;
         });
+    };
+    // ---- WL: the store epilogue of the wave's whole 128 x 128 part in the whole-line map.  Per token tile j and component r one 16-byte store of
+    // features 8 fc .. 8 fc + 7 of token 16 j + 4 fq + r: an instruction writes 4 token rows x 256 contiguous bytes (8 whole lines; the map above
+    // writes 64 separate 16-byte pieces, and the store path takes about a cycle per distinct lane address).  The eight values of a store are two
+    // f32x4 of consecutive features, i.e. the operand form of the epi_*4 helpers: the same operations in the same order per element as above.
+    // ROPE: at least one of the wave's two 64-feature halves is a q / k head that rotates (wave-uniform branch, as above); r0 / r1 say which, a
+    // lane's features lie in half fc >> 3.
+    [[maybe_unused]] auto store_wave_impl = [&](auto actc, auto ropec, [[maybe_unused]] bool r0, [[maybe_unused]] bool r1) {
+        constexpr int ACT = decltype(actc)::value;
+        constexpr bool ROPE = decltype(ropec)::value;
+        // (the lane's indices through an opaque asm, one scalar base + one 32-bit lane offset: resid_tile below says why)
+        int fc = lane & 15, fq4 = (lane >> 4) * 4;
+        asm volatile("" : "+v"(fc), "+v"(fq4));
+        char* const sbase = reinterpret_cast<char*>(p.out_t) + ((size_t)(m0 + wm * WROWS) * p.ldo + n0 + wn * 128) * 2;
+        const unsigned loff = (unsigned)((fq4 * p.ldo + 8 * fc) * 2);
+        const size_t rstride = (size_t)p.ldo * 2;
+        // (cos, sin) of a token's eight features: requested four stores ahead of their use, each into the registers of the values just used
+        [[maybe_unused]] f32x4 rp[4][2];
+        [[maybe_unused]] int pos0 = 0;
+        [[maybe_unused]] bool rot_lane = false;
+        auto load_rope = [&](int rowi, f32x4 (&dst)[2]) {
+            int pos = pos0 + rowi;
+            pos -= pos >= p.rows_per_batch ? p.rows_per_batch : 0;  // rows_per_batch >= 128 (launcher)
+            const char* t = reinterpret_cast<const char*>(p.rope) + (unsigned)((pos * 64 + 8 * (fc & 7)) * 4);
+            dst[0] = *reinterpret_cast<const f32x4*>(t);
+            dst[1] = *reinterpret_cast<const f32x4*>(t + 16);
+        };
+        if constexpr (ROPE) {
+            pos0 = (p.row0 + m0 + wm * WROWS + fq4) % p.rows_per_batch;
+            rot_lane = fc < 8 ? r0 : r1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) load_rope(r, rp[r]);
+        }
+        // LayerNorm fold: the lane's column constants once (16 registers), a token tile's four (mean, rstd) one tile ahead
+        [[maybe_unused]] f32x4 c1l[2], c2l[2], stj[2][2];
+        if constexpr (LNF) {
+#pragma unroll
+            for (int ii = 0; ii < 2; ++ii) {
+                c1l[ii] = *reinterpret_cast<const f32x4*>(lnf_lds + (8 * fc + 4 * ii) * 4);
+                c2l[ii] = *reinterpret_cast<const f32x4*>(lnf_lds + 512 + (8 * fc + 4 * ii) * 4);
+            }
+            stj[0][0] = *reinterpret_cast<const f32x4*>(lnf_lds + 1024 + fq4 * 8);
+            stj[0][1] = *reinterpret_cast<const f32x4*>(lnf_lds + 1024 + fq4 * 8 + 16);
+        }
+        static_for<MI>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (LNF && j + 1 < MI) {
+                stj[(j + 1) & 1][0] = *reinterpret_cast<const f32x4*>(lnf_lds + 1024 + ((j + 1) * 16 + fq4) * 8);
+                stj[(j + 1) & 1][1] = *reinterpret_cast<const f32x4*>(lnf_lds + 1024 + ((j + 1) * 16 + fq4) * 8 + 16);
+            }
+            f32x4 a[8];
+            static_for<8>([&](auto ic) { a[decltype(ic)::value] = W4_ACC(decltype(ic)::value, j); });
+            static_for<4>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                f32x4 v[2] = {f32x4{a[0][r], a[1][r], a[2][r], a[3][r]}, f32x4{a[4][r], a[5][r], a[6][r], a[7][r]}};
+#pragma unroll
+                for (int ii = 0; ii < 2; ++ii) {
+                    if constexpr (LNF) v[ii] = epi_lnf4(v[ii], stj[j & 1][r >> 1][(r & 1) * 2], stj[j & 1][r >> 1][(r & 1) * 2 + 1], c1l[ii], c2l[ii]);
+                    if constexpr (ACT == ACT_GELU_TANH) v[ii] = epi_gelu_tanh4(v[ii]);
+                    if constexpr (ROPE) {  // x_transformers apply_rotary_pos_emb: adjacent pairs, fp32 math
+                        const f32x4 w = epi_rope4(v[ii], rp[r][ii]);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[ii][e] = rot_lane ? w[e] : v[ii][e];
+                    }
+                }
+                const u32x2 q0 = __builtin_bit_cast(u32x2, to_el4<EL>(v[0])), q1 = __builtin_bit_cast(u32x2, to_el4<EL>(v[1]));
+                *reinterpret_cast<u32x4*>(sbase + (size_t)(16 * j + r) * rstride + loff) = u32x4{q0[0], q0[1], q1[0], q1[1]};
+                if constexpr (ROPE && j + 1 < MI) load_rope(16 * (j + 1) + r, rp[r]);
+            });
+        });
+    };
+    [[maybe_unused]] auto store_wave = [&](auto actc) {
+        if constexpr (EPI == EPI_ROPE_T) {
+            auto rotates = [&](int h) {
+                const int nb = n0 + wn * 128 + h * 64;
+                const int part = nb / p.rope_inner;
+                return part < 2 && ((nb - part * p.rope_inner) >> 6) < p.rope_heads;
+            };
+            const bool r0 = rotates(0), r1 = rotates(1);
+            if (r0 || r1) {
+                store_wave_impl(actc, std::true_type{}, r0, r1);
+                return;
+            }
+        }
+        store_wave_impl(actc, std::false_type{}, false, false);
     };
     [[maybe_unused]] auto store_half = [&](auto hc, auto actc) {
         if constexpr (EPI == EPI_ROPE_T) {
@@ -492,12 +611,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     front_advance();
     issue_all(1);
     front_advance();
-    f32x4 bstart[8];
+    f32x4 bstart[NBS];
     if constexpr (LNF) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) bstart[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NBS; ++i) bstart[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     } else {
         load_bias(n0, bstart);
+        // (waited for where the compiler sees it: left pending into the tile loop, its own wait bookkeeping puts a vmcnt(0) in front of the first
+        //  instruction that reuses these registers -- a fragment read in the middle of an iteration)
+        if constexpr (WL) {
+#pragma unroll
+            for (int i = 0; i < NBS; ++i) asm volatile("" ::"v"(bstart[i]));
+        }
     }
     acc_from(bstart);
     if constexpr (EPI == EPI_RESID) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (this thread's part of the bias / gate image is written)
@@ -531,19 +656,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         } else {
             // the NEXT tile's accumulator start is requested before the stores and waited for while only loads are in flight (loads and stores
             // share vmcnt: a wait behind the stores would hold the wave until they are acknowledged)
-            f32x4 bn[8];
+            f32x4 bn[NBS];
             if constexpr (LNF) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) bn[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int i = 0; i < NBS; ++i) bn[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             } else {
                 load_bias(nn0, bn);
 #pragma unroll
-                for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(bn[i]));
+                for (int i = 0; i < NBS; ++i) asm volatile("" ::"v"(bn[i]));
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // ... and the stages requested ahead (and this tile's fold operands) have landed
             __builtin_amdgcn_sched_barrier(0);
             finish_stats();
-            if (p.act == ACT_GELU_TANH) {
+            if constexpr (WL) {
+                if (p.act == ACT_GELU_TANH)
+                    store_wave(std::integral_constant<int, ACT_GELU_TANH>{});
+                else
+                    store_wave(std::integral_constant<int, ACT_NONE>{});
+            } else if (p.act == ACT_GELU_TANH) {
                 store_half(X0{}, std::integral_constant<int, ACT_GELU_TANH>{});
                 store_half(X1{}, std::integral_constant<int, ACT_GELU_TANH>{});
             } else {

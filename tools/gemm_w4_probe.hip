@@ -16,6 +16,10 @@
 //   42 .. 47  sub-step-1 reads in the first 16 slots, requests spread wide (every 4 - 6 slots); 46 = the library's schedule
 //   50        deferred stores: half of a tile's packed output leaves during the next tile's first four iterations (slower)
 //   60        schedule 46 with the vendor kernel's request form, buffer_load_dwordx4 ... offen lds (no difference)
+//   70 .. 73  whole-line epilogue: the MFMA's operand roles swapped (tokens on the row index) and the weight rows permuted on their way into LDS
+//             (LDS row 16 i + c of a wave's 128 <- weight row 8 c + i), so that a lane's eight accumulators over i are eight consecutive features of
+//             one token and 16 adjacent lanes write 256 contiguous bytes per store.  70: on schedule 46; 71: on schedule 1; 72 / 73: the
+//             read-modify-write forms of 30 / 33 in that map (on schedule 1, as they are; 72 loads four token tiles ahead, not all eight)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -84,7 +88,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int row = (wave * 8 + jj) * 8 + (lane >> 3);
         const int logical = (lane & 7) ^ ((row >> 1) & 7);
         voffA[jj] = (unsigned)(row * lda * 2 + logical * 16);
-        voffW[jj] = (unsigned)(row * ldw * 2 + logical * 16);
+        // whole-line epilogue: LDS row 16 i + c of a wave's 128 features receives weight row 8 c + i (the swizzle stays keyed on the LDS row)
+        const int wrow = (SCHED >= 70 && SCHED <= 73) ? (row & ~127) + 8 * (row & 15) + ((row & 127) >> 4) : row;
+        voffW[jj] = (unsigned)(wrow * ldw * 2 + logical * 16);
     }
     const char* baseA;  // DMA front: tile row / feature base at the front's K position
     const char* baseW;
@@ -160,14 +166,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // with that start skew; 20: schedule 1 without the stores
         constexpr bool NO_DMA = SCHED == 10 || SCHED == 12 || SCHED == 13 || SCHED == 17 || SCHED == 18, NO_RD = SCHED == 11 || NO_DMA && SCHED != 10, NO_BAR = SCHED == 13 || SCHED == 14 || SCHED == 17 || SCHED == 18;
         constexpr bool M0E = SCHED == 40 || SCHED == 41;
-        constexpr bool S42 = (SCHED >= 42 && SCHED <= 47) || SCHED == 50 || SCHED == 51 || SCHED == 60;  // family of schedule 42: reads of sub-step 1 in the first 16 slots, requests spread wide
-        constexpr int R1S = SCHED == 0 ? 3 : (S42 ? 1 : 2), B1P = SCHED == 0 ? 49 : (S42 ? ((SCHED == 46 || SCHED == 50 || SCHED == 60) ? 20 : 24) : 40), D0 = SCHED == 0 ? 50 : (S42 ? ((SCHED == 46 || SCHED == 50 || SCHED == 60) ? 22 : 26) : 42), DS = (SCHED == 2 || SCHED == 4 || SCHED == 41) ? 2 : (SCHED == 43 ? 5 : (SCHED == 44 || SCHED == 46 || SCHED == 50 || SCHED == 60 ? 6 : (S42 ? 4 : 3)));
+        constexpr bool S42 = (SCHED >= 42 && SCHED <= 47) || SCHED == 50 || SCHED == 51 || SCHED == 60 || SCHED == 70;  // family of schedule 42: reads of sub-step 1 in the first 16 slots, requests spread wide
+        constexpr int R1S = SCHED == 0 ? 3 : (S42 ? 1 : 2), B1P = SCHED == 0 ? 49 : (S42 ? ((SCHED == 46 || SCHED == 50 || SCHED == 60 || SCHED == 70) ? 20 : 24) : 40), D0 = SCHED == 0 ? 50 : (S42 ? ((SCHED == 46 || SCHED == 50 || SCHED == 60 || SCHED == 70) ? 22 : 26) : 42), DS = (SCHED == 2 || SCHED == 4 || SCHED == 41) ? 2 : (SCHED == 43 ? 5 : (SCHED == 44 || SCHED == 46 || SCHED == 50 || SCHED == 60 || SCHED == 70 ? 6 : (S42 ? 4 : 3)));
         constexpr int B2P = SCHED == 0 ? 100 : (SCHED == 3 || SCHED == 4 ? 78 : (SCHED == 45 ? 104 : (SCHED == 47 ? 94 : 86))), R0 = B2P + 2, R0S = SCHED == 0 ? 0 : (SCHED == 45 ? 1 : 2);
         static_for<128>([&](auto nc) {
             (void)acc; (void)fw; (void)fa;
             constexpr int n = decltype(nc)::value;
             constexpr int s = n / 64, i = (n % 64) / 8, j = n % 8;
-            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fw[s][i]), "v"(fa[s][j]));
+            if constexpr (SCHED >= 70 && SCHED <= 73)  // tokens on the row index: a lane holds tokens 4 fq + r of the feature its LDS row carries
+                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fa[s][j]), "v"(fw[s][i]));
+            else
+                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fw[s][i]), "v"(fa[s][j]));
             if constexpr (!NO_RD && n < 16 * R1S && n % R1S == 0) rd(std::integral_constant<int, 1>{}, xc, std::integral_constant<int, n / R1S>{});
             if constexpr (n == B1P && !NO_BAR) {  // B1: every wave is done with buffer X
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -264,6 +273,48 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             dbase = reinterpret_cast<const char*>(C + (size_t)(m0 + wm * 128) * ldc + n0 + wn * 128);
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) doff[jj] = (unsigned)(((fr + 16 * (jj + 4)) * ldc + 16 * (fq & 1) + 8 * (fq >> 1)) * 2);
+            return;
+        }
+        if constexpr (SCHED >= 70 && SCHED <= 73) {
+            // whole-line map: lane (fq, fr) holds tokens 16 j + 4 fq + r and features 8 fr + i; per (j, r) one 16-byte store, 16 adjacent lanes
+            // cover 256 contiguous bytes, an instruction 4 token rows x 256 bytes.  72: the stream loads four token tiles ahead of their use; 73: step-wise
+            bf16_t* wrow = C + (size_t)(m0 + wm * 128 + 4 * fq) * ldc + n0 + wn * 128 + 8 * fr;
+            [[maybe_unused]] u32x4 xs[8][4];
+            if constexpr (SCHED == 72) {  // (all eight token tiles ahead do not fit beside the 32 unpacked values of a step: four ahead)
+                static_for<4>([&](auto jc) {
+                    static_for<4>([&](auto rc) {
+                        constexpr int j = decltype(jc)::value, r = decltype(rc)::value;
+                        xs[j][r] = *reinterpret_cast<const u32x4*>(wrow + (size_t)(16 * j + r) * ldc);
+                    });
+                });
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            static_for<8>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                __builtin_amdgcn_sched_barrier(0);
+                f32x4 v[8];
+                static_for<8>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value;
+                    asm volatile("" : "+a"(acc[i][j]));
+                    v[i] = acc[i][j];
+                });
+                static_for<4>([&](auto rc) {
+                    constexpr int r = decltype(rc)::value;
+                    if constexpr (SCHED == 73) xs[j][r] = *reinterpret_cast<const u32x4*>(wrow + (size_t)(16 * j + r) * ldc);
+                    if constexpr (SCHED == 72 && j >= 4) xs[j][r] = xs[j - 4][r];
+                    f32x4 a{v[0][r], v[1][r], v[2][r], v[3][r]}, b{v[4][r], v[5][r], v[6][r], v[7][r]};
+                    if constexpr (SCHED >= 72) {
+                        const u32x4 x = xs[j][r];
+                        a[0] += __builtin_bit_cast(float, x[0] << 16); a[1] += __builtin_bit_cast(float, x[0] & 0xffff0000u);
+                        a[2] += __builtin_bit_cast(float, x[1] << 16); a[3] += __builtin_bit_cast(float, x[1] & 0xffff0000u);
+                        b[0] += __builtin_bit_cast(float, x[2] << 16); b[1] += __builtin_bit_cast(float, x[2] & 0xffff0000u);
+                        b[2] += __builtin_bit_cast(float, x[3] << 16); b[3] += __builtin_bit_cast(float, x[3] & 0xffff0000u);
+                    }
+                    const u32x2 qa = __builtin_bit_cast(u32x2, to_bf16x4(a)), qb = __builtin_bit_cast(u32x2, to_bf16x4(b));
+                    *reinterpret_cast<u32x4*>(wrow + (size_t)(16 * j + r) * ldc) = u32x4{qa[0], qa[1], qb[0], qb[1]};
+                    if constexpr (SCHED == 72 && j < 4) xs[j][r] = *reinterpret_cast<const u32x4*>(wrow + (size_t)(16 * (j + 4) + r) * ldc);
+                });
+            });
             return;
         }
         if constexpr (SCHED >= 30 && SCHED <= 34) {
@@ -402,7 +453,7 @@ static uint16_t f2bf(float f) { uint32_t u; memcpy(&u, &f, 4); u += 0x7fff + ((u
 
 static void launch(int sched, dim3 grid, const bf16_t* dA, const bf16_t* dW, bf16_t* dC, int M, int N, int K, int tiles_n, int nblocks) {
 #define W4_CASE(S) case S: hipLaunchKernelGGL(w4_kernel<S>, grid, dim3(256), 0, 0, dA, dW, dC, M, N, K, K, K, N, tiles_n, nblocks, 8); break;
-    switch (sched) { W4_CASE(0) W4_CASE(1) W4_CASE(3) W4_CASE(10) W4_CASE(11) W4_CASE(12) W4_CASE(13) W4_CASE(14) W4_CASE(17) W4_CASE(18) W4_CASE(19) W4_CASE(20) W4_CASE(21) W4_CASE(22) W4_CASE(23) W4_CASE(30) W4_CASE(31) W4_CASE(32) W4_CASE(33) W4_CASE(40) W4_CASE(41) W4_CASE(42) W4_CASE(43) W4_CASE(44) W4_CASE(45) W4_CASE(46) W4_CASE(47) W4_CASE(50) W4_CASE(60) }
+    switch (sched) { W4_CASE(0) W4_CASE(1) W4_CASE(3) W4_CASE(10) W4_CASE(11) W4_CASE(12) W4_CASE(13) W4_CASE(14) W4_CASE(17) W4_CASE(18) W4_CASE(19) W4_CASE(20) W4_CASE(21) W4_CASE(22) W4_CASE(23) W4_CASE(30) W4_CASE(31) W4_CASE(32) W4_CASE(33) W4_CASE(40) W4_CASE(41) W4_CASE(42) W4_CASE(43) W4_CASE(44) W4_CASE(45) W4_CASE(46) W4_CASE(47) W4_CASE(50) W4_CASE(60) W4_CASE(70) W4_CASE(71) W4_CASE(72) W4_CASE(73) }
 }
 
 int main(int argc, char** argv) {
@@ -412,7 +463,7 @@ int main(int argc, char** argv) {
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, 0));
     ncu = prop.multiProcessorCount & ~7;
-    for (int sched : {46, 60, 46, 60})
+    for (int sched : {1, 20, 46, 70, 71, 30, 33, 72, 73, 1, 20, 70, 71})
     for (const Shape& sh : shapes) {
         const int M = sh.M, N = sh.N, K = sh.K;
         std::vector<uint16_t> hA((size_t)M * K), hW((size_t)N * K);
@@ -468,7 +519,7 @@ int main(int argc, char** argv) {
             if (ms / 10 < best) best = ms / 10;
         }
         printf("[sched %d] %s M=%d N=%d K=%d: %.1f us = %.0f TF | max abs err %.4g (max |ref| %.3g)%s\n", sched, sh.name, M, N, K, best * 1e3, 2.0 * M * N * K / best / 1e9, maxerr, maxref,
-               (sched >= 10 && sched != 22 && sched < 40) ? "  (timing only)" : (maxerr <= 0.02 * maxref + 1e-3 ? "" : "  <-- MISMATCH"));
+               ((sched >= 10 && sched != 22 && sched < 40) || sched == 72 || sched == 73) ? "  (timing only)" : (maxerr <= 0.02 * maxref + 1e-3 ? "" : "  <-- MISMATCH"));
         fflush(stdout);
         (void)hipFree(dA); (void)hipFree(dW); (void)hipFree(dC); (void)hipFree(dRows); (void)hipFree(dRef);
     }
