@@ -34,8 +34,8 @@ from ..model import CFM
 from ..model import backbones as _backbones
 from ..model.utils import convert_char_to_pinyin, get_tokenizer, list_str_to_idx
 from . import audio as _audio
-from .utils_infer import (DEFAULT_VOCAB, WaveStream, chunk_groups, chunk_text, cross_fade_concat, decode_utterances, device_tail_kind, finish_waves,
-                          load_checkpoint, load_vocoder, mel_rows_of, split_voice_script)
+from .utils_infer import (DEFAULT_VOCAB, WaveStream, chunk_groups, chunk_text, cross_fade_concat, decode_utterances, device_tail_kind, load_checkpoint,
+                          load_vocoder, mel_rows_of, split_voice_script, waves_of_mels)
 
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs")
 
@@ -237,6 +237,8 @@ class F5TTSWrapper:
         return self.ref_audio_len + int(durations[0].item() / local_speed)
 
     # ------------------------------------------------------------------ synthesis
+    # A single-voice call is a multi-voice call with one voice and one segment (include/f5hip.h: f5_wave_finish IS f5_wave_finish_segments with
+    # one segment and rms index 0, the same bytes): the four entry points differ in how the script is planned and share everything behind that.
     def generate(self, text: str, output_path: Optional[str] = None, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
                  sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
                  cross_fade_duration: Optional[float] = None, use_duration_predictor: Optional[bool] = None,
@@ -247,186 +249,8 @@ class F5TTSWrapper:
         the option after `utils_infer.remove_silence_for_generated_wav`; the returned wave (float, or the truncating PCM with
         ``return_pcm16``) holds the same kept samples, and the spectrogram is untouched.  Where the device tail runs the decision is taken
         there (`utils_infer.remove_silence`) and only the kept samples are copied; an all-silent result is empty."""
-        (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs = self._plan_jobs(
-            text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
-        return self._generate_jobs(jobs, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration, return_numpy,
-                                   return_spectrogram, return_pcm16, remove_silence)
-
-    def _plan_jobs(self, text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor):
-        """The host work of generate() / generate_stream() before any sampling: the arguments' defaults, the text cut into chunks, and per chunk
-        the token list and the frames asked for (duration rule or predictor) -- the ``jobs`` list."""
-        if self.ref_audio_processed is None or self.ref_text is None:
-            raise ValueError("Reference audio not preprocessed. Call preprocess_reference() first.")
-        nfe_step = nfe_step if nfe_step is not None else self.nfe_step
-        cfg_strength = cfg_strength if cfg_strength is not None else self.cfg_strength
-        sway_sampling_coef = sway_sampling_coef if sway_sampling_coef is not None else self.sway_sampling_coef
-        speed = speed if speed is not None else self.speed
-        fix_duration = fix_duration if fix_duration is not None else self.fix_duration
-        cross_fade_duration = cross_fade_duration if cross_fade_duration is not None else self.cross_fade_duration
-        use_predictor = use_duration_predictor if use_duration_predictor is not None else self.use_duration_predictor
-        can_use_predictor = use_predictor and self.has_duration_predictor
-
-        audio_len = self.ref_audio_processed.shape[-1] / self.target_sample_rate
-        max_chars = int(len(self.ref_text.encode("utf-8")) / audio_len * (22 - audio_len))
-        text_batches = chunk_text(text, max_chars=max_chars)
-        for i, text_batch in enumerate(text_batches):
-            print(f"Text batch {i}: {text_batch}")
-        print("\n")
-
-        jobs = []  # (token list, frames asked for) per chunk -- host work of the reference's loop (:476-510), before any sampling
-        for i, text_batch in enumerate(text_batches):
-            local_speed = 0.3 if len(text_batch.encode("utf-8")) < 10 else speed
-            final_text_list = convert_char_to_pinyin([self.ref_text + text_batch])
-            if fix_duration is not None:
-                duration = int(fix_duration * self.target_sample_rate / self.hop_length)
-                print(f"Using fixed duration: {fix_duration}s ({duration} frames)")
-            elif can_use_predictor:
-                if isinstance(final_text_list[0], str):
-                    text_tokens = list_str_to_idx(final_text_list, self.vocab_char_map).to(self.device)
-                else:
-                    text_tokens = torch.tensor(final_text_list, device=self.device)
-                text_lengths = torch.tensor([len(t) for t in final_text_list], device=self.device)
-                duration = self.calculate_duration_with_predictor(text_tokens, text_lengths, local_speed)
-                print(f"Duration predictor output: {duration} frames")
-            else:
-                ref_text_len, gen_text_len = len(self.ref_text.encode("utf-8")), len(text_batch.encode("utf-8"))
-                duration = self.ref_audio_len + int(self.ref_audio_len / ref_text_len * gen_text_len / local_speed)
-                print(f"Calculated duration based on text ratio: {duration} frames")
-            jobs.append((final_text_list, int(duration)))
-        return (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs
-
-    def _sample_jobs(self, jobs, nfe_step, cfg_strength, sway_sampling_coef, voices=None):
-        """The mels of these jobs, in order, by the sampler their list calls for: ragged when the backbone is the DiT and there are at least 2 jobs,
-        all of at least 256 and at most 4096 frames; otherwise sample() per job, up to `chunk_streams` of them in flight.  ``voices`` (one field
-        dict per job, generate_multi): every job takes its own voice's prompt mel -- in a ragged call one prompt per utterance, zero-padded
-        to the longest, with ``lens``; None: the main prompt for all."""
-        transformer = getattr(self.model, "transformer", None)
-        # The text chunks of one call are independent (the reference samples them one after the other, :476-533).  Here up to `chunk_streams`
-        # of them are in flight at once, each on a HIP stream (and a libf5hip plan) of its own: a single-utterance sample() fills a fraction
-        # of the 256 CUs, so the streams overlap.  Every chunk runs exactly the launches of the serial path -- same shapes, same kernels --
-        # so its mel is bit-identical to the serial result; noise is drawn in chunk order either way.
-        # Several chunks, each long enough for the tuned kernels: ONE ragged batch per group of chunks -- the utterances concatenated along the
-        # token axis, no padding to a common length, every chunk with the arithmetic of its own batch-1 call (bit-identical mels, same noise
-        # order).  A single-utterance sample() fills a fraction of the 256 CUs; the concatenation fills them.
-        ragged = (int(self.ragged_chunks) >= 2 and len(jobs) >= 2 and torch.cuda.is_available() and hasattr(transformer, "native_sample_ragged")
-                  and getattr(transformer, "BACKBONE", None) == 0 and min(d for _, d in jobs) >= 256 and max(d for _, d in jobs) <= 4096)
-        n_streams = 1
-        if not ragged and torch.cuda.is_available() and hasattr(transformer, "finish_pending"):
-            n_streams = max(1, min(len(jobs), int(self.chunk_streams)))
-        main = torch.cuda.current_stream() if n_streams > 1 else None
-        streams = self._chunk_stream_pool(n_streams) if n_streams > 1 else []
-        for st in streams:
-            st.wait_stream(main)  # the preprocessed prompt was produced on the caller's stream
-        mels = []
-        if ragged:
-            with torch.inference_mode():
-                for idx in chunk_groups([d for _, d in jobs], 0, int(self.ragged_chunks)):
-                    group = [jobs[i] for i in idx]
-                    cond, lens = self.ref_audio_processed, None
-                    if voices is not None:
-                        prompts = [voices[i]["mel"][0] for i in idx]
-                        lens = torch.tensor([int(m.shape[0]) for m in prompts], device=prompts[0].device, dtype=torch.long)
-                        cond = torch.nn.utils.rnn.pad_sequence(prompts, batch_first=True, padding_value=0.0)
-                    mels += self.model.sample_ragged(cond, [j[0][0] for j in group], [j[1] for j in group], lens=lens, steps=nfe_step,
-                                                     cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
-        for i, (final_text_list, duration) in enumerate(jobs if not ragged else []):
-            prompt = self.ref_audio_processed if voices is None else voices[i]["mel"]
-            with torch.inference_mode():
-                if n_streams > 1:
-                    with torch.cuda.stream(streams[i % n_streams]):
-                        generated, _ = self.model.sample(cond=prompt, text=final_text_list, duration=duration, steps=nfe_step,
-                                                         cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, return_trajectory=False,
-                                                         defer_guard=True)
-                else:
-                    generated, _ = self.model.sample(cond=prompt, text=final_text_list, duration=duration, steps=nfe_step,
-                                                     cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, return_trajectory=False)
-                mels.append(generated)
-        if n_streams > 1:
-            transformer.finish_pending()  # reads every chunk's fp16 range-guard flag (and lets the library redo a chunk whose guard fired)
-            # finish_pending() synchronises a stream only when its plan has a guard to read (bf16 mode with fp16 storage); the vocoder below runs
-            # on the caller's stream, so that stream must be ordered behind EVERY chunk stream whatever the precision (round 4: the fp32 mode
-            # decoded mels that were still being written -- found by test_generate_end_to_end_matches_the_oracle_chain[fp32-False])
-            for st in streams:
-                main.wait_stream(st)
-            with torch.inference_mode():
-                for generated in mels:
-                    generated.record_stream(main)
-        return mels
-
-    def _silence_step(self, signal, pcm16=None):
-        """The step behind the tail when ``remove_silence`` is on: ``(kept signal, kept pcm16 or None)`` at the reference's four values
-        (`utils_infer.SILENCE_DEFAULTS`), on the device for device tensors (the `finish_waves` outputs), by the host functions for arrays."""
-        from .utils_infer import SILENCE_DEFAULTS, remove_silence
-        kept = remove_silence(signal, self.target_sample_rate, pcm16=pcm16, **SILENCE_DEFAULTS)
-        return kept if pcm16 is not None else (kept, None)
-
-    def _generate_jobs(self, jobs, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration, return_numpy, return_spectrogram,
-                       return_pcm16, remove_silence=False):
-        generated_waves, spectrograms = [], []
-        mels = self._sample_jobs(jobs, nfe_step, cfg_strength, sway_sampling_coef)
-        want_spec = return_spectrogram or output_path is not None
-        want_float = not return_pcm16 or output_path is not None
-        final_wave = final_pcm = None
-        with torch.inference_mode():
-            # The tail on the device where the vocoder is one of ours: the mels of all chunks go to ONE ragged vocoder call (the prompt frames
-            # skipped by a row offset, no permute copy), then one wave_finish (rms rule decided on the device from the device-resident prompt,
-            # cross-fade, PCM) and one copy to the host.  Byte-identical to the per-chunk loop below, which foreign vocoder objects keep.
-            kind = device_tail_kind(self.vocoder, self.ref_audio_processed, *mels)
-            if kind is not None and (kind == self.mel_spec_type) and mels and min(int(m.shape[1]) for m in mels) - self.ref_audio_len >= 2:
-                rows, row_start, frames = mel_rows_of(mels, self.ref_audio_len)
-                wave_buf, samples = decode_utterances(self.vocoder, kind, rows, row_start, frames)
-                rms = torch.sqrt(torch.mean(torch.square(self.ref_audio_processed)))  # of the stored, already boosted prompt (:529-531)
-                done = finish_waves(wave_buf, samples, cross_fade_duration, self.target_sample_rate, rms=rms.to(torch.float32), target_rms=self.target_rms,
-                                    want_float=want_float or remove_silence, want_pcm16=return_pcm16)  # (the float wave is what is judged)
-                if want_spec:
-                    spectrograms = [rows[r: r + t].t().cpu().numpy() for r, t in zip(row_start, frames)]
-                if done is not None:
-                    if remove_silence:
-                        done, remove_silence = self._silence_step(*done), False
-                    final_wave = done[0].cpu().numpy() if want_float else None
-                    final_pcm = done[1].cpu().numpy() if return_pcm16 else None
-                else:  # utterances shorter than their cross-fades (F5_ENOTSUP): the decoded waves take the host functions
-                    apply_gain = bool(rms < self.target_rms)
-                    for w in torch.split(wave_buf, samples):
-                        generated_waves.append((w * rms / self.target_rms if apply_gain else w).cpu().numpy())
-            else:
-                for generated in mels:
-                    generated = generated.to(torch.float32)[:, self.ref_audio_len:, :].permute(0, 2, 1)
-                    if self.mel_spec_type == "vocos":
-                        generated_wave = self.vocoder.decode(generated)
-                    elif self.mel_spec_type == "bigvgan":
-                        generated_wave = self.vocoder(generated)
-                    rms = torch.sqrt(torch.mean(torch.square(self.ref_audio_processed)))  # of the stored, already boosted prompt (:529-531)
-                    if rms < self.target_rms:
-                        generated_wave = generated_wave * rms / self.target_rms
-                    generated_waves.append(generated_wave.squeeze().cpu().numpy())
-                    if want_spec:
-                        spectrograms.append(generated.squeeze().cpu().numpy())
-
-        if final_wave is None and final_pcm is None:
-            if not generated_waves:
-                raise RuntimeError("No audio generated")
-            final_wave = cross_fade_concat(generated_waves, cross_fade_duration, self.target_sample_rate)
-        if return_pcm16 and final_pcm is None:
-            from ..streaming.wire import pcm16_bytes
-            final_pcm = np.frombuffer(pcm16_bytes(final_wave), dtype=np.int16)
-        if remove_silence:  # the host tails (a foreign vocoder, or joints that chain): the same rule by the host functions
-            final_wave, final_pcm = self._silence_step(final_wave, final_pcm)
-        combined_spectrogram = np.concatenate(spectrograms, axis=1) if spectrograms else None
-        if output_path is not None:
-            output_dir = os.path.dirname(output_path)
-            if output_dir and not os.path.exists(output_dir):
-                os.makedirs(output_dir)
-            _audio.write_wav(output_path, final_wave, self.target_sample_rate)
-            if return_spectrogram:
-                np.save(os.path.splitext(output_path)[0] + "_spec.npy", combined_spectrogram)  # matplotlib is not in the image
-            if not return_numpy:
-                return output_path
-        if return_pcm16:
-            final_wave = final_pcm
-        if return_spectrogram:
-            return final_wave, self.target_sample_rate, combined_spectrogram
-        return final_wave, self.target_sample_rate
+        plan = self._plan_jobs(text, False, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
+        return self._synthesize(*plan, output_path, return_numpy, return_spectrogram, return_pcm16, remove_silence)
 
     def generate_stream(self, text: str, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
                         sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
@@ -446,74 +270,8 @@ class F5TTSWrapper:
         the bits of its batch-1 calls, so the byte-equality with ``generate()`` holds for dropout off only.  ``return_numpy`` and
         ``return_spectrogram`` are accepted for the signature's sake: a piece is always an array, and no spectrogram is streamed.  Closing the
         generator early frees the session and leaves the wrapper as it was."""
-        (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs = self._plan_jobs(
-            text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
-        frames = self._generated_frames(jobs)
-        kind = device_tail_kind(self.vocoder, self.ref_audio_processed)
-        session = None
-        if kind is not None and kind == self.mel_spec_type and frames and min(frames) >= 2:
-            samples = [(t - 1) * self.hop_length for t in frames] if kind == "vocos" else [t * self.vocoder._total_up() for t in frames]
-            with torch.inference_mode():
-                rms = torch.sqrt(torch.mean(torch.square(self.ref_audio_processed)))  # of the stored, already boosted prompt (:529-531)
-                session = WaveStream(samples, cross_fade_duration, self.target_sample_rate, rms=rms.to(torch.float32), target_rms=self.target_rms,
-                                     want_float=not return_pcm16, want_pcm16=return_pcm16)
-        if session is None or not session.ok:
-            wave, rate = self._generate_jobs(jobs, None, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration, True, False, return_pcm16)
-            yield wave, rate
-            return
-        try:
-            first = 0
-            for group in chunk_groups([d for _, d in jobs], int(self.stream_first_chunks), int(self.ragged_chunks)):
-                mels = self._sample_jobs([jobs[i] for i in group], nfe_step, cfg_strength, sway_sampling_coef)
-                with torch.inference_mode():
-                    rows, row_start, got = mel_rows_of(mels, self.ref_audio_len)
-                    if got != frames[first: first + len(group)]:
-                        raise RuntimeError(f"the sampler returned {got} generated frames where {frames[first: first + len(group)]} were planned")
-                    wave_buf, counts = decode_utterances(self.vocoder, kind, rows, row_start, got)
-                    signal, pcm = session.push(wave_buf, counts)
-                    piece = (pcm if return_pcm16 else signal).cpu().numpy()
-                first += len(group)
-                yield piece, self.target_sample_rate
-        finally:
-            session.close()
-
-    # ------------------------------------------------------------------ one script in several voices
-    def _plan_multi(self, text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor):
-        """`_plan_jobs` per piece of the script, each with its voice's fields: the arguments' defaults, the flat job list, the voice (field
-        dict) of every job and the jobs per segment (one segment per piece, in order)."""
-        voices = self.voices
-        if "main" not in voices:
-            raise ValueError("Reference audio not preprocessed. Call preprocess_reference() first.")
-        settings, jobs, job_voices, seg_sizes = None, [], [], []
-        for name, piece in split_voice_script(text, voices):
-            print(f"Voice: {name}")
-            with self._voice_installed(voices[name]):
-                settings, piece_jobs = self._plan_jobs(piece, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration,
-                                                       use_duration_predictor)
-            if piece_jobs:
-                jobs += piece_jobs
-                job_voices += [voices[name]] * len(piece_jobs)
-                seg_sizes.append(len(piece_jobs))
-        if not jobs:
-            raise RuntimeError("No audio generated")
-        return settings, jobs, job_voices, seg_sizes
-
-    @staticmethod
-    def _voice_rms_table(job_voices):
-        """``(rms vector on the device: one value per distinct voice, index of every job's voice in it)``"""
-        distinct, index = [], []
-        for v in job_voices:
-            at = next((i for i, d in enumerate(distinct) if d is v), None)
-            if at is None:
-                at = len(distinct)
-                distinct.append(v)
-            index.append(at)
-        return torch.stack([v["rms"].reshape(()) for v in distinct]), index
-
-    @staticmethod
-    def _own_pcm_flags(seg_sizes):
-        """per job: it is a segment of its own, whose generate() call forms its int16 from the fp32 product (`finish_waves`'s ``pcm_f32``)"""
-        return [g == 1 for g in seg_sizes for _ in range(g)]
+        plan = self._plan_jobs(text, False, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
+        yield from self._synthesize_stream(*plan, return_pcm16)
 
     def generate_multi(self, text: str, output_path: Optional[str] = None, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
                        sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
@@ -527,79 +285,8 @@ class F5TTSWrapper:
         attention dropout off the result is byte for byte ``np.concatenate([generate(piece, ...) with that voice installed for voice, piece
         in split_voice_script(text, voices)])`` -- float (float64 as soon as one piece cross-faded), ``return_pcm16`` and the written file;
         ``remove_silence`` applies to the whole result (infer_cli.py:360-363).  Same arguments and return shapes as ``generate()``."""
-        (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs, job_voices, seg_sizes = self._plan_multi(
-            text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
-        return self._generate_multi_jobs(jobs, job_voices, seg_sizes, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration,
-                                         return_numpy, return_spectrogram, return_pcm16, remove_silence)
-
-    def _generate_multi_jobs(self, jobs, job_voices, seg_sizes, output_path, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration,
-                             return_numpy, return_spectrogram, return_pcm16, remove_silence=False):
-        """`_generate_jobs` for a flat job list over several voices: ``job_voices[i]`` is job i's voice, ``seg_sizes`` the jobs per piece."""
-        mels = self._sample_jobs(jobs, nfe_step, cfg_strength, sway_sampling_coef, voices=job_voices)
-        want_spec = return_spectrogram or output_path is not None
-        want_float = not return_pcm16 or output_path is not None
-        final_wave = final_pcm = None
-        generated_waves, spectrograms = [], []
-        skips = [v["ref_audio_len"] for v in job_voices]
-        with torch.inference_mode():
-            kind = device_tail_kind(self.vocoder, *[v["audio"] for v in job_voices], *mels)
-            if kind is not None and kind == self.mel_spec_type and min(int(m.shape[1]) - k for m, k in zip(mels, skips)) >= 2:
-                rows, row_start, frames = mel_rows_of(mels, skips)
-                wave_buf, samples = decode_utterances(self.vocoder, kind, rows, row_start, frames)
-                rms, rms_index = self._voice_rms_table(job_voices)
-                done = finish_waves(wave_buf, samples, cross_fade_duration, self.target_sample_rate, rms=rms, target_rms=self.target_rms,
-                                    want_float=want_float or remove_silence, want_pcm16=return_pcm16, segments=seg_sizes, rms_index=rms_index,
-                                    pcm_f32=self._own_pcm_flags(seg_sizes))
-                if want_spec:
-                    spectrograms = [rows[r: r + t].t().cpu().numpy() for r, t in zip(row_start, frames)]
-                if done is not None:
-                    if remove_silence:
-                        done, remove_silence = self._silence_step(*done), False
-                    final_wave = done[0].cpu().numpy() if want_float else None
-                    final_pcm = done[1].cpu().numpy() if return_pcm16 else None
-                else:  # utterances shorter than their cross-fades (F5_ENOTSUP): the decoded waves take the host functions
-                    for w, v in zip(torch.split(wave_buf, samples), job_voices):
-                        generated_waves.append((w * v["rms"] / self.target_rms if bool(v["rms"] < self.target_rms) else w).cpu().numpy())
-            else:
-                for generated, v in zip(mels, job_voices):
-                    generated = generated.to(torch.float32)[:, v["ref_audio_len"]:, :].permute(0, 2, 1)
-                    if self.mel_spec_type == "vocos":
-                        generated_wave = self.vocoder.decode(generated)
-                    elif self.mel_spec_type == "bigvgan":
-                        generated_wave = self.vocoder(generated)
-                    rms = torch.sqrt(torch.mean(torch.square(v["audio"])))  # of the stored, already boosted prompt (:529-531)
-                    if rms < self.target_rms:
-                        generated_wave = generated_wave * rms / self.target_rms
-                    generated_waves.append(generated_wave.squeeze().cpu().numpy())
-                    if want_spec:
-                        spectrograms.append(generated.squeeze().cpu().numpy())
-
-        if final_wave is None and final_pcm is None:  # the host tail: cross_fade_concat per piece, np.concatenate of the pieces
-            from ..streaming.wire import pcm16_bytes
-            pieces, k = [], 0
-            for g in seg_sizes:
-                pieces.append(cross_fade_concat(generated_waves[k: k + g], cross_fade_duration, self.target_sample_rate))
-                k += g
-            final_wave = np.concatenate(pieces)
-            if return_pcm16:  # (each piece's int16 from its own dtype, as its generate() call forms it)
-                final_pcm = np.concatenate([np.frombuffer(pcm16_bytes(p), dtype=np.int16) for p in pieces])
-        if remove_silence:  # the host tails (a foreign vocoder, or joints that chain): the same rule by the host functions
-            final_wave, final_pcm = self._silence_step(final_wave, final_pcm)
-        combined_spectrogram = np.concatenate(spectrograms, axis=1) if spectrograms else None
-        if output_path is not None:
-            output_dir = os.path.dirname(output_path)
-            if output_dir and not os.path.exists(output_dir):
-                os.makedirs(output_dir)
-            _audio.write_wav(output_path, final_wave, self.target_sample_rate)
-            if return_spectrogram:
-                np.save(os.path.splitext(output_path)[0] + "_spec.npy", combined_spectrogram)
-            if not return_numpy:
-                return output_path
-        if return_pcm16:
-            final_wave = final_pcm
-        if return_spectrogram:
-            return final_wave, self.target_sample_rate, combined_spectrogram
-        return final_wave, self.target_sample_rate
+        plan = self._plan_jobs(text, True, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
+        return self._synthesize(*plan, output_path, return_numpy, return_spectrogram, return_pcm16, remove_silence)
 
     def generate_multi_stream(self, text: str, nfe_step: Optional[int] = None, cfg_strength: Optional[float] = None,
                               sway_sampling_coef: Optional[float] = None, speed: Optional[float] = None, fix_duration: Optional[float] = None,
@@ -610,31 +297,197 @@ class F5TTSWrapper:
         decode and one push into a segmented `WaveStream`; a group that ends a voice's piece emits all of it.  The pieces, concatenated,
         are byte for byte what ``generate_multi()`` returns (attention dropout off).  When the streamed tail does not apply -- decided
         before any sampling, by `generate_stream`'s conditions -- the generator yields exactly once, with ``generate_multi()``'s result."""
-        (nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration), jobs, job_voices, seg_sizes = self._plan_multi(
-            text, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
-        skips = [v["ref_audio_len"] for v in job_voices]
-        frames = [min(max(max(len(tokens[0]), int(v["mel"].shape[1])) + 1, duration), 4096) - v["ref_audio_len"]
-                  for (tokens, duration), v in zip(jobs, job_voices)]  # (`_generated_frames` with each job's own prompt)
-        kind = device_tail_kind(self.vocoder, *[v["audio"] for v in job_voices])
+        plan = self._plan_jobs(text, True, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
+        yield from self._synthesize_stream(*plan, return_pcm16)
+
+    def _plan_jobs(self, text, tagged=False, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, speed=None, fix_duration=None,
+                   cross_fade_duration=None, use_duration_predictor=None):
+        """The host work before any sampling: ``(settings, jobs, voices, seg_sizes)`` -- the arguments every entry point takes as one value,
+        each with the wrapper's attribute of the same name where it is None; per text chunk the token list and the frames asked for (duration
+        rule or predictor); the voice (field dict) of every job; and the jobs per segment.  ``tagged``: the text is a script whose ``[name]``
+        tags pick the voices, one segment per piece; otherwise all of it is the main voice's, one segment, and no tag is looked for."""
+        voices = self.voices
+        if "main" not in voices:
+            raise ValueError("Reference audio not preprocessed. Call preprocess_reference() first.")
+        given = dict(nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration,
+                     cross_fade_duration=cross_fade_duration, use_duration_predictor=use_duration_predictor)
+        settings = types.SimpleNamespace(**{k: v if v is not None else getattr(self, k) for k, v in given.items()})
+        can_use_predictor = settings.use_duration_predictor and self.has_duration_predictor
+        jobs, job_voices, seg_sizes = [], [], []
+        for name, piece in split_voice_script(text, voices) if tagged else [("main", text)]:
+            if tagged:
+                print(f"Voice: {name}")
+            voice = voices[name]
+            ref_text, ref_audio_len = voice["ref_text"], voice["ref_audio_len"]
+            audio_len = voice["audio"].shape[-1] / self.target_sample_rate
+            max_chars = int(len(ref_text.encode("utf-8")) / audio_len * (22 - audio_len))
+            text_batches = chunk_text(piece, max_chars=max_chars)
+            for i, text_batch in enumerate(text_batches):
+                print(f"Text batch {i}: {text_batch}")
+            print("\n")
+
+            for text_batch in text_batches:  # host work of the reference's loop (:476-510)
+                local_speed = 0.3 if len(text_batch.encode("utf-8")) < 10 else settings.speed
+                final_text_list = convert_char_to_pinyin([ref_text + text_batch])
+                if settings.fix_duration is not None:
+                    duration = int(settings.fix_duration * self.target_sample_rate / self.hop_length)
+                    print(f"Using fixed duration: {settings.fix_duration}s ({duration} frames)")
+                elif can_use_predictor:
+                    if isinstance(final_text_list[0], str):
+                        text_tokens = list_str_to_idx(final_text_list, self.vocab_char_map).to(self.device)
+                    else:
+                        text_tokens = torch.tensor(final_text_list, device=self.device)
+                    text_lengths = torch.tensor([len(t) for t in final_text_list], device=self.device)
+                    with self._voice_installed(voice):  # (the reference's public method reads self.ref_audio_len)
+                        duration = self.calculate_duration_with_predictor(text_tokens, text_lengths, local_speed)
+                    print(f"Duration predictor output: {duration} frames")
+                else:
+                    ref_text_len, gen_text_len = len(ref_text.encode("utf-8")), len(text_batch.encode("utf-8"))
+                    duration = ref_audio_len + int(ref_audio_len / ref_text_len * gen_text_len / local_speed)
+                    print(f"Calculated duration based on text ratio: {duration} frames")
+                jobs.append((final_text_list, int(duration)))
+                job_voices.append(voice)
+            if text_batches:
+                seg_sizes.append(len(text_batches))
+        if not jobs:
+            raise RuntimeError("No audio generated")
+        return settings, jobs, job_voices, seg_sizes
+
+    def _generated_frames(self, jobs, voices):
+        """Frames each job's sample() call generates behind its voice's prompt, from the host values alone: the sampler raises the frames asked
+        for to one more than the longer of the text and the prompt's mel, and caps them at 4096 (model/cfm.py)."""
+        return [min(max(max(len(tokens[0]), int(v["mel"].shape[1])) + 1, duration), 4096) - v["ref_audio_len"]
+                for (tokens, duration), v in zip(jobs, voices)]
+
+    def _sample_jobs(self, jobs, voices, settings):
+        """The mels of these jobs, in order, each over its own voice's prompt mel (``voices``: one field dict per job).  The text chunks of one
+        call are independent (the reference samples them one after the other, :476-533), and a single-utterance sample() fills a fraction
+        of the 256 CUs, so they run together, either way with the arithmetic of their own batch-1 calls and the noise drawn in chunk order
+        (bit-identical mels):
+          * ragged -- the backbone is the DiT and there are at least 2 jobs, all of at least 256 frames (the row count from which a batch-1
+            call takes the tuned kernels too) and at most 4096: ONE ragged batch per group of chunks (`chunk_groups`), the utterances
+            concatenated along the token axis without padding, one prompt per utterance zero-padded to the longest, with ``lens``;
+          * otherwise sample() per job, up to `chunk_streams` of them in flight, each on a HIP stream (and a libf5hip plan) of its own."""
+        transformer = getattr(self.model, "transformer", None)
+        sample_kw = dict(steps=settings.nfe_step, cfg_strength=settings.cfg_strength, sway_sampling_coef=settings.sway_sampling_coef)
+        ragged = (int(self.ragged_chunks) >= 2 and len(jobs) >= 2 and torch.cuda.is_available() and hasattr(transformer, "native_sample_ragged")
+                  and getattr(transformer, "BACKBONE", None) == 0 and min(d for _, d in jobs) >= 256 and max(d for _, d in jobs) <= 4096)
+        if ragged:
+            mels = []
+            with torch.inference_mode():
+                for idx in chunk_groups([d for _, d in jobs], 0, int(self.ragged_chunks)):
+                    prompts = [voices[i]["mel"][0] for i in idx]
+                    lens = torch.tensor([int(m.shape[0]) for m in prompts], device=prompts[0].device, dtype=torch.long)
+                    cond = torch.nn.utils.rnn.pad_sequence(prompts, batch_first=True, padding_value=0.0)
+                    mels += self.model.sample_ragged(cond, [jobs[i][0][0] for i in idx], [jobs[i][1] for i in idx], lens=lens, **sample_kw)
+            return mels
+        n_streams = 1
+        if torch.cuda.is_available() and hasattr(transformer, "finish_pending"):
+            n_streams = max(1, min(len(jobs), int(self.chunk_streams)))
+        main, streams = (torch.cuda.current_stream(), self._chunk_stream_pool(n_streams)) if n_streams > 1 else (None, [])
+        for st in streams:
+            st.wait_stream(main)  # the prompts' mels were produced on the caller's stream
+        mels = []
+        for i, ((tokens, duration), v) in enumerate(zip(jobs, voices)):
+            with torch.inference_mode(), torch.cuda.stream(streams[i % n_streams]) if streams else contextlib.nullcontext():
+                mels.append(self.model.sample(cond=v["mel"], text=tokens, duration=duration, return_trajectory=False, **sample_kw,
+                                              **({"defer_guard": True} if streams else {}))[0])
+        if not streams:
+            return mels
+        transformer.finish_pending()  # reads every chunk's fp16 range-guard flag (and lets the library redo a chunk whose guard fired)
+        # finish_pending() synchronises a stream only when its plan has a guard to read (bf16 mode with fp16 storage); the vocoder runs on the
+        # caller's stream, so that stream must be ordered behind EVERY chunk stream whatever the precision (round 4: the fp32 mode decoded
+        # mels that were still being written -- found by test_generate_end_to_end_matches_the_oracle_chain[fp32-False])
+        for st in streams:
+            main.wait_stream(st)
+        with torch.inference_mode():
+            for generated in mels:
+                generated.record_stream(main)
+        return mels
+
+    def _silence_step(self, signal, pcm16=None):
+        """The step behind the tail when ``remove_silence`` is on: ``(kept signal, kept pcm16 or None)`` at the reference's four values
+        (`utils_infer.SILENCE_DEFAULTS`), on the device for device tensors (the `finish_waves` outputs), by the host functions for arrays."""
+        from .utils_infer import SILENCE_DEFAULTS, remove_silence
+        kept = remove_silence(signal, self.target_sample_rate, pcm16=pcm16, **SILENCE_DEFAULTS)
+        return kept if pcm16 is not None else (kept, None)
+
+    def _tail_kw(self, settings, voices, seg_sizes):
+        """What `finish_waves` and `WaveStream` take alike for these jobs: the cross-fade, the rms rule as a device vector with one value per
+        distinct voice and every job's index into it, the segments, and per job whether it is a segment of its own, whose int16 a call over
+        it alone forms from the fp32 product (``pcm_f32``)."""
+        distinct, index = [], []
+        for v in voices:
+            at = next((i for i, d in enumerate(distinct) if d is v), None)
+            if at is None:
+                at = len(distinct)
+                distinct.append(v)
+            index.append(at)
+        return dict(cross_fade_duration=settings.cross_fade_duration, sample_rate=self.target_sample_rate, target_rms=self.target_rms,
+                    rms=torch.stack([v["rms"].reshape(()) for v in distinct]), rms_index=index, segments=seg_sizes,
+                    pcm_f32=[g == 1 for g in seg_sizes for _ in range(g)])
+
+    def _synthesize(self, settings, jobs, voices, seg_sizes, output_path=None, return_numpy=False, return_spectrogram=False, return_pcm16=False,
+                    remove_silence=False):
+        """Sampler, mel -> wave (`utils_infer.waves_of_mels`: on the device where the vocoder is one of ours), and delivery in the three return
+        shapes of generate()."""
+        mels = self._sample_jobs(jobs, voices, settings)
+        want_float = not return_pcm16 or output_path is not None
+        want_spec = return_spectrogram or output_path is not None
+        with torch.inference_mode():
+            done, generated_waves, spectrograms = waves_of_mels(
+                self.vocoder, self.mel_spec_type, mels, [v["ref_audio_len"] for v in voices], want_spec=want_spec, want_pcm16=return_pcm16,
+                want_float=want_float or remove_silence, **self._tail_kw(settings, voices, seg_sizes))  # (the float wave is what is judged)
+            if done is not None and remove_silence:
+                done, remove_silence = self._silence_step(*done), False
+        if done is not None:
+            final_wave = done[0].cpu().numpy() if want_float else None
+            final_pcm = done[1].cpu().numpy() if return_pcm16 else None
+        else:  # the host tail: cross_fade_concat per segment, np.concatenate of the segments
+            pieces, k = [], 0
+            for g in seg_sizes:
+                pieces.append(cross_fade_concat(generated_waves[k: k + g], settings.cross_fade_duration, self.target_sample_rate))
+                k += g
+            final_wave, final_pcm = np.concatenate(pieces), None
+            if return_pcm16:  # (each segment's int16 from its own dtype, as its generate() call forms it)
+                from ..streaming.wire import pcm16_bytes
+                final_pcm = np.concatenate([np.frombuffer(pcm16_bytes(p), dtype=np.int16) for p in pieces])
+        if remove_silence:  # the host tails (a foreign vocoder, or joints that chain): the same rule by the host functions
+            final_wave, final_pcm = self._silence_step(final_wave, final_pcm)
+        combined_spectrogram = np.concatenate(spectrograms, axis=1) if spectrograms else None
+        if output_path is not None:
+            output_dir = os.path.dirname(output_path)
+            if output_dir and not os.path.exists(output_dir):
+                os.makedirs(output_dir)
+            _audio.write_wav(output_path, final_wave, self.target_sample_rate)
+            if return_spectrogram:
+                np.save(os.path.splitext(output_path)[0] + "_spec.npy", combined_spectrogram)  # matplotlib is not in the image
+            if not return_numpy:
+                return output_path
+        if return_pcm16:
+            final_wave = final_pcm
+        if return_spectrogram:
+            return final_wave, self.target_sample_rate, combined_spectrogram
+        return final_wave, self.target_sample_rate
+
+    def _synthesize_stream(self, settings, jobs, voices, seg_sizes, return_pcm16):
+        """`_synthesize` group by group, as a generator of ``(piece, sample_rate)``; where the streamed tail does not apply, its result once."""
+        frames = self._generated_frames(jobs, voices)
+        kind = device_tail_kind(self.vocoder, *[v["audio"] for v in voices])
         session = None
         if kind is not None and kind == self.mel_spec_type and min(frames) >= 2:
             samples = [(t - 1) * self.hop_length for t in frames] if kind == "vocos" else [t * self.vocoder._total_up() for t in frames]
             with torch.inference_mode():
-                rms, rms_index = self._voice_rms_table(job_voices)
-                session = WaveStream(samples, cross_fade_duration, self.target_sample_rate, rms=rms, target_rms=self.target_rms,
-                                     want_float=not return_pcm16, want_pcm16=return_pcm16, segments=seg_sizes, rms_index=rms_index,
-                                     pcm_f32=self._own_pcm_flags(seg_sizes))
+                session = WaveStream(samples, want_float=not return_pcm16, want_pcm16=return_pcm16, **self._tail_kw(settings, voices, seg_sizes))
         if session is None or not session.ok:
-            wave, rate = self._generate_multi_jobs(jobs, job_voices, seg_sizes, None, nfe_step, cfg_strength, sway_sampling_coef, cross_fade_duration,
-                                                   True, False, return_pcm16)
-            yield wave, rate
+            yield self._synthesize(settings, jobs, voices, seg_sizes, return_numpy=True, return_pcm16=return_pcm16)
             return
         try:
             first = 0
             for group in chunk_groups([d for _, d in jobs], int(self.stream_first_chunks), int(self.ragged_chunks)):
-                mels = self._sample_jobs([jobs[i] for i in group], nfe_step, cfg_strength, sway_sampling_coef, voices=[job_voices[i] for i in group])
+                mels = self._sample_jobs([jobs[i] for i in group], [voices[i] for i in group], settings)
                 with torch.inference_mode():
-                    rows, row_start, got = mel_rows_of(mels, [skips[i] for i in group])
+                    rows, row_start, got = mel_rows_of(mels, [voices[i]["ref_audio_len"] for i in group])
                     if got != frames[first: first + len(group)]:
                         raise RuntimeError(f"the sampler returned {got} generated frames where {frames[first: first + len(group)]} were planned")
                     wave_buf, counts = decode_utterances(self.vocoder, kind, rows, row_start, got)
@@ -644,12 +497,6 @@ class F5TTSWrapper:
                 yield piece, self.target_sample_rate
         finally:
             session.close()
-
-    def _generated_frames(self, jobs):
-        """Frames each job's sample() call generates behind the prompt, from the host values alone: the sampler raises the frames asked for to
-        one more than the longer of the text and the prompt's mel, and caps them at 4096 (model/cfm.py)."""
-        cond_frames = self.model.mel_spec.frame_count(self.ref_audio_processed.shape[-1])
-        return [min(max(max(len(tokens[0]), cond_frames) + 1, duration), 4096) - self.ref_audio_len for tokens, duration in jobs]
 
     def _chunk_stream_pool(self, n):
         pool = getattr(self, "_chunk_streams_pool", None) or []

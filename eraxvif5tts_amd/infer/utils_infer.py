@@ -180,10 +180,11 @@ def cross_fade_concat(waves, cross_fade_duration, sample_rate=target_sample_rate
 
 
 # ---------------------------------------------------------------------------- the tail behind the sampler, on the device
-# generate(), infer_batch_process() and eval.prompts.infer_prompts() used to run, per utterance, one batch-1 vocoder call, the rms rule with a
-# device -> host comparison, a device -> host copy, and then cross_fade_concat / pcm16_bytes in numpy.  With the HIP vocoders the same arithmetic
-# runs as ONE ragged decode (Vocos.decode_ragged / BigVGAN.decode_ragged), ONE f5_wave_finish and ONE copy; the results are byte-identical (tests/test_gpu_wave_tail.py), so no
-# switch selects it: it is taken whenever the objects at hand allow it, and the per-utterance host loop otherwise.
+# Per utterance the reference runs one batch-1 vocoder call, the rms rule with a device -> host comparison, a device -> host copy, and then
+# cross_fade_concat / pcm16_bytes in numpy.  With the HIP vocoders the same arithmetic runs as ONE ragged decode (Vocos.decode_ragged /
+# BigVGAN.decode_ragged), ONE f5_wave_finish and ONE copy, byte-identical (tests/test_gpu_wave_tail.py), so no switch selects it:
+# `waves_of_mels` (F5TTSWrapper, infer_batch_process) and eval.prompts.infer_prompts take it whenever the objects at hand allow it, and the
+# per-utterance host loop otherwise.
 
 def plan_wave_tail(lengths, cross_fade_duration, sample_rate=target_sample_rate):
     """What `cross_fade_concat` does to waves of these lengths, from the lengths alone: ``joints`` (the n of every joint, by the reference's
@@ -616,6 +617,41 @@ def decode_utterances(vocoder, kind, rows, row_start, frames):
     return vocoder.decode_ragged_buffer(rows, row_start, frames)
 
 
+def waves_of_mels(vocoder, mel_spec_type, mels, skip, cross_fade_duration, sample_rate=target_sample_rate, rms=None, target_rms=target_rms,
+                  rms_index=None, want_spec=True, **tail):
+    """The mel -> wave stage behind the sampler (`F5TTSWrapper` and `infer_batch_process`): ``(done, waves, spectrograms)``.  With one of the
+    HIP vocoders and at least 2 generated frames per utterance, ONE ragged decode of all ``mels`` (the first ``skip`` frames of each left
+    out, see `mel_rows_of`) and ONE `finish_waves` (``rms`` / ``rms_index`` in its forms, ``tail``: its other arguments): ``done`` is its
+    ``(signal, pcm16)`` on the device and ``waves`` is empty.  Where the library answers F5_ENOTSUP (utterances shorter than their
+    cross-fades), and for a foreign vocoder object (per utterance a batch-1 call on the permuted slice), ``done`` is None and ``waves`` holds
+    every utterance's wave on the host, the rms rule applied, for `cross_fade_concat`.  ``spectrograms``: [mel, T_i] host arrays (none
+    unless ``want_spec``).  Byte-identical results either way (tests/test_gpu_wave_tail.py)."""
+    skips = [int(x) for x in skip] if isinstance(skip, (list, tuple)) else [int(skip)] * len(mels)
+
+    def gained(wave, i):  # the rms rule of the reference's loop (:491-492), for utterance i
+        r = None if rms is None else rms[rms_index[i]] if rms_index is not None else rms[i] if isinstance(rms, (list, tuple)) else rms
+        return wave * r / target_rms if r is not None and r < target_rms else wave
+
+    waves, spectrograms = [], []
+    kind = device_tail_kind(vocoder, *mels)
+    if kind is not None and (kind == "vocos") == (mel_spec_type == "vocos") and min(int(m.shape[1]) - k for m, k in zip(mels, skips)) >= 2:
+        rows, row_start, frames = mel_rows_of(mels, skips)
+        wave_buf, samples = decode_utterances(vocoder, kind, rows, row_start, frames)
+        done = finish_waves(wave_buf, samples, cross_fade_duration, sample_rate, rms=rms, target_rms=target_rms, rms_index=rms_index, **tail)
+        if want_spec:
+            spectrograms = [rows[r: r + t].t().cpu().numpy() for r, t in zip(row_start, frames)]
+        if done is None:
+            waves = [gained(w, i).cpu().numpy() for i, w in enumerate(torch.split(wave_buf, samples))]
+        return done, waves, spectrograms
+    for i, (generated, k) in enumerate(zip(mels, skips)):
+        generated = generated.to(torch.float32)[:, k:, :].permute(0, 2, 1)
+        generated_wave = vocoder.decode(generated) if mel_spec_type == "vocos" else vocoder(generated)  # reference :485-488
+        waves.append(gained(generated_wave, i).squeeze().cpu().numpy())
+        if want_spec:
+            spectrograms.append(generated[0].cpu().numpy())
+    return None, waves, spectrograms
+
+
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,
                   target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=device):
@@ -684,7 +720,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
             for chunk in process_batch(gen_text):
                 yield chunk
         return
-    generated_waves, spectrograms, mels = [], [], []
+    mels = []
     # Several text batches, each long enough for the tuned kernels: ONE ragged batch per group (F5TTSWrapper.generate does the same; every
     # utterance keeps the arithmetic -- and the noise draw order -- of its own batch-1 sample() call, so the audio is bit-identical).
     transformer = getattr(model_obj, "transformer", None)
@@ -693,16 +729,9 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     if (group_max >= 2 and len(jobs) >= 2 and hasattr(model_obj, "sample_ragged") and hasattr(transformer, "native_sample_ragged")
             and getattr(transformer, "BACKBONE", None) == 0 and min(d for _, d in jobs) >= 256 and max(d for _, d in jobs) <= 4096):
         with torch.inference_mode():
-            i = 0
-            while i < len(jobs):
-                group, rows = [], 0
-                while i < len(jobs) and len(group) < group_max and (not group or rows + jobs[i][1] <= 16384):
-                    group.append(jobs[i])
-                    rows += jobs[i][1]
-                    i += 1
-                for generated in model_obj.sample_ragged(audio, [j[0][0] for j in group], [j[1] for j in group], steps=nfe_step,
-                                                         cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef):
-                    mels.append(generated)
+            for idx in chunk_groups([d for _, d in jobs], 0, group_max):
+                mels += model_obj.sample_ragged(audio, [jobs[i][0][0] for i in idx], [jobs[i][1] for i in idx], steps=nfe_step,
+                                                cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef)
         batches = []
     for gen_text in batches:  # the reference's thread pool resolves to serial generators on the caller thread
         final_text_list, duration = plan_batch(gen_text)
@@ -710,28 +739,12 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
             generated, _ = model_obj.sample(cond=audio, text=final_text_list, duration=duration, steps=nfe_step, cfg_strength=cfg_strength,
                                             sway_sampling_coef=sway_sampling_coef, return_trajectory=False)
         mels.append(generated)
-    # mel -> wave for all batches at once on the device (one ragged vocoder call, one wave_finish, one copy) where the vocoder allows it
-    kind = device_tail_kind(vocoder, *mels)
-    if kind is not None and (kind == "vocos") == (mel_spec_type == "vocos") and min(int(m.shape[1]) for m in mels) - ref_audio_len >= 2:
-        with torch.inference_mode():
-            rows, row_start, frames = mel_rows_of(mels, ref_audio_len)
-            wave_buf, samples = decode_utterances(vocoder, kind, rows, row_start, frames)
-            done = finish_waves(wave_buf, samples, cross_fade_duration, rms=rms, target_rms=target_rms)
-            spectrograms = [rows[r: r + t].t().cpu().numpy() for r, t in zip(row_start, frames)]
-            if done is not None:
-                yield done[0].cpu().numpy(), target_sample_rate, np.concatenate(spectrograms, axis=1)
-                return
-            for w in torch.split(wave_buf, samples):  # utterances shorter than their cross-fades: the host functions join them
-                if rms < target_rms:
-                    w = w * rms / target_rms
-                generated_waves.append(w.cpu().numpy())
-    else:
-        with torch.inference_mode():
-            for generated in mels:
-                wave, mel = finish_batch(generated)
-                generated_waves.append(wave)
-                spectrograms.append(mel)
-    if generated_waves:
+    with torch.inference_mode():  # (the host-side pre-boost rms: the decision `rms < target_rms` is taken as the reference's loop takes it)
+        done, generated_waves, spectrograms = waves_of_mels(vocoder, mel_spec_type, mels, ref_audio_len, cross_fade_duration, rms=rms,
+                                                            target_rms=target_rms)
+    if done is not None:
+        yield done[0].cpu().numpy(), target_sample_rate, np.concatenate(spectrograms, axis=1)
+    elif generated_waves:
         yield cross_fade_concat(generated_waves, cross_fade_duration), target_sample_rate, np.concatenate(spectrograms, axis=1)
     else:
         yield None, target_sample_rate, None

@@ -56,6 +56,35 @@ def test_grouping_edge_cases():
     assert chunk_groups([300, 400], first=-2, group_max=8) == [[0, 1]]
 
 
+def _loop_of_infer_batch_process(durations, group_max):
+    """the grouping `infer_batch_process` carried as a loop of its own before it called `chunk_groups`, restated"""
+    groups, i = [], 0
+    while i < len(durations):
+        group, rows = [], 0
+        while i < len(durations) and len(group) < group_max and (not group or rows + durations[i] <= 16384):
+            group.append(i)
+            rows += durations[i]
+            i += 1
+        groups.append(group)
+    return groups
+
+
+def test_chunk_groups_is_the_loop_infer_batch_process_had():
+    rng = np.random.default_rng(1234)
+    lists = [[], [300], [16384], [16385], [20000, 100], [100, 20000, 100], [8192, 8192, 1], [8192, 8193], [4096] * 9]
+    for _ in range(400):
+        n = int(rng.integers(1, 25))
+        d = [int(x) for x in rng.integers(256, 4097, n)]
+        if rng.random() < 0.3:  # chunks above the row cap, which stand alone
+            for k in rng.integers(0, n, int(rng.integers(1, 3))):
+                d[int(k)] = int(rng.integers(16385, 40000))
+        lists.append(d)
+    assert sum(1 for d in lists if d and max(d) > 16384) >= 50
+    for d in lists:
+        for g in range(2, 10):
+            assert chunk_groups(d, 0, g) == _loop_of_infer_batch_process(d, g), (d, g)
+
+
 # ---------------------------------------------------------------------------------------------------------------- emitted counts
 @pytest.mark.parametrize("d", [0.0, 0.15, 1 / 24000])
 def test_emitted_counts_follow_the_plan(d):

@@ -34,8 +34,8 @@ def _whole(tts, text, seed, **kw):
 
 def _chunk_samples(tts, text):
     """sample counts of the chunks' waves, from the host rule alone (Vocos: (T - 1) * hop)"""
-    _, jobs = tts._plan_jobs(text, None, None, None, None, None, None, None)
-    return [(t - 1) * tts.hop_length for t in tts._generated_frames(jobs)]
+    _, jobs, voices, _ = tts._plan_jobs(text)
+    return [(t - 1) * tts.hop_length for t in tts._generated_frames(jobs, voices)]
 
 
 @pytest.mark.parametrize("nchunks", [2, 4])

@@ -89,7 +89,7 @@ def main():
                 tts.add_voice(name, path, text)
         voices = dict(tts.voices)
         pieces = split_voice_script(SCRIPT, voices)
-        _, jobs, job_voices, seg_sizes = tts._plan_multi(SCRIPT, None, None, None, None, None, None, None)
+        _, jobs, job_voices, seg_sizes = tts._plan_jobs(SCRIPT, tagged=True)
     assert len(pieces) == 12 and seg_sizes == [1] * 12, f"{len(pieces)} pieces, jobs per piece {seg_sizes}: a line is meant to be one chunk"
     line_secs = [(d - v["ref_audio_len"]) * 256 / SR for (_, d), v in zip(jobs, job_voices)]
     assert 8.0 <= min(line_secs) and max(line_secs) <= 15.0, line_secs
