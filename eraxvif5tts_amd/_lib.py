@@ -97,6 +97,7 @@ _PROTOS = {
     "f5_op_fold_weights": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f5_op_attention_ragged": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, _P, _P, _P]),
     "f5_op_conv_pos_embed": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_op_conv31": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "f5_op_layernorm_res": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "f5_op_f32_to_f16": (_I, [C.c_int64, _P, _P, _P, _P]),
     "f5_op_qknorm_rope": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -108,6 +109,7 @@ _PROTOS = {
     "f5_bench_mfma_rate": (_I, [_I, C.POINTER(C.c_float), _P]),
     "f5_tuning_set": (_I, [C.c_char_p, _I]),
     "f5_debug_gemm_clock": (_I, [_P]),
+    "f5_debug_last_gemm": (_I, [C.POINTER(C.c_int)] * 5),
     "f5_vocoder_create": (_I, [C.POINTER(VocosConfig), C.POINTER(_P)]),
     "f5_vocoder_set_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
     "f5_vocoder_has_tensor": (_I, [_P, C.c_char_p, C.POINTER(C.c_int64)]),

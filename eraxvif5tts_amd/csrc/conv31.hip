@@ -154,6 +154,7 @@ int launch_conv31(const GemmParams& p, int precision, hipStream_t stream) {
         else
             hipLaunchKernelGGL(conv31_kernel<128>, dim3(tiles, p.N / 64, nb), dim3(256), 0, stream, p, tiles);
         F5_LAUNCH_CHECK();
+        gemm_record_launch(GEMM_FAMILY_CONV31, 128, 64, GEMM_SCHED_PLAIN, precision == F5_PREC_FP16 ? GEMM_LAUNCH_F16 : 0);
         return 0;
     }
     const int tiles = cdiv(L, 256);
@@ -162,5 +163,6 @@ int launch_conv31(const GemmParams& p, int precision, hipStream_t stream) {
     else
         hipLaunchKernelGGL(conv31_kernel<256>, dim3(tiles, p.N / 64, nb), dim3(256), 0, stream, p, tiles);
     F5_LAUNCH_CHECK();
+    gemm_record_launch(GEMM_FAMILY_CONV31, 256, 64, GEMM_SCHED_PLAIN, precision == F5_PREC_FP16 ? GEMM_LAUNCH_F16 : 0);
     return 0;
 }

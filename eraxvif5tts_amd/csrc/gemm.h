@@ -90,6 +90,18 @@ struct GemmParams {
     unsigned long long* clk;  // diagnostic (f5_debug_gemm_clock): [workgroups][4] = (s_memtime, s_memrealtime) at workgroup start and end, or null
 };
 
+// What the last GEMM / conv31 launcher of this process launched (host-side record for the tests that force a tile: f5_debug_last_gemm).
+// Plain int stores by the launchers; nothing on the device reads it.
+enum GemmFamily { GEMM_FAMILY_TILE = 0, GEMM_FAMILY_FAST = 1, GEMM_FAMILY_W4 = 2, GEMM_FAMILY_CONV31 = 3 };  // tile kernel / 8-wave / one wave per SIMD / conv31
+enum GemmSchedule { GEMM_SCHED_PLAIN = 0, GEMM_SCHED_STAGGERED = 1, GEMM_SCHED_PERSISTENT = 2 };
+enum GemmLaunchFlags { GEMM_LAUNCH_F16 = 1, GEMM_LAUNCH_LNF = 2, GEMM_LAUNCH_F32 = 4, GEMM_LAUNCH_CONV = 8 };  // element type (neither: bf16), LNF build, implicit-GEMM conv
+struct GemmLaunchRecord {
+    int family, bm, bn;  // bm x bn: token x feature tile (conv31: tokens per workgroup x 64)
+    int schedule, flags;
+};
+extern GemmLaunchRecord g_last_gemm;  // gemm.hip
+inline void gemm_record_launch(int family, int bm, int bn, int schedule, int flags) { g_last_gemm = GemmLaunchRecord{family, bm, bn, schedule, flags}; }
+
 // kernel_kind: 0 = reference tile kernel (any shape), 1 = tuned 256x256 LDS-DMA bf16 kernel
 int launch_gemm(const GemmParams& p, int precision, int mode, int epi, int kernel_kind, hipStream_t stream);
 // true when the tuned kernel can run this problem (bf16 / fp16, tile-multiple shapes, supported epilogue)

@@ -1,5 +1,7 @@
 // gemm.hip -- reference tile kernel (any shape, bf16 / fp16 or fp32-input MFMA) + dispatch.
 // The tuned 256x256 LDS-DMA kernel lives in gemm_fast.hip.
+#include <type_traits>
+
 #include "gemm.h"
 #include "gemm_epilogue.h"
 
@@ -136,10 +138,14 @@ __global__ __launch_bounds__(256) void gemm_tile_kernel(GemmParams p) {
         }
 }
 
+GemmLaunchRecord g_last_gemm = {-1, 0, 0, 0, 0};
+
 template <typename T, int MODE, int EPI> static int launch_tile(const GemmParams& p, hipStream_t stream) {
     dim3 grid(cdiv(p.M, 64), cdiv(p.N, 64));
     hipLaunchKernelGGL((gemm_tile_kernel<T, MODE, EPI>), grid, dim3(256), 0, stream, p);
     F5_LAUNCH_CHECK();
+    gemm_record_launch(GEMM_FAMILY_TILE, 64, 64, GEMM_SCHED_PLAIN,
+                       (sizeof(T) == 4 ? GEMM_LAUNCH_F32 : std::is_same<T, f16_t>::value ? GEMM_LAUNCH_F16 : 0) | (MODE == GEMM_CONV31 ? GEMM_LAUNCH_CONV : 0));
     return 0;
 }
 

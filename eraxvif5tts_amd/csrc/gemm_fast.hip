@@ -1014,21 +1014,28 @@ template <int BN, int WM, int MODE, int EPI, bool LNF = false> static int launch
     const bool resid_ok = EPI == EPI_RESID && p.add2_f16 && p.out_f && (p.ldof & 7) == 0 && p.act == ACT_NONE && (!p.gate || p.gate_bstride == 0) &&
                           (!p.rowmask || p.rowbits);  // in-place update of the fp16 residual stream
     const bool persist_ok = MODE == GEMM_DENSE && (store_ok || resid_ok) && p.M % 256 == 0 && p.K >= 128 && p.N % 256 == 0 && (p.bias || LNF);
+    int sched = GEMM_SCHED_PLAIN;
     if constexpr (BN == 256) {
         if (g_gemm_variant == 0)
             hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 0, 4, LNF, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
         else if (g_gemm_persist && persist_ok) {
+            sched = GEMM_SCHED_PERSISTENT;
             if constexpr (EPI == EPI_STORE_T || EPI == EPI_GATE_T || EPI == EPI_ROPE_T || EPI == EPI_RESID)
                 hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, GEMM_DENSE, EPI, 30, 5, LNF, F5_EL>), dim3(nblocks < persist_grid() ? nblocks : persist_grid()), block,
                                    0, stream, p, tiles_n, nblocks);
-        } else
+        } else {
+            sched = GEMM_SCHED_STAGGERED;
             hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 1, 5, LNF, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
+        }
     } else if (BN == 128 && g_gemm_variant != 0) {  // staggered wave groups pay on the 128-wide tile too (M = 8192: FF2 44.6 -> 41.5 us, out-projection 26.3 -> 24.4 us)
+        sched = GEMM_SCHED_STAGGERED;
         hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 1, 5, LNF, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     } else {
         hipLaunchKernelGGL((gemm_fast_kernel<BN, WM, MODE, EPI, 0, 4, LNF, F5_EL>), grid, block, 0, stream, p, tiles_n, nblocks);
     }
     F5_LAUNCH_CHECK();
+    gemm_record_launch(GEMM_FAMILY_FAST, BMv, BN, sched,
+                       (Elem<F5_EL>::F16 ? GEMM_LAUNCH_F16 : 0) | (LNF ? GEMM_LAUNCH_LNF : 0) | (MODE == GEMM_CONV31 ? GEMM_LAUNCH_CONV : 0));
     return 0;
 }
 

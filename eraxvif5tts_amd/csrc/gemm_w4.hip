@@ -783,6 +783,7 @@ template <int MI> static int launch_w4(const GemmParams& p, int epi, hipStream_t
     else
         return f5_fail(F5_EINVAL, "gemm_w4: unsupported epilogue %d", epi);
     F5_LAUNCH_CHECK();
+    gemm_record_launch(GEMM_FAMILY_W4, MI * 32, 256, GEMM_SCHED_PERSISTENT, (Elem<F5_EL>::F16 ? GEMM_LAUNCH_F16 : 0) | (lnf ? GEMM_LAUNCH_LNF : 0));
     return 0;
 }
 

@@ -294,36 +294,72 @@ extern "C" int f5_op_attention_ragged(int precision, int attn_kernel, int nbr, i
 
 int g_op_conv_kernel = 0;  // tuning knob ("op_conv_kernel"): f5_op_conv_pos_embed runs the tuned conv kernels (bf16)
 
+// the padded input-channel window one 64-channel output tile of the grouped Conv1d(k = 31, groups = 16) reads (GemmParams::conv_win)
+static int conv31_window(int dim) {
+    const int cg = dim / 16;
+    int win = 0;
+    for (int n0 = 0; n0 < dim; n0 += 64) win = std::max(win, ((n0 + 63) / cg + 1) * cg - (n0 / cg) * cg);
+    return (int)round_up(win, 64);
+}
+
+// rearranges one conv weight [dim, dim/16, 31] (f32, on the device: copied back first) on the host into the tap-major image [31][dim][win] of
+// GEMM_CONV31 and uploads it in the precision's dtype
+static int upload_conv31_weight(DevArena& a, int precision, int dim, int win, const float* w, void** wr) {
+    const int cg = dim / 16;
+    std::vector<float> hw((size_t)dim * cg * 31), r((size_t)31 * dim * win, 0.f);
+    if (hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return f5_fail(F5_EHIP, "weight copy failed");
+    for (int n = 0; n < dim; ++n) {
+        const int w0c = ((n / 64 * 64) / cg) * cg, g0 = (n / cg) * cg;
+        for (int ci = 0; ci < cg; ++ci)
+            for (int tap = 0; tap < 31; ++tap) r[((size_t)tap * dim + n) * win + (g0 + ci - w0c)] = hw[((size_t)n * cg + ci) * 31 + tap];
+    }
+    return f5_upload_t(a, precision, r.data(), r.size(), wr);
+}
+
+// One grouped Conv1d(k = 31, groups = 16, padding 15) + bias (+ Mish) on its own, through exactly the GemmParams of the first launch of
+// f5_op_conv_pos_embed (test hook).  kernel 0 = the reference tile kernel, 1 = the tuned route as the model takes it (conv31 / conv31_tok knobs).
+extern "C" int f5_op_conv31(int precision, int kernel, int B, int N, int dim, const float* x, const float* w, const float* b, int act, float* out,
+                            f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (B <= 0 || N <= 0 || dim <= 0 || dim % 128 != 0 || !x || !w || !b || !out) return f5_fail(F5_EINVAL, "bad argument");
+    if (act != ACT_NONE && act != ACT_MISH) return f5_fail(F5_EINVAL, "f5_op_conv31: act is none (0) or mish (3)");
+    if (kernel != 0 && kernel != 1) return f5_fail(F5_EINVAL, "f5_op_conv31: kernel is 0 (tile kernel) or 1 (tuned route)");
+    if (kernel == 1 && precision != F5_PREC_BF16 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "f5_op_conv31: the tuned route runs the 16-bit modes");
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = B * N, cg = dim / 16, win = conv31_window(dim);
+    const size_t es = f5_elem_size(precision);
+    DevArena a;
+    int rc = 0;
+    do {
+        void *wr = nullptr, *xt = nullptr, *c1 = nullptr;
+        if ((rc = upload_conv31_weight(a, precision, dim, win, w, &wr))) break;
+        if ((rc = a.alloc(&xt, (size_t)rows * dim * es))) break;
+        if ((rc = a.alloc(&c1, (size_t)rows * dim * es))) break;
+        if ((rc = launch_convert_pad(precision, x, dim, rows, dim, dim, xt, dim, st))) break;
+        GemmParams g;
+        memset(&g, 0, sizeof(g));
+        g.A = xt; g.lda = dim; g.W = wr; g.M = rows; g.N = dim; g.K = 31 * win; g.bias = b; g.act = act;
+        g.rows_per_batch = N; g.conv_cg = cg; g.conv_win = win; g.out_t = c1; g.ldo = dim;
+        if (kernel == 1 && !gemm_fast_supported(g, precision, GEMM_CONV31, EPI_STORE_T)) { rc = f5_fail(F5_ENOTSUP, "f5_op_conv31: the tuned kernels cannot run this shape"); break; }
+        if ((rc = launch_gemm(g, precision, GEMM_CONV31, EPI_STORE_T, kernel, st))) break;
+        rc = launch_convert_back(precision, c1, dim, rows, dim, out, dim, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
 extern "C" int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const float* x, const float* w0, const float* b0, const float* w1,
                                     const float* b1, float* out, f5_stream_t stream) {
     F5_TRY(f5_check_device());
     if (B <= 0 || N <= 0 || dim <= 0 || dim % 128 != 0 || !x || !w0 || !b0 || !w1 || !b1 || !out) return f5_fail(F5_EINVAL, "bad argument");
     hipStream_t st = (hipStream_t)stream;
-    const int rows = B * N, cg = dim / 16;
-    int win = 0;
-    for (int n0 = 0; n0 < dim; n0 += 64) win = std::max(win, ((n0 + 63) / cg + 1) * cg - (n0 / cg) * cg);
-    win = (int)round_up(win, 64);
+    const int rows = B * N, cg = dim / 16, win = conv31_window(dim);
     const size_t es = f5_elem_size(precision);
     DevArena a;
     int rc = 0;
     do {
-        // rearrange the two weights on the host (weights come from the device: copy back first)
-        std::vector<float> hw((size_t)dim * cg * 31), r((size_t)31 * dim * win);
         void* wr[2] = {nullptr, nullptr};
         const float* ws[2] = {w0, w1};
-        for (int li = 0; li < 2 && rc == 0; ++li) {
-            if (hipMemcpy(hw.data(), ws[li], hw.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = f5_fail(F5_EHIP, "weight copy failed");
-                break;
-            }
-            std::fill(r.begin(), r.end(), 0.f);
-            for (int n = 0; n < dim; ++n) {
-                const int w0c = ((n / 64 * 64) / cg) * cg, g0 = (n / cg) * cg;
-                for (int ci = 0; ci < cg; ++ci)
-                    for (int tap = 0; tap < 31; ++tap) r[((size_t)tap * dim + n) * win + (g0 + ci - w0c)] = hw[((size_t)n * cg + ci) * 31 + tap];
-            }
-            rc = f5_upload_t(a, precision, r.data(), r.size(), &wr[li]);
-        }
+        for (int li = 0; li < 2 && rc == 0; ++li) rc = upload_conv31_weight(a, precision, dim, win, ws[li], &wr[li]);
         if (rc) break;
         void *xt = nullptr, *c1 = nullptr;
         float* acc = nullptr;
@@ -694,6 +730,17 @@ extern unsigned long long* g_gemm_clk_buf;
 // diagnostic: while dev_buf (u64 [workgroups * 4]) is non-null the tuned GEMM writes (s_memtime, s_memrealtime) at workgroup start and end
 extern "C" int f5_debug_gemm_clock(void* dev_buf) {
     g_gemm_clk_buf = reinterpret_cast<unsigned long long*>(dev_buf);
+    return 0;
+}
+
+// diagnostic: what the last GEMM / conv31 launcher of this process launched (gemm.h: GemmLaunchRecord; family -1 = nothing yet)
+extern "C" int f5_debug_last_gemm(int* family, int* bm, int* bn, int* schedule, int* flags) {
+    if (!family || !bm || !bn || !schedule || !flags) return f5_fail(F5_EINVAL, "null argument");
+    *family = g_last_gemm.family;
+    *bm = g_last_gemm.bm;
+    *bn = g_last_gemm.bn;
+    *schedule = g_last_gemm.schedule;
+    *flags = g_last_gemm.flags;
     return 0;
 }
 

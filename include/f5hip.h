@@ -340,6 +340,11 @@ F5_API int f5_op_attention_ragged(int precision, int attn_kernel, int nbr, int c
  * [dim, dim/16, 31] + bias [dim] (two layers) */
 F5_API int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const float* x, const float* w0, const float* b0,
                          const float* w1, const float* b1, float* out, f5_stream_t stream);
+/* One of its convolutions alone (test hook): out f32 [B, N, dim] = act(conv(x) + b), grouped Conv1d(k = 31, groups = 16, padding 15) with exactly
+ * the launch parameters of the first convolution above, the precision's dtype in and out.  act: 0 = none, 3 = mish.  kernel 0 = the reference
+ * tile kernel, 1 = the tuned route as the model takes it (knobs "conv31", "conv31_tok"; the 16-bit modes). */
+F5_API int f5_op_conv31(int precision, int kernel, int B, int N, int dim, const float* x, const float* w, const float* b, int act, float* out,
+                        f5_stream_t stream);
 
 /* Test and diagnostic entry points of the row-wise kernels: each stages its f32 device inputs into the dtypes the model path uses and calls
  * the production launcher, so the launcher's own dispatch (and its tuning knobs) decides which kernel runs.  All pointers are device pointers.
@@ -385,6 +390,11 @@ F5_API int f5_bench_mfma_rate(int random_operands, float* tflops, f5_stream_t st
 /* the clock the chip holds under the tuned GEMM: while dev_buf (dev u64 [workgroups * 4]) is non-NULL every workgroup writes (s_memtime,
  * s_memrealtime) at its start and end; clock = d(s_memtime) / d(s_memrealtime) x 100 MHz */
 F5_API int f5_debug_gemm_clock(void* dev_buf);
+/* What the last GEMM / conv31 launcher of this process launched (a host-side record; tests that force a tile prove with it that the tile ran):
+ * family 0 = reference tile kernel, 1 = tuned 8-wave kernel, 2 = one-wave-per-SIMD kernel, 3 = conv31 (-1: nothing launched yet); bm x bn = token x
+ * feature tile (conv31: tokens per workgroup x 64); schedule 0 = plain ring, 1 = staggered wave groups, 2 = persistent grid; flags: 1 = fp16
+ * elements, 4 = fp32 elements (neither: bf16), 2 = LayerNorm-fold build, 8 = grouped conv as an implicit GEMM. */
+F5_API int f5_debug_last_gemm(int* family, int* bm, int* bn, int* schedule, int* flags);
 /* process-wide kernel tuning knobs for A/B measurements ("gemm_variant": main-loop schedule of the tuned GEMM) */
 F5_API int f5_tuning_set(const char* key, int value);
 

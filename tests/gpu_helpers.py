@@ -1,7 +1,9 @@
 """Shared helpers of the GPU parity tests (everything goes through the C ABI of libf5hip.so)."""
 import ctypes as C
+import math
 
 import torch
+import torch.nn.functional as F
 
 from eraxvif5tts_amd import _lib
 from eraxvif5tts_amd.model import CFM, DiT
@@ -118,8 +120,244 @@ def op_ln_fold(epi, x, A, Wo, bo, gate, W, bias, scale, shift, pivot=None, act="
     return xs.cpu(), stats.cpu(), out.cpu()
 
 
+def op_linear_fused_p(precision, kernel, epi, A, W, bias, act="none", gate=None, rowmask=None, rope=None, rope_heads=0, seq=0, stream_in=None):
+    """include/f5hip.h: f5_op_linear_fused_p -- op_linear_fused in the 16-bit mode `precision` (0 bf16, 2 fp16)."""
+    lib = _lib.load()
+    M, K = A.shape
+    N = W.shape[0]
+    dev = [None if t is None else t.cuda().float().contiguous() for t in (A, W, bias, gate, rope)]
+    mk = None if rowmask is None else rowmask.cuda().to(torch.uint8).contiguous()
+    out = torch.empty(M, N, device="cuda") if stream_in is None else stream_in.cuda().float().contiguous().clone()
+    _lib.check(lib.f5_op_linear_fused_p(precision, kernel, epi, M, N, K, _lib.ptr(dev[0]), _lib.ptr(dev[1]), _lib.ptr(dev[2]), _lib.ACT[act],
+                                        _lib.ptr(dev[3]), _lib.ptr(mk), _lib.ptr(dev[4]), rope_heads, seq, _lib.ptr(out), _lib.stream_ptr()))
+    return out.cpu()
+
+
+def op_ln_fold_p(precision, epi, x, A, Wo, bo, gate, W, bias, scale, shift, pivot=None, act="none", rope=None, rope_heads=0, seq=0):
+    """include/f5hip.h: f5_op_ln_fold_p.  Returns (updated fp16 stream as f32 [M, D], stats [M, 2] = (mean, rstd), out [M, N])."""
+    lib = _lib.load()
+    M, D = x.shape
+    N, Kb = W.shape[0], A.shape[1]
+    dev = [None if t is None else t.cuda().float().contiguous() for t in (A, Wo, bo, gate, pivot, W, bias, scale, shift, rope)]
+    xs = x.cuda().float().contiguous().clone()
+    stats = torch.empty(M, 2, device="cuda")
+    out = torch.empty(M, N, device="cuda")
+    _lib.check(lib.f5_op_ln_fold_p(precision, epi, M, D, N, Kb, _lib.ptr(xs), *[_lib.ptr(t) for t in dev[:9]], _lib.ACT[act], _lib.ptr(dev[9]), rope_heads,
+                                   seq, _lib.ptr(stats), _lib.ptr(out), _lib.stream_ptr()))
+    return xs.cpu(), stats.cpu(), out.cpu()
+
+
+def op_conv31(precision, kernel, x, w, b, act="none"):
+    """include/f5hip.h: f5_op_conv31 -- one grouped Conv1d(k = 31, groups = 16, padding 15) + bias (+ Mish): x [B, N, dim], w [dim, dim/16, 31]."""
+    lib = _lib.load()
+    B, N, D = x.shape
+    xs = [t.cuda().float().contiguous() for t in (x, w, b)]
+    out = torch.empty(B, N, D, device="cuda")
+    _lib.check(lib.f5_op_conv31(precision, kernel, B, N, D, *[_lib.ptr(t) for t in xs], _lib.ACT[act], _lib.ptr(out), _lib.stream_ptr()), "f5_op_conv31")
+    return out.cpu()
+
+
+# f5_debug_last_gemm (include/f5hip.h): kernel families, schedules and flag bits of the launch record
+FAM_TILE, FAM_FAST, FAM_W4, FAM_CONV31 = 0, 1, 2, 3
+SCHED_PLAIN, SCHED_STAGGERED, SCHED_PERSISTENT = 0, 1, 2
+FLAG_F16, FLAG_LNF, FLAG_F32, FLAG_CONV = 1, 2, 4, 8
+
+
+def last_gemm():
+    """(family, bm, bn, schedule, flags) of the last GEMM / conv31 launch of this process."""
+    v = [C.c_int(0) for _ in range(5)]
+    _lib.check(_lib.load().f5_debug_last_gemm(*[C.byref(t) for t in v]))
+    return tuple(t.value for t in v)
+
+
+# ----------------------------------------------------------------------------- element-wise comparison of the 16-bit GEMM / conv kernels
+P_BF16, P_FP16 = 0, 2
+F32_ULPS = 8 * 2.0 ** -23
+
+
+def round_to(precision, t):
+    """`t` rounded once (to nearest even) to the stored type of the 16-bit mode `precision`, as f32."""
+    return (t.float().half() if precision == P_FP16 else t.float().to(torch.bfloat16)).float()
+
+
+def check_elementwise(name, out, ref, scale, precision=P_FP16, extra=None):
+    """|out - ref| <= 1 ulp(ref) of the stored type (fp16 / bf16) + 8 fp32 ulps of `scale` (+ extra), element-wise; prints the worst share of
+    the bound before it asserts.  Pure tensor arithmetic: runs on the CPU."""
+    ref = ref.double()
+    err = (out.double() - ref).abs()
+    ulp = fp16_ulp(ref) if precision == P_FP16 else bf16_ulp(ref)
+    tname = "fp16" if precision == P_FP16 else "bf16"
+    bound = ulp + F32_ULPS * scale.double().abs()
+    if extra is not None:
+        bound = bound + extra.double()
+    ratio = err / bound
+    worst = float(ratio.max())
+    print(f"  {name}: worst {worst:.3f} of the bound, {float((err / ulp).max()):.3f} {tname} ulp")
+    assert torch.isfinite(out).all(), name
+    bad = ratio > 1
+    assert not bad.any(), f"{name}: {int(bad.sum())} elements out of bound (worst {worst:.3f} of it), first at {bad.nonzero()[0].tolist()}"
+    return worst
+
+
+def linear_ref(A, W, b, act):
+    """fp64 result and the magnitude the fp32 arithmetic works on (GELU's derivative is below 1.13: the accumulation error passes through it)."""
+    ref = A.double() @ W.double().t() + b.double()
+    scale = A.double().abs() @ W.double().abs().t() + b.double().abs()
+    if act == "gelu_tanh":
+        ref, scale = F.gelu(ref, approximate="tanh"), 1.13 * scale
+    return ref, scale
+
+
+def rope_ref(lin, ls, rope, seq, rope_heads=1):
+    """x_transformers' rotation of adjacent feature pairs on the q | k columns of the first rope_heads heads of a fused QKV output [M, 3 * inner]
+    (fp64) and of its magnitude; rope [seq, 32, 2] = (cos, sin), position = row % seq."""
+    M, inner = lin.shape[0], lin.shape[1] // 3
+    ref, scale = lin.clone(), ls.clone()
+    cs = rope.double().reshape(seq, 32, 2)[torch.arange(M) % seq]
+    cos, sin = cs[..., 0], cs[..., 1]
+    for part in range(2):
+        for h in range(rope_heads):
+            c0 = part * inner + h * 64
+            v, s = lin[:, c0:c0 + 64].reshape(M, 32, 2), ls[:, c0:c0 + 64].reshape(M, 32, 2)
+            ref[:, c0:c0 + 64] = torch.stack([v[..., 0] * cos - v[..., 1] * sin, v[..., 1] * cos + v[..., 0] * sin], dim=-1).reshape(M, 64)
+            scale[:, c0:c0 + 64] = torch.stack([s[..., 0] * cos.abs() + s[..., 1] * sin.abs(), s[..., 1] * cos.abs() + s[..., 0] * sin.abs()], dim=-1).reshape(M, 64)
+    return ref, scale
+
+
+def fused_ref(epi_name, A, W, b, act="none", gate=None, rowmask=None, x=None, rope=None, rope_heads=1, seq=0):
+    """fp64 reference and fp32 magnitude of one fused epilogue (oracle/cpu_ref.py: dit_block's linears, apply_rope): store | gate | rope | resid."""
+    lin, ls = linear_ref(A, W, b, act)
+    keep = None if rowmask is None else rowmask.double()[:, None]
+    if epi_name == "resid":
+        upd = gate.double() * lin if keep is None else gate.double() * lin * keep  # masked rows are left as they are
+        return x.double() + upd, x.double().abs() + gate.double().abs() * ls
+    if epi_name == "gate":
+        return (gate.double() * lin if keep is None else gate.double() * lin * keep), gate.double().abs() * ls  # masked rows are zeros
+    if epi_name == "store":
+        return lin, ls
+    return rope_ref(lin, ls, rope, seq, rope_heads)
+
+
+def run_fused(precision, kernel, epi_name, A, W, b, act="none", gate=None, rowmask=None, x=None, rope=None, rope_heads=1, seq=0):
+    if epi_name == "resid":
+        return op_linear_fused_p(precision, kernel, EPI_RESID, A, W, b, "none", gate, rowmask, stream_in=x)
+    if epi_name == "gate":
+        return op_linear_fused_p(precision, kernel, EPI_GATE_T, A, W, b, act, gate, rowmask)
+    if epi_name == "store":
+        return op_linear_fused_p(precision, kernel, EPI_STORE_T, A, W, b, act)
+    return op_linear_fused_p(precision, kernel, EPI_ROPE_T, A, W, b, "none", None, None, rope, rope_heads, seq)
+
+
+def linear_problem(precision, M, N, K, seed):
+    """randn operands rounded to the mode's 16-bit type on the host (so the kernel's own input conversion is exact), fp32 bias"""
+    g = torch.Generator().manual_seed(seed)
+    A, W, b = round_to(precision, torch.randn(M, K, generator=g)), round_to(precision, torch.randn(N, K, generator=g) / math.sqrt(K)), torch.randn(N, generator=g)
+    return g, A, W, b
+
+
+def fused_case(precision, epi_name, M, N, K, seq, seed):
+    """Random real-valued inputs, the launch and the fp64 reference + fp32 magnitude of one fused epilogue in the 16-bit mode `precision`:
+    resid (in place on the fp16 stream, gate), gate (+ row mask), store (GELU tanh), rope (one head)."""
+    g, A, W, b = linear_problem(precision, M, N, K, seed)
+    kw = {}
+    if epi_name == "resid":
+        kw = dict(gate=torch.randn(N, generator=g), x=(torch.randn(M, N, generator=g) * 3).half().float())
+    elif epi_name == "gate":
+        kw = dict(gate=torch.randn(N, generator=g), rowmask=torch.rand(M, generator=g) > 0.2)
+    elif epi_name == "store":
+        kw = dict(act="gelu_tanh")
+    else:
+        ang = torch.rand(seq, 32, generator=g) * 6.28
+        kw = dict(rope=torch.stack([ang.cos(), ang.sin()], dim=-1), rope_heads=1, seq=seq)
+    ref, scale = fused_ref(epi_name, A, W, b, **kw)
+    run = lambda kernel=1: run_fused(precision, kernel, epi_name, A, W, b, **kw)
+    return run, ref, scale
+
+
+def ln_fold_inputs(M, D, N, Kb, epi, offset=40.0):
+    """One LayerNorm-fold site at offset 40 (f5_op_ln_fold_p): the positional arguments (x, A, Wo, bo, gate, W, bias, scale, shift) and the keyword
+    arguments (pivots; FF1 + GELU for epi 0, fused QKV + RoPE on one head with seq = M / 2 for epi 4).  A and Wo are exact in bf16 and in fp16."""
+    g = torch.Generator().manual_seed(M + N + int(offset))
+    both = lambda t: torch.where(t.abs() < 2.0 ** -14, torch.zeros_like(t), t.to(torch.bfloat16).float())  # exact in bf16 and in fp16
+    x = torch.randn(M, D, generator=g) * 1.7 + offset + torch.randn(M, 1, generator=g) * 0.5
+    A = both(torch.randn(M, Kb, generator=g))
+    Wo = both(torch.randn(D, Kb, generator=g) / Kb ** 0.5)
+    bo = torch.randn(D, generator=g) * 0.1
+    gate = torch.randn(D, generator=g) * 0.3
+    W = torch.randn(N, D, generator=g) / D ** 0.5
+    bias = torch.randn(N, generator=g) * 0.1
+    scale, shift = torch.randn(D, generator=g) * 0.2, torch.randn(D, generator=g) * 0.3
+    seq = M // 2 if epi == 4 else M
+    rope = None
+    if epi == 4:
+        ang = torch.arange(seq)[:, None] * (1.0 / 10000.0 ** (torch.arange(0, 64, 2) / 64.0))[None, :]
+        rope = torch.stack([ang.cos(), ang.sin()], dim=-1).reshape(seq, 64).float()
+    xh = x.half().float()
+    pivot = torch.stack([xh.mean(dim=1) + 0.01, torch.ones(M)], dim=1)
+    kw = dict(pivot=pivot, act="gelu_tanh" if epi == 0 else "none", rope=rope, rope_heads=1, seq=seq)
+    return (x, A, Wo, bo, gate, W, bias, scale, shift), kw
+
+
+def ln_fold_ref(args, kw, epi, xs, stats):
+    """fp64 reference and fp32 magnitude of the folded projection rstd (x . W'^T - mean c1) + c2 from the kernel's own stream `xs`, statistics
+    and fold table (f5_op_fold_weights), through GELU (epi 0) or RoPE (epi 4)."""
+    lib = _lib.load()
+    _, _, _, _, _, W, bias, scale, shift = args
+    N, D = W.shape
+    M = xs.shape[0]
+    dev = [t.cuda().float().contiguous() for t in (W, bias, scale, shift, scale, shift)]
+    Wt, c1, c2 = torch.empty(N, D, device="cuda"), torch.empty(N, device="cuda"), torch.empty(N, device="cuda")
+    _lib.check(lib.f5_op_fold_weights(N, N, 0, D, 0, *[_lib.ptr(t) for t in dev], _lib.ptr(Wt), _lib.ptr(c1), _lib.ptr(c2), _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    Wt, c1, c2 = Wt.cpu().double(), c1.cpu().double(), c2.cpu().double()
+    mean, rstd = stats[:, 0].double()[:, None], stats[:, 1].double()[:, None]
+    ref = rstd * (xs.double() @ Wt.t() - mean * c1) + c2
+    mag = rstd * (xs.double().abs() @ Wt.abs().t() + mean.abs() * Wt.abs().sum(dim=1)) + bias.double().abs() + W.double().abs() @ shift.double().abs()
+    if epi == 0:
+        return F.gelu(ref, approximate="tanh"), 1.13 * mag
+    return rope_ref(ref, mag, kw["rope"], kw["seq"], 1)
+
+
+def ints(g, shape, lo, hi):
+    return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+def exact_case(epi, M, N, K, seq, rope_heads, masked, seed):
+    """Exact inputs of one epilogue (test_gpu_gemm_tiles.py: integers and halves whose every product, partial sum and epilogue value is exact
+    in fp32): (positional A, W, b), keyword arguments of G.run_fused / G.fused_ref."""
+    g = torch.Generator().manual_seed(seed)
+    A, W, b = ints(g, (M, K), -2, 2), ints(g, (N, K), -1, 1), ints(g, (N,), -8, 8)
+    kw = {}
+    if epi in ("gate", "resid"):
+        kw["gate"] = torch.tensor([0.5, -0.5, 1.0, -1.0, 2.0, -2.0])[torch.randint(0, 6, (N,), generator=g)]
+        if masked:
+            kw["rowmask"] = torch.rand(M, generator=g) > 0.2
+    if epi == "resid":
+        kw["x"] = ints(g, (M, N), -128, 128) * 0.5
+    if epi == "rope":
+        table = torch.tensor([[1.0, 0.0], [0.0, 1.0], [-1.0, 0.0], [0.0, -1.0], [0.5, 0.5]])
+        kw.update(rope=table[torch.randint(0, 5, (seq, 32), generator=g)], rope_heads=rope_heads, seq=seq)
+    return (A, W, b), kw
+
+
+def conv31_ref(x, w, b):
+    """Grouped Conv1d(k = 31, groups = 16, padding 15) of x [B, L, dim] in fp64, zero padding inside each utterance; one matmul per group."""
+    B, L, dim = x.shape
+    cg = dim // 16
+    xp = F.pad(x.double(), (0, 0, 15, 15))
+    win = xp.unfold(1, 31, 1)  # [B, L, dim, 31]
+    out = torch.empty(B, L, dim, dtype=torch.float64)
+    for gi in range(16):
+        a = win[:, :, gi * cg:(gi + 1) * cg, :].reshape(B * L, cg * 31)
+        out[:, :, gi * cg:(gi + 1) * cg] = (a @ w[gi * cg:(gi + 1) * cg].double().reshape(cg, cg * 31).t()).reshape(B, L, cg)
+    return out + b.double()
+
+
 # ----------------------------------------------------------------------------- row-wise kernels (include/f5hip.h: test and diagnostic entry points)
-KNOB_DEFAULTS = {b"ln_rows": 2, b"ln_rows_min": 16384, b"ln_wide": 1, b"residual_f16": 1}
+# defaults of the tuning knobs the tests set: the `int g_... = ...;` definitions of csrc/
+KNOB_DEFAULTS = {b"ln_rows": 2, b"ln_rows_min": 16384, b"ln_wide": 1, b"residual_f16": 1,
+                 b"gemm_tile": 0, b"gemm_bm128": 1, b"gemm_group": 0, b"gemm_persist_grid": 0, b"gemm_reverse_sites": 8, b"gemm_w4": 1, b"gemm_w4_bm": 0,
+                 b"gemm_persist": 1, b"gemm_lean": 1, b"gemm_variant": 1, b"conv31": 1, b"conv31_tok": 0, b"op_conv_kernel": 0}
 
 
 class knobs:

@@ -34,19 +34,10 @@ def f16r(t):
 
 
 def check_f16(name, out, ref, scale, extra=None):
-    """|out - ref| <= 1 fp16 ulp(ref) + 8 fp32 ulps of `scale` (+ extra), element-wise; prints the worst share of the bound before it asserts."""
-    ref = ref.double()
-    err = (out.double() - ref).abs()
-    bound = fp16_ulp(ref) + F32_ULPS * scale.double().abs()
-    if extra is not None:
-        bound = bound + extra.double()
-    ratio = err / bound
-    worst = float(ratio.max())
-    print(f"  {name}: worst {worst:.3f} of the bound, {float((err / fp16_ulp(ref)).max()):.3f} fp16 ulp")
-    assert torch.isfinite(out).all(), name
-    bad = ratio > 1
-    assert not bad.any(), f"{name}: {int(bad.sum())} elements out of bound (worst {worst:.3f} of it), first at {bad.nonzero()[0].tolist()}"
-    return worst
+    """|out - ref| <= 1 fp16 ulp(ref) + 8 fp32 ulps of `scale` (+ extra), element-wise; prints the worst share of the bound before it asserts
+    (gpu_helpers.check_elementwise: the comparator shared with test_gpu_gemm_tiles.py)."""
+    import gpu_helpers as G
+    return G.check_elementwise(name, out, ref, scale, P_FP16, extra)
 
 
 class knobs:
@@ -67,46 +58,24 @@ class knobs:
         return False
 
 
-def op_linear_fused_p(precision, kernel, epi, A, W, bias, act="none", gate=None, rowmask=None, rope=None, rope_heads=0, seq=0, stream_in=None):
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
-    M, K = A.shape
-    N = W.shape[0]
-    dev = [None if t is None else t.cuda().float().contiguous() for t in (A, W, bias, gate, rope)]
-    mk = None if rowmask is None else rowmask.cuda().to(torch.uint8).contiguous()
-    out = torch.empty(M, N, device="cuda") if stream_in is None else stream_in.cuda().float().contiguous().clone()
-    _lib.check(lib.f5_op_linear_fused_p(precision, kernel, epi, M, N, K, _lib.ptr(dev[0]), _lib.ptr(dev[1]), _lib.ptr(dev[2]), _lib.ACT[act],
-                                        _lib.ptr(dev[3]), _lib.ptr(mk), _lib.ptr(dev[4]), rope_heads, seq, _lib.ptr(out), _lib.stream_ptr()))
-    return out.cpu()
+def op_linear_fused_p(*args, **kw):
+    import gpu_helpers as G
+    return G.op_linear_fused_p(*args, **kw)
 
 
-def op_ln_fold_p(precision, epi, x, A, Wo, bo, gate, W, bias, scale, shift, pivot=None, act="none", rope=None, rope_heads=0, seq=0):
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
-    M, D = x.shape
-    N, Kb = W.shape[0], A.shape[1]
-    dev = [None if t is None else t.cuda().float().contiguous() for t in (A, Wo, bo, gate, pivot, W, bias, scale, shift, rope)]
-    xs = x.cuda().float().contiguous().clone()
-    stats = torch.empty(M, 2, device="cuda")
-    out = torch.empty(M, N, device="cuda")
-    _lib.check(lib.f5_op_ln_fold_p(precision, epi, M, D, N, Kb, _lib.ptr(xs), *[_lib.ptr(t) for t in dev[:9]], _lib.ACT[act], _lib.ptr(dev[9]), rope_heads,
-                                   seq, _lib.ptr(stats), _lib.ptr(out), _lib.stream_ptr()))
-    return xs.cpu(), stats.cpu(), out.cpu()
+def op_ln_fold_p(*args, **kw):
+    import gpu_helpers as G
+    return G.op_ln_fold_p(*args, **kw)
 
 
 def _problem(M, N, K, seed):
-    g = torch.Generator().manual_seed(seed)
-    A, W, b = f16r(torch.randn(M, K, generator=g)), f16r(torch.randn(N, K, generator=g) / math.sqrt(K)), torch.randn(N, generator=g)
-    return g, A, W, b
+    import gpu_helpers as G
+    return G.linear_problem(P_FP16, M, N, K, seed)
 
 
 def _linear_ref(A, W, b, act):
-    """fp64 result and the magnitude the fp32 arithmetic works on (GELU's derivative is below 1.13: the accumulation error passes through it)."""
-    ref = A.double() @ W.double().t() + b.double()
-    scale = A.double().abs() @ W.double().abs().t() + b.double().abs()
-    if act == "gelu_tanh":
-        ref, scale = F.gelu(ref, approximate="tanh"), 1.13 * scale
-    return ref, scale
+    import gpu_helpers as G
+    return G.linear_ref(A, W, b, act)
 
 
 # ----------------------------------------------------------------------------- 1. generic tile kernel
@@ -139,43 +108,9 @@ def test_tuned_gemm(shape, act, kn):
 
 
 def _fused_case(epi_name, M, N, K, seq, seed):
-    """Inputs, the launch and the fp64 reference + fp32 magnitude of one fused epilogue (oracle/cpu_ref.py: dit_block's linears, apply_rope)."""
+    """Inputs, the launch and the fp64 reference + fp32 magnitude of one fused epilogue (gpu_helpers.fused_case in fp16 mode)."""
     import gpu_helpers as G
-    g, A, W, b = _problem(M, N, K, seed)
-    if epi_name == "resid":
-        gate = torch.randn(N, generator=g)
-        x = f16r(torch.randn(M, N, generator=g) * 3)
-        lin, ls = _linear_ref(A, W, b, "none")
-        ref = x.double() + gate.double() * lin
-        scale = x.double().abs() + gate.double().abs() * ls
-        run = lambda kernel=1: op_linear_fused_p(P_FP16, kernel, G.EPI_RESID, A, W, b, "none", gate, None, stream_in=x)
-        return run, ref, scale
-    if epi_name == "gate":
-        gate = torch.randn(N, generator=g)
-        rowmask = torch.rand(M, generator=g) > 0.2
-        lin, ls = _linear_ref(A, W, b, "none")
-        ref = gate.double() * lin * rowmask.double()[:, None]
-        scale = gate.double().abs() * ls
-        run = lambda kernel=1: op_linear_fused_p(P_FP16, kernel, G.EPI_GATE_T, A, W, b, "none", gate, rowmask)
-        return run, ref, scale
-    if epi_name == "store":
-        ref, scale = _linear_ref(A, W, b, "gelu_tanh")
-        run = lambda kernel=1: op_linear_fused_p(P_FP16, kernel, G.EPI_STORE_T, A, W, b, "gelu_tanh")
-        return run, ref, scale
-    ang = torch.rand(seq, 32, generator=g) * 6.28
-    rope, heads = torch.stack([ang.cos(), ang.sin()], dim=-1), 1
-    lin, ls = _linear_ref(A, W, b, "none")
-    ref, scale = lin.clone(), ls.clone()
-    inner = N // 3
-    cs = rope.double()[torch.arange(M) % seq]
-    cos, sin = cs[..., 0], cs[..., 1]
-    for part in range(2):
-        c0 = part * inner
-        v, s = lin[:, c0:c0 + 64].reshape(M, 32, 2), ls[:, c0:c0 + 64].reshape(M, 32, 2)
-        ref[:, c0:c0 + 64] = torch.stack([v[..., 0] * cos - v[..., 1] * sin, v[..., 1] * cos + v[..., 0] * sin], dim=-1).reshape(M, 64)
-        scale[:, c0:c0 + 64] = torch.stack([s[..., 0] * cos.abs() + s[..., 1] * sin.abs(), s[..., 1] * cos.abs() + s[..., 0] * sin.abs()], dim=-1).reshape(M, 64)
-    run = lambda kernel=1: op_linear_fused_p(P_FP16, kernel, G.EPI_ROPE_T, A, W, b, "none", None, None, rope, heads, seq)
-    return run, ref, scale
+    return G.fused_case(P_FP16, epi_name, M, N, K, seq, seed)
 
 
 @pytest.mark.parametrize("kn", KNOB_SETS, ids=KNOB_IDS)
@@ -211,52 +146,12 @@ def test_layernorm_fold_site(M, D, N, Kb, epi):
     """One fold site at offset 40 through f5_op_ln_fold_p: the output now carries fp16 rounding; the stream and the statistics are bit-equal to
     the bf16-mode call on the same inputs (A and Wo hold values exact in both 16-bit types).  The reference of the folded projection is
     rstd (x . W'^T - mean c1) + c2 in fp64 from the kernel's own stream, statistics and table (f5_op_fold_weights)."""
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
-    offset = 40.0
-    g = torch.Generator().manual_seed(M + N + int(offset))
-    both = lambda t: torch.where(t.abs() < 2.0 ** -14, torch.zeros_like(t), t.to(torch.bfloat16).float())  # exact in bf16 and in fp16
-    x = torch.randn(M, D, generator=g) * 1.7 + offset + torch.randn(M, 1, generator=g) * 0.5
-    A = both(torch.randn(M, Kb, generator=g))
-    Wo = both(torch.randn(D, Kb, generator=g) / Kb ** 0.5)
-    bo = torch.randn(D, generator=g) * 0.1
-    gate = torch.randn(D, generator=g) * 0.3
-    W = torch.randn(N, D, generator=g) / D ** 0.5
-    bias = torch.randn(N, generator=g) * 0.1
-    scale, shift = torch.randn(D, generator=g) * 0.2, torch.randn(D, generator=g) * 0.3
-    seq = M // 2 if epi == 4 else M
-    rope = None
-    if epi == 4:
-        ang = torch.arange(seq)[:, None] * (1.0 / 10000.0 ** (torch.arange(0, 64, 2) / 64.0))[None, :]
-        rope = torch.stack([ang.cos(), ang.sin()], dim=-1).reshape(seq, 64).float()
-    xh = x.half().float()
-    pivot = torch.stack([xh.mean(dim=1) + 0.01, torch.ones(M)], dim=1)
-    kw = dict(pivot=pivot, act="gelu_tanh" if epi == 0 else "none", rope=rope, rope_heads=1, seq=seq)
-    xs, stats, out = op_ln_fold_p(P_FP16, epi, x, A, Wo, bo, gate, W, bias, scale, shift, **kw)
-    xs_b, stats_b, _ = op_ln_fold_p(P_BF16, epi, x, A, Wo, bo, gate, W, bias, scale, shift, **kw)
+    import gpu_helpers as G
+    args, kw = G.ln_fold_inputs(M, D, N, Kb, epi)
+    xs, stats, out = op_ln_fold_p(P_FP16, epi, *args, **kw)
+    xs_b, stats_b, _ = op_ln_fold_p(P_BF16, epi, *args, **kw)
     assert torch.equal(xs, xs_b) and torch.equal(stats, stats_b)
-    # the table the folded projection multiplies
-    dev = [t.cuda().float().contiguous() for t in (W, bias, scale, shift, scale, shift)]
-    Wt, c1, c2 = torch.empty(N, D, device="cuda"), torch.empty(N, device="cuda"), torch.empty(N, device="cuda")
-    _lib.check(lib.f5_op_fold_weights(N, N, 0, D, 0, *[_lib.ptr(t) for t in dev], _lib.ptr(Wt), _lib.ptr(c1), _lib.ptr(c2), _lib.stream_ptr()))
-    torch.cuda.synchronize()
-    Wt, c1, c2 = Wt.cpu().double(), c1.cpu().double(), c2.cpu().double()
-    mean, rstd = stats[:, 0].double()[:, None], stats[:, 1].double()[:, None]
-    ref = rstd * (xs.double() @ Wt.t() - mean * c1) + c2
-    mag = rstd * (xs.double().abs() @ Wt.abs().t() + mean.abs() * Wt.abs().sum(dim=1)) + bias.double().abs() + W.double().abs() @ shift.double().abs()
-    if epi == 0:
-        ref, mag = F.gelu(ref, approximate="tanh"), 1.13 * mag
-    else:
-        inner = N // 3
-        cs = rope.double()[torch.arange(M) % seq].reshape(M, 32, 2)
-        cos, sin = cs[..., 0], cs[..., 1]
-        r, s = ref.clone(), mag.clone()
-        for part in (0, 1):
-            c0 = part * inner
-            v, m = ref[:, c0:c0 + 64].reshape(M, 32, 2), mag[:, c0:c0 + 64].reshape(M, 32, 2)
-            r[:, c0:c0 + 64] = torch.stack([v[..., 0] * cos - v[..., 1] * sin, v[..., 1] * cos + v[..., 0] * sin], dim=-1).reshape(M, 64)
-            s[:, c0:c0 + 64] = torch.stack([m[..., 0] * cos.abs() + m[..., 1] * sin.abs(), m[..., 1] * cos.abs() + m[..., 0] * sin.abs()], dim=-1).reshape(M, 64)
-        ref, mag = r, s
+    ref, mag = G.ln_fold_ref(args, kw, epi, xs, stats)
     check_f16(f"ln_fold epi {epi}", out, ref, mag)
     assert torch.equal(out, out.half().float())  # the values are fp16 numbers
 

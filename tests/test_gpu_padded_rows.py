@@ -17,7 +17,7 @@ from conftest import rel_l2
 pytestmark = pytest.mark.gpu
 
 DEPTH = 22
-_DEFAULTS = {"gemm_pad_rows": 1, "gemm_w4_ink": 1, "gemm_w4": 1, "ln_fold_inkernel": 0}
+_DEFAULTS = {"gemm_pad_rows": 1, "gemm_w4_ink": 1, "gemm_w4": 1, "ln_fold_inkernel": 0, "gemm_reverse_sites": 8, "gemm_group": 0, "gemm_persist_grid": 0}
 
 # (B, N) -> (in-kernel statistics on the QKV launch, on the FF1 launch), as measured on the MI355X (256-CU persistent grid) and pinned here through
 # the timing sites.  A folded consumer finishes the statistics itself on the one-wave-per-SIMD kernel's 128-row tiles only where the 8-wave kernel
@@ -151,6 +151,23 @@ def test_padded_launches_equal_every_equivalent_path(models, B, N):
     err = rel_l2(ref[:, n_ref:], want[:, n_ref:])
     print(f"{B} x {N} ({rows} -> {_rows_g(rows)} rows): bf16 vs fp32 mode rel-L2 {err:.3e}; launches at LN1 / LN2 {n['ln1']} / {n['ln2']}")
     assert err < 2e-2
+
+
+@pytest.mark.parametrize("knob,value", [("gemm_reverse_sites", 0), ("gemm_reverse_sites", 15), ("gemm_group", 1), ("gemm_group", 3), ("gemm_persist_grid", 8),
+                                        ("gemm_persist_grid", 24)])
+def test_tile_walk_knobs_change_no_bit(models, knob, value):
+    """2 x 900 (3600 -> 3840 rows), 3 Euler steps: the order in which a block GEMM walks its tiles -- backwards at no call site or at all four
+    (gemm_reverse_sites; op launches carry no call site, so the reversed walk runs here only), L2 patches of 1 and 3 token tiles (gemm_group),
+    persistent grids of 8 and 24 workgroups (gemm_persist_grid, which also moves the tile rule) -- gives the default path's bits: "same values
+    either way" is what the knobs' comments promise."""
+    model, cfm = models["bf16"]
+    kw = dict(_problem(2, 900, seed=20900), steps=3)
+    ref = cfm.sample(use_graph=False, **kw)[0].cpu()
+    assert torch.isfinite(ref).all()
+    with knobs(**{knob: value}):
+        out = cfm.sample(use_graph=False, **kw)[0].cpu()
+    assert torch.equal(out, ref), (knob, value, float((out - ref).abs().max()))
+    assert model.residual_fallbacks() == 0
 
 
 def test_padded_launches_with_the_other_statistics_forms(models):
