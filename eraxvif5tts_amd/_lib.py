@@ -108,6 +108,8 @@ _PROTOS = {
     "f5_bench_attention": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_float), _P]),
     "f5_bench_mfma_rate": (_I, [_I, C.POINTER(C.c_float), _P]),
     "f5_tuning_set": (_I, [C.c_char_p, _I]),
+    "f5_tuning_get": (_I, [C.c_char_p, C.POINTER(C.c_int)]),
+    "f5_tuning_key": (C.c_char_p, [_I]),
     "f5_debug_gemm_clock": (_I, [_P]),
     "f5_debug_last_gemm": (_I, [C.POINTER(C.c_int)] * 5),
     "f5_vocoder_create": (_I, [C.POINTER(VocosConfig), C.POINTER(_P)]),
@@ -166,7 +168,7 @@ def load(build_if_missing: bool = False):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     _lib = lib
-    # developer knobs for A/B runs: F5HIP_TUNING="gemm_nt=33,attn_variant=1" -> f5_tuning_set(key, value)
+    # developer knobs for A/B runs: F5HIP_TUNING="gemm_variant=0,attn_variant=2" -> f5_tuning_set(key, value)
     for item in filter(None, os.environ.get("F5HIP_TUNING", "").split(",")):
         key, _, val = item.partition("=")
         if lib.f5_tuning_set(key.strip().encode(), int(val)) != 0:

@@ -15,6 +15,7 @@
 //     is built with -fno-slp-vectorize (packed fp32 VALU beside MFMAs is slower, MI355X_MICROARCH.md cycle constants).
 // K/V staging, fragment reads and the maximum-free softmax are described at the kernel.
 #include "kernels.h"
+#include "tuning.h"
 #include <type_traits>
 
 typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
@@ -507,7 +508,6 @@ int launch_attention_wide_f16(bool masked, int B, int N, int H, const void* qkv,
     return launch_wide(masked, B, N, H, qkv, ldq, mask, out, ldo, stream, bstride, qscaled);
 }
 #else
-int g_attn_variant = 0;  // tuning knob ("attn_variant"): 0 = by grid size, 2 = 64 queries per wave, 5 = software-pipelined 32 queries per wave
 
 bool attention_fast_supported(int precision, int N, int H) { return (precision == F5_PREC_BF16 || precision == F5_PREC_FP16) && N >= 1 && H >= 1; }
 

@@ -34,6 +34,7 @@
 #include "gemm.h"
 #include "kernels.h"
 #include "runtime.h"
+#include "tuning.h"
 
 struct BvConv {
     float *w = nullptr, *b = nullptr;  // [Cout][Kp] (column = tap * Cin + c), [Cout]
@@ -420,7 +421,6 @@ struct BvRagged {
     std::vector<UttExtents> tabs;
     int cnt = 0, frames = 0;
 };
-int g_bigvgan_group_frames = 2048;  // tuning knob ("bigvgan_group_frames"): frame budget of one launch set (bounds the im2col workspace; measured: profiles/r5_bigvgan_ragged_ab.md)
 
 // x: T rows (ragged: of all utterances, `up` rows per mel frame; src_ld > 0: conv_pre from the caller's frame-major mel) -> out [T, cout]
 static int bv_conv(f5_bigvgan_s* v, const BvConv& cv, const float* x, int T, int dil, int chan_major, float* out, bool residual, const BvRagged* rg, int up,

@@ -16,6 +16,7 @@
 // Weights are the tap-major image the model already builds for the generic path: [31][dim][64] (GemmParams::conv_win == 64).
 #include "gemm_tile.h"
 #include "runtime.h"
+#include "tuning.h"
 
 __device__ __attribute__((aligned(256))) unsigned char g_conv_zero_page[256];  // zero-initialised: Conv1d zero padding / rows outside the utterance
 
@@ -131,7 +132,6 @@ __global__ __launch_bounds__(256, 2) void conv31_kernel(GemmParams p, int tiles_
 
 }  // namespace
 
-int g_conv31 = 1;  // tuning knob ("conv31"): 1 = dedicated halo-tile kernel for the dim-1024 grouped conv, 0 = implicit GEMM (gemm_fast.hip)
 
 bool conv31_supported(const GemmParams& p, int precision, int epi) {
     if (!g_conv31 || (precision != F5_PREC_BF16 && precision != F5_PREC_FP16)) return false;
@@ -142,7 +142,6 @@ bool conv31_supported(const GemmParams& p, int precision, int epi) {
     return epi == EPI_STORE_T;
 }
 
-int g_conv31_tok = 0;  // tuning knob ("conv31_tok"): tokens per workgroup, 0 = by grid size, 128 or 256 forced
 int launch_conv31(const GemmParams& p, int precision, hipStream_t stream) {
     const int L = p.rows_per_batch, nb = p.M / L;
     if (nb > 65535) return f5_fail(F5_EINVAL, "conv31: batch %d too large for one launch", nb);

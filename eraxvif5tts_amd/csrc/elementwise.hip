@@ -2,6 +2,7 @@
 // embedding gather, timestep embedding, small-M fp32 linears (AdaLN modulation), packing, CFG + ODE step.
 // All row-wise kernels use one 64-lane wavefront per row with 16-byte vector accesses and wave-shuffle reductions.
 #include "kernels.h"
+#include "tuning.h"
 
 // ----------------------------------------------------------------------------- LayerNorm (+ modulation)
 // x[r] (+= y[r], written back) -> out[r] = LN(x[r]) * (add_one + mul[b]) + add[b].  The optional y is the previous
@@ -304,9 +305,6 @@ __global__ __launch_bounds__(256) void layernorm1024_h_rows_kernel(const _Float1
 #pragma unroll
     for (int r = 0; r < 4; ++r) asm volatile("" ::"v"(pfv[r]));  // keeps the prefetch loads alive
 }
-int g_ln_rows_min = 16384;  // tuning knob ("ln_rows_min"): smallest launch (token rows) that takes the multi-row kernel
-int g_ln_rows = 2;  // tuning knob ("ln_rows"): rows per wave of the read-only LayerNorm pass (1 = the one-row kernel; same-box A/B at C2, pair of passes: 96.4 us -> 90.8 with 2, 93.3 with 4)
-int g_ln_wide = 1;  // tuning knob ("ln_wide"): 16-byte form of the LayerNorm pass at its production shape
 
 template <typename TO, int MAXV, typename XI = float, typename XO = float>
 static void ln_launch(const void* x, void* xo, int ldx, int rows, int dim, const void* y, int ldy, const void* y2, int ymode, const float* mul,

@@ -1,28 +1,11 @@
-// eval_common.hip -- what every backbone evaluation shares: tuning knobs, GEMM dispatch, stage taps, the AdaLN table (modules.py:311,332), the text
+// eval_common.hip -- what every backbone evaluation shares: GEMM dispatch, stage taps, the AdaLN table (modules.py:311,332), the text
 // embedding (dit.py:49-79), the hoisted half of the input embedding (dit.py:88-96), and the public single-evaluation entry points.
 #include "model_internal.h"
 
 // ----------------------------------------------------------------------------- helpers
-int g_w_prefetch = 16384;  // tuning knob ("w_prefetch"): LayerNorm passes prefetch the following GEMMs' weights when the launch has at most this many token rows
-                            // (0 = never).  M = 8192: +2.3 %, M = 2048: +2.9 % mel-frames/s; M = 65536: no effect (each weight line serves 256 token tiles there)
-int g_res_f16 = 1;   // tuning knob ("residual_f16"): bf16 production mode keeps the residual stream in fp16 from the first block on (0 = fp32)
-int g_ln_defer = 1;  // tuning knob ("ln_defer"): write the residual stream once per DiT block (0 = after every LayerNorm pass)
-int g_resid_rmw = 1;  // tuning knob ("resid_rmw"): see dit_eval
-int g_ln_fold = 1;    // tuning knob ("ln_fold"): LayerNorm fold (dit_eval); 0 = the two LayerNorm passes per block of round 3
-int g_ln_fold_inkernel = 0;  // tuning knob ("ln_fold_inkernel"): 1 = folded projections on tiles narrower than 256 take their row statistics from the
-                             // partial sums INSIDE the kernel, no statistics launch in front (and the producers prefetch the weights).  Same bits
-                             // (tested), but measured slower where it applies -- 1 x 1024: 79.0 - 80.1 against 76.9 - 77.6 ms per sample(), 2 x 1024:
-                             // 107.8 - 108.6 against 105.5 - 105.9 ms (gpurun_out/r4h_*): the 16 partial loads per row sit in front of a
-                             // latency-bound main loop and cost more than the 44 small launches they replace.  Off.
-int g_gemm_pad_rows = 1;  // tuning knob ("gemm_pad_rows"): the block GEMMs of a DiT evaluation run over the token rows rounded up to 256 (dit_eval)
-int g_sync_evals = 0;  // diagnostic knob ("sync_evals"): an eager sample() synchronises the stream after every network evaluation, which bounds the
-                       // number of dispatches in flight (profiles/r3_rocprof_pmc_sigsegv.md: rocprofv3 --pmc died under ~5 400 queued dispatches)
-
-// fp16 residual storage for this plan's evaluations (bf16 mode without stage taps; the plan option overrides the process-wide knob)
 // Pre-scaled q: bf16 production mode of the DiT backbone on the tuned attention kernels, no qk_norm, no stage taps.  The
 // softmax scale then sits in the weights that project q -- the fold table's q rows and block 0's second copy -- and the attention kernels
 // apply none.  It rides on the LayerNorm fold: an evaluation that runs unfolded keeps q as projected (dit_eval).
-int g_attn_prescale = 1;  // tuning knob ("attn_prescale"); the plan option of the same name overrides it
 bool plan_attn_prescale(const f5_plan_s* p) {
     const f5_dit_config& c = p->m->cfg;
     const bool want = p->attn_prescale < 0 ? g_attn_prescale != 0 : p->attn_prescale != 0;
@@ -44,6 +27,7 @@ int plan_attn_dropout_advance(f5_plan_s* p, uint32_t by, hipStream_t st) {
     if (!(p->drop_p > 0.0)) return 0;
     return launch_attn_dropout_advance(p->drop_base, by, st);
 }
+// fp16 residual storage for this plan's evaluations (bf16 mode without stage taps; the plan option overrides the process-wide knob)
 bool plan_res_f16(const f5_plan_s* p) {
     const bool want = p->res_f16 < 0 ? g_res_f16 != 0 : p->res_f16 != 0;
     if (p->m->cfg.backbone != F5_BACKBONE_DIT || p->m->cfg.long_skip) return false;  // (UNetT, MMDiT and the long-skip DiT keep fp32 streams)

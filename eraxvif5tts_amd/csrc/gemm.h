@@ -101,6 +101,8 @@ struct GemmLaunchRecord {
 };
 extern GemmLaunchRecord g_last_gemm;  // gemm.hip
 inline void gemm_record_launch(int family, int bm, int bn, int schedule, int flags) { g_last_gemm = GemmLaunchRecord{family, bm, bn, schedule, flags}; }
+extern unsigned long long* g_gemm_clk_buf;  // diagnostic (f5_debug_gemm_clock): GemmParams::clk of every tuned launch (gemm_fast.hip)
+int gemm_persist_grid();  // workgroups of a persistent-grid launch: the "gemm_persist_grid" knob, or the device's CU count (gemm_fast.hip)
 
 // kernel_kind: 0 = reference tile kernel (any shape), 1 = tuned 256x256 LDS-DMA bf16 kernel
 int launch_gemm(const GemmParams& p, int precision, int mode, int epi, int kernel_kind, hipStream_t stream);

@@ -23,6 +23,7 @@
 //   * rows >= M / features >= N are clamped on load and dropped in the epilogue, so no padding contract on the caller.
 #include "gemm_tile.h"
 #include "lnf_stats_math.h"
+#include "tuning.h"
 
 // This file is compiled as TWO translation units (build time): gemm_fast.hip itself holds every instantiation without the LayerNorm fold,
 // gemm_fast_lnf.hip (#define F5_LNF_TU + #include of this file) the LNF ones behind launch_gemm_fast_lnf().
@@ -942,17 +943,8 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(GemmParams p, int til
     clk_end();
 }
 
-#if defined(F5_LNF_TU) || defined(F5_F16_TU)
-extern unsigned long long* g_gemm_clk_buf;
-extern int g_gemm_variant, g_gemm_group, g_gemm_persist_grid, g_gemm_persist, g_gemm_reverse_sites, g_gemm_group_sites, g_gemm_tile, g_gemm_bm128, g_gemm_lean;
-int gemm_persist_grid();
-static int persist_grid() { return gemm_persist_grid(); }
-#else
+#if !defined(F5_LNF_TU) && !defined(F5_F16_TU)  // the base translation unit owns what the four share (declared in gemm.h)
 unsigned long long* g_gemm_clk_buf = nullptr;  // diagnostic (f5_debug_gemm_clock)
-int g_gemm_variant = 1;  // tuning knob (f5_tuning_set("gemm_variant", v)): 0 = plain ring everywhere, 1 = staggered wave groups (+ persistent grid)
-int g_gemm_group = 0;    // tuning knob ("gemm_group"): token tiles per L2 patch (0 = by shape, 1 = feature-tile-fastest order)
-int g_gemm_persist_grid = 0;  // tuning knob ("gemm_persist_grid"): workgroups of the persistent kernel (0 = one per CU of the device)
-int g_gemm_persist = 1;       // tuning knob ("gemm_persist"): 1 = whole-tile block linears run on the persistent grid
 int gemm_persist_grid() {
     if (g_gemm_persist_grid > 0) return g_gemm_persist_grid;
     static int cus = 0;
@@ -964,18 +956,8 @@ int gemm_persist_grid() {
     }
     return cus;
 }
-// tuning knob ("gemm_reverse_sites"): bit mask of block call sites (bit 0 qkv, 1 out, 2 ff1, 3 ff2) that walk their tiles backwards.  Default 8:
-// FF2 reads FF1's 256 MiB output -- more than the 256 MB Infinity Cache holds -- so walking it in FF1's order finds the oldest lines evicted
-// all the way, the opposite order meets the newest half while it is still cached: FF2 272.5 -> 267.3 us in situ, C2 30 185 -> 30 328
-// mel-frames/s (same-box A/B; reversing FF1 instead does the same, both together nothing, the other sites nothing).  Same values either way.
-int g_gemm_reverse_sites = 8;
-int g_gemm_group_sites = 0;  // diagnostic knob ("gemm_group_sites"): patch height per block call site, two decimal digits each: qkv|out|ff1|ff2
-int g_gemm_tile = 0;   // diagnostic knob ("gemm_tile"): bm * 1000 + bn forces the tile of every tuned-GEMM launch that supports it (0 = by shape)
-int g_gemm_bm128 = 1;  // tuning knob ("gemm_bm128"): 128-row token tiles when the 256-row ones leave CUs without a workgroup (single-utterance launches)
-int g_gemm_lean = 1;   // tuning knob ("gemm_lean"): 1 = lean epilogue on whole tiles, 0 = generic epilogue everywhere
-
-static int persist_grid() { return gemm_persist_grid(); }
 #endif
+static int persist_grid() { return gemm_persist_grid(); }
 
 // tile walk of a launch: L2 patch height and direction per block call site (also used by the one-wave-per-SIMD kernel, gemm_w4.hip)
 static void apply_site_knobs(GemmParams& p) {
@@ -983,6 +965,9 @@ static void apply_site_knobs(GemmParams& p) {
     // that launch in isolation, but in situ the FF2 launch behind it reads FF1's output and runs 277 -> 267 us when FF1 wrote it in patches of
     // 8 like its own: same-box A/B x 3 at C2, 30 408 -> 30 575 mel-frames/s.)
     p.tile_group = g_gemm_group > 0 ? g_gemm_group : 8;
+    // Default 8: FF2 reads FF1's 256 MiB output -- more than the 256 MB Infinity Cache holds -- so walking it in FF1's order finds the oldest
+    // lines evicted all the way, the opposite order meets the newest half while it is still cached (numbers: tuning.h; reversing FF1 instead
+    // does the same, both together nothing, the other sites nothing).
     if (g_gemm_reverse_sites > 0) {  // bit 0 qkv, 1 out-projection, 2 FF1, 3 FF2 walk their tiles backwards
         const int site = p.site - 1;
         if (site >= 0 && ((g_gemm_reverse_sites >> site) & 1)) p.tile_reverse = 1;

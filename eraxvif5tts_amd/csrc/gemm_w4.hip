@@ -35,6 +35,7 @@
 // persistent 8-wave build, and enough tiles for the CUs (w4_tile_rows: 256-row tiles from three quarters of the CUs on, else 128-row tiles from half).
 #include "gemm_tile.h"
 #include "lnf_stats_math.h"
+#include "tuning.h"
 #include <string.h>
 
 typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
@@ -704,14 +705,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // (#define F5_F16_TU + #include of this file) the EL = f16_t instantiations of the fp16 precision mode behind launch_gemm_w4_f16().
 #ifdef F5_F16_TU
 #define F5_EL f16_t
-int gemm_persist_grid();  // gemm_fast.hip
 #else
 #define F5_EL bf16_t
-int g_gemm_w4 = 1;  // tuning knob ("gemm_w4"): 1 = whole-tile block linears with enough tiles for the CUs (w4_tile_rows) run on the one-wave-per-SIMD kernel
-int g_gemm_w4_ink = 1;  // tuning knob ("gemm_w4_ink"): folded projections on the kernel's 128-row tiles finish the row statistics themselves (no statistics launch)
-int g_gemm_w4_bm = 0;  // diagnostic knob ("gemm_w4_bm"): token rows per tile, 0 = by tile count, 128 / 256 forced where the shape allows
-
-int gemm_persist_grid();  // gemm_fast.hip
 
 // token rows per tile of this launch on the one-wave-per-SIMD kernel (0: the launch does not take it).  Measured at 1 - 16 utterances x 1024 frames
 // (gpurun_out/r4ak_ab.log, r4am_ab.log; t256 / t128 = tiles of the two heights, as a share of the CUs):

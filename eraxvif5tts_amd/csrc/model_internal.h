@@ -13,6 +13,7 @@
 #include "gemm.h"
 #include "kernels.h"
 #include "runtime.h"
+#include "tuning.h"
 
 static const int MELP = 128;  // mel channels padded to one MFMA k-block multiple
 
@@ -87,8 +88,6 @@ struct f5_model_s {
     std::vector<std::string> read_names;  // f5_model_finalize: host tensors read since the last weight upload (model.hip: up_t)
     ~f5_model_s();
 };
-
-extern int g_tuning_epoch;  // bumped by every f5_tuning_set: graphs captured under other knob values are dropped (ops.hip)
 
 struct GraphEntry {
     int B, N, nt, steps, method, cfg_on, mask_on;
@@ -240,9 +239,7 @@ int finish_if_pending(f5_plan_s* p);  // completes a deferred sample() before th
 
 
 // ---- eval_common.hip
-extern int g_w_prefetch, g_res_f16, g_ln_defer, g_resid_rmw, g_ln_fold, g_ln_fold_inkernel, g_gemm_pad_rows, g_sync_evals, g_gemm_w4;
 bool plan_res_f16(const f5_plan_s* p);
-extern int g_attn_prescale;
 bool plan_attn_prescale(const f5_plan_s* p);  // pre-scaled q wanted and possible for this plan (what its fold table is built for)
 // the dropout descriptor of block l's attention call in the running evaluation (prob 0 when the mode is off)
 AttnDropout plan_attn_dropout(const f5_plan_s* p, int l, uint32_t bw0 = 0, uint32_t bw_step = 1);

@@ -5,6 +5,7 @@
 #include "gemm.h"
 #include "kernels.h"
 #include "runtime.h"
+#include "tuning.h"
 
 static int sync_and_release(DevArena& a, hipStream_t st, int rc) {
     hipError_t e = hipStreamSynchronize(st);
@@ -292,7 +293,6 @@ extern "C" int f5_op_attention_ragged(int precision, int attn_kernel, int nbr, i
     return sync_and_release(a, st, rc);
 }
 
-int g_op_conv_kernel = 0;  // tuning knob ("op_conv_kernel"): f5_op_conv_pos_embed runs the tuned conv kernels (bf16)
 
 // the padded input-channel window one 64-channel output tile of the grouped Conv1d(k = 31, groups = 16) reads (GemmParams::conv_win)
 static int conv31_window(int dim) {
@@ -554,7 +554,6 @@ __global__ __launch_bounds__(256) void fill_random_f32_kernel(float* dst, size_t
     dst[i] = ((float)(x >> 8) * (1.0f / 8388608.0f) - 1.0f) * scale;
 }
 
-static int g_bench_pad_a = 0, g_bench_pad_w = 0;
 
 // Times `iters` back-to-back launches of ONE GEMM kernel (bf16, the epilogue/shape of the DiT call site `site`) with HIP
 // events on `stream`; *ms_avg = average device time of one launch.  site: 0 = fused QKV projection + RoPE (N = 3*inner),
@@ -719,14 +718,6 @@ extern "C" int f5_bench_mfma_rate(int random_operands, float* tflops, f5_stream_
     return sync_and_release(a, st, rc);
 }
 
-extern int g_attn_prescale;
-extern int g_sync_evals, g_resid_rmw, g_ln_fold, g_ln_fold_inkernel, g_gemm_pad_rows;
-extern int g_conv31_tok, g_bigvgan_group_frames;
-extern int g_gemm_bm128, g_gemm_tile, g_gemm_group_sites, g_gemm_reverse_sites;
-extern int g_gemm_w4, g_gemm_w4_bm, g_gemm_w4_ink;
-extern int g_gemm_variant, g_gemm_group, g_gemm_persist_grid, g_gemm_persist, g_gemm_lean, g_ln_defer, g_ln_wide, g_ln_rows, g_ln_rows_min, g_w_prefetch, g_res_f16, g_conv31, g_attn_variant, g_vocos_fft;
-int g_tuning_epoch = 0;
-extern unsigned long long* g_gemm_clk_buf;
 // diagnostic: while dev_buf (u64 [workgroups * 4]) is non-null the tuned GEMM writes (s_memtime, s_memrealtime) at workgroup start and end
 extern "C" int f5_debug_gemm_clock(void* dev_buf) {
     g_gemm_clk_buf = reinterpret_cast<unsigned long long*>(dev_buf);
@@ -742,141 +733,4 @@ extern "C" int f5_debug_last_gemm(int* family, int* bm, int* bn, int* schedule, 
     *schedule = g_last_gemm.schedule;
     *flags = g_last_gemm.flags;
     return 0;
-}
-
-extern "C" int f5_tuning_set(const char* key, int value) {
-    if (!key) return f5_fail(F5_EINVAL, "null key");
-    ++g_tuning_epoch;  // hipGraphs captured by plans under the previous knob values are dropped at their next use (model.hip)
-    if (strcmp(key, "gemm_variant") == 0) {
-        g_gemm_variant = value;
-        return 0;
-    }
-    if (strcmp(key, "resid_rmw") == 0) {
-        g_resid_rmw = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "sync_evals") == 0) {
-        g_sync_evals = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "w_prefetch") == 0) {
-        g_w_prefetch = value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_reverse_sites") == 0) {
-        g_gemm_reverse_sites = value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_group_sites") == 0) {
-        g_gemm_group_sites = value;
-        return 0;
-    }
-    if (strcmp(key, "conv31_tok") == 0) {
-        g_conv31_tok = value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_tile") == 0) {
-        g_gemm_tile = value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_bm128") == 0) {
-        g_gemm_bm128 = value;
-        return 0;
-    }
-    if (strcmp(key, "ln_rows") == 0) {
-        g_ln_rows = value;
-        return 0;
-    }
-    if (strcmp(key, "ln_rows_min") == 0) {
-        g_ln_rows_min = value;
-        return 0;
-    }
-    if (strcmp(key, "ln_wide") == 0) {
-        g_ln_wide = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "residual_f16") == 0) {
-        g_res_f16 = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "vocos_fft") == 0) {
-        g_vocos_fft = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "bigvgan_group_frames") == 0) {
-        if (value < 1) return f5_fail(F5_EINVAL, "bigvgan_group_frames must be at least 1");
-        g_bigvgan_group_frames = value;
-        return 0;
-    }
-    if (strcmp(key, "attn_prescale") == 0) {
-        g_attn_prescale = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "attn_variant") == 0) {
-        if (value == 6) return f5_fail(F5_EINVAL, "attn_variant 6 (the persistent-grid kernel) was removed: 0 = by grid size, 2 = 64 queries per wave, 5 = pipelined");
-        g_attn_variant = value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_group") == 0) {
-        g_gemm_group = value;
-        return 0;
-    }
-    if (strcmp(key, "op_conv_kernel") == 0) {
-        g_op_conv_kernel = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "conv31") == 0) {
-        g_conv31 = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "ln_defer") == 0) {
-        g_ln_defer = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "gemm_lean") == 0) {
-        g_gemm_lean = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "gemm_pad_rows") == 0) {
-        g_gemm_pad_rows = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "ln_fold_inkernel") == 0) {
-        g_ln_fold_inkernel = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "ln_fold") == 0) {
-        g_ln_fold = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "gemm_w4_ink") == 0) {
-        g_gemm_w4_ink = value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_w4_bm") == 0) {
-        g_gemm_w4_bm = value;
-        return 0;
-    }
-    if (strcmp(key, "gemm_w4") == 0) {
-        g_gemm_w4 = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "gemm_persist") == 0) {
-        g_gemm_persist = value != 0;
-        return 0;
-    }
-    if (strcmp(key, "gemm_persist_grid") == 0) {
-        if (value != 0 && (value < 8 || value > 4096)) return f5_fail(F5_EINVAL, "gemm_persist_grid must be 0 (= CU count) or in [8, 4096]");
-        g_gemm_persist_grid = value;
-        return 0;
-    }
-    if (strcmp(key, "bench_pad_a") == 0) {
-        g_bench_pad_a = value;
-        return 0;
-    }
-    if (strcmp(key, "bench_pad_w") == 0) {
-        g_bench_pad_w = value;
-        return 0;
-    }
-    return f5_fail(F5_EINVAL, "unknown tuning key '%s'", key);
 }

@@ -10,6 +10,7 @@
 #include "gemm.h"
 #include "kernels.h"
 #include "runtime.h"
+#include "tuning.h"
 
 struct VocosBlockW {
     float *dw_wt = nullptr, *dw_b = nullptr, *ln_w = nullptr, *ln_b = nullptr, *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *gamma = nullptr;
@@ -193,7 +194,6 @@ extern "C" int f5_vocoder_destroy(f5_vocoder_t v) {
     return 0;
 }
 
-int g_vocos_fft = 1;  // tuning knob ("vocos_fft"): ISTFT head by FFT (1) or by the dense inverse-DFT GEMM (0: the parity cross-check)
 
 static int ensure_work(f5_vocoder_s* v, size_t rows) {
     if (rows <= v->work_rows) return 0;

@@ -397,6 +397,10 @@ F5_API int f5_debug_gemm_clock(void* dev_buf);
 F5_API int f5_debug_last_gemm(int* family, int* bm, int* bn, int* schedule, int* flags);
 /* process-wide kernel tuning knobs for A/B measurements ("gemm_variant": main-loop schedule of the tuned GEMM) */
 F5_API int f5_tuning_set(const char* key, int value);
+/* The value a knob holds now (no side effect; F5_EINVAL for a null argument or an unknown key), and the key of knob `index` in the library's
+ * table, NULL past the end: together they enumerate every knob with its value. */
+F5_API int f5_tuning_get(const char* key, int* value);
+F5_API const char* f5_tuning_key(int index);
 
 /* ------------------------------------------------------------------ Vocos vocoder (plug point B) */
 typedef struct f5_vocos_config {

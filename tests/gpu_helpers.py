@@ -354,28 +354,38 @@ def conv31_ref(x, w, b):
 
 
 # ----------------------------------------------------------------------------- row-wise kernels (include/f5hip.h: test and diagnostic entry points)
-# defaults of the tuning knobs the tests set: the `int g_... = ...;` definitions of csrc/
-KNOB_DEFAULTS = {b"ln_rows": 2, b"ln_rows_min": 16384, b"ln_wide": 1, b"residual_f16": 1,
-                 b"gemm_tile": 0, b"gemm_bm128": 1, b"gemm_group": 0, b"gemm_persist_grid": 0, b"gemm_reverse_sites": 8, b"gemm_w4": 1, b"gemm_w4_bm": 0,
-                 b"gemm_persist": 1, b"gemm_lean": 1, b"gemm_variant": 1, b"conv31": 1, b"conv31_tok": 0, b"op_conv_kernel": 0}
+def knob_get(key):
+    """The value tuning knob `key` holds now (include/f5hip.h: f5_tuning_get)."""
+    v = C.c_int()
+    _lib.check(_lib.load().f5_tuning_get(key.encode(), C.byref(v)), f"f5_tuning_get({key})")
+    return v.value
 
 
 class knobs:
-    """with knobs(ln_rows=4, ln_rows_min=1): ... -- tuning knobs set through f5_tuning_set, put back to their defaults on the way out."""
+    """with knobs(ln_rows=4, ln_rows_min=1): ... -- tuning knobs set through f5_tuning_set.  On the way out, an exception included, each gets back
+    the value that f5_tuning_get read before it was set, last set first: nested uses unwind, and a value F5HIP_TUNING put in force survives."""
 
     def __init__(self, **kv):
-        self.kv = {k.encode(): v for k, v in kv.items()}
+        self.kv = kv
+        self.found = []
 
     def __enter__(self):
         lib = _lib.load()
-        for k, v in self.kv.items():
-            _lib.check(lib.f5_tuning_set(k, v))
+        try:
+            for k, v in self.kv.items():
+                was = knob_get(k)
+                _lib.check(lib.f5_tuning_set(k.encode(), int(v)), f"f5_tuning_set({k}, {v})")
+                self.found.append((k, was))
+        except BaseException:
+            self.__exit__()
+            raise
         return self
 
     def __exit__(self, *exc):
         lib = _lib.load()
-        for k in self.kv:
-            _lib.check(lib.f5_tuning_set(k, KNOB_DEFAULTS[k]))
+        while self.found:
+            k, was = self.found.pop()
+            _lib.check(lib.f5_tuning_set(k.encode(), was))
         return False
 
 

@@ -263,8 +263,6 @@ def test_range_guard_rerun_repeats_the_calls_own_masks():
     library repeats the loop with fp32 residual storage.  With dropout on the rerun must start from the call's own base word: the result equals,
     bit for bit, a model that stored fp32 from the start (same seed), and the base has advanced once, not twice."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     arch = dict(dim=256, depth=2, heads=4, ff_mult=2, text_dim=128, conv_layers=2, pe_attn_head=1, text_mask_padding=False)
     V = 60
     W = cpu_ref.random_dit_weights(arch, V, seed=77)
@@ -286,11 +284,8 @@ def test_range_guard_rerun_repeats_the_calls_own_masks():
     assert cfm.transformer.residual_fallbacks() == 1
     assert _opt(cfm.transformer, "attn_dropout_base") == [3 * arch["depth"]]
     second = cfm.sample(use_graph=False, **kw)[0].clone()  # (fp32 storage now; the next call's words)
-    _lib.check(lib.f5_tuning_set(b"residual_f16", 0))  # fp32 residual storage from the start
-    try:
+    with G.knobs(residual_f16=0):  # fp32 residual storage from the start
         ref_cfm = G.make_cfm(arch, V, big, "bf16")
         ref_cfm.transformer.set_attn_dropout(P, SEED)
         ref = [ref_cfm.sample(use_graph=False, **kw)[0].clone() for _ in range(2)]
-    finally:
-        _lib.check(lib.f5_tuning_set(b"residual_f16", 1))
     assert torch.equal(out, ref[0]) and torch.equal(second, ref[1]) and not torch.equal(out, second)

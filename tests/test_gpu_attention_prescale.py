@@ -107,20 +107,18 @@ def _gpu():
 
 
 def _run(qkv, mask, prescaled, variant=2):
+    import gpu_helpers as G
     from eraxvif5tts_amd import _lib
     lib = _lib.load()
     B, N, three, H, dh = qkv.shape
     q = qkv.cuda().float().contiguous()
     mk = None if mask is None else mask.cuda().to(torch.uint8).contiguous()
     out = torch.empty(B, N, H * 64, device="cuda")
-    _lib.check(lib.f5_tuning_set(b"attn_variant", variant))  # 2: the 64-queries-per-wave kernel whatever the grid size
-    try:
+    with G.knobs(attn_variant=variant):  # 2: the 64-queries-per-wave kernel whatever the grid size
         if prescaled:
             _lib.check(lib.f5_op_attention_prescaled(1, B, N, H, _lib.ptr(q), _lib.ptr(mk), _lib.ptr(out), _lib.stream_ptr()))
         else:
             _lib.check(lib.f5_op_attention(0, 1, B, N, H, _lib.ptr(q), _lib.ptr(mk), _lib.ptr(out), _lib.stream_ptr()))
-    finally:
-        _lib.check(lib.f5_tuning_set(b"attn_variant", 0))
     return out.cpu()
 
 

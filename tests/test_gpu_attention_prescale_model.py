@@ -17,11 +17,6 @@ def _gpu():
     _lib.require_gpu()
 
 
-def _knob(on):
-    from eraxvif5tts_amd import _lib
-    _lib.check(_lib.load().f5_tuning_set(b"attn_prescale", int(on)))
-
-
 def _active(model):
     """"attn_prescale_active" of the model's live plans"""
     from eraxvif5tts_amd import _lib
@@ -50,9 +45,8 @@ def test_tiny_dit_sample_on_against_off(monkeypatch):
               y0=torch.from_numpy(z["y0"]))
     dur, ref = z["duration"], torch.from_numpy(z["out"])
     outs = {}
-    try:
-        for on in (1, 0):
-            _knob(on)
+    for on in (1, 0):
+        with G.knobs(attn_prescale=on):
             c = G.make_cfm(arch, int(z["vocab"]), W, "bf16")
             eager = c.sample(**kw, use_graph=False)[0].cpu()
             assert _active(c.transformer) == [on]
@@ -60,8 +54,6 @@ def test_tiny_dit_sample_on_against_off(monkeypatch):
             assert c.transformer.residual_fallbacks() == 0
             outs[on] = eager
             del c
-    finally:
-        _knob(1)
     e_on, e_off = [rel_l2(_gen_rows(outs[k], dur), _gen_rows(ref, dur)) for k in (1, 0)]
     d = rel_l2(_gen_rows(outs[1], dur), _gen_rows(outs[0], dur))
     print(f"tiny_base vs golden: pre-scaled {e_on:.3e}, as projected {e_off:.3e}; on vs off {d:.3e}")
@@ -73,9 +65,8 @@ def test_c1_shape_sample_on_against_off_and_taps_switch_it_off():
     off, eager and graph; the same with the 64-queries-per-wave kernel forced (its reference-free build inside the model); and a plan with a
     stage tap reports the option as inactive."""
     import bench
-    from eraxvif5tts_amd import _lib
+    import gpu_helpers as G
     from eraxvif5tts_amd.model import CFM, DiT
-    lib = _lib.load()
     B, N = 1, 256
     cond, text, lens, dur = bench.synth_batch(B, N, "cuda", seed=61)
     y0 = torch.randn(B, N, 100, generator=torch.Generator().manual_seed(62))
@@ -84,18 +75,14 @@ def test_c1_shape_sample_on_against_off_and_taps_switch_it_off():
     model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision="bf16"), seed=0)
     cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}).cuda()
     outs = {}
-    try:
-        for on in (1, 0):
-            _knob(on)
+    for on in (1, 0):
+        with G.knobs(attn_prescale=on):
             outs[on] = cfm.sample(**kw, use_graph=False)[0].cpu()
             assert _active(model) == [on]
             assert torch.equal(cfm.sample(**kw, use_graph=True)[0].cpu(), outs[on])
-        _knob(1)
-        _lib.check(lib.f5_tuning_set(b"attn_variant", 2))
-        try:
+    with G.knobs(attn_prescale=1):
+        with G.knobs(attn_variant=2):
             outs["wide"] = cfm.sample(**kw, use_graph=False)[0].cpu()
-        finally:
-            _lib.check(lib.f5_tuning_set(b"attn_variant", 0))
         assert model.residual_fallbacks() == 0
         (_, plan), = model._plans
         tap = torch.zeros(B, N, bench.BASE_ARCH["dim"], device="cuda")
@@ -105,8 +92,6 @@ def test_c1_shape_sample_on_against_off_and_taps_switch_it_off():
         finally:
             model.set_tap(plan, None, None)
         assert _active(model) == [1]
-    finally:
-        _knob(1)
     n_ref = cond.shape[1]
     gen = lambda t: t[0, n_ref:N]
     d, dw = rel_l2(gen(outs[1]), gen(outs[0])), rel_l2(gen(outs["wide"]), gen(outs[0]))

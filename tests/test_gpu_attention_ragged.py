@@ -81,19 +81,14 @@ def _pack(utts, off, rows, nbr, H, ldq_extra):
 def _run(prec, attn_kernel, variant, lens, nbr, H, first=0, ldq_extra=0, ldo_extra=0, ref_heads=None):
     """One ragged call under `variant`, with assertions (a), (b), (c).  Returns the raw output [nbr, rows, H * 64 + ldo_extra]."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     utts, off, rows, heads, refs = _case(tuple(lens), nbr, H, first, None if ref_heads is None else tuple(ref_heads), prec == P_FP16)
     inner, ldo = H * 64, H * 64 + ldo_extra
     qkv = _pack(utts, off, rows, nbr, H, ldq_extra)
     out0 = torch.full((nbr * rows, ldo), SENTINEL)
     kind = 1 if (prec in (P_BF16, P_FP16) and attn_kernel != 0) else 0  # the tuned kernels exist for both 16-bit modes
-    _lib.check(lib.f5_tuning_set(b"attn_variant", variant))
-    try:
+    with G.knobs(attn_variant=variant):
         out = G.op_attention_ragged(prec, attn_kernel, nbr, off, list(lens), H, rows, qkv, out0, ldq_extra, ldo_extra).view(nbr, rows, ldo)
         own = [G.op_attention(prec, kind, u) for u in utts]
-    finally:
-        _lib.check(lib.f5_tuning_set(b"attn_variant", 0))
     untouched = torch.ones(nbr, rows, ldo, dtype=torch.bool)
     cols = torch.cat([torch.arange(h * 64, h * 64 + 64) for h in heads])
     for u, (o, n) in enumerate(zip(off, lens)):
@@ -190,12 +185,9 @@ def _refused(prec, attn_kernel, off, n, rows, ldq_extra=0, H=2, nbr=2):
     from eraxvif5tts_amd import _lib
     qkv = torch.zeros(nbr * rows, 3 * H * 64 + ldq_extra)
     out0 = torch.full((nbr * rows, H * 64), SENTINEL)
-    _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 5))
-    try:
+    with G.knobs(attn_variant=5):
         rc, out = G.op_attention_ragged_rc(prec, attn_kernel, nbr, off, n, H, rows, qkv, out0, ldq_extra, 0)
         msg = _lib.last_error()
-    finally:
-        _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 0))
     assert rc != 0
     assert (out == SENTINEL).all(), "a refused call wrote to `out`"
     return msg

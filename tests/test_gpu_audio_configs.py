@@ -221,12 +221,9 @@ def _check_head(voc, n_fft, hop, T, window, what):
 
 
 def _dense(fn):
-    from eraxvif5tts_amd import _lib
-    _lib.check(_lib.load().f5_tuning_set(b"vocos_fft", 0))
-    try:
+    import gpu_helpers as G
+    with G.knobs(vocos_fft=0):
         fn()
-    finally:
-        _lib.check(_lib.load().f5_tuning_set(b"vocos_fft", 1))
 
 
 @pytest.mark.parametrize("T", [2, 3, 7])  # fewer frames than one full overlap, and just past it

@@ -15,7 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_helpers import fp16_ulp
+from gpu_helpers import fp16_ulp, knobs
 from oracle import cpu_ref
 
 pytestmark = pytest.mark.gpu
@@ -38,24 +38,6 @@ def check_f16(name, out, ref, scale, extra=None):
     (gpu_helpers.check_elementwise: the comparator shared with test_gpu_gemm_tiles.py)."""
     import gpu_helpers as G
     return G.check_elementwise(name, out, ref, scale, P_FP16, extra)
-
-
-class knobs:
-    DEFAULTS = {"gemm_persist": 1, "gemm_lean": 1, "gemm_w4": 1, "attn_variant": 0, "op_conv_kernel": 0, "conv31": 1}
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        from eraxvif5tts_amd import _lib
-        for k, v in self.kv.items():
-            _lib.check(_lib.load().f5_tuning_set(k.encode(), v))
-
-    def __exit__(self, *exc):
-        from eraxvif5tts_amd import _lib
-        for k in self.kv:
-            _lib.check(_lib.load().f5_tuning_set(k.encode(), self.DEFAULTS[k]))
-        return False
 
 
 def op_linear_fused_p(*args, **kw):

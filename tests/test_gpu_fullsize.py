@@ -125,9 +125,8 @@ def test_layernorm_fold_against_the_unfolded_path_and_fp32_mode():
     mode, F5TTS_Base depth, B = 2 with a key mask, N = 1024, NFE 8, CFG 2.  The fold must be at least as close to fp32 as the passes were
     (it rounds less: no bf16 copy of the normalised rows, fp16 instead of bf16 weights), and eager == graph replay bit for bit."""
     import bench
-    from eraxvif5tts_amd import _lib
+    import gpu_helpers as G
     from eraxvif5tts_amd.model import CFM, DiT
-    lib = _lib.load()
     B, N = 2, 1024
     cond, text, lens, dur = bench.synth_batch(B, N, "cuda", seed=19)
     dur[1] = 870
@@ -137,8 +136,7 @@ def test_layernorm_fold_against_the_unfolded_path_and_fp32_mode():
     kw = dict(cond=cond, text=text, duration=dur, lens=lens, steps=8, cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y0, return_trajectory=False)
     outs = {}
     for tag, prec, fold in (("fp32", "fp32", 1), ("fold", "bf16", 1), ("passes", "bf16", 0)):
-        _lib.check(lib.f5_tuning_set(b"ln_fold", fold))
-        try:
+        with G.knobs(ln_fold=fold):
             torch.manual_seed(1234)
             model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision=prec), seed=0)
             cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}).cuda()
@@ -146,8 +144,6 @@ def test_layernorm_fold_against_the_unfolded_path_and_fp32_mode():
             if tag == "fold":
                 assert torch.equal(cfm.sample(use_graph=True, **kw)[0].cpu(), outs[tag])
                 assert model.residual_fallbacks() == 0
-        finally:
-            _lib.check(lib.f5_tuning_set(b"ln_fold", 1))
         del cfm, model
         torch.cuda.empty_cache()
     n_ref = cond.shape[1]
@@ -162,9 +158,8 @@ def test_in_kernel_row_statistics_equal_the_statistics_kernel():
     ln_fold_inkernel = 1; off by default: measured slower) instead of from stats_finalize_kernel: the two forms share lnf_stats_math.h and the
     summation order, so a single-utterance sample() -- the shape that would take the in-kernel form -- must not change by one bit."""
     import bench
-    from eraxvif5tts_amd import _lib
+    import gpu_helpers as G
     from eraxvif5tts_amd.model import CFM, DiT
-    lib = _lib.load()
     torch.manual_seed(4321)
     model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision="bf16"), seed=0)
     cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}).cuda()
@@ -173,11 +168,8 @@ def test_in_kernel_row_statistics_equal_the_statistics_kernel():
     kw = dict(cond=cond, text=text, duration=dur, lens=lens, steps=2, cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y0, return_trajectory=False, use_graph=False)
     outs = []
     for ink in (0, 1):
-        _lib.check(lib.f5_tuning_set(b"ln_fold_inkernel", ink))
-        try:
+        with G.knobs(ln_fold_inkernel=ink):
             outs.append(cfm.sample(**kw)[0].cpu())
-        finally:
-            _lib.check(lib.f5_tuning_set(b"ln_fold_inkernel", 0))
     assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
 
 
@@ -189,9 +181,8 @@ def test_w4_kernel_finishes_the_row_statistics_itself(B, N):
     stats_finalize_kernel (lnf_stats_math.h), so sample() must not change by one bit against the statistics launches (gemm_w4_ink = 0) and against
     the 8-wave kernel (gemm_w4 = 0), eager and graph replay."""
     import bench
-    from eraxvif5tts_amd import _lib
+    import gpu_helpers as G
     from eraxvif5tts_amd.model import CFM, DiT
-    lib = _lib.load()
     torch.manual_seed(4321)
     model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision="bf16"), seed=0)
     cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}).cuda()
@@ -200,16 +191,11 @@ def test_w4_kernel_finishes_the_row_statistics_itself(B, N):
     kw = dict(cond=cond, text=text, duration=dur, lens=lens, steps=3, cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y0, return_trajectory=False)
     outs = {}
     for tag, knobs in (("ink", {}), ("launches", {"gemm_w4_ink": 0}), ("8wave", {"gemm_w4": 0})):
-        for k, v in knobs.items():
-            _lib.check(lib.f5_tuning_set(k.encode(), v))
-        try:
+        with G.knobs(**knobs):
             outs[tag] = cfm.sample(use_graph=False, **kw)[0].cpu()
             if tag == "ink":
                 for _ in range(2):
                     assert torch.equal(cfm.sample(use_graph=True, **kw)[0].cpu(), outs[tag])
-        finally:
-            for k in knobs:
-                _lib.check(lib.f5_tuning_set(k.encode(), {"gemm_w4_ink": 1, "gemm_w4": 1}[k]))
     assert torch.isfinite(outs["ink"]).all()
     assert torch.equal(outs["ink"], outs["launches"]) and torch.equal(outs["ink"], outs["8wave"])
     assert model.residual_fallbacks() == 0
@@ -289,7 +275,7 @@ def test_fp16_residual_stream_against_fp32_residual_stream():
     that reaches +-65504 makes f5_sample repeat the loop with fp32 storage instead of clipping; this test also asserts that the well-scaled
     network never trips that guard.)"""
     import bench
-    from eraxvif5tts_amd import _lib
+    import gpu_helpers as G
     from eraxvif5tts_amd.model import CFM, DiT
     B, N = 2, 512
     cond, text, lens, dur = bench.synth_batch(B, N, "cuda", seed=3)
@@ -300,12 +286,9 @@ def test_fp16_residual_stream_against_fp32_residual_stream():
         torch.manual_seed(1234)
         model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision=prec), seed=0)
         cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}).cuda()
-        _lib.check(_lib.load().f5_tuning_set(b"residual_f16", knob))
-        try:
+        with G.knobs(residual_f16=knob):
             out, _ = cfm.sample(cond=cond, text=text, duration=dur, lens=lens, steps=8, cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y0,
                                 return_trajectory=False)
-        finally:
-            _lib.check(_lib.load().f5_tuning_set(b"residual_f16", 1))
         outs[tag] = out[:, n_ref:].cpu()
         if prec == "bf16":
             fallbacks += model.residual_fallbacks()
@@ -323,7 +306,7 @@ def test_lean_and_generic_epilogues_give_the_same_sampler_output():
     fp16 form of the input embedding's add); `gemm_lean = 0` sends every launch through the generic epilogue.  The two differ only in
     fp32 rounding before the bf16 / fp16 stores: F5TTS_Base, B = 2, N = 512 (2 048 token rows = whole 256-row tiles), two Euler steps."""
     import bench
-    from eraxvif5tts_amd import _lib
+    import gpu_helpers as G
     from eraxvif5tts_amd.model import CFM, DiT
     B, N = 2, 512
     cond, text, lens, dur = bench.synth_batch(B, N, "cuda", seed=6)
@@ -333,12 +316,9 @@ def test_lean_and_generic_epilogues_give_the_same_sampler_output():
     cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}).cuda()
     outs = []
     for lean in (1, 0):
-        _lib.check(_lib.load().f5_tuning_set(b"gemm_lean", lean))
-        try:
+        with G.knobs(gemm_lean=lean):
             out, _ = cfm.sample(cond=cond, text=text, duration=dur, lens=lens, steps=2, cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y0,
                                 return_trajectory=False)
-        finally:
-            _lib.check(_lib.load().f5_tuning_set(b"gemm_lean", 1))
         outs.append(out.cpu())
     err = rel_l2(outs[0], outs[1])
     print(f"lean vs generic epilogues: rel-L2 {err:.3e}")

@@ -183,30 +183,28 @@ def test_full_size_rk4_bf16_against_fp32_mode():
     """F5TTS_Base, B = 2, N = 1024 (durations 1024 / 900: key mask on), rk4 with 8 steps (32 evaluation times: LayerNorm-fold table),
     gemm_w4 + ln_fold forced: bf16 against the fp32 parity mode, rel-L2 < 2e-2 on the generated frames, no fp32 fallback."""
     import bench
-    from eraxvif5tts_amd import _lib
+    import gpu_helpers as G
     from eraxvif5tts_amd.model import CFM, DiT
-    lib = _lib.load()
     B, N = 2, 1024
     cond, text, lens, dur = bench.synth_batch(B, N, "cuda", seed=71)
     dur[1] = 900
     y0 = torch.randn(B, N, 100, generator=torch.Generator().manual_seed(72))
     y0[1, 900:] = 0
     kw = dict(cond=cond, text=text, duration=dur, lens=lens, steps=8, cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y0, return_trajectory=False)
-    for k in ("gemm_w4", "ln_fold"):
-        _lib.check(lib.f5_tuning_set(k.encode(), 1))
     outs = {}
-    for prec in ("fp32", "bf16"):
-        torch.manual_seed(1234)
-        model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision=prec), seed=0)
-        if prec == "bf16":
-            model.set_kernels(gemm=1, attn=1)
-        cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}, odeint_kwargs={"method": "rk4"}).cuda()
-        outs[prec] = cfm.sample(use_graph=False, **kw)[0].cpu()
-        if prec == "bf16":
-            assert torch.equal(cfm.sample(use_graph=True, **kw)[0].cpu(), outs[prec])
-            assert model.residual_fallbacks() == 0
-        del cfm, model
-        torch.cuda.empty_cache()
+    with G.knobs(gemm_w4=1, ln_fold=1):
+        for prec in ("fp32", "bf16"):
+            torch.manual_seed(1234)
+            model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision=prec), seed=0)
+            if prec == "bf16":
+                model.set_kernels(gemm=1, attn=1)
+            cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}, odeint_kwargs={"method": "rk4"}).cuda()
+            outs[prec] = cfm.sample(use_graph=False, **kw)[0].cpu()
+            if prec == "bf16":
+                assert torch.equal(cfm.sample(use_graph=True, **kw)[0].cpu(), outs[prec])
+                assert model.residual_fallbacks() == 0
+            del cfm, model
+            torch.cuda.empty_cache()
     gen = ~cpu_ref.lens_to_mask(lens.cpu(), N) & cpu_ref.lens_to_mask(dur.cpu(), N)
     err = rel_l2(outs["bf16"][gen], outs["fp32"][gen])
     print(f"rk4, 22 blocks x 8 steps: bf16 vs fp32 mode rel-L2 {err:.3e}")

@@ -93,8 +93,6 @@ def _fused_ref(epi, A, W, b, act, gate, rowmask, rope, rope_heads, seq):
                                                 ("gate", (1100, 768, 768), 0), ("rope", (2002, 2304, 768), 1001)])
 def test_linear_fused_epilogues(knobs, epi_name, shape, seq):
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     M, N, K = shape
     epi = {"store": G.EPI_STORE_T, "gate": G.EPI_GATE_T, "rope": G.EPI_ROPE_T}[epi_name]
     g = torch.Generator().manual_seed(M + 3 * N + K)
@@ -107,13 +105,8 @@ def test_linear_fused_epilogues(knobs, epi_name, shape, seq):
         ang = torch.rand(seq, 32, generator=g) * 6.28
         rope, heads = torch.stack([ang.cos(), ang.sin()], dim=-1), (1 if N == 3072 else N // 3 // 64)
     ref = _fused_ref(epi, A, W, b, act, gate, rowmask, rope, heads, seq)
-    try:
-        for k, v in knobs.items():
-            _lib.check(lib.f5_tuning_set(k.encode(), v))
+    with G.knobs(**knobs):
         out = G.op_linear_fused(1, epi, A, W, b, act, gate, rowmask, rope, heads, seq)
-    finally:
-        for k in knobs:
-            _lib.check(lib.f5_tuning_set(k.encode(), {"gemm_lean": 1, "gemm_variant": 1, "gemm_persist": 1}[k]))
     base = G.op_linear_fused(0, epi, A, W, b, act, gate, rowmask, rope, heads, seq)
     assert rel_l2(base, ref) < 3e-3   # bf16 output rounding: 2^-9 relative per element
     assert rel_l2(out, ref) < 3e-3
@@ -133,8 +126,6 @@ def test_linear_in_place_residual_epilogue(knobs, shape, masked):
     every schedule the launcher can pick and the reference tile kernel against fp64 on the same fp16-rounded stream; the tuned schedules
     against each other bit for bit (the fp32 sums and the update are the same in every variant)."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     M, N, K = shape
     g = torch.Generator().manual_seed(M + 5 * N + K)
     A, W, b = G.bf16_round(torch.randn(M, K, generator=g)), G.bf16_round(torch.randn(N, K, generator=g) / math.sqrt(K)), torch.randn(N, generator=g)
@@ -145,13 +136,8 @@ def test_linear_in_place_residual_epilogue(knobs, shape, masked):
     if masked:
         upd = upd * rowmask[:, None].double()
     ref = (x.double() + upd).float()
-    try:
-        for k, v in knobs.items():
-            _lib.check(lib.f5_tuning_set(k.encode(), v))
+    with G.knobs(**knobs):
         out = G.op_linear_fused(1, G.EPI_RESID, A, W, b, "none", gate, rowmask, stream_in=x)
-    finally:
-        for k in knobs:
-            _lib.check(lib.f5_tuning_set(k.encode(), {"gemm_lean": 1, "gemm_variant": 1, "gemm_persist": 1}[k]))
     base = G.op_linear_fused(0, G.EPI_RESID, A, W, b, "none", gate, rowmask, stream_in=x)
     dflt = G.op_linear_fused(1, G.EPI_RESID, A, W, b, "none", gate, rowmask, stream_in=x)
     assert rel_l2(out, ref) < 6e-4 and rel_l2(base, ref) < 6e-4   # one fp16 rounding of the result: 2^-11 relative
@@ -210,8 +196,6 @@ def test_conv_pos_embed_tuned_kernels(conv31, dim, B, N):
     gemm_fast.hip, against the oracle and against the reference tile kernel.  Ragged last tiles, utterance edges (zero padding) and
     several utterances per launch are all in these shapes."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     g = torch.Generator().manual_seed(dim + N)
     x = G.bf16_round(torch.randn(B, N, dim, generator=g))
     cg = dim // 16
@@ -221,13 +205,8 @@ def test_conv_pos_embed_tuned_kernels(conv31, dim, B, N):
          "input_embed.conv_pos_embed.conv1d.2.weight": w1, "input_embed.conv_pos_embed.conv1d.2.bias": b1}
     ref = cpu_ref.conv_pos_embed(W, x)
     base = G.op_conv_pos(P_BF16, x, w0, b0, w1, b1)
-    try:
-        _lib.check(lib.f5_tuning_set(b"op_conv_kernel", 1))
-        _lib.check(lib.f5_tuning_set(b"conv31", conv31))
+    with G.knobs(op_conv_kernel=1, conv31=conv31):
         out = G.op_conv_pos(P_BF16, x, w0, b0, w1, b1)
-    finally:
-        _lib.check(lib.f5_tuning_set(b"op_conv_kernel", 0))
-        _lib.check(lib.f5_tuning_set(b"conv31", 1))
     assert rel_l2(base, ref) < 4e-3  # the intermediate activation between the two convolutions is rounded to bf16
     assert rel_l2(out, ref) < 6e-3   # ... and so is the stored branch of the tuned path
     assert rel_l2(out, base) < 4e-3
@@ -254,8 +233,6 @@ def test_linear_tuned_kernel(shape, act):
 @pytest.mark.parametrize("variant", [0, 2, 5], ids=["by_grid_size", "64_queries_per_wave", "pipelined_32_queries_per_wave"])
 def test_attention_tuned_kernel(B, N, H, masked, variant):
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    _lib.check(_lib.load().f5_tuning_set(b"attn_variant", variant))
     g = torch.Generator().manual_seed(N + H)
     qkv = G.bf16_round(torch.randn(B, N, 3, H, 64, generator=g) * 1.5)
     mask = None
@@ -263,10 +240,8 @@ def test_attention_tuned_kernel(B, N, H, masked, variant):
         lens = torch.tensor([N, max(1, N - 13), max(1, N // 2)][:B])
         mask = torch.arange(N)[None, :] < lens[:, None]
     ref = _attn_ref(qkv, mask)
-    try:
+    with G.knobs(attn_variant=variant):
         out = G.op_attention(P_BF16, 1, qkv, mask)
-    finally:
-        _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 0))
     # P is rounded to bf16 before the PV product and the output is bf16: 2^-9 relative each
     assert rel_l2(out, ref) < 6e-3
     valid = slice(None) if mask is None else mask
@@ -282,7 +257,6 @@ def test_attention_tuned_kernel_long_sequences(variant, N, masked):
     launcher can select there -- the default one included -- against the fp64 softmax, whole tiles (2048, 4096), ragged last tiles
     (2050, 4000) and ragged per-utterance lengths behind the key-padding mask (modules.py:483-501)."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
     B, H = (2, 2) if masked else (1, 2)
     g = torch.Generator().manual_seed(N + 7 * variant)
     qkv = G.bf16_round(torch.randn(B, N, 3, H, 64, generator=g) * 1.5)
@@ -291,11 +265,8 @@ def test_attention_tuned_kernel_long_sequences(variant, N, masked):
         lens = torch.tensor([N, N - 1037])
         mask = torch.arange(N)[None, :] < lens[:, None]
     ref = _attn_ref(qkv, mask)
-    _lib.check(_lib.load().f5_tuning_set(b"attn_variant", variant))
-    try:
+    with G.knobs(attn_variant=variant):
         out = G.op_attention(P_BF16, 1, qkv, mask)
-    finally:
-        _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 0))
     valid = slice(None) if mask is None else mask
     assert torch.isfinite(out).all()
     assert rel_l2(out[valid], ref[valid]) < 6e-3
@@ -309,16 +280,11 @@ def test_attention_wide_kernel_whole_blocks(B, N, H):
     (batch x head) count that is a multiple of the 8 XCDs with several rounds of workgroups per CU (20 x 16 heads x 3 blocks), the shortest
     such sequence (256 = 4 key tiles) and N = 4096."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     g = torch.Generator().manual_seed(N + H + B)
     qkv = G.bf16_round(torch.randn(B, N, 3, H, 64, generator=g) * 1.5)
     ref = _attn_ref(qkv, None)
-    _lib.check(lib.f5_tuning_set(b"attn_variant", 2))
-    try:
+    with G.knobs(attn_variant=2):
         out = G.op_attention(P_BF16, 1, qkv, None)
-    finally:
-        _lib.check(lib.f5_tuning_set(b"attn_variant", 0))
     assert torch.isfinite(out).all()
     assert rel_l2(out, ref) < 6e-3 and (out - ref).abs().max() < 0.05
 
@@ -328,17 +294,13 @@ def test_attention_beyond_the_validity_table(masked):
     """N = 8320 = 130 key tiles: past the 128-tile table of key validity bits the wide kernel keeps in LDS.  Unmasked (whole tiles) it still
     runs; with a mask the launcher must hand the call to the pipelined kernel.  One head, against the fp64 softmax."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
     B, N, H = 1, 8320, 1
     g = torch.Generator().manual_seed(4)
     qkv = G.bf16_round(torch.randn(B, N, 3, H, 64, generator=g) * 1.5)
     mask = (torch.arange(N)[None, :] < torch.tensor([N - 301])[:, None]) if masked else None
     ref = _attn_ref(qkv, mask)
-    _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 2))
-    try:
+    with G.knobs(attn_variant=2):
         out = G.op_attention(P_BF16, 1, qkv, mask)
-    finally:
-        _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 0))
     valid = slice(None) if mask is None else mask
     assert torch.isfinite(out).all()
     assert rel_l2(out[valid], ref[valid]) < 6e-3
@@ -348,7 +310,6 @@ def test_attention_beyond_the_validity_table(masked):
 def test_attention_long_sequence_spiked_scores(variant):
     """online-softmax rescale path of every schedule at N = 4096: the running max jumps late (key 3900) and in the first tile."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
     g = torch.Generator().manual_seed(11)
     B, N, H = 1, 4096, 2
     qkv = torch.randn(B, N, 3, H, 64, generator=g)
@@ -356,11 +317,8 @@ def test_attention_long_sequence_spiked_scores(variant):
     qkv[0, 3, 1] = qkv[0, 2049, 0] * 6.0    # key 3 aligned with query 2049
     qkv = G.bf16_round(qkv)
     ref = _attn_ref(qkv, None)
-    _lib.check(_lib.load().f5_tuning_set(b"attn_variant", variant))
-    try:
+    with G.knobs(attn_variant=variant):
         out = G.op_attention(P_BF16, 1, qkv, None)
-    finally:
-        _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 0))
     assert rel_l2(out, ref) < 6e-3
 
 
@@ -370,7 +328,6 @@ def test_attention_deferred_rescale_thresholds(variant):
     than 2^16; 64-queries-per-wave kernel: no maximum unless a row sum leaves the guarded range): score jumps just below and far above
     the 2^16 threshold, early and late, and a row whose maximum keeps creeping up tile by tile -- against the fp64 softmax."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
     g = torch.Generator().manual_seed(9)
     B, N, H = 1, 1024, 2
     qkv = torch.randn(B, N, 3, H, 64, generator=g) * 0.5
@@ -383,11 +340,8 @@ def test_attention_deferred_rescale_thresholds(variant):
         qkv[0, key, 1] = qn[300] * (1.5 * (i + 1))
     qkv = G.bf16_round(qkv)
     ref = _attn_ref(qkv, None)
-    _lib.check(_lib.load().f5_tuning_set(b"attn_variant", variant))
-    try:
+    with G.knobs(attn_variant=variant):
         out = G.op_attention(P_BF16, 1, qkv, None)
-    finally:
-        _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 0))
     assert torch.isfinite(out).all()
     assert rel_l2(out, ref) < 6e-3
     for q in (5, 37, 90, 200, 300):
@@ -402,7 +356,6 @@ def test_attention_wide_kernel_range_guard(masked):
     inf), early and late in the sequence, a query whose maximum creeps up tile by tile, and -- masked -- an utterance whose whole first
     tile is masked out (its queries enter the second tile with the finite start reference), against the fp64 softmax."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
     g = torch.Generator().manual_seed(21)
     B, N, H = 2, 1024, 2
     qkv = torch.randn(B, N, 3, H, 64, generator=g) * 0.5
@@ -425,11 +378,8 @@ def test_attention_wide_kernel_range_guard(masked):
         mask[1, 1000:] = False
         mask[0, 990:] = False
     ref = _attn_ref(qkv, mask)
-    _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 2))
-    try:
+    with G.knobs(attn_variant=2):
         out = G.op_attention(P_BF16, 1, qkv, mask)
-    finally:
-        _lib.check(_lib.load().f5_tuning_set(b"attn_variant", 0))
     assert torch.isfinite(out).all()
     if mask is None:
         assert rel_l2(out, ref) < 6e-3
@@ -526,15 +476,6 @@ def test_layernorm_fold_site_against_fp64(M, D, N, Kb, epi, offset):
     assert err < 3e-3  # bf16 output rounding (2^-9 relative per element) + fp16 rounding of W'
 
 
-def _with_knob(lib, key, value, fn):
-    from eraxvif5tts_amd import _lib
-    _lib.check(lib.f5_tuning_set(key, value))
-    try:
-        return fn()
-    finally:
-        _lib.check(lib.f5_tuning_set(key, 1))
-
-
 @pytest.mark.parametrize("epi_name,shape,seq", [("rope", (2048, 3072, 1024), 1024), ("store", (2048, 2048, 1024), 0), ("resid", (6144, 1024, 2048), 0),
                                                 ("store", (6144, 2048, 1024), 0),
                                                 ("rope", (2048, 2304, 768), 1024), ("resid", (8192, 768, 1536), 0)])  # dim 768: 144 / 192 short tiles
@@ -543,8 +484,6 @@ def test_w4_kernel_on_partly_filled_grids(epi_name, shape, seq):
     (128-row tiles) -- single-utterance projections (192 / 128 short tiles), three utterances' FF1 (192 tall tiles) and FF2 (192 short ones).  A
     workgroup then walks one tile and the request front re-walks it past the end; outputs bit for bit as the 8-wave kernel's."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     M, N, K = shape
     g = torch.Generator().manual_seed(M + 11 * N + K)
     A, W, b = G.bf16_round(torch.randn(M, K, generator=g)), G.bf16_round(torch.randn(N, K, generator=g) / math.sqrt(K)), torch.randn(N, generator=g)
@@ -560,7 +499,8 @@ def test_w4_kernel_on_partly_filled_grids(epi_name, shape, seq):
             rope, heads = torch.stack([ang.cos(), ang.sin()], dim=-1), 1
         run = lambda: G.op_linear_fused(1, epi, A, W, b, "gelu_tanh" if epi_name == "store" else "none", None, None, rope, heads, seq)
     new = run()
-    old = _with_knob(lib, b"gemm_w4", 0, run)
+    with G.knobs(gemm_w4=0):
+        old = run()
     assert torch.isfinite(new).all() and torch.equal(new, old)
 
 
@@ -580,8 +520,6 @@ def test_w4_kernel_equals_the_8_wave_kernel(bm, epi_name, shape, seq):
     heights of the kernel (knob gemm_w4_bm: 256 x 256 with 128 x 128 per wave, 128 x 256 with 64 x 128 per wave; a shape the forced height cannot
     fill the CUs with falls back to the 8-wave kernel, M = 8320 is a multiple of 128 only)."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     M, N, K = shape
     g = torch.Generator().manual_seed(M + 7 * N + K)
     A, W, b = G.bf16_round(torch.randn(M, K, generator=g)), G.bf16_round(torch.randn(N, K, generator=g) / math.sqrt(K)), torch.randn(N, generator=g)
@@ -603,12 +541,10 @@ def test_w4_kernel_equals_the_8_wave_kernel(bm, epi_name, shape, seq):
             rope, heads = torch.stack([ang.cos(), ang.sin()], dim=-1), (1 if N in (3072, 2304) else N // 3 // 64)
         run = lambda: G.op_linear_fused(1, epi, A, W, b, act, None, None, rope, heads, seq)
         ref, tol = _fused_ref(epi, A, W, b, act, None, None, rope, heads, seq), 3e-3
-    _lib.check(lib.f5_tuning_set(b"gemm_w4_bm", bm))
-    try:
+    with G.knobs(gemm_w4_bm=bm):
         new = run()
-    finally:
-        _lib.check(lib.f5_tuning_set(b"gemm_w4_bm", 0))
-    old = _with_knob(lib, b"gemm_w4", 0, run)
+    with G.knobs(gemm_w4=0):
+        old = run()
     assert rel_l2(new, ref) < tol and rel_l2(old, ref) < tol
     assert torch.equal(new, old)
 
@@ -624,8 +560,6 @@ def test_w4_kernel_layernorm_fold_site_equals_the_8_wave_kernel(bm, D, N, Kb, ep
     tiles): in-place residual epilogue with partial row statistics -> statistics -> fp16-operand projection with the fold epilogue (+ RoPE / GELU).
     Stream, statistics and output bit for bit against the 8-wave kernel (gemm_w4 = 0)."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     M = 16384
     rope_heads = 1
     if epi < 0:
@@ -644,11 +578,9 @@ def test_w4_kernel_layernorm_fold_site_equals_the_8_wave_kernel(bm, D, N, Kb, ep
         rope = torch.stack([ang.cos(), ang.sin()], dim=-1).reshape(seq, 64).float()
     run = lambda: G.op_ln_fold(epi, x, A, Wo, bo, gate, W, bias, scale, shift, pivot=None, act="gelu_tanh" if epi == 0 else "none", rope=rope,
                                rope_heads=rope_heads, seq=seq)
-    _lib.check(lib.f5_tuning_set(b"gemm_w4_bm", bm))
-    try:
+    with G.knobs(gemm_w4_bm=bm):
         new = run()
-    finally:
-        _lib.check(lib.f5_tuning_set(b"gemm_w4_bm", 0))
-    old = _with_knob(lib, b"gemm_w4", 0, run)
+    with G.knobs(gemm_w4=0):
+        old = run()
     for a, c in zip(new, old):
         assert torch.isfinite(a).all() and torch.equal(a, c)

@@ -6,18 +6,17 @@ that may reach a real row or the fp16 range guard: outputs must equal the unpadd
 fallback to fp32 storage.
 
 F5TTS_Base width and depth, synthetic weights and batches as the neighbouring full-size tests; CFG 2 throughout (token rows = 2 B N)."""
-import contextlib
 import ctypes as C
 
 import pytest
 import torch
 
 from conftest import rel_l2
+from gpu_helpers import knobs
 
 pytestmark = pytest.mark.gpu
 
 DEPTH = 22
-_DEFAULTS = {"gemm_pad_rows": 1, "gemm_w4_ink": 1, "gemm_w4": 1, "ln_fold_inkernel": 0, "gemm_reverse_sites": 8, "gemm_group": 0, "gemm_persist_grid": 0}
 
 # (B, N) -> (in-kernel statistics on the QKV launch, on the FF1 launch), as measured on the MI355X (256-CU persistent grid) and pinned here through
 # the timing sites.  A folded consumer finishes the statistics itself on the one-wave-per-SIMD kernel's 128-row tiles only where the 8-wave kernel
@@ -47,19 +46,6 @@ def _ragged_rows(frames, gap=16):
 
 def _rows_g(rows):
     return -(-rows // 256) * 256 if rows >= 3584 and rows % 256 else rows
-
-
-@contextlib.contextmanager
-def knobs(**kv):
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
-    try:
-        for k, v in kv.items():
-            _lib.check(lib.f5_tuning_set(k.encode(), int(v)))
-        yield
-    finally:
-        for k in kv:
-            _lib.check(lib.f5_tuning_set(k.encode(), _DEFAULTS[k]))
 
 
 def _make(prec, scale=None, seed=1234):

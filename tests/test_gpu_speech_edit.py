@@ -157,9 +157,8 @@ def test_full_size_masked_bf16_against_fp32_mode(method):
     the masked bf16 path against the fp32 parity mode with the same mask: rel-L2 <= 2e-2 on the generated frames (the tolerance of the
     unmasked test_true_depth_bf16_sampler_stays_within_tolerance_of_fp32_mode); every kept frame equals cond exactly."""
     import bench
-    from eraxvif5tts_amd import _lib
+    import gpu_helpers as G
     from eraxvif5tts_amd.model import CFM, DiT
-    lib = _lib.load()
     B, N = 2, 1024
     cond, text, lens, dur = bench.synth_batch(B, N, "cuda", seed=51)
     dur[1] = 900
@@ -172,20 +171,19 @@ def test_full_size_masked_bf16_against_fp32_mode(method):
     kw = dict(cond=cond, text=text, duration=dur, lens=lens, steps=steps, cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y0,
               return_trajectory=False, edit_mask=edit)
     outs = {}
-    for k in ("gemm_w4", "ln_fold"):
-        _lib.check(lib.f5_tuning_set(k.encode(), 1))
-    for prec in ("fp32", "bf16"):
-        torch.manual_seed(1234)
-        model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision=prec), seed=0)
-        if prec == "bf16":
-            model.set_kernels(gemm=1, attn=1)
-        cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}, odeint_kwargs={"method": method}).cuda()
-        outs[prec] = cfm.sample(use_graph=False, **kw)[0].cpu()
-        if prec == "bf16":
-            assert torch.equal(cfm.sample(use_graph=True, **kw)[0].cpu(), outs[prec])
-            assert model.residual_fallbacks() == 0
-        del cfm, model
-        torch.cuda.empty_cache()
+    with G.knobs(gemm_w4=1, ln_fold=1):
+        for prec in ("fp32", "bf16"):
+            torch.manual_seed(1234)
+            model = bench.synth_weights(DiT(**bench.BASE_ARCH, text_num_embeds=bench.VOCAB, mel_dim=100, precision=prec), seed=0)
+            if prec == "bf16":
+                model.set_kernels(gemm=1, attn=1)
+            cfm = CFM(transformer=model, mel_spec_kwargs={"mel_spec_type": "vocos"}, odeint_kwargs={"method": method}).cuda()
+            outs[prec] = cfm.sample(use_graph=False, **kw)[0].cpu()
+            if prec == "bf16":
+                assert torch.equal(cfm.sample(use_graph=True, **kw)[0].cpu(), outs[prec])
+                assert model.residual_fallbacks() == 0
+            del cfm, model
+            torch.cuda.empty_cache()
     keep = torch.nn.functional.pad(edit.cpu() & cpu_ref.lens_to_mask(lens.cpu()), (0, N - nc))
     regen = ~keep & cpu_ref.lens_to_mask(dur.cpu(), N)
     err = rel_l2(outs["bf16"][regen], outs["fp32"][regen])
@@ -228,8 +226,6 @@ def test_deferred_guard_and_fp32_fallback_keep_the_staged_mask():
     """defer_guard=True + finish_pending() gives the synchronous call's output bit for bit; and on a checkpoint that leaves the fp16 range the
     fallback rerun (deferred to finish_pending) reuses the staged mask: equal to a run with fp32 residual storage from the start."""
     import gpu_helpers as G
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
     V, B, N = 60, 2, 96
     W = cpu_ref.random_dit_weights(SMALL, V, seed=77)
     cond, text, y0 = _small_problem(B, N, 78, nc=30)
@@ -252,13 +248,10 @@ def test_deferred_guard_and_fp32_fallback_keep_the_staged_mask():
         out, traj = cfm.sample(use_graph=False, defer_guard=True, **kw)
         cfm.transformer.finish_pending()
     assert cfm.transformer.residual_fallbacks() == 1 and torch.isfinite(out).all()
-    _lib.check(lib.f5_tuning_set(b"residual_f16", 0))
-    try:
+    with G.knobs(residual_f16=0):
         with warnings.catch_warnings():
             warnings.simplefilter("error")
             ref, ref_traj = G.make_cfm(SMALL, V, big, "bf16").sample(use_graph=False, **kw)
-    finally:
-        _lib.check(lib.f5_tuning_set(b"residual_f16", 1))
     assert torch.equal(out, ref) and torch.equal(traj, ref_traj)
     keep = torch.nn.functional.pad(edit & cpu_ref.lens_to_mask(lens.cpu()).cuda(), (0, N - 30))
     assert torch.equal(out[keep], torch.nn.functional.pad(cond, (0, 0, 0, N - 30))[keep])

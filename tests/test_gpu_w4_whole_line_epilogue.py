@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from conftest import rel_l2
-from test_gpu_ops import _fused_ref, _with_knob
+from test_gpu_ops import _fused_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -26,14 +26,11 @@ def _gpu():
 
 def _both(run, bm=256):
     """(one-wave-per-SIMD kernel at tile height bm, 8-wave kernel)"""
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
-    _lib.check(lib.f5_tuning_set(b"gemm_w4_bm", bm))
-    try:
+    import gpu_helpers as G
+    with G.knobs(gemm_w4_bm=bm):
         new = run()
-    finally:
-        _lib.check(lib.f5_tuning_set(b"gemm_w4_bm", 0))
-    return new, _with_knob(lib, b"gemm_w4", 0, run)
+    with G.knobs(gemm_w4=0):
+        return new, run()
 
 
 def test_store_gelu_second_tile_and_shortest_loop():

@@ -48,11 +48,6 @@ def _layout(frames, prefix, gap, ld=100, seed=0):
     return buf, starts
 
 
-def _fft_knob(value):
-    from eraxvif5tts_amd import _lib
-    _lib.check(_lib.load().f5_tuning_set(b"vocos_fft", value))
-
-
 RANDOM32 = [int(x) for x in np.random.default_rng(20).integers(50, 901, 32)]
 FRAME_LISTS = {"short_next_to_long": [2, 3, 7, 64, 683], "long_short_long": [683, 2, 300], "single": [129], "random32": RANDOM32,
                "more_than_one_table": [int(x) for x in np.random.default_rng(21).integers(2, 21, 70)]}
@@ -63,12 +58,12 @@ FRAME_LISTS = {"short_next_to_long": [2, 3, 7, 64, 683], "long_short_long": [683
 @pytest.mark.parametrize("name", list(FRAME_LISTS))
 def test_ragged_decode_equals_batch1_decode_bit_for_bit(voc, name, prefix, fft):
     """Check 1.  No tolerance: both sides are the same fp32 arithmetic in the same order (FFT head and dense-DFT head)."""
+    import gpu_helpers as G
     voc, _ = voc
     frames = FRAME_LISTS[name]
     buf, starts = _layout(frames, prefix, gap=0 if prefix == 0 else 2, seed=len(frames))
     rows = buf.cuda()
-    _fft_knob(fft)
-    try:
+    with G.knobs(vocos_fft=fft):
         waves = voc.decode_ragged(rows, starts, frames)
         assert len(waves) == len(frames)
         base = waves[0].data_ptr()
@@ -77,8 +72,6 @@ def test_ragged_decode_equals_batch1_decode_bit_for_bit(voc, name, prefix, fft):
             assert waves[i].shape == one.shape == (1, (t - 1) * 256)
             assert waves[i].data_ptr() == base + 4 * 256 * sum(x - 1 for x in frames[:i])  # views of ONE buffer, back to back
             assert torch.equal(waves[i], one), (name, i, t)
-    finally:
-        _fft_knob(1)
 
 
 @pytest.mark.parametrize("ld", [100, 104])

@@ -12,7 +12,6 @@ and the row-wise time MLP / AdaLN kernel (K = dim: 8 vectors per lane above 1024
 Reference: the CPU oracle (oracle/cpu_ref.py, fp32; it differs from its own fp64 evaluation by rel-L2 5e-7 .. 7e-7 at these widths, two orders
 of magnitude below the tightest tolerance) on seeded weights.  Tolerances: the project's own -- tests/test_gpu_model.py (fp32 2e-4, bf16 2e-2;
 stages 1e-4 / 1.5e-2) and tests/test_gpu_fp16_model.py (fp16 5e-3; stages 3.75e-3), imported from there.  Every test prints its figures."""
-import contextlib
 import ctypes as C
 import glob
 import os
@@ -37,7 +36,6 @@ CONFIG_DIR = os.path.join(ROOT, "eraxvif5tts_amd", "configs")
 SMALL_DIT = dict(dim=768, depth=2, heads=12, ff_mult=2, text_dim=512, text_mask_padding=False, conv_layers=4, pe_attn_head=1)  # F5TTS_Small.yaml, depth 2
 SMALL_UNETT = dict(dim=768, heads=12, ff_mult=4, text_mask_padding=False, pe_attn_head=1, skip_connect_type="concat")  # E2TTS_Small.yaml (+ depth)
 SAMPLE_KW = dict(steps=2, cfg_strength=2.0, sway_sampling_coef=-1.0)
-_KNOB_DEFAULTS = {"gemm_w4": 1, "ln_fold": 1, "gemm_pad_rows": 1}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -51,19 +49,6 @@ def _launcher_defaults(monkeypatch):
     """the kernels the launcher picks by itself (by token rows): that is what the regimes below are worked out for"""
     for k in ("F5HIP_GEMM_KERNEL", "F5HIP_ATTN_KERNEL", "F5HIP_PRECISION", "F5HIP_ROPE_LAYOUT"):
         monkeypatch.delenv(k, raising=False)
-
-
-@contextlib.contextmanager
-def _knobs(**kv):
-    from eraxvif5tts_amd import _lib
-    lib = _lib.load()
-    try:
-        for k, v in kv.items():
-            _lib.check(lib.f5_tuning_set(k.encode(), int(v)))
-        yield
-    finally:
-        for k in kv:
-            _lib.check(lib.f5_tuning_set(k.encode(), _KNOB_DEFAULTS[k]))
 
 
 def _problem(B, N, seed, mel=100):
@@ -236,17 +221,17 @@ def test_small_dit_knob_equalities(B, N):
     cfm = G.make_cfm(SMALL_DIT, V, W, "bf16")
     fold = run(cfm)
     assert torch.isfinite(fold).all() and _plan_option(cfm.transformer, "ln_fold_active") == 1
-    with _knobs(gemm_w4=0):
+    with G.knobs(gemm_w4=0):
         out = run(cfm)
     assert torch.equal(out, fold), ("gemm_w4 = 0", float((out - fold).abs().max()))
     if (2 * B * N) % 256:
-        with _knobs(gemm_pad_rows=0):
+        with G.knobs(gemm_pad_rows=0):
             out = run(cfm)
         assert torch.equal(out, fold), ("gemm_pad_rows = 0", float((out - fold).abs().max()))
     assert cfm.transformer.residual_fallbacks() == 0
     del cfm
     torch.cuda.empty_cache()
-    with _knobs(ln_fold=0):
+    with G.knobs(ln_fold=0):
         cfm = G.make_cfm(SMALL_DIT, V, W, "bf16")
         passes = run(cfm)
         assert cfm.transformer.residual_fallbacks() == 0 and _plan_option(cfm.transformer, "ln_fold_active") == 0  # (the leg really ran the passes)
