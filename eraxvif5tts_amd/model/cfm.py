@@ -9,9 +9,14 @@ HIP ``DiT``.  For any other backbone object (plug point A accepts arbitrary modu
 The solver is ``odeint_kwargs["method"]``, one of torchdiffeq's fixed-grid methods (``ODE_METHODS``): euler, midpoint, rk4 (torchdiffeq's
 ``rk4_alt_step_func``, the 3/8 rule), heun2, heun3 -- 1 / 2 / 4 / 2 / 3 network evaluations per step.  Adaptive solvers, the Adams family and
 other odeint options raise ``ValueError`` before any work.
-``forward()`` (the training loss, cfm.py:210-283) is outside the hot path and not provided.
+``forward()`` (cfm.py:210-283) returns the flow-matching loss of a batch, FORWARD ONLY, for validation runs: ``flow_loss()`` restates the
+reference's host logic with its random draws in the reference's order, calls the backbone once, and on the device wraps it in two HIP kernels
+(``f5_cfm_noise``, ``f5_cfm_loss``: csrc/cfm_loss.hip).  It runs under ``no_grad``; gradients, the optimiser and the trainer are not provided.
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
+from random import random
 
 import torch
 import torch.nn.functional as F
@@ -19,7 +24,50 @@ from torch import nn
 from torch.nn.utils.rnn import pad_sequence
 
 from .modules import MelSpec
-from .utils import default, exists, lens_to_mask, list_str_to_idx, list_str_to_tensor
+from .utils import default, exists, lens_to_mask, list_str_to_idx, list_str_to_tensor, mask_from_frac_lengths
+
+
+@dataclass
+class FlowLoss:
+    """What ``CFM.flow_loss`` returns: the loss, its per-utterance parts, the backbone's tensors, and the random draws it used."""
+    loss: torch.Tensor            # 0-dim: sum(sums) / sum(counts)
+    sums: torch.Tensor            # f64 [b]: sum of the selected squared differences
+    counts: torch.Tensor          # i64 [b]: selected rows x mel
+    cond: torch.Tensor            # [b, n, mel]: where(rand_span_mask, 0, x1)
+    pred: torch.Tensor            # [b, n, mel]: the backbone's output
+    x0: torch.Tensor              # [b, n, mel]: the noise
+    time: torch.Tensor            # [b]
+    rand_span_mask: torch.Tensor  # bool [b, n], after the length mask
+    drop_audio_cond: bool
+    drop_text: bool
+
+
+def _native_noise(x1, x0, time, span8):
+    """f5_cfm_noise: (phi, cond) of device fp32 [b, n, mel] tensors; span8 u8 [b, n], time f32 [b]."""
+    from .. import _lib
+    lib = _lib.load()
+    b, n, mel = x1.shape
+    phi, cond = torch.empty_like(x1), torch.empty_like(x1)
+    _lib.check(lib.f5_cfm_noise(b, n, mel, _lib.ptr(x1), _lib.ptr(x0), _lib.ptr(time), _lib.ptr(span8), _lib.ptr(phi), _lib.ptr(cond),
+                                _lib.stream_ptr()), "cfm_noise")
+    return phi, cond
+
+
+def _native_loss(pred, x1, x0, span8):
+    """f5_cfm_loss: (loss f32 0-dim, sums f64 [b], counts i64 [b]) on the device."""
+    from .. import _lib
+    lib = _lib.load()
+    b, n, mel = x1.shape
+    nbytes = lib.f5_cfm_loss_workspace(b, n, mel)
+    if nbytes < 0:
+        _lib.check(int(nbytes), "cfm_loss_workspace")
+    work = torch.empty(nbytes, device=x1.device, dtype=torch.uint8)
+    sums = torch.empty(b, device=x1.device, dtype=torch.float64)
+    counts = torch.empty(b, device=x1.device, dtype=torch.int64)
+    loss = torch.empty(1, device=x1.device, dtype=torch.float32)
+    _lib.check(lib.f5_cfm_loss(b, n, mel, _lib.ptr(pred), _lib.ptr(x1), _lib.ptr(x0), _lib.ptr(span8), _lib.ptr(sums), _lib.ptr(counts),
+                               _lib.ptr(loss), _lib.ptr(work), _lib.stream_ptr()), "cfm_loss")
+    return loss.reshape(()), sums, counts
 
 
 def _euler(fn, t0, t1, y):
@@ -94,8 +142,95 @@ class CFM(nn.Module):
     def device(self):
         return next(self.parameters()).device
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError("CFM.forward is the training loss (reference cfm.py:210-283); only sample() is on the MI355X path")
+    def forward(self, inp, text, *, lens=None, noise_scheduler=None):
+        """The reference's ``CFM.forward`` (cfm.py:210-283): same arguments, same ``(loss, cond, pred)``, the VALUE only -- it runs under
+        ``torch.no_grad()`` through kernels that have no backward, so nothing returned here can be differentiated.  See ``flow_loss``."""
+        r = self.flow_loss(inp, text, lens=lens)
+        return r.loss, r.cond, r.pred
+
+    @torch.no_grad()
+    def flow_loss(self, inp, text, *, lens=None, x0=None, time=None, rand_span_mask=None, drop_audio_cond=None, drop_text=None):
+        """The flow-matching loss of one batch, forward only (validation runs: picking a checkpoint, judging a pruned model).  NOTHING HERE
+        CAN BE DIFFERENTIATED: no gradient, optimiser or trainer exists in this package, and the result carries no graph.
+
+        Follows reference cfm.py:210-283 line by line -- raw wave -> mel, text -> ids, ``lens`` default, length mask, random span, noise, time,
+        the two drop flags, ONE backbone call ``transformer(x=phi, cond=cond, text=text, time=time, drop_audio_cond=, drop_text=)`` (no mask, no
+        cache: any module at plug point A works), masked MSE against ``x1 - x0`` -- and makes the random draws in the reference's order and on
+        its devices: ``uniform_`` for the span fractions and the ``rand_like`` inside ``mask_from_frac_lengths`` (both on the model's device),
+        ``randn_like(x1)``, ``torch.rand((batch,))`` on the model's device, then Python's ``random()`` twice.  After the same
+        ``torch.manual_seed(s); random.seed(s)`` a CPU run draws what the reference draws.
+
+        A draw given by keyword is NOT drawn; the draws after it keep their order.  ``rand_span_mask`` (bool [b, n]) stands for the two span
+        draws and is still and-ed with the length mask; ``x0`` [b, n, mel]; ``time`` [b]; a given ``drop_audio_cond`` / ``drop_text`` is final and
+        its ``random()`` call is skipped, a drawn ``drop_text`` follows the reference's rule (it also sets a DRAWN ``drop_audio_cond``).
+
+        CUDA tensors (fp32) take the two HIP kernels: ``f5_cfm_noise`` (phi and cond: torch's bits) and ``f5_cfm_loss`` (the selected squared
+        differences summed in fp64 in a fixed order: the same input gives the same bits; the flow and the elementwise loss never reach
+        memory).  CPU tensors (an oracle backbone) take the torch expressions of the reference.
+
+        Returns ``FlowLoss``: ``loss`` (0-dim; NaN when the span is empty, as ``mean()`` of an empty tensor), ``sums`` f64 [b] and ``counts`` i64
+        [b] (per utterance: selected rows x mel; loss = sum(sums) / sum(counts)), ``cond``, ``pred``, and the draws used: ``x0``, ``time``,
+        ``rand_span_mask`` (after the length mask), ``drop_audio_cond``, ``drop_text``."""
+        if inp.ndim == 2:  # raw wave
+            inp = self.mel_spec(inp)
+            inp = inp.permute(0, 2, 1)
+            assert inp.shape[-1] == self.num_channels
+        batch, seq_len, dtype, device = *inp.shape[:2], inp.dtype, self.device
+
+        if isinstance(text, list):
+            if exists(self.vocab_char_map):
+                text = list_str_to_idx(text, self.vocab_char_map).to(device)
+            else:
+                text = list_str_to_tensor(text).to(device)
+            assert text.shape[0] == batch
+
+        if not exists(lens):
+            lens = torch.full((batch,), seq_len, device=device)
+        mask = lens_to_mask(lens, length=seq_len)
+
+        if not exists(rand_span_mask):
+            frac_lengths = torch.zeros((batch,), device=self.device).float().uniform_(*self.frac_lengths_mask)
+            rand_span_mask = mask_from_frac_lengths(lens, frac_lengths)
+        rand_span_mask = rand_span_mask.to(mask.device) & mask
+
+        x1 = inp
+        x0 = torch.randn_like(x1) if not exists(x0) else x0.to(device=x1.device, dtype=dtype)
+        time = torch.rand((batch,), dtype=dtype, device=self.device) if not exists(time) else time.to(device=self.device, dtype=dtype)
+
+        native = x1.is_cuda
+        if native:
+            if dtype != torch.float32:
+                raise TypeError(f"flow_loss on the device takes fp32 mels, not {dtype}")
+            x1, x0 = x1.contiguous(), x0.contiguous()
+            span8 = rand_span_mask.to(device=x1.device, dtype=torch.uint8).contiguous()
+            phi, cond = _native_noise(x1, x0, time.to(x1.device).contiguous(), span8)
+        else:
+            t = time.unsqueeze(-1).unsqueeze(-1)
+            phi = (1 - t) * x0 + t * x1
+            cond = torch.where(rand_span_mask[..., None], torch.zeros_like(x1), x1)
+
+        # cfg training with a drop rate (cfm.py:266-271): p_drop, then p_uncond
+        audio_given = exists(drop_audio_cond)
+        if not audio_given:
+            drop_audio_cond = random() < self.audio_drop_prob
+        if not exists(drop_text):
+            drop_text = random() < self.cond_drop_prob
+            if drop_text and not audio_given:
+                drop_audio_cond = True
+        drop_audio_cond, drop_text = bool(drop_audio_cond), bool(drop_text)
+
+        pred = self.transformer(x=phi, cond=cond, text=text, time=time, drop_audio_cond=drop_audio_cond, drop_text=drop_text)
+
+        if native:
+            loss, sums, counts = _native_loss(pred.to(device=x1.device, dtype=torch.float32).contiguous(), x1, x0, span8)
+        else:
+            flow = x1 - x0
+            elem = F.mse_loss(pred, flow, reduction="none")
+            loss = elem[rand_span_mask].mean()
+            sums = torch.where(rand_span_mask[..., None], elem.double(), torch.zeros((), dtype=torch.float64)).sum(dim=(1, 2))
+            counts = rand_span_mask.sum(dim=1) * x1.shape[-1]
+        return FlowLoss(loss=loss, sums=sums, counts=counts, cond=cond, pred=pred, x0=x0, time=time, rand_span_mask=rand_span_mask,
+                        drop_audio_cond=drop_audio_cond, drop_text=drop_text)
 
     @torch.no_grad()
     def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None, seed=None,

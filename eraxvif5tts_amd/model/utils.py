@@ -1,6 +1,7 @@
 """Text front-end and tensor helpers of the inference path (host side, bit-identical id tensors).
 
-Mirrors ``f5_tts/model/utils.py`` of the reference: ``lens_to_mask`` (:42-47), ``list_str_to_tensor`` (:81-84),
+Mirrors ``f5_tts/model/utils.py`` of the reference: ``lens_to_mask`` (:42-47), ``mask_from_start_end_indices`` (:50-55),
+``mask_from_frac_lengths`` (:58-66), ``list_str_to_tensor`` (:81-84),
 ``list_str_to_idx`` (:88-95), ``get_tokenizer`` (:118-241), ``convert_char_to_pinyin`` (:243-284), ``seed_everything`` (:18-25).
 """
 from __future__ import annotations
@@ -35,6 +36,24 @@ def lens_to_mask(t, length=None):
         length = t.amax()
     seq = torch.arange(length, device=t.device)
     return seq[None, :] < t[:, None]
+
+
+def mask_from_start_end_indices(seq_len, start, end):
+    """bool [b, max(seq_len)]: start <= position < end of each row (reference utils.py:50-55)."""
+    max_seq_len = seq_len.max().item()
+    seq = torch.arange(max_seq_len, device=start.device).long()
+    return (seq[None, :] >= start[:, None]) & (seq[None, :] < end[:, None])
+
+
+def mask_from_frac_lengths(seq_len, frac_lengths):
+    """A random span of ``frac_lengths * seq_len`` frames per row (reference utils.py:58-66): both products are truncated by ``.long()``, and
+    the span's start comes from ONE ``torch.rand_like(frac_lengths)`` draw, on ``frac_lengths``' device."""
+    lengths = (frac_lengths * seq_len).long()
+    max_start = seq_len - lengths
+    rand = torch.rand_like(frac_lengths)
+    start = (max_start * rand).long().clamp(min=0)
+    end = start + lengths
+    return mask_from_start_end_indices(seq_len, start, end)
 
 
 def list_str_to_tensor(text, padding_value=-1):

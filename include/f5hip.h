@@ -194,6 +194,27 @@ F5_API int f5_dit_forward(f5_plan_t p, int B, int N, const float* x, const float
 F5_API int f5_mmdit_forward(f5_plan_t p, int B, int N, int nt, const float* x, const float* cond, const float* text_embed,
                      const float* time, int drop_audio_cond, const uint8_t* mask, float* out, f5_stream_t stream);
 
+/* ------------------------------------------------------------------ flow-matching loss (CFM.forward, cfm.py:210-283; forward only)
+ * The flow-matching layer around ONE backbone evaluation (f5_dit_forward / f5_mmdit_forward with a time per sample), for validation runs: no
+ * gradient of anything here exists.  Detected by symbol, like the round-5 entries.  All tensors dev f32 [B, N, mel] unless said otherwise;
+ * span dev u8 [B, N] (1 = the frame lies in the random span: rand_span_mask & mask, cfm.py:241-245); time dev f32 [B].
+ * Noising (cfm.py:257-263) in one pass over x1 (the mel) and x0 (the noise):
+ *   phi  = (1 - t_b) * x0 + t_b * x1   the four fp32 operations rounded one by one, no FMA: torch's bits for cfm.py:259
+ *   cond = span ? 0 : x1               cfm.py:263 */
+F5_API int f5_cfm_noise(int B, int N, int mel, const float* x1, const float* x0, const float* time, const uint8_t* span, float* phi,
+                        float* cond, f5_stream_t stream);
+/* The loss (cfm.py:260, 280-283): per element (pred - (x1 - x0))^2 with every step rounded in fp32 as F.mse_loss(pred, x1 - x0, reduction =
+ * "none") rounds it, summed in fp64 over the rows where span is set.  sums dev f64 [B]; counts dev i64 [B] = selected rows x mel; loss dev f32 [1]
+ * = float(sum of sums / sum of counts): NaN when nothing is selected, as mean() of an empty tensor; an utterance without a selected row gets
+ * sums = 0 and counts = 0.  The flow and the elementwise loss never reach memory, and rows outside the span are not read.  The sum has a fixed
+ * order (per-workgroup partials in `workspace`, added by index; the partition depends on N and mel alone; no atomics): the same input gives the
+ * same bits on every run.  workspace: dev, 8-byte aligned, at least the bytes the _workspace entry answers (a negative F5_* code for a shape it
+ * refuses).  F5_EINVAL with a message for a null pointer or B, N or mel below 1.  16-byte loads when mel % 4 == 0 and the tensors are 16-byte
+ * aligned, element loads otherwise.  Nothing synchronises. */
+F5_API int64_t f5_cfm_loss_workspace(int B, int N, int mel);
+F5_API int f5_cfm_loss(int B, int N, int mel, const float* pred, const float* x1, const float* x0, const uint8_t* span, double* sums,
+                       int64_t* counts, float* loss, void* workspace, f5_stream_t stream);
+
 /* debug/parity taps: after the next f5_dit_forward / f5_sample evaluation, copy the named internal stage
  * (converted to f32, row-major [rows, cols]) into `dst` (dev f32).  Names: "t_emb", "input_embed",
  * "blk<i>.n1", "blk<i>.attn", "blk<i>.out", "final_norm".  Pass dst = NULL to clear all taps. */
