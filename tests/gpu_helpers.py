@@ -199,6 +199,176 @@ def check_elementwise(name, out, ref, scale, precision=P_FP16, extra=None):
     return worst
 
 
+# ----------------------------------------------------------------------------- attention: the fp64 reference with the terms of the element-wise
+# bound, the CPU restatement of the bf16 kernels' arithmetic, and the adversarial inputs the bf16 tests share
+LN2, LOG2E = 0.6931471805599453, 1.4426950408889634
+QSCALE = 0.125 * LOG2E  # what a pre-scaled q carries: 1 / sqrt(64) * log2(e)
+
+
+def attn_ref_terms(qkv, mask, precision, base2=False, keep=None, p=0.0):
+    """fp64 softmax attention of qkv [B, N, 3, H, 64] over the keys `mask` [B, N] allows, and the terms of the element-wise bound
+    (check_elementwise): (ref, mag, extra), each [B, N, H * 64] in fp64.
+        ref    sum_k p_k v_k
+        mag    pv (1 + 2 max_k sum_d |q_d k_d| scale), pv = sum_k p_k |v_k|: what the fp32 arithmetic works on -- the PV sum and, through the
+               exponential, the score sum (an error ds of a score is a relative error ds of its numerator, once in the numerator, once in l)
+        extra  one rounding (to nearest even) of each un-normalised numerator to the stored type:
+               fp16  2^-11 pv + N 2^-25 max |v|   (half an ulp of 10 stored bits; numerators in the subnormal range, spacing 2^-24, against
+                                                   l >= 1: the exponent reference is a score of the row)
+               bf16  2^-8 pv                      (half an ulp of 7 stored bits; no subnormal term: bf16 has fp32's exponent range and the
+                                                   kernels keep row sums below 2^64)
+    base2: q is pre-scaled (QSCALE is in it): scores q . k ln 2, and the score magnitude sum_d |q_d k_d| as it stands.  keep [B, H, N, N] bool
+    and p: the dropout mask and the factor 1 / (1 - p) on p_k, in ref and in pv."""
+    B, N = qkv.shape[0], qkv.shape[1]
+    outs = ([], [], [])
+    for b in range(B):  # one batch item at a time: the [H, N, N] fp64 temporaries of a long sequence are large
+        q, k, v = [qkv[b, :, i].transpose(0, 1).double() for i in range(3)]  # [H, N, 64]
+        s = q @ k.transpose(-1, -2) * (LN2 if base2 else 0.125)
+        sabs = q.abs() @ k.abs().transpose(-1, -2) * (1.0 if base2 else 0.125)
+        if mask is not None:
+            s = s.masked_fill(~mask[b][None, None, :], float("-inf"))
+            sabs = sabs.masked_fill(~mask[b][None, None, :], 0.0)
+        pr = torch.softmax(s, dim=-1)
+        if keep is not None:
+            pr = pr * keep[b].double() / (1.0 - p)
+        o = pr @ v
+        pv = pr @ v.abs()  # sum_k p_k |v_k| / l
+        mag = pv * (1.0 + 2.0 * sabs.amax(dim=-1, keepdim=True))
+        if precision == P_FP16:
+            extra = 2.0 ** -11 * pv + N * 2.0 ** -25 * v.abs().amax(dim=(-1, -2), keepdim=True)
+        else:
+            extra = 2.0 ** -8 * pv
+        for dst, t in zip(outs, (o, mag, extra.expand_as(o))):
+            dst.append(t.transpose(0, 1).reshape(N, -1))
+    return tuple(torch.stack(t) for t in outs)
+
+
+def bf16_trunc(t):
+    """fp32 -> bf16 by dropping the low 16 bits (round toward zero), as f32"""
+    return (t.float().contiguous().view(torch.int32) & -65536).view(torch.float32)
+
+
+EMULATE_VARIANTS = ("rne", "trunc_p", "trunc_out", "drop_last_valid_key", "leak_first_masked_key")
+
+
+def attn_emulate_bf16(qkv, mask, variant="rne", base2=False):
+    """CPU restatement of the bf16 flash kernels' arithmetic (attention_fast.hip, attention_pipe.hip): fp32 scores, numerators exp2(s c - m) in
+    fp32 against a reference m (the row maximum here; softmax does not depend on it), the row sum from the UNROUNDED numerators, the numerators
+    rounded once to bf16 (to nearest even) for the PV product, fp32 accumulation, one bf16 rounding of o / l.  -> [B, N, H * 64] f32.
+    Variants other than `rne` are the defects the element-wise bound and the bias statistic must catch:
+        trunc_p / trunc_out     the numerators / the outputs truncated to bf16 instead of rounded
+        drop_last_valid_key     the last valid key of every batch item is left out
+        leak_first_masked_key   the first masked key of a batch item counts; where its mask hides none, the ragged last tile's first padding
+                                row does: it holds the last key again (the kernels re-read key N - 1 there); a whole last tile: nothing"""
+    assert variant in EMULATE_VARIANTS
+    B, N, _, H, _ = qkv.shape
+    valid = torch.ones(B, N, dtype=torch.bool) if mask is None else mask.clone()
+    twice = torch.zeros(B, dtype=torch.bool)  # the last key counted twice
+    for b in range(B):
+        if variant == "drop_last_valid_key":
+            valid[b, int(valid[b].nonzero()[-1])] = False
+        elif variant == "leak_first_masked_key":
+            hidden = (~valid[b]).nonzero()
+            if len(hidden):
+                valid[b, int(hidden[0])] = True
+            else:
+                twice[b] = N % 64 != 0
+    q, k, v = [qkv[:, :, i].transpose(1, 2).float() for i in range(3)]  # [B, H, N, 64]
+    c = torch.tensor(1.0 if base2 else QSCALE, dtype=torch.float32)  # base2: q is pre-scaled, as f5_op_attention_prescaled takes it
+    s = (q @ k.transpose(-1, -2)).masked_fill(~valid[:, None, None, :], float("-inf"))
+    m = (s * c).amax(dim=-1, keepdim=True)
+    num = torch.exp2(torch.addcmul(-m, s, c))
+    dup = twice[:, None, None].float() * num[..., N - 1]  # [B, H, N]
+    l = num.sum(dim=-1) + dup
+    rnd = bf16_trunc if variant == "trunc_p" else bf16_round
+    o = rnd(num) @ v + (rnd(dup)[..., None] * v[:, :, N - 1:N, :])
+    o = o / l[..., None]
+    o = bf16_trunc(o) if variant == "trunc_out" else bf16_round(o)
+    return o.transpose(1, 2).reshape(B, N, H * 64)
+
+
+def attn_randn_case(B, N, H, masked, seed=None, positive_v=False):
+    """bf16(randn * 1.5) inputs [B, N, 3, H, 64] and the ragged-lengths key mask (N, N - 13, ...) of the attention tests; positive_v: V replaced
+    by bf16(|V| + 0.5), so that every output is at least 0.5 and sum_k p_k |v_k| is the output itself (the rounding-bias statistic)."""
+    g = torch.Generator().manual_seed(N + H if seed is None else seed)
+    qkv = bf16_round(torch.randn(B, N, 3, H, 64, generator=g) * 1.5)
+    if positive_v:
+        qkv[:, :, 2] = bf16_round(qkv[:, :, 2].abs() + 0.5)
+    mask = None
+    if masked:
+        lens = torch.tensor([N, max(1, N - 13)][:B])
+        mask = torch.arange(N)[None, :] < lens[:, None]
+    return qkv, mask
+
+
+def mean_signed_error(out, ref, valid=None):
+    """m = mean over the valid rows of (out - ref) / ref: the rounding-bias statistic (inputs of attn_randn_case(positive_v=True))"""
+    out, ref = (out, ref) if valid is None else (out[valid], ref[valid])
+    return float(((out.double() - ref.double()) / ref.double()).mean())
+
+
+def attn_case_deferred_rescale():
+    """Inputs of test_attention_deferred_rescale_thresholds (tests/test_gpu_ops.py): score jumps just below and far above the pipelined
+    kernel's 2^16 threshold, early and late, and a row whose maximum creeps up tile by tile.  -> (qkv, planted query rows)"""
+    g = torch.Generator().manual_seed(9)
+    B, N, H = 1, 1024, 2
+    qkv = torch.randn(B, N, 3, H, 64, generator=g) * 0.5
+    qn = qkv[0, :, 0] / qkv[0, :, 0].norm(dim=-1, keepdim=True)      # unit queries
+    for q, (key, nat) in {5: (700, 10.0), 37: (130, 12.5), 90: (1000, 40.0), 200: (3, 60.0)}.items():
+        qkv[0, q, 0] = qn[q] * 8.0                                   # |q| = 8: q.k / 8 = |k| cos
+        qkv[0, key, 1] = qn[q] * nat                                 # score of (q, key) = nat nats (16 log2 units = 11.1 nats)
+    qkv[0, 300, 0] = qn[300] * 8.0
+    for i, key in enumerate(range(10, 1024, 64)):                    # one key per tile, each 1.5 nats above the previous
+        qkv[0, key, 1] = qn[300] * (1.5 * (i + 1))
+    return bf16_round(qkv), (5, 37, 90, 200, 300)
+
+
+def attn_case_range_guard(masked):
+    """Inputs of test_attention_wide_kernel_range_guard (tests/test_gpu_ops.py): score jumps around the wide kernel's 2^64 guard, a creeping
+    maximum and -- masked -- an utterance whose whole first tile is masked out.  -> (qkv, mask or None, planted query rows)"""
+    g = torch.Generator().manual_seed(21)
+    B, N, H = 2, 1024, 2
+    qkv = torch.randn(B, N, 3, H, 64, generator=g) * 0.5
+    jumps = {5: (700, 62.0 / LOG2E), 37: (130, 65.5 / LOG2E), 90: (1000, 144.0 / LOG2E), 200: (3, 430.0 / LOG2E), 411: (200, 90.0 / LOG2E),
+             600: (90, 63.5 / LOG2E), 777: (960, 64.5 / LOG2E)}
+    for bb in range(B):
+        qn = qkv[bb, :, 0] / qkv[bb, :, 0].norm(dim=-1, keepdim=True)
+        for q, (key, nat) in jumps.items():
+            qkv[bb, q, 0] = qn[q] * 8.0          # |q| = 8: q.k / 8 = |k| cos
+            qkv[bb, key, 1] = qn[q] * nat        # score of (q, key) = nat nats
+        qkv[bb, 300, 0] = qn[300] * 8.0
+        for i, key in enumerate(range(74, 1024, 64)):   # one key per tile, each 6 nats above the previous
+            qkv[bb, key, 1] = qn[300] * (6.0 * (i + 1))
+    qkv = bf16_round(qkv)
+    mask = None
+    if masked:
+        mask = torch.ones(B, N, dtype=torch.bool)
+        mask[1, :70] = False      # the first tile (and 6 keys of the second) of utterance 1
+        mask[1, 1000:] = False
+        mask[0, 990:] = False
+    return qkv, mask, list(jumps) + [300]
+
+
+def attn_case_spiked_512():
+    """Inputs of test_attention_tuned_kernel_spiked_scores (tests/test_gpu_ops.py): one key dominates late in the sequence."""
+    g = torch.Generator().manual_seed(5)
+    B, N, H = 1, 512, 2
+    qkv = bf16_round(torch.randn(B, N, 3, H, 64, generator=g))
+    qkv[0, 400, 1] = qkv[0, 7, 0] * 8.0  # key 400 aligned with query 7
+    return bf16_round(qkv)
+
+
+def op_attention_prescaled(kernel, qkv, mask=None):
+    """include/f5hip.h: f5_op_attention_prescaled (bf16; the q part of qkv carries QSCALE)"""
+    lib = _lib.load()
+    B, N, three, H, dh = qkv.shape
+    assert three == 3 and dh == 64
+    q = qkv.cuda().float().contiguous()
+    mk = None if mask is None else mask.cuda().to(torch.uint8).contiguous()
+    out = torch.empty(B, N, H * 64, device="cuda")
+    _lib.check(lib.f5_op_attention_prescaled(kernel, B, N, H, _lib.ptr(q), _lib.ptr(mk), _lib.ptr(out), _lib.stream_ptr()), "f5_op_attention_prescaled")
+    return out.cpu()
+
+
 def linear_ref(A, W, b, act):
     """fp64 result and the magnitude the fp32 arithmetic works on (GELU's derivative is below 1.13: the accumulation error passes through it)."""
     ref = A.double() @ W.double().t() + b.double()

@@ -12,7 +12,9 @@ Every result-checking test asserts, for every utterance and branch,
       utterance alone").  The own launch has B = nbr, as launch_attention_ragged states it and as the batch-1 sample() makes it: by grid size
       (attn_variant 0) the kernel choice depends on B;
   (b) accuracy against the fp64 softmax of that utterance, with the bounds the packed-form tests of test_gpu_ops.py use at this input scale
-      (tuned bf16 kernels: rel-L2 < 6e-3, max-abs < 0.05, all finite; reference kernels: rel-L2 < 3e-6 in fp32, < 4e-3 in bf16); in the
+      (tuned bf16 kernels: rel-L2 < 6e-3, max-abs < 0.05, all finite, and next to them the ELEMENT-WISE fp64 bound of
+      test_gpu_attention_bf16_elementwise.py: 1 bf16 ulp + 8 fp32 ulps of the sums of magnitudes + 2^-8 sum_k p_k |v_k|, per utterance and
+      branch; reference kernels: rel-L2 < 3e-6 in fp32, < 4e-3 in bf16); in the
       fp16 mode (P_FP16: utterances rounded to fp16, a cache entry of their own) the ELEMENT-WISE fp64 bound of test_gpu_fp16_ops.py
       (1 fp16 ulp + 8 fp32 ulps of the sums of magnitudes + the numerator-rounding terms) per utterance and branch, no rel-L2 number;
   (c) no stray write: every element of `out` outside the utterances' rows and head columns, in every branch, still holds 776.0."""
@@ -34,13 +36,6 @@ def _gpu():
     _lib.require_gpu()
 
 
-def _attn_ref(qkv):
-    """fp64 softmax attention (test_gpu_ops.py: _attn_ref, no mask): qkv [B, N, 3, H, 64] -> [B, N, H * 64]"""
-    q, k, v = [qkv[:, :, i].transpose(1, 2).double() for i in range(3)]
-    o = torch.softmax(q @ k.transpose(-1, -2) / 8.0, dim=-1) @ v
-    return o.transpose(1, 2).reshape(qkv.shape[0], qkv.shape[1], -1).float()
-
-
 def _layout(lens, first=0):
     """The sampler's rule: utterance u owns round_up(n_u + 16, 16) rows.  Returns (offsets, rows of one branch)."""
     off, o = [], first
@@ -53,19 +48,15 @@ def _layout(lens, first=0):
 @functools.lru_cache(maxsize=2)
 def _case(lens, nbr, H, first, ref_heads, fp16=False):
     """Seeded utterances [nbr, n, 3, H, 64] (rounded to bf16, or to fp16 for the fp16 mode), their layout, and the fp64 reference of each over
-    the heads `ref_heads` (None: all) -- for fp16 the triple (reference, fp32 magnitude, numerator-rounding allowance) of
-    test_gpu_fp16_ops._attn_ref.  Shared by the parametrisations that differ only in the schedule; nobody modifies it."""
+    the heads `ref_heads` (None: all): the triple (reference, fp32 magnitude, numerator-rounding allowance) of gpu_helpers.attn_ref_terms in
+    the 16-bit type the utterances were rounded to.  Shared by the parametrisations that differ only in the schedule; nobody modifies it."""
     import gpu_helpers as G
     g = torch.Generator().manual_seed(sum(lens) + 131 * nbr + 7 * H + first)
     rnd = (lambda t: t.half().float()) if fp16 else G.bf16_round
     utts = [rnd(torch.randn(nbr, n, 3, H, 64, generator=g) * 1.5) for n in lens]
     off, rows = _layout(lens, first)
     heads = list(range(H)) if ref_heads is None else list(ref_heads)
-    if fp16:
-        from test_gpu_fp16_ops import _attn_ref as attn_ref_f16
-        refs = [attn_ref_f16(u[:, :, :, heads], None) for u in utts]
-    else:
-        refs = [_attn_ref(u[:, :, :, heads]) for u in utts]
+    refs = [G.attn_ref_terms(u[:, :, :, heads], None, P_FP16 if fp16 else P_BF16) for u in utts]
     return utts, off, rows, heads, refs
 
 
@@ -103,12 +94,14 @@ def _run(prec, attn_kernel, variant, lens, nbr, H, first=0, ldq_extra=0, ldo_ext
             for br in range(nbr):
                 check_f16(f"(b) utterance {u} n={n} branch {br}", got[br][:, cols], ref[br], mag[br], extra[br])
             continue
+        ref, mag, extra = refs[u]
         for br in range(nbr):
-            g, r = got[br][:, cols], refs[u][br]
+            g, r = got[br][:, cols], ref[br].float()
             rl, ma = rel_l2(g, r), float((g - r).abs().max())
             print(f"  utterance {u} n={n} branch {br}: rel-L2 {rl:.3e}, max-abs {ma:.3e}")
             if kind == 1:
                 assert rl < 6e-3 and ma < 0.05, f"(b) utterance {u} (n = {n}) branch {br}: rel-L2 {rl:.3e}, max-abs {ma:.3e}"
+                G.check_elementwise(f"(b) utterance {u} n={n} branch {br}", g, ref[br], mag[br], P_BF16, extra[br])
             else:
                 assert rl < (3e-6 if prec == P_FP32 else 4e-3), f"(b) utterance {u} (n = {n}) branch {br}: rel-L2 {rl:.3e}"
     stray = (out != SENTINEL) & untouched

@@ -191,22 +191,10 @@ def test_position_conv_untuned(dim, B, N):
 
 # ----------------------------------------------------------------------------- 6. / 7. attention
 def _attn_ref(qkv, mask):
-    """fp64 softmax attention and the terms of the bound (module docstring): (ref, fp32 magnitude, numerator-rounding allowance)."""
-    q, k, v = [qkv[:, :, i].transpose(1, 2).double() for i in range(3)]  # [B, H, N, 64]
-    s = q @ k.transpose(-1, -2) / 8.0
-    sabs = (q.abs() @ k.abs().transpose(-1, -2) / 8.0)
-    if mask is not None:
-        s = s.masked_fill(~mask[:, None, None, :], float("-inf"))
-        sabs = sabs.masked_fill(~mask[:, None, None, :], 0.0)
-    p = torch.softmax(s, dim=-1)
-    o = p @ v
-    pv = p @ v.abs()  # sum_k p_k |v_k| / l
-    N = qkv.shape[1]
-    vmax = v.abs().amax(dim=(-1, -2), keepdim=True)
-    back = lambda t: t.transpose(1, 2).reshape(qkv.shape[0], N, -1)
-    mag = pv * (1.0 + 2.0 * sabs.amax(dim=-1, keepdim=True))
-    extra = 2.0 ** -11 * pv + N * 2.0 ** -25 * vmax
-    return back(o), back(mag), back(extra.expand_as(o))
+    """fp64 softmax attention and the terms of the bound (module docstring): (ref, fp32 magnitude, numerator-rounding allowance) -- the fp16
+    terms of gpu_helpers.attn_ref_terms, the reference the bf16 element-wise tests share."""
+    import gpu_helpers as G
+    return G.attn_ref_terms(qkv, mask, P_FP16)
 
 
 def _run_attention(qkv, mask, variant):

@@ -328,17 +328,8 @@ def test_attention_deferred_rescale_thresholds(variant):
     than 2^16; 64-queries-per-wave kernel: no maximum unless a row sum leaves the guarded range): score jumps just below and far above
     the 2^16 threshold, early and late, and a row whose maximum keeps creeping up tile by tile -- against the fp64 softmax."""
     import gpu_helpers as G
-    g = torch.Generator().manual_seed(9)
-    B, N, H = 1, 1024, 2
-    qkv = torch.randn(B, N, 3, H, 64, generator=g) * 0.5
-    qn = qkv[0, :, 0] / qkv[0, :, 0].norm(dim=-1, keepdim=True)      # unit queries
-    for q, (key, nat) in {5: (700, 10.0), 37: (130, 12.5), 90: (1000, 40.0), 200: (3, 60.0)}.items():
-        qkv[0, q, 0] = qn[q] * 8.0                                   # |q| = 8: q.k / 8 = |k| cos
-        qkv[0, key, 1] = qn[q] * nat                                 # score of (q, key) = nat nats (16 log2 units = 11.1 nats)
-    qkv[0, 300, 0] = qn[300] * 8.0
-    for i, key in enumerate(range(10, 1024, 64)):                    # one key per tile, each 1.5 nats above the previous
-        qkv[0, key, 1] = qn[300] * (1.5 * (i + 1))
-    qkv = G.bf16_round(qkv)
+    qkv, planted = G.attn_case_deferred_rescale()  # (the inputs, shared with test_gpu_attention_bf16_elementwise.py)
+    assert planted == (5, 37, 90, 200, 300)
     ref = _attn_ref(qkv, None)
     with G.knobs(attn_variant=variant):
         out = G.op_attention(P_BF16, 1, qkv, None)
@@ -356,27 +347,9 @@ def test_attention_wide_kernel_range_guard(masked):
     inf), early and late in the sequence, a query whose maximum creeps up tile by tile, and -- masked -- an utterance whose whole first
     tile is masked out (its queries enter the second tile with the finite start reference), against the fp64 softmax."""
     import gpu_helpers as G
-    g = torch.Generator().manual_seed(21)
-    B, N, H = 2, 1024, 2
-    qkv = torch.randn(B, N, 3, H, 64, generator=g) * 0.5
-    LOG2E = 1.4426950408889634
-    jumps = {5: (700, 62.0 / LOG2E), 37: (130, 65.5 / LOG2E), 90: (1000, 144.0 / LOG2E), 200: (3, 430.0 / LOG2E), 411: (200, 90.0 / LOG2E),
-             600: (90, 63.5 / LOG2E), 777: (960, 64.5 / LOG2E)}
-    for bb in range(B):
-        qn = qkv[bb, :, 0] / qkv[bb, :, 0].norm(dim=-1, keepdim=True)
-        for q, (key, nat) in jumps.items():
-            qkv[bb, q, 0] = qn[q] * 8.0          # |q| = 8: q.k / 8 = |k| cos
-            qkv[bb, key, 1] = qn[q] * nat        # score of (q, key) = nat nats
-        qkv[bb, 300, 0] = qn[300] * 8.0
-        for i, key in enumerate(range(74, 1024, 64)):   # one key per tile, each 6 nats above the previous
-            qkv[bb, key, 1] = qn[300] * (6.0 * (i + 1))
-    qkv = G.bf16_round(qkv)
-    mask = None
-    if masked:
-        mask = torch.ones(B, N, dtype=torch.bool)
-        mask[1, :70] = False      # the first tile (and 6 keys of the second) of utterance 1
-        mask[1, 1000:] = False
-        mask[0, 990:] = False
+    qkv, mask, planted = G.attn_case_range_guard(masked)  # (the inputs, shared with test_gpu_attention_bf16_elementwise.py)
+    B = qkv.shape[0]
+    assert planted == [5, 37, 90, 200, 411, 600, 777, 300]
     ref = _attn_ref(qkv, mask)
     with G.knobs(attn_variant=2):
         out = G.op_attention(P_BF16, 1, qkv, mask)
@@ -386,18 +359,14 @@ def test_attention_wide_kernel_range_guard(masked):
     else:  # masked QUERIES are computed and dropped downstream; compare the valid ones
         assert rel_l2(out[mask], ref[mask]) < 6e-3
     for bb in range(B):
-        for q in list(jumps) + [300]:
+        for q in planted:
             assert (out[bb, q] - ref[bb, q]).abs().max() < 0.03 * max(1.0, float(ref[bb, q].abs().max())), (bb, q)
 
 
 def test_attention_tuned_kernel_spiked_scores():
     """online-softmax rescale path: one key dominates late in the sequence (running max jumps by > 60)."""
     import gpu_helpers as G
-    g = torch.Generator().manual_seed(5)
-    B, N, H = 1, 512, 2
-    qkv = G.bf16_round(torch.randn(B, N, 3, H, 64, generator=g))
-    qkv[0, 400, 1] = qkv[0, 7, 0] * 8.0  # key 400 aligned with query 7
-    qkv = G.bf16_round(qkv)
+    qkv = G.attn_case_spiked_512()  # (the inputs, shared with test_gpu_attention_bf16_elementwise.py)
     ref = _attn_ref(qkv, None)
     out = G.op_attention(P_BF16, 1, qkv, None)
     assert rel_l2(out, ref) < 6e-3
