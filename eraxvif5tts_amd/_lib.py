@@ -55,6 +55,12 @@ class DurationWeights(C.Structure):  # struct f5_duration_weights
                [("cond_w", C.c_void_p), ("cond_b", C.c_void_p), ("gin_channels", C.c_int32)]
 
 
+class TileGemm(C.Structure):  # struct f5_tile_gemm (f5_op_tile_gemm: the reference tile kernel, test hook)
+    _fields_ = [(n, C.c_void_p) for n in ("A", "W", "bias", "gate", "rope", "addend", "rowmask", "out_t", "out_f")] + \
+               [(n, C.c_int32) for n in ("precision", "mode", "epi", "M", "N", "K", "a_row_mod", "act", "gate_bstride", "rows_per_batch", "rope_heads",
+                                         "ldadd", "add2_f16", "ldo", "ldof", "out_rows")]
+
+
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 _PROTOS = {
     "f5_last_error": (C.c_char_p, []),
@@ -101,6 +107,7 @@ _PROTOS = {
     "f5_op_attention_ragged": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, _P, _P, _P]),
     "f5_op_conv_pos_embed": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "f5_op_conv31": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "f5_op_tile_gemm": (_I, [C.POINTER(TileGemm), _P]),
     "f5_op_layernorm_res": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "f5_op_f32_to_f16": (_I, [C.c_int64, _P, _P, _P, _P]),
     "f5_op_qknorm_rope": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

@@ -347,6 +347,114 @@ extern "C" int f5_op_conv31(int precision, int kernel, int B, int N, int dim, co
     return sync_and_release(a, st, rc);
 }
 
+// Test staging of a caller's output buffer into the element type a kernel stores and back: plain casts over the whole buffer, padding columns
+// and guard rows included, so that NaN fill survives and a write outside [M, N] shows.
+template <typename T> __global__ __launch_bounds__(256) void stage_cast_kernel(const float* __restrict__ src, T* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = (T)src[i];
+}
+template <typename T> __global__ __launch_bounds__(256) void unstage_cast_kernel(const T* __restrict__ src, float* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = (float)src[i];
+}
+template <typename T> static int stage_cast(const float* src, void* dst, size_t n, hipStream_t st) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL((stage_cast_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, (T*)dst, n);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+template <typename T> static int unstage_cast(const void* src, float* dst, size_t n, hipStream_t st) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL((unstage_cast_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const T*)src, dst, n);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+static int stage_cast_p(int precision, const float* src, void* dst, size_t n, hipStream_t st) {
+    return precision == F5_PREC_BF16 ? stage_cast<bf16_t>(src, dst, n, st) : precision == F5_PREC_FP16 ? stage_cast<f16_t>(src, dst, n, st) : stage_cast<float>(src, dst, n, st);
+}
+static int unstage_cast_p(int precision, const void* src, float* dst, size_t n, hipStream_t st) {
+    return precision == F5_PREC_BF16 ? unstage_cast<bf16_t>(src, dst, n, st) : precision == F5_PREC_FP16 ? unstage_cast<f16_t>(src, dst, n, st) : unstage_cast<float>(src, dst, n, st);
+}
+
+// The reference tile kernel (gemm.hip: gemm_tile_kernel, kernel_kind 0) with every parameter its epilogues branch on in the caller's hands
+// (test hook; include/f5hip.h: f5_tile_gemm).  The outputs are the caller's buffers [out_rows, ldo / ldof]: staged into the stored type whole,
+// handed to the kernel, and staged back whole.
+extern "C" int f5_op_tile_gemm(const f5_tile_gemm* t, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (!t) return f5_fail(F5_EINVAL, "bad argument");
+    const int P = t->precision, mode = t->mode, epi = t->epi, M = t->M, N = t->N, K = t->K;
+    if (P != F5_PREC_BF16 && P != F5_PREC_FP32 && P != F5_PREC_FP16) return f5_fail(F5_EINVAL, "f5_op_tile_gemm: bad precision %d", P);
+    if (mode != GEMM_DENSE && mode != GEMM_CONV31) return f5_fail(F5_EINVAL, "f5_op_tile_gemm: mode is 0 (dense) or 1 (conv31)");
+    if (epi < EPI_STORE_T || epi > EPI_GATE_T || (mode == GEMM_CONV31 && epi != EPI_STORE_T && epi != EPI_RESID && epi != EPI_GATE_T))
+        return f5_fail(F5_EINVAL, "f5_op_tile_gemm: unsupported mode/epilogue %d/%d", mode, epi);
+    if (M <= 0 || N <= 0 || !t->A || !t->W) return f5_fail(F5_EINVAL, "bad argument");
+    const int rpb = t->rows_per_batch > 0 ? t->rows_per_batch : M;
+    if (mode == GEMM_DENSE && (K <= 0 || K % 32 != 0 || t->a_row_mod < 0)) return f5_fail(F5_EINVAL, "f5_op_tile_gemm: K must be a positive multiple of 32");
+    if (mode == GEMM_CONV31 && (N % 128 != 0 || M % rpb != 0 || t->a_row_mod != 0)) return f5_fail(F5_EINVAL, "f5_op_tile_gemm(conv31): dim % 128, whole sequences");
+    const bool needs_t = epi == EPI_STORE_T || epi == EPI_ROPE_T || epi == EPI_GATE_T || epi == EPI_ADD2;
+    const bool needs_f = epi == EPI_STORE_F32 || epi == EPI_RESID || epi == EPI_ADD2;
+    if (t->out_rows < M || (needs_t && (!t->out_t || t->ldo < N)) || (needs_f && (!t->out_f || t->ldof < N)))
+        return f5_fail(F5_EINVAL, "f5_op_tile_gemm: an output buffer is missing or smaller than [M, N]");
+    if (epi == EPI_ADD2 && (!t->addend || t->ldadd < N)) return f5_fail(F5_EINVAL, "f5_op_tile_gemm: EPI_ADD2 needs an addend [M, ldadd >= N]");
+    if (t->add2_f16 && epi != EPI_RESID && epi != EPI_ADD2) return f5_fail(F5_EINVAL, "f5_op_tile_gemm: add2_f16 belongs to EPI_RESID / EPI_ADD2");
+    if (t->gate_bstride < 0 || ((t->gate || t->rowmask) && epi != EPI_RESID && epi != EPI_GATE_T))
+        return f5_fail(F5_EINVAL, "f5_op_tile_gemm: gate / rowmask belong to EPI_RESID / EPI_GATE_T");
+    if (epi == EPI_ROPE_T && (!t->rope || N % 3 != 0 || (N / 3) % 64 != 0 || t->rope_heads < 0 || t->rope_heads > N / 192))
+        return f5_fail(F5_EINVAL, "bad RoPE arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t es = f5_elem_size(P);
+    const size_t nt = (size_t)t->out_rows * t->ldo, nf = (size_t)t->out_rows * t->ldof;
+    DevArena a;
+    void *At = nullptr, *Wt = nullptr, *Ot = nullptr, *Of = nullptr, *Ad = nullptr;
+    int rc = 0;
+    do {
+        GemmParams g;
+        memset(&g, 0, sizeof(g));
+        if (mode == GEMM_DENSE) {
+            const int arows = t->a_row_mod > 0 ? t->a_row_mod : M;
+            if ((rc = a.alloc(&At, (size_t)arows * K * es))) break;
+            if ((rc = a.alloc(&Wt, (size_t)N * K * es))) break;
+            if ((rc = launch_convert_pad(P, t->A, K, arows, K, K, At, K, st))) break;
+            if ((rc = launch_convert_pad(P, t->W, K, N, K, K, Wt, K, st))) break;
+            g.lda = K; g.ldw = K; g.K = K; g.a_row_mod = t->a_row_mod;
+        } else {
+            const int win = conv31_window(N);
+            if ((rc = upload_conv31_weight(a, P, N, win, t->W, &Wt))) break;
+            if ((rc = a.alloc(&At, (size_t)M * N * es))) break;
+            if ((rc = launch_convert_pad(P, t->A, N, M, N, N, At, N, st))) break;
+            g.lda = N; g.K = 31 * win; g.conv_cg = N / 16; g.conv_win = win;
+        }
+        g.A = At; g.W = Wt; g.M = M; g.N = N; g.bias = t->bias; g.act = t->act;
+        g.gate = t->gate; g.gate_bstride = t->gate_bstride; g.rows_per_batch = rpb; g.rowmask = t->rowmask;
+        if (epi == EPI_ROPE_T) { g.rope = t->rope; g.rope_inner = N / 3; g.rope_heads = t->rope_heads; }
+        if (needs_t) {
+            if ((rc = a.alloc(&Ot, nt * es))) break;
+            if ((rc = stage_cast_p(P, t->out_t, Ot, nt, st))) break;
+            g.out_t = Ot; g.ldo = t->ldo;
+        }
+        if (needs_f) {
+            g.out_f = t->out_f; g.ldof = t->ldof; g.add2_f16 = t->add2_f16 ? 1 : 0;
+            if (t->add2_f16) {  // the fp16 residual stream
+                if ((rc = a.alloc(&Of, nf * 2))) break;
+                if ((rc = stage_cast<f16_t>(t->out_f, Of, nf, st))) break;
+                g.out_f = reinterpret_cast<float*>(Of);
+            }
+        }
+        if (epi == EPI_ADD2) {
+            g.addend = t->addend; g.ldadd = t->ldadd;
+            if (t->add2_f16) {
+                if ((rc = a.alloc(&Ad, (size_t)M * t->ldadd * 2))) break;
+                if ((rc = stage_cast<f16_t>(t->addend, Ad, (size_t)M * t->ldadd, st))) break;
+                g.addend = reinterpret_cast<const float*>(Ad);
+            }
+        }
+        if ((rc = launch_gemm(g, P, mode, epi, 0, st))) break;
+        if (needs_t && (rc = unstage_cast_p(P, Ot, t->out_t, nt, st))) break;
+        if (needs_f && t->add2_f16) rc = unstage_cast<f16_t>(Of, t->out_f, nf, st);
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
 extern "C" int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const float* x, const float* w0, const float* b0, const float* w1,
                                     const float* b1, float* out, f5_stream_t stream) {
     F5_TRY(f5_check_device());

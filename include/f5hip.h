@@ -366,6 +366,27 @@ F5_API int f5_op_conv_pos_embed(int precision, int B, int N, int dim, const floa
  * tile kernel, 1 = the tuned route as the model takes it (knobs "conv31", "conv31_tok"; the 16-bit modes). */
 F5_API int f5_op_conv31(int precision, int kernel, int B, int N, int dim, const float* x, const float* w, const float* b, int act, float* out,
                         f5_stream_t stream);
+/* The reference 64 x 64 tile kernel -- the only GEMM of the fp32 mode, of Vocos, BigVGAN and the mel front-end -- with every parameter its
+ * epilogues branch on in the caller's hands (test hook; detect it by symbol).  All tensors f32 on the device, converted there.
+ *   mode 0 (dense):   A [a_row_mod > 0 ? a_row_mod : M, K] (row m reads A[m % a_row_mod]), W [N, K], K % 32 == 0
+ *   mode 1 (conv31):  A = x [M, N] with M = batches * rows_per_batch token rows and N = dim (dim % 128 == 0), W [dim, dim / 16, 31]; K unused
+ *   epi  0  out_t = act(acc + bias)                          1  out_f = act(acc + bias)                     (dense only)
+ *        2  out_f += gate * act(acc + bias) in place, rows with rowmask[m] == 0 untouched
+ *        3  v = acc + bias + addend [M, ldadd];  out_t = v, out_f = v                                      (dense only)
+ *        4  out_t = rope(acc + bias): N = 3 * inner, rope [rows_per_batch][32][2] (cos, sin), first rope_heads heads   (dense only)
+ *        5  out_t = gate * act(acc + bias), rows with rowmask[m] == 0 zeros
+ *   gate [N] (gate_bstride 0) or [batches][gate_bstride], batch = m / rows_per_batch (0: one batch of M rows); rowmask u8 [M]; both or NULL
+ *   add2_f16 (epi 2 / 3): out_f and the addend hold fp16 elements, as in the bf16 mode's residual stream
+ *   out_t [out_rows, ldo] is staged whole into the precision's type (a plain cast: NaN stays NaN), handed to the kernel and staged back whole;
+ *   out_f [out_rows, ldof] is the kernel's own buffer (fp32), or staged the same way through fp16 (add2_f16).  out_rows >= M, ldo / ldof >= N,
+ *   any alignment: what the kernel does not write -- padding columns, guard rows -- comes back as the caller left it. */
+typedef struct f5_tile_gemm {
+    const float *A, *W, *bias, *gate, *rope, *addend;
+    const uint8_t* rowmask;
+    float *out_t, *out_f;
+    int32_t precision, mode, epi, M, N, K, a_row_mod, act, gate_bstride, rows_per_batch, rope_heads, ldadd, add2_f16, ldo, ldof, out_rows;
+} f5_tile_gemm;
+F5_API int f5_op_tile_gemm(const f5_tile_gemm* g, f5_stream_t stream);
 
 /* Test and diagnostic entry points of the row-wise kernels: each stages its f32 device inputs into the dtypes the model path uses and calls
  * the production launcher, so the launcher's own dispatch (and its tuning knobs) decides which kernel runs.  All pointers are device pointers.

@@ -171,22 +171,30 @@ def last_gemm():
 
 
 # ----------------------------------------------------------------------------- element-wise comparison of the 16-bit GEMM / conv kernels
-P_BF16, P_FP16 = 0, 2
+P_BF16, P_FP32, P_FP16 = 0, 1, 2
+PREC_NAMES = {P_BF16: "bf16", P_FP32: "fp32", P_FP16: "fp16"}
 F32_ULPS = 8 * 2.0 ** -23
 
 
 def round_to(precision, t):
-    """`t` rounded once (to nearest even) to the stored type of the 16-bit mode `precision`, as f32."""
+    """`t` rounded once (to nearest even) to the stored type of the mode `precision` (bf16 0, fp32 1, fp16 2), as f32."""
+    if precision == P_FP32:
+        return t.float()
     return (t.float().half() if precision == P_FP16 else t.float().to(torch.bfloat16)).float()
 
 
+def stored_ulp(precision, ref):
+    """Spacing of the stored type of the mode `precision` at |ref| (fp64)."""
+    return fp32_ulp(ref) if precision == P_FP32 else fp16_ulp(ref) if precision == P_FP16 else bf16_ulp(ref)
+
+
 def check_elementwise(name, out, ref, scale, precision=P_FP16, extra=None):
-    """|out - ref| <= 1 ulp(ref) of the stored type (fp16 / bf16) + 8 fp32 ulps of `scale` (+ extra), element-wise; prints the worst share of
-    the bound before it asserts.  Pure tensor arithmetic: runs on the CPU."""
+    """|out - ref| <= 1 ulp(ref) of the stored type (fp16 / bf16 / fp32) + 8 fp32 ulps of `scale` (+ extra), element-wise; prints the worst
+    share of the bound before it asserts.  Pure tensor arithmetic: runs on the CPU."""
     ref = ref.double()
     err = (out.double() - ref).abs()
-    ulp = fp16_ulp(ref) if precision == P_FP16 else bf16_ulp(ref)
-    tname = "fp16" if precision == P_FP16 else "bf16"
+    ulp = stored_ulp(precision, ref)
+    tname = PREC_NAMES[precision]
     bound = ulp + F32_ULPS * scale.double().abs()
     if extra is not None:
         bound = bound + extra.double()
@@ -216,6 +224,7 @@ def attn_ref_terms(qkv, mask, precision, base2=False, keep=None, p=0.0):
                                                    l >= 1: the exponent reference is a score of the row)
                bf16  2^-8 pv                      (half an ulp of 7 stored bits; no subnormal term: bf16 has fp32's exponent range and the
                                                    kernels keep row sums below 2^64)
+               fp32  0                            (the numerators stay in fp32: the reference kernel of the fp32 mode)
     base2: q is pre-scaled (QSCALE is in it): scores q . k ln 2, and the score magnitude sum_d |q_d k_d| as it stands.  keep [B, H, N, N] bool
     and p: the dropout mask and the factor 1 / (1 - p) on p_k, in ref and in pv."""
     B, N = qkv.shape[0], qkv.shape[1]
@@ -235,6 +244,8 @@ def attn_ref_terms(qkv, mask, precision, base2=False, keep=None, p=0.0):
         mag = pv * (1.0 + 2.0 * sabs.amax(dim=-1, keepdim=True))
         if precision == P_FP16:
             extra = 2.0 ** -11 * pv + N * 2.0 ** -25 * v.abs().amax(dim=(-1, -2), keepdim=True)
+        elif precision == P_FP32:
+            extra = torch.zeros_like(pv)
         else:
             extra = 2.0 ** -8 * pv
         for dst, t in zip(outs, (o, mag, extra.expand_as(o))):
@@ -375,6 +386,10 @@ def linear_ref(A, W, b, act):
     scale = A.double().abs() @ W.double().abs().t() + b.double().abs()
     if act == "gelu_tanh":
         ref, scale = F.gelu(ref, approximate="tanh"), 1.13 * scale
+    elif act == "gelu_erf":  # (the Vocos feed-forward; its derivative stays below 1.13 as well)
+        ref, scale = F.gelu(ref), 1.13 * scale
+    elif act == "mish":      # (derivative below 1.1)
+        ref, scale = F.mish(ref), 1.1 * scale
     return ref, scale
 
 
@@ -394,10 +409,14 @@ def rope_ref(lin, ls, rope, seq, rope_heads=1):
     return ref, scale
 
 
-def fused_ref(epi_name, A, W, b, act="none", gate=None, rowmask=None, x=None, rope=None, rope_heads=1, seq=0):
-    """fp64 reference and fp32 magnitude of one fused epilogue (oracle/cpu_ref.py: dit_block's linears, apply_rope): store | gate | rope | resid."""
-    lin, ls = linear_ref(A, W, b, act)
+def fused_ref(epi_name, A, W, b, act="none", gate=None, rowmask=None, x=None, rope=None, rope_heads=1, seq=0, addend=None, lin=None):
+    """fp64 reference and fp32 magnitude of one fused epilogue (oracle/cpu_ref.py: dit_block's linears, apply_rope): store | gate | rope | resid
+    | add2 (lin + addend, both outputs).  gate [N], or one row per token row [M, N] (a per-batch gate, expanded by the caller).  lin: (fp64
+    result, magnitude) of the contraction where it is not A W^T + b (a convolution)."""
+    lin, ls = linear_ref(A, W, b, act) if lin is None else lin
     keep = None if rowmask is None else rowmask.double()[:, None]
+    if epi_name == "add2":
+        return lin + addend.double(), ls + addend.double().abs()
     if epi_name == "resid":
         upd = gate.double() * lin if keep is None else gate.double() * lin * keep  # masked rows are left as they are
         return x.double() + upd, x.double().abs() + gate.double().abs() * ls
@@ -492,14 +511,17 @@ def ints(g, shape, lo, hi):
     return torch.randint(lo, hi + 1, shape, generator=g).float()
 
 
-def exact_case(epi, M, N, K, seq, rope_heads, masked, seed):
+def exact_case(epi, M, N, K, seq, rope_heads, masked, seed, gate_batches=0, a_rows=None):
     """Exact inputs of one epilogue (test_gpu_gemm_tiles.py: integers and halves whose every product, partial sum and epilogue value is exact
-    in fp32): (positional A, W, b), keyword arguments of G.run_fused / G.fused_ref."""
+    in fp32): (positional A, W, b), keyword arguments of G.run_fused / G.fused_ref.  gate_batches > 0: one gate row per batch item
+    [gate_batches, N]; a_rows: A holds that many rows (a_row_mod); epi "add2": an addend of multiples of 1/2 in +-64."""
     g = torch.Generator().manual_seed(seed)
-    A, W, b = ints(g, (M, K), -2, 2), ints(g, (N, K), -1, 1), ints(g, (N,), -8, 8)
+    A, W, b = ints(g, (a_rows or M, K), -2, 2), ints(g, (N, K), -1, 1), ints(g, (N,), -8, 8)
     kw = {}
+    if epi == "add2":
+        kw["addend"] = ints(g, (M, N), -128, 128) * 0.5
     if epi in ("gate", "resid"):
-        kw["gate"] = torch.tensor([0.5, -0.5, 1.0, -1.0, 2.0, -2.0])[torch.randint(0, 6, (N,), generator=g)]
+        kw["gate"] = torch.tensor([0.5, -0.5, 1.0, -1.0, 2.0, -2.0])[torch.randint(0, 6, (gate_batches, N) if gate_batches else (N,), generator=g)]
         if masked:
             kw["rowmask"] = torch.rand(M, generator=g) > 0.2
     if epi == "resid":
@@ -675,6 +697,12 @@ def bf16_ulp(ref):
     return torch.pow(2.0, (e - 8).clamp(min=-133).double())
 
 
+def fp32_ulp(ref):
+    """Spacing of fp32 at |ref| (fp64): 2^(floor(log2 |ref|) - 23), at least the subnormal spacing 2^-149."""
+    _, e = torch.frexp(ref.abs().double())
+    return torch.pow(2.0, (e - 24).clamp(min=-149).double())
+
+
 def fp16_ulp(ref):
     """Spacing of fp16 at |ref| (fp64): 2^(floor(log2 |ref|) - 10), at least the subnormal spacing 2^-24."""
     _, e = torch.frexp(ref.abs().double())
@@ -709,3 +737,195 @@ def check_rounded(name, out, ref, scale, precision):
     assert not bad.any(), (f"{name}: {int(bad.sum())} elements out of bound, first at {bad.nonzero()[0].tolist()}: "
                            f"out {float(out.reshape(-1)[bad.reshape(-1).nonzero()[0]])} ref {float(ref.reshape(-1)[bad.reshape(-1).nonzero()[0]])}")
     return worst, sums
+
+
+# ----------------------------------------------------------------------------- the reference tile kernel (f5_op_tile_gemm) and the CPU
+# restatements of its arithmetic and of the reference attention kernel's (tests/test_tile_kernel_bound_host.py)
+EPI_STORE_F32, EPI_ADD2 = 1, 3
+TILE_EPI = {"store": EPI_STORE_T, "store_f32": EPI_STORE_F32, "resid": EPI_RESID, "add2": EPI_ADD2, "rope": EPI_ROPE_T, "gate": EPI_GATE_T}
+
+
+def op_tile_gemm(precision, epi_name, A, W, b, act="none", gate=None, gate_bstride=0, rows_per_batch=0, rowmask=None, x=None, rope=None, rope_heads=0,
+                 seq=0, addend=None, a_row_mod=0, f16_stream=False, pad=0, guard=2, conv=False):
+    """include/f5hip.h: f5_op_tile_gemm -- gemm_tile_kernel in the mode `precision` with the epilogue `epi_name` (TILE_EPI).  Dense: A [M or
+    a_row_mod, K], W [N, K], M = the rows of x / addend, else of A.  conv: A = x [B, L, dim], W [dim, dim / 16, 31].  The output buffers are
+    [M + guard, N + pad] filled with NaN (the residual stream x in its [M, N] corner); the helper asserts that padding columns and guard rows
+    come back as NaN.  f16_stream: the stream / addend and out_f hold fp16 (add2_f16).  seq is a synonym of rows_per_batch (RoPE).
+    Returns (out_t [M, N] or None, out_f [M, N] or None)."""
+    lib = _lib.load()
+    epi = TILE_EPI[epi_name]
+    if conv:
+        Bc, L, N = A.shape
+        M, K, rows_per_batch = Bc * L, 0, L
+        A = A.reshape(M, N)
+    else:
+        N, K = W.shape
+        M = x.shape[0] if x is not None else addend.shape[0] if addend is not None else A.shape[0]
+        assert A.shape == ((a_row_mod or M), K)
+    rpb = rows_per_batch or seq or M
+    nb = -(-M // rpb)
+    ld = N + pad
+    nan = float("nan")
+    dev = lambda t: None if t is None else t.float().contiguous().cuda()
+
+    def buf(init):
+        t = torch.full((M + guard, ld), nan)
+        if init is not None:
+            t[:M, :N] = init
+        return t.cuda()
+
+    needs_t, needs_f = epi_name in ("store", "rope", "gate", "add2"), epi_name in ("store_f32", "resid", "add2")
+    ot, of = buf(None) if needs_t else None, buf(x) if needs_f else None
+    keepalive = [dev(A), dev(W), dev(b), dev(gate), dev(rope), None if addend is None else _pad_cols(addend.float(), ld, nan).cuda(),
+                 None if rowmask is None else rowmask.to(torch.uint8).contiguous().cuda()]
+    if gate is not None:
+        assert gate.numel() >= (nb - 1) * gate_bstride + N
+    if rowmask is not None:
+        assert rowmask.numel() == M
+    if rope is not None:
+        assert rope.numel() == rpb * 64
+    a = _lib.TileGemm()
+    for name, t in zip(("A", "W", "bias", "gate", "rope", "addend", "rowmask"), keepalive):
+        setattr(a, name, None if t is None else t.data_ptr())
+    a.out_t, a.out_f = (None if ot is None else ot.data_ptr()), (None if of is None else of.data_ptr())
+    a.precision, a.mode, a.epi, a.M, a.N, a.K, a.a_row_mod, a.act = precision, int(conv), epi, M, N, K, a_row_mod, _lib.ACT[act]
+    a.gate_bstride, a.rows_per_batch, a.rope_heads, a.ldadd, a.add2_f16 = gate_bstride, rpb, rope_heads, ld, int(f16_stream)
+    a.ldo, a.ldof, a.out_rows = ld, ld, M + guard
+    _lib.check(lib.f5_op_tile_gemm(C.byref(a), _lib.stream_ptr()), "f5_op_tile_gemm")
+    torch.cuda.synchronize()
+    res = []
+    for name, t in (("out_t", ot), ("out_f", of)):
+        if t is None:
+            res.append(None)
+            continue
+        t = t.cpu()
+        assert t[:, N:].isnan().all(), f"{name}: the tile kernel wrote a padding column (ld = N + {pad})"
+        assert t[M:].isnan().all(), f"{name}: the tile kernel wrote a guard row"
+        res.append(t[:M, :N].contiguous())
+    return tuple(res)
+
+
+def expect_tile_launch(what, precision, conv=False):
+    """the launch record names the 64 x 64 tile family with the element type and conv flags of the case"""
+    want = (FAM_TILE, 64, 64, SCHED_PLAIN, {P_BF16: 0, P_FP16: FLAG_F16, P_FP32: FLAG_F32}[precision] | (FLAG_CONV if conv else 0))
+    rec = last_gemm()
+    assert rec == want, f"{what}: launched (family, bm, bn, schedule, flags) = {rec}, intended {want}"
+
+
+def expand_gate(gate, M, rows_per_batch):
+    """a per-batch gate [nb, N] as one row per token row [M, N]"""
+    return gate[torch.arange(M) // rows_per_batch]
+
+
+def tile_stored(precision, epi_name, f16_stream, ref):
+    """what the tile kernel stores of the fp64 result `ref`: (out_t, out_f), rounded once to the mode's type / to the stream's (fp32 or fp16)"""
+    t = round_to(precision, ref) if epi_name in ("store", "rope", "gate", "add2") else None
+    f = round_to(P_FP16 if f16_stream else P_FP32, ref) if epi_name in ("store_f32", "resid", "add2") else None
+    return t, f
+
+
+TILE_DEFECTS = ("none", "drop_last_k_chunk", "tail_column_neighbour_bias", "gate_of_previous_batch", "rope_pair_swapped", "a_row_mod_ignored")
+
+
+def _act_f32(v, act):
+    if act == "gelu_tanh":
+        return F.gelu(v, approximate="tanh")
+    if act == "gelu_erf":
+        return F.gelu(v)
+    if act == "mish":
+        return F.mish(v)
+    return v
+
+
+def tile_emulate(precision, epi_name, A, W, b, act="none", gate=None, rows_per_batch=0, rowmask=None, x=None, rope=None, rope_heads=0, seq=0,
+                 addend=None, a_row_mod=0, f16_stream=False, defect="none"):
+    """CPU restatement of gemm_tile_kernel + gemm_epilogue4 in float32 (csrc/gemm.hip, csrc/gemm_epilogue.h): operands in the mode's type, one
+    fp32 accumulator per output that takes the products k = 0, 1, ... as fused multiply-adds (v_mfma_f32_16x16x4_f32 is an fp32 FMA chain;
+    the products of two 16-bit operands are exact in fp32), then bias, activation, gate / RoPE / addend in separate fp32 operations (the
+    build has FMA contraction off), one rounding to the stored type.  gate [N] or [batches, N] (batch = m // rows_per_batch).
+    -> (out_t, out_f) as tile_stored.  `defect` (TILE_DEFECTS) plants what the device test is there to catch:
+        drop_last_k_chunk            the last 32-wide K chunk is left out
+        tail_column_neighbour_bias   the last column of a partial 4-lane group (N % 4 != 0) takes the bias of the column before it
+        gate_of_previous_batch       every row of a 64-row tile takes the gate of the batch item the tile's first row lies in
+        rope_pair_swapped            the two (cos, sin) pairs of a 4-lane group change places
+        a_row_mod_ignored            row m reads A[m]: past the a_row_mod rows of A, zeros"""
+    assert defect in TILE_DEFECTS
+    N, K = W.shape
+    M = x.shape[0] if x is not None else addend.shape[0] if addend is not None else A.shape[0]
+    A, W = round_to(precision, A), round_to(precision, W)
+    if a_row_mod:
+        if defect == "a_row_mod_ignored":
+            A = torch.cat([A, torch.zeros(M - a_row_mod, K)])
+        else:
+            A = A[torch.arange(M) % a_row_mod]
+    acc = torch.zeros(M, N, dtype=torch.float32)
+    for k in range(K - 32 if defect == "drop_last_k_chunk" else K):
+        acc = (acc.double() + A[:, k, None].double() * W[None, :, k].double()).float()  # one rounding: an FMA
+    bias = b.float().clone()
+    if defect == "tail_column_neighbour_bias" and N % 4 != 0 and N > 1:
+        bias[N - 1] = bias[N - 2]
+    v = acc + bias
+    rpb = rows_per_batch or seq or M
+    g = None
+    if gate is not None:
+        rows = torch.arange(M)
+        batch = (rows // 64 * 64 if defect == "gate_of_previous_batch" else rows) // rpb
+        g = gate.float()[batch] if gate.dim() == 2 else gate.float()[None, :]
+    keep = torch.ones(M, dtype=torch.bool) if rowmask is None else rowmask.bool()
+    if epi_name in ("store", "store_f32"):
+        res = _act_f32(v, act)
+    elif epi_name == "gate":
+        res = _act_f32(v, act)
+        res = torch.where(keep[:, None], res if g is None else res * g, torch.zeros_like(res))
+    elif epi_name == "resid":
+        t = _act_f32(v, act)
+        t = t if g is None else t * g
+        cur = round_to(P_FP16 if f16_stream else P_FP32, x)
+        res = torch.where(keep[:, None], cur + t, cur)
+    elif epi_name == "add2":
+        res = v + round_to(P_FP16 if f16_stream else P_FP32, addend)
+    else:
+        inner = N // 3
+        cs = rope.float().reshape(rpb, 32, 2)[torch.arange(M) % rpb]
+        if defect == "rope_pair_swapped":
+            cs = cs.reshape(M, 16, 2, 2).flip(2).reshape(M, 32, 2)
+        cos, sin = cs[..., 0], cs[..., 1]
+        res = v.clone()
+        for part in range(2):
+            for h in range(rope_heads):
+                c0 = part * inner + h * 64
+                p = v[:, c0:c0 + 64].reshape(M, 32, 2)
+                res[:, c0:c0 + 64] = torch.stack([p[..., 0] * cos - p[..., 1] * sin, p[..., 1] * cos + p[..., 0] * sin], dim=-1).reshape(M, 64)
+    return tile_stored(precision, epi_name, f16_stream, res)
+
+
+def attn_emulate_ref(qkv, mask, precision, base2=False, leak_padding_key=False):
+    """CPU restatement of attn_ref_kernel (csrc/attention.hip) in float32: 64-key tiles, fp32 scores times the scale, the running maximum and
+    row sum rescaled by expf(m_old - m_new), numerators expf(s - m_new) kept in fp32, fp32 PV sums, o * (1 / l) rounded once to the stored type.
+    leak_padding_key: the defect the device test is there to catch -- the first padding row of the ragged last tile (zeros: the kernel
+    zero-fills it) counts as a key: score 0, value 0.  -> [B, N, H * 64] f32."""
+    B, N, _, H, _ = qkv.shape
+    valid = torch.ones(B, N, dtype=torch.bool) if mask is None else mask
+    x = round_to(precision, qkv)
+    q, k, v = [x[:, :, i].transpose(1, 2).float() for i in range(3)]  # [B, H, N, 64]
+    scale = torch.tensor(LN2 if base2 else 0.125, dtype=torch.float32)
+    m_i = torch.full((B, H, N), float("-inf"))
+    l_i, o = torch.zeros(B, H, N), torch.zeros(B, H, N, 64)
+    for k0 in range(0, N, 64):
+        k1 = min(N, k0 + 64)
+        s = (q @ k[:, :, k0:k1].transpose(-1, -2)) * scale
+        ok = valid[:, None, None, k0:k1].expand_as(s)
+        vt = v[:, :, k0:k1]
+        if leak_padding_key and k1 == N and N % 64 != 0:
+            s = torch.cat([s, torch.zeros(B, H, N, 1)], dim=-1)
+            ok = torch.cat([ok, torch.ones(B, H, N, 1, dtype=torch.bool)], dim=-1)
+            vt = torch.cat([vt, torch.zeros(B, H, 1, 64)], dim=2)
+        s = s.masked_fill(~ok, float("-inf"))
+        m_new = torch.maximum(m_i, s.amax(dim=-1))
+        alpha = torch.where(m_i == float("-inf"), torch.zeros_like(m_i), torch.exp(m_i - m_new))
+        p = torch.where(s == float("-inf"), torch.zeros_like(s), torch.exp(s - m_new[..., None]))
+        l_i = l_i * alpha + p.sum(dim=-1)
+        o = o * alpha[..., None] + p @ vt
+        m_i = m_new
+    inv = torch.where(l_i > 0, 1.0 / l_i, torch.zeros_like(l_i))
+    return round_to(precision, (o * inv[..., None]).transpose(1, 2).reshape(B, N, H * 64))

@@ -14,7 +14,8 @@ Every result-checking test asserts, for every utterance and branch,
   (b) accuracy against the fp64 softmax of that utterance, with the bounds the packed-form tests of test_gpu_ops.py use at this input scale
       (tuned bf16 kernels: rel-L2 < 6e-3, max-abs < 0.05, all finite, and next to them the ELEMENT-WISE fp64 bound of
       test_gpu_attention_bf16_elementwise.py: 1 bf16 ulp + 8 fp32 ulps of the sums of magnitudes + 2^-8 sum_k p_k |v_k|, per utterance and
-      branch; reference kernels: rel-L2 < 3e-6 in fp32, < 4e-3 in bf16); in the
+      branch; reference kernels: rel-L2 < 3e-6 in fp32, < 4e-3 in bf16, and element-wise 1 ulp of the stored type (fp32 / bf16) + 8 fp32
+      ulps of the sums of magnitudes, the bound of test_gpu_attention_ref_elementwise.py); in the
       fp16 mode (P_FP16: utterances rounded to fp16, a cache entry of their own) the ELEMENT-WISE fp64 bound of test_gpu_fp16_ops.py
       (1 fp16 ulp + 8 fp32 ulps of the sums of magnitudes + the numerator-rounding terms) per utterance and branch, no rel-L2 number;
   (c) no stray write: every element of `out` outside the utterances' rows and head columns, in every branch, still holds 776.0."""
@@ -104,6 +105,8 @@ def _run(prec, attn_kernel, variant, lens, nbr, H, first=0, ldq_extra=0, ldo_ext
                 G.check_elementwise(f"(b) utterance {u} n={n} branch {br}", g, ref[br], mag[br], P_BF16, extra[br])
             else:
                 assert rl < (3e-6 if prec == P_FP32 else 4e-3), f"(b) utterance {u} (n = {n}) branch {br}: rel-L2 {rl:.3e}"
+                # the reference kernel keeps its numerators in fp32: no numerator-rounding term in either type
+                G.check_elementwise(f"(b) reference kernel, utterance {u} n={n} branch {br}", g, ref[br], mag[br], prec)
     stray = (out != SENTINEL) & untouched
     assert not stray.any(), f"(c) {int(stray.sum())} elements outside the utterances were written, first at (branch, row, col) {stray.nonzero()[0].tolist()}"
     return out

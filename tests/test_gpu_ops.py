@@ -1,7 +1,12 @@
 """Per-op parity of the HIP kernels against the CPU oracle / plain fp32 torch math (through the C ABI).
 
 Tolerances (stated): fp32-input MFMA path rel-L2 <= 2e-6 (accumulation order only); bf16 path, with operands pre-rounded
-to bf16 so only the accumulation order and the output rounding differ, rel-L2 <= 2e-5 for f32 outputs."""
+to bf16 so only the accumulation order and the output rounding differ, rel-L2 <= 2e-5 for f32 outputs.
+
+The reference tile kernel (gemm_tile_kernel) and the reference attention kernel (attn_ref_kernel) are additionally held to the element-wise
+fp64 bound here; their per-element tests proper -- every epilogue, precision, leading dimension and tile edge of the tile kernel, bit
+equality on exact inputs -- are in tests/test_gpu_tile_kernel.py, those of attn_ref_kernel in tests/test_gpu_attention_ref_elementwise.py,
+and tests/test_tile_kernel_bound_host.py shows on the CPU that the bound holds for the stated arithmetic and fails for planted defects."""
 import math
 
 import pytest
@@ -35,6 +40,9 @@ def test_linear_tile_kernel(prec, shape, act):
     ref = {"none": lambda v: v, "gelu_tanh": lambda v: F.gelu(v, approximate="tanh"), "gelu_erf": F.gelu, "mish": F.mish}[act](ref).float()
     out = G.op_linear(prec, 0, A, W, b, act)
     assert rel_l2(out, ref) < (2e-6 if prec == P_FP32 else 2e-5)
+    # per element: 1 fp32 ulp(ref) + 8 fp32 ulps of sum |a w| (x 1.13 through GELU, x 1.1 through Mish); the output of this entry point is fp32
+    ref64, scale = G.linear_ref(A, W, b, act)
+    G.check_elementwise(f"tile kernel {'fp32' if prec == P_FP32 else 'bf16'} {shape} {act}", out, ref64, scale, G.P_FP32)
 
 
 def test_layernorm_modulate():
@@ -163,6 +171,10 @@ def test_attention_reference_kernel(prec, B, N, H, masked):
     out = G.op_attention(prec, 0, qkv, mask)
     tol = 3e-6 if prec == P_FP32 else 4e-3  # bf16: only the final output rounding (8-bit mantissa)
     assert rel_l2(out, ref) < tol
+    # per element: 1 ulp(ref) of the stored type + 8 fp32 ulps of the sums of magnitudes (the kernel keeps its numerators in fp32)
+    ref64, mag, _ = G.attn_ref_terms(qkv, mask, prec)
+    valid = slice(None) if mask is None else mask
+    G.check_elementwise(f"attn_ref_kernel {'fp32' if prec == P_FP32 else 'bf16'} {(B, N, H, masked)}", out[valid], ref64[valid], mag[valid], prec)
 
 
 @pytest.mark.parametrize("prec", [P_FP32, P_BF16])
