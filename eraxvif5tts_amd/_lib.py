@@ -81,6 +81,7 @@ _PROTOS = {
     "f5_text_embed": (_I, [_P, _I, _I, _P, _I, _I, _P, _P]),
     "f5_dit_forward": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     "f5_sample_ragged": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, C.c_float, _I, _P, _P]),
+    "f5_sample_ragged_ex": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, C.c_float, _P, _I, _P, _P]),
     "f5_mmdit_forward": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     "f5_cfm_noise": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "f5_cfm_loss_workspace": (C.c_int64, [_I, _I, _I]),

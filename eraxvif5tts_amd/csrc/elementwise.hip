@@ -989,12 +989,10 @@ int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, 
 }
 
 // ----------------------------------------------------------------------------- CFG combine + fixed-grid ODE step
-__global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ x_base, const float* __restrict__ vc, const float* __restrict__ vu, int ldv,
-                                                       int rows, int mel, float cfg, const float* __restrict__ coef, float* __restrict__ x_out,
-                                                       float* __restrict__ x_out2) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)rows * mel) return;
-    const int r = (int)(i / mel), c = (int)(i % mel);
+// one element of the step; both kernels below are this body, so a row's arithmetic does not depend on where its guidance strength came from
+__device__ __forceinline__ void cfg_step_elem(const float* __restrict__ x_base, const float* __restrict__ vc, const float* __restrict__ vu, int ldv, int mel,
+                                              float cfg, const float* __restrict__ coef, float* __restrict__ x_out, float* __restrict__ x_out2, size_t i,
+                                              int r, int c) {
     const float pc = vc[(size_t)r * ldv + c];
     float f = pc;
     if (vu) f = pc + (pc - vu[(size_t)r * ldv + c]) * cfg;  // pred + (pred - null_pred) * cfg_strength (cfm.py:173)
@@ -1002,11 +1000,32 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
     x_out[i] = y;
     if (x_out2) x_out2[i] = y;
 }
+__global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ x_base, const float* __restrict__ vc, const float* __restrict__ vu, int ldv,
+                                                       int rows, int mel, float cfg, const float* __restrict__ coef, float* __restrict__ x_out,
+                                                       float* __restrict__ x_out2) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)rows * mel) return;
+    const int r = (int)(i / mel), c = (int)(i % mel);
+    cfg_step_elem(x_base, vc, vu, ldv, mel, cfg, coef, x_out, x_out2, i, r, c);
+}
+// the guidance strength of row r is cfg_rows[r] (f5_sample_ragged_ex: one value per utterance, spread over its rows)
+__global__ __launch_bounds__(256) void cfg_step_rows_kernel(const float* __restrict__ x_base, const float* __restrict__ vc, const float* __restrict__ vu,
+                                                            int ldv, int rows, int mel, const float* __restrict__ cfg_rows,
+                                                            const float* __restrict__ coef, float* __restrict__ x_out, float* __restrict__ x_out2) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)rows * mel) return;
+    const int r = (int)(i / mel), c = (int)(i % mel);
+    cfg_step_elem(x_base, vc, vu, ldv, mel, cfg_rows[r], coef, x_out, x_out2, i, r, c);
+}
 int launch_cfg_step(const float* x_base, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* coef,
-                    float* x_out, float* x_out2, hipStream_t stream) {
+                    float* x_out, float* x_out2, hipStream_t stream, const float* cfg_rows) {
     if (rows <= 0) return 0;
     const size_t total = (size_t)rows * mel;
-    hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x_base, vc, vu, ldv, rows, mel, cfg, coef, x_out, x_out2);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (cfg_rows && vu)
+        hipLaunchKernelGGL(cfg_step_rows_kernel, grid, dim3(256), 0, stream, x_base, vc, vu, ldv, rows, mel, cfg_rows, coef, x_out, x_out2);
+    else
+        hipLaunchKernelGGL(cfg_step_kernel, grid, dim3(256), 0, stream, x_base, vc, vu, ldv, rows, mel, cfg, coef, x_out, x_out2);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -1028,9 +1047,12 @@ template <int V> __device__ __forceinline__ void vstore(float* p, const float (&
     __builtin_memcpy(&x, v, sizeof(x));
     *reinterpret_cast<typename VecF<V>::T*>(p) = x;
 }
-template <int V>
+// CfgT: float (one guidance strength, a kernel argument) or const float* (one per row: f5_sample_ragged_ex); the arithmetic is the same
+__device__ __forceinline__ float rk_cfg_of(float cfg, int) { return cfg; }
+__device__ __forceinline__ float rk_cfg_of(const float* cfg_rows, int r) { return cfg_rows[r]; }
+template <int V, typename CfgT = float>
 __global__ __launch_bounds__(256) void rk_stage_kernel(const float* __restrict__ y0, const float* __restrict__ vc, const float* __restrict__ vu, int ldv,
-                                                       int rows, int mel, float cfg, const float* __restrict__ dtp, RkStage sg,
+                                                       int rows, int mel, CfgT cfg, const float* __restrict__ dtp, RkStage sg,
                                                        const float* __restrict__ slots, size_t slot_stride, float* __restrict__ kst,
                                                        float* __restrict__ out) {
     const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1043,8 +1065,9 @@ __global__ __launch_bounds__(256) void rk_stage_kernel(const float* __restrict__
     if (vu) {
         float u[V];
         vload<V>(vu + (size_t)r * ldv + c, u);
+        const float cfg_r = rk_cfg_of(cfg, r);
 #pragma unroll
-        for (int e = 0; e < V; ++e) f[e] = __builtin_fmaf(f[e] - u[e], cfg, f[e]);  // pred + (pred - null_pred) * cfg_strength (cfm.py:173)
+        for (int e = 0; e < V; ++e) f[e] = __builtin_fmaf(f[e] - u[e], cfg_r, f[e]);  // pred + (pred - null_pred) * cfg_strength (cfm.py:173)
     }
     if (kst) vstore<V>(kst + i, f);
 #pragma unroll
@@ -1064,14 +1087,19 @@ __global__ __launch_bounds__(256) void rk_stage_kernel(const float* __restrict__
     vstore<V>(out + i, y);
 }
 int launch_rk_stage(const float* y0, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* dt, const RkStage& sg,
-                    const float* slots, size_t slot_stride, float* kst, float* out, hipStream_t stream) {
+                    const float* slots, size_t slot_stride, float* kst, float* out, hipStream_t stream, const float* cfg_rows) {
     if (rows <= 0) return 0;
     if (sg.nk < 0 || sg.nk > 3 || (sg.nk > 0 && !slots)) return f5_fail(F5_EINVAL, "rk stage: bad slot count %d", sg.nk);
     auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     const bool vec = mel % 4 == 0 && ldv % 4 == 0 && slot_stride % 4 == 0 && a16(y0) && a16(vc) && a16(vu) && a16(slots) && a16(kst) && a16(out);
     const size_t total = (size_t)rows * (vec ? mel / 4 : mel);
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (vec)
+    if (cfg_rows && vu) {
+        if (vec)
+            hipLaunchKernelGGL((rk_stage_kernel<4, const float*>), grid, block, 0, stream, y0, vc, vu, ldv, rows, mel, cfg_rows, dt, sg, slots, slot_stride, kst, out);
+        else
+            hipLaunchKernelGGL((rk_stage_kernel<1, const float*>), grid, block, 0, stream, y0, vc, vu, ldv, rows, mel, cfg_rows, dt, sg, slots, slot_stride, kst, out);
+    } else if (vec)
         hipLaunchKernelGGL(rk_stage_kernel<4>, grid, block, 0, stream, y0, vc, vu, ldv, rows, mel, cfg, dt, sg, slots, slot_stride, kst, out);
     else
         hipLaunchKernelGGL(rk_stage_kernel<1>, grid, block, 0, stream, y0, vc, vu, ldv, rows, mel, cfg, dt, sg, slots, slot_stride, kst, out);

@@ -132,8 +132,9 @@ int launch_convert_back(int precision_in, const void* src, int lds, int rows, in
 int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, const uint8_t* cmask, const float* text_embed, int B, int N, int mel,
                      int melp, int td, int zero_cond, void* dst, int ldd, hipStream_t stream);
 // x_out = x_base + coef[0] * (vc + (vc - vu) * cfg)   (cfm.py:173 + torchdiffeq step); vu == null -> x_base + coef * vc
+// cfg_rows (dev f32 [rows], or null): row r takes cfg_rows[r] in place of cfg, with the same operations (f5_sample_ragged_ex)
 int launch_cfg_step(const float* x_base, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* coef,
-                    float* x_out, float* x_out2 /*or null*/, hipStream_t stream);
+                    float* x_out, float* x_out2 /*or null*/, hipStream_t stream, const float* cfg_rows = nullptr);
 // One stage of an explicit Runge-Kutta step (rk4 / heun2 / heun3, sampler.hip: the method table).  With f = vc + (vc - vu) * cfg (vu == null
 // -> vc) and the slopes k_j = slots + j * slot_stride (j < nk) of the step's earlier stages:
 //   kst (or null) = f;   out = y0 + (dt[0] * (wk[0] k_0 + .. + wk[nk-1] k_{nk-1} + wf f)) * post
@@ -144,7 +145,8 @@ struct RkStage {
     int nk;
 };
 int launch_rk_stage(const float* y0, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* dt, const RkStage& sg,
-                    const float* slots, size_t slot_stride, float* kst /*or null*/, float* out, hipStream_t stream);
+                    const float* slots, size_t slot_stride, float* kst /*or null*/, float* out, hipStream_t stream,
+                    const float* cfg_rows = nullptr /* as for launch_cfg_step */);
 // out = frame < lens[b] ? cond : x   (cfm.py:200-202); with cmask (u8 [B, N], or null): out = cmask[b][frame] ? cond : x
 int launch_final_where(const float* cond, const float* x, const int32_t* lens, const uint8_t* cmask, int B, int N, int mel, float* out, hipStream_t stream);
 // mask[b][n] = n < durations[b]

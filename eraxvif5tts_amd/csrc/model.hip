@@ -526,6 +526,7 @@ extern "C" int f5_plan_create(f5_model_t m, int max_batch, int max_seq, int max_
         if (c.backbone == F5_BACKBONE_DIT) {
             if ((rc = A.alloc_t(&p->rope_exp, (rows / 2 + 1) * 64))) break;
             if ((rc = A.alloc_t(&p->gapflag, rows))) break;
+            if ((rc = A.alloc_t(&p->cfg_rows, rows / 2 + 1))) break;
         }
         if (c.long_skip) {  // the input embedding kept for the end of the evaluation, and cat(x, residual) in the activation dtype
             p->skips.assign(1, nullptr);

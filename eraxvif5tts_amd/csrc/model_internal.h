@@ -96,6 +96,7 @@ struct GraphEntry {
     uint64_t fold_id = 0;  // the FoldTable whose addresses the capture baked (0 = none)
     int cmask_on = 0;      // captured with the staged per-frame condition mask (f5_sample_masked)
     std::vector<int> rn;   // ragged sample(): the utterances' frame counts (empty: a uniform batch)
+    int cfg_rows = 0;      // captured with the per-row guidance strengths of p->cfg_rows (the VALUES are read at replay, not baked)
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
 };
@@ -104,6 +105,7 @@ struct SampleArgs {
     int B, N, nt, steps, method, cfg_on, mask_on;
     float cfg;
     int cmask_on = 0;  // the condition mask is the staged cmask_in (f5_sample_masked), not the lens prefix
+    int cfg_rows = 0;  // f5_sample_ragged_ex with cfg_host: row r is combined with p->cfg_rows[r], not with cfg
 };
 // f5_sample_ragged: utterances of different frame counts concatenated along the token axis.  One CFG half holds utterance i at rows
 // [off[i], off[i] + n[i]) followed by at least RAGGED_GAP rows that are kept ZERO wherever the position conv reads them, so the conv's own
@@ -170,6 +172,7 @@ struct f5_plan_s {
     // ragged sampler: RoPE table expanded per row of a half (position restarts at every utterance), gap-row flags over both halves
     float* rope_exp = nullptr;
     uint8_t* gapflag = nullptr;
+    float* cfg_rows = nullptr;         // f5_sample_ragged_ex: guidance strength per row of a half (staged per call, outside any capture)
     const Ragged* rg = nullptr;        // set while a ragged sample() runs its evaluations
     // MMDiT (mmdit.py:146-190): the text is a second residual stream of nt tokens per utterance; attention runs over [frames | text]
     float* cres = nullptr;             // text stream [2B * nt, D] f32

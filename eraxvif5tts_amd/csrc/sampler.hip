@@ -52,11 +52,12 @@ static int rk_step(f5_plan_s* p, const SampleArgs& a, int s, const float* xs, fl
     const size_t state = (size_t)rows * mel;
     float* slots = p->traj + (size_t)(a.steps + 1) * state;  // (see the slot invariant above)
     const float* vu = a.cfg_on ? p->vout + (size_t)rows * MELP : nullptr;
+    const float* cfgr = a.cfg_rows ? p->cfg_rows : nullptr;
     for (int j = 0; j < om.evals; ++j) {
         const int ev = om.evals * s + j;
         F5_TRY(net_eval(p, j == 0 ? xs : p->xmid, rows, nb, N, ev, 0, mask, st));
         F5_TRY(launch_rk_stage(xs, p->vout, vu, MELP, rows, mel, a.cfg, p->coefs + ev, om.stage[j], slots, state,
-                               om.slot[j] >= 0 ? slots + (size_t)om.slot[j] * state : nullptr, j == om.evals - 1 ? xn : p->xmid, st));
+                               om.slot[j] >= 0 ? slots + (size_t)om.slot[j] * state : nullptr, j == om.evals - 1 ? xn : p->xmid, st, cfgr));
     }
     return 0;
 }
@@ -150,12 +151,13 @@ static int run_sample_loop(f5_plan_s* p, const SampleArgs& a, int use_graph, hip
         }
         for (auto& g : p->graphs)
             if (g.B == a.B && g.N == a.N && g.nt == a.nt && g.steps == a.steps && g.method == a.method && g.cfg_on == a.cfg_on &&
-                g.mask_on == a.mask_on && g.cmask_on == a.cmask_on && g.cfg == a.cfg && g.fold_id == (p->fold && g_ln_fold ? p->fold->id : 0) &&
+                g.mask_on == a.mask_on && g.cmask_on == a.cmask_on && g.cfg_rows == a.cfg_rows && g.cfg == a.cfg && g.fold_id == (p->fold && g_ln_fold ? p->fold->id : 0) &&
                 g.rn == (p->rg ? p->rg->n : std::vector<int>()))
                 ge = &g;
         if (!ge) {
             GraphEntry g{a.B, a.N, a.nt, a.steps, a.method, a.cfg_on, a.mask_on, a.cfg, g_tuning_epoch, (p->fold && g_ln_fold) ? p->fold->id : 0};
             g.cmask_on = a.cmask_on;
+            g.cfg_rows = a.cfg_rows;
             if (p->rg) g.rn = p->rg->n;
             if (!p->cap_stream) F5_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
             F5_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed));
@@ -419,21 +421,24 @@ static int sample_body_ragged(f5_plan_s* p, const SampleArgs& a, hipStream_t st)
             F5_HIP(hipMemcpy2DAsync(p->text_in + (size_t)B * a.nt, (size_t)nt_eff * 4, p->text_in + (size_t)u * a.nt, (size_t)a.nt * 4, (size_t)nt_eff * 4, 1,
                                     hipMemcpyDeviceToDevice, st));
             F5_TRY(compute_text_embed(p, p->text_in + (size_t)B * a.nt, nt_eff, 1, nu, br, te, st));
-            F5_TRY(compute_base(p, p->cond_in + (size_t)rg.off[u] * mel, p->lens_in + u, te, 1, nu, br, (size_t)br * T + rg.off[u], st));
+            // (the staged per-frame condition mask, utterance u's slice at its row offset: a replay sees the current call's mask)
+            F5_TRY(compute_base(p, p->cond_in + (size_t)rg.off[u] * mel, p->lens_in + u, te, 1, nu, br, (size_t)br * T + rg.off[u], st,
+                                a.cmask_on ? p->cmask_in + rg.off[u] : nullptr));
         }
     const int nb = a.cfg_on ? 2 : 1;
+    const float* cfgr = a.cfg_rows ? p->cfg_rows : nullptr;  // (read at run time: a replay honours the vector staged by the current call)
     for (int s = 0; s < a.steps; ++s) {
         float* xs = p->traj + (size_t)s * state;
         float* xn = p->traj + (size_t)(s + 1) * state;
         const float* vu = a.cfg_on ? p->vout + (size_t)T * MELP : nullptr;
         if (a.method == F5_ODE_EULER) {
             F5_TRY(net_eval(p, xs, T, nb, T, s, 0, nullptr, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + s, xn, nullptr, st));
+            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + s, xn, nullptr, st, cfgr));
         } else if (a.method == F5_ODE_MIDPOINT) {
             F5_TRY(net_eval(p, xs, T, nb, T, 2 * s, 0, nullptr, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + 2 * s, p->xmid, nullptr, st));
+            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + 2 * s, p->xmid, nullptr, st, cfgr));
             F5_TRY(net_eval(p, p->xmid, T, nb, T, 2 * s + 1, 0, nullptr, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + 2 * s + 1, xn, nullptr, st));
+            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + 2 * s + 1, xn, nullptr, st, cfgr));
         } else {
             F5_TRY(rk_step(p, a, s, xs, xn, T, nb, T, nullptr, st));
         }
@@ -441,9 +446,11 @@ static int sample_body_ragged(f5_plan_s* p, const SampleArgs& a, hipStream_t st)
     return plan_attn_dropout_advance(p, sample_call_words(p, a), st);
 }
 
-extern "C" int f5_sample_ragged(f5_plan_t p, int B, const int32_t* frames_host, const float* cond, const int32_t* text, int nt, const int32_t* lens,
-                                const float* y0, const float* tgrid_host, int steps, float cfg_strength, int ode_method, float* out,
-                                f5_stream_t stream) {
+// f5_sample_ragged and f5_sample_ragged_ex: cond_mask (dev u8 [sum(frames)]) or null = the lens prefix of every utterance; cfg_host (host
+// f32 [B]) or null = cfg_strength for all of them
+static int sample_ragged_impl(f5_plan_t p, int B, const int32_t* frames_host, const float* cond, const int32_t* text, int nt, const int32_t* lens,
+                              const uint8_t* cond_mask, const float* y0, const float* tgrid_host, int steps, float cfg_strength,
+                              const float* cfg_host, int ode_method, float* out, f5_stream_t stream) {
     if (!p) return f5_fail(F5_EINVAL, "null plan");
     F5_TRY(f5_check_device());
     if (!frames_host || !cond || !text || !lens || !y0 || !tgrid_host || !out) return f5_fail(F5_EINVAL, "null argument");
@@ -455,6 +462,18 @@ extern "C" int f5_sample_ragged(f5_plan_t p, int B, const int32_t* frames_host, 
     const int nev = om->evals * steps;
     if (nev > p->maxE) return f5_fail(F5_EINVAL, "%d evaluations exceed the plan's max_evals=%d", nev, p->maxE);
     if (!p->taps.empty() || p->timing) return f5_fail(F5_ESTATE, "f5_sample_ragged: stage taps / in-situ timing are not available here");
+    // One doubled batch cannot hold utterances of both branches of cfm.py:167 (below 1e-5 the reference makes ONE pass, and its bits are
+    // those of an undoubled batch): refused before anything is staged or launched; the caller keeps such requests in different calls.
+    bool cfg_on = cfg_strength >= 1e-5f;
+    if (cfg_host) {
+        cfg_on = cfg_host[0] >= 1e-5f;
+        for (int u = 0; u < B; ++u) {
+            if (!(cfg_host[u] == cfg_host[u])) return f5_fail(F5_EINVAL, "utterance %d: guidance strength is NaN", u);
+            if ((cfg_host[u] >= 1e-5f) != cfg_on)
+                return f5_fail(F5_EINVAL, "guidance strengths below and at or above 1e-5 in one call (utterances 0 and %d): sample them in separate calls", u);
+        }
+    }
+    const bool cfg_vec = cfg_host && cfg_on;  // (below 1e-5 no combine runs: the vector has nothing to say)
     Ragged rg;
     size_t total = 0;
     for (int u = 0; u < B; ++u) {
@@ -492,23 +511,48 @@ extern "C" int f5_sample_ragged(f5_plan_t p, int B, const int32_t* frames_host, 
     }
     F5_HIP(hipMemcpyAsync(p->text_in, text, (size_t)B * nt * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     F5_HIP(hipMemcpyAsync(p->lens_in, lens, B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (cond_mask) {  // the per-frame condition masks at the utterances' row offsets (compute_base and the final where read their slices)
+        F5_HIP(hipMemsetAsync(p->cmask_in, 0, (size_t)T, st));
+        src = 0;
+        for (int u = 0; u < B; ++u) {
+            F5_HIP(hipMemcpyAsync(p->cmask_in + rg.off[u], cond_mask + src, (size_t)rg.n[u], hipMemcpyDeviceToDevice, st));
+            src += (size_t)rg.n[u];
+        }
+    }
+    if (cfg_vec) {  // one value per row of a half, staged here -- outside the captured region -- so a replayed graph reads this call's values
+        F5_TRY(launch_fill_f32(p->cfg_rows, (size_t)T, 0.0f, st));
+        for (int u = 0; u < B; ++u) F5_TRY(launch_fill_f32(p->cfg_rows + rg.off[u], (size_t)rg.n[u], cfg_host[u], st));
+    }
 
-    SampleArgs a{B, T, nt, steps, ode_method, cfg_strength >= 1e-5f ? 1 : 0, 0, cfg_strength};  // cfm.py:167
+    SampleArgs a{B, T, nt, steps, ode_method, cfg_on ? 1 : 0, 0, cfg_vec ? 0.0f : cfg_strength, cond_mask ? 1 : 0, cfg_vec ? 1 : 0};  // cfm.py:167
     p->pending = PendingSample{};
     p->rg = &rg;
     const int use_graph = p->ragged_graph;  // a bucket shape that recurs (batch inference over fixed buckets) replays its capture
     int rc = run_sample_loop(p, a, use_graph, st);
-    if (rc == 0 && plan_res_f16(p) && p->sat_check) rc = guard_check_and_fallback(p, a, use_graph, st);  // (always checked inside the call)
+    // (always checked inside the call; the rerun reads the same staged mask and guidance rows)
+    if (rc == 0 && plan_res_f16(p) && p->sat_check) rc = guard_check_and_fallback(p, a, use_graph, st);
     p->rg = nullptr;
     F5_TRY(rc);
     const float* xf = p->traj + (size_t)steps * T * mel;
     src = 0;
     for (int u = 0; u < B; ++u) {
         const size_t off = rg.off[u];
-        F5_TRY(launch_final_where(p->cond_in + off * mel, xf + off * mel, p->lens_in + u, nullptr, 1, rg.n[u], mel, out + src * mel, st));
+        F5_TRY(launch_final_where(p->cond_in + off * mel, xf + off * mel, p->lens_in + u, cond_mask ? p->cmask_in + off : nullptr, 1, rg.n[u], mel,
+                                  out + src * mel, st));
         src += (size_t)rg.n[u];
     }
     (void)total;
     return 0;
 }
 
+extern "C" int f5_sample_ragged(f5_plan_t p, int B, const int32_t* frames_host, const float* cond, const int32_t* text, int nt, const int32_t* lens,
+                                const float* y0, const float* tgrid_host, int steps, float cfg_strength, int ode_method, float* out,
+                                f5_stream_t stream) {
+    return sample_ragged_impl(p, B, frames_host, cond, text, nt, lens, nullptr, y0, tgrid_host, steps, cfg_strength, nullptr, ode_method, out, stream);
+}
+
+extern "C" int f5_sample_ragged_ex(f5_plan_t p, int B, const int32_t* frames_host, const float* cond, const int32_t* text, int nt, const int32_t* lens,
+                                   const uint8_t* cond_mask, const float* y0, const float* tgrid_host, int steps, float cfg_strength,
+                                   const float* cfg_host, int ode_method, float* out, f5_stream_t stream) {
+    return sample_ragged_impl(p, B, frames_host, cond, text, nt, lens, cond_mask, y0, tgrid_host, steps, cfg_strength, cfg_host, ode_method, out, stream);
+}

@@ -21,6 +21,7 @@ when the loaded model carries one; otherwise the reference's own fallback branch
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import os
 import re
 import types
@@ -34,10 +35,29 @@ from ..model import CFM
 from ..model import backbones as _backbones
 from ..model.utils import convert_char_to_pinyin, get_tokenizer, list_str_to_idx
 from . import audio as _audio
-from .utils_infer import (DEFAULT_VOCAB, WaveStream, chunk_groups, chunk_text, cross_fade_concat, decode_utterances, device_tail_kind, load_checkpoint,
-                          load_vocoder, mel_rows_of, split_voice_script, waves_of_mels)
+from .utils_infer import (DEFAULT_VOCAB, WaveStream, chunk_groups, chunk_text, cross_fade_concat, decode_utterances, device_tail_kind, finish_waves,
+                          load_checkpoint, load_vocoder, mel_rows_of, plan_request_groups, plan_wave_tail_segments, split_voice_script,
+                          waves_of_mels)
 
 _CONFIG_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs")
+
+
+@dataclasses.dataclass
+class TTSJob:
+    """One request of `F5TTSWrapper.generate_batch`: the text, the stored voice that speaks it, and `generate()`'s settings for this request
+    alone (None: the wrapper's attribute of the same name -- for ``speed`` the voice's own speed first, see `add_voice`).  ``seed``: the
+    request's noise comes from a generator of its own seeded with it, so its audio does not depend on the requests around it."""
+    text: str
+    voice: str = "main"
+    nfe_step: Optional[int] = None
+    cfg_strength: Optional[float] = None
+    sway_sampling_coef: Optional[float] = None
+    speed: Optional[float] = None
+    fix_duration: Optional[float] = None
+    cross_fade_duration: Optional[float] = None
+    use_duration_predictor: Optional[bool] = None
+    remove_silence: bool = False
+    seed: Optional[int] = None
 
 
 class F5TTSWrapper:
@@ -172,14 +192,21 @@ class F5TTSWrapper:
         return audio, ref_text
 
     # ------------------------------------------------------------------ further voices (generate_multi)
-    def add_voice(self, name: str, ref_audio_path: str, ref_text: str = "", clip_short: bool = True):
+    def add_voice(self, name: str, ref_audio_path: str, ref_text: str = "", clip_short: bool = True, speed: Optional[float] = None):
         """One more reference voice for `generate_multi`, under ``name`` (a ``\\w+`` word other than "main", which is the voice
         `preprocess_reference` stored): exactly the steps of `preprocess_reference`, with the prompt's mel and its rms computed once.  The main
-        fields are not touched.  Returns ``(audio, ref_text)`` as `preprocess_reference` does."""
+        fields are not touched.  Returns ``(audio, ref_text)`` as `preprocess_reference` does.
+        ``speed`` (the reference's per-voice ``speed`` of infer_cli's voice table): kept in the voice's fields and used for this voice's pieces
+        where a call (`generate_multi`, `generate_multi_stream`) or a request (`generate_batch`) gives no ``speed`` of its own; None: the
+        wrapper's ``speed``, as before."""
+        if speed is not None and not float(speed) > 0:
+            raise ValueError(f"voice {name!r}: speed {speed!r} is not a positive number")
         if not isinstance(name, str) or not re.fullmatch(r"\w+", name) or name == "main":
             raise ValueError(f"voice name {name!r}: a name is one \\w+ word (what a [name] tag can hold) and \"main\" is the voice of preprocess_reference()")
         audio, ref_text = self._preprocess_voice(ref_audio_path, ref_text, clip_short)
         self._voices[name] = self._voice_fields(audio, ref_text)
+        if speed is not None:
+            self._voices[name]["speed"] = float(speed)
         return audio, ref_text
 
     def remove_voice(self, name: str):
@@ -300,6 +327,147 @@ class F5TTSWrapper:
         plan = self._plan_jobs(text, True, nfe_step, cfg_strength, sway_sampling_coef, speed, fix_duration, cross_fade_duration, use_duration_predictor)
         yield from self._synthesize_stream(*plan, return_pcm16)
 
+    def generate_batch(self, requests, return_pcm16: bool = False, return_spectrogram: bool = False):
+        """Several INDEPENDENT requests -- what a server has in flight -- through one set of ragged batches: ``requests`` is a list of `TTSJob`
+        objects (or dicts with its fields), each with its own voice (`preprocess_reference`: "main", `add_voice`), step count, guidance
+        strength, sway coefficient, speed, duration, cross-fade and ``remove_silence``.  Returns a list in request order; entry i is what
+        ``generate(text_i, <request i's settings>, return_numpy=True, return_pcm16=, return_spectrogram=)`` returns with voice i's fields
+        installed: ``(wave, sample_rate)`` or ``(wave, sample_rate, spectrogram)``.
+
+        Every request is planned as generate() plans it; all chunks of all requests form one flat list.  The initial noise of every chunk is
+        drawn BEFORE any sampling, in flat order and with the shapes sample() draws: requests without ``seed`` from torch's global generator
+        (the CPU generator under ``noise_device = "cpu"``), a request with ``seed`` from a ``torch.Generator`` of its own seeded with it.  So
+          * after one ``torch.manual_seed(s)`` the results are byte for byte (dtype included) those of the generate() calls made one after the
+            other after the same seed -- float, ``return_pcm16`` and the spectrogram;
+          * a seeded request's result does not depend on its place in the list or on the other requests, and the unseeded requests around
+            it equal the serial route over the unseeded requests alone.
+        The sampler calls are formed by `utils_infer.plan_request_groups`: jobs of one ``(nfe_step, sway_sampling_coef, cfg_strength >= 1e-5)``
+        share a time grid and run as ragged batches of up to ``ragged_chunks`` utterances / 16384 frames with one prompt and one guidance
+        strength per utterance (libf5hip ``f5_sample_ragged_ex``) where generate()'s ragged rule holds for the group (DiT, at least 2 jobs, all
+        of 256 .. 4096 frames); the jobs of every other group take sample() on the chunk streams.  Unguided requests (``cfg_strength`` below
+        1e-5, the reference's single pass) share no call with other requests: their batch is not doubled, so below 512 frames the kernels a
+        job meets -- and with them its bits in the 16-bit modes -- depend on the rows around it, and only generate()'s own groups keep them.  One ragged vocoder call decodes all jobs,
+        one segmented wave tail per distinct cross-fade length finishes them (a segment per request), each request gets its slice, and
+        ``remove_silence`` runs per request on its slice, on the device.  A foreign vocoder object, or a request whose joints chain (the tail
+        answers F5_ENOTSUP), is finished per request by the host functions under the same contracts.  The ODE method is the wrapper's.
+        With attention dropout on, a ragged call does not promise the bits of its batch-1 calls: the contracts then hold in distribution
+        only, as for `generate_multi`.
+        Raises ``ValueError`` naming the request's index -- before any sampling -- for an unknown voice, an empty text, ``nfe_step < 1`` or an
+        unknown field, and for an empty list."""
+        voices = self.voices
+        if "main" not in voices and not self._voices:
+            raise ValueError("Reference audio not preprocessed. Call preprocess_reference() first.")
+        reqs = list(requests) if requests is not None else []
+        if not reqs:
+            raise ValueError("generate_batch: no requests")
+        fields = [f.name for f in dataclasses.fields(TTSJob)]
+        plans = []  # per request: (settings, voice, jobs)
+        for r, req in enumerate(reqs):
+            if isinstance(req, dict):
+                unknown = sorted(set(req) - set(fields))
+                if unknown or "text" not in req:
+                    raise ValueError(f"request {r}: " + (f"unknown fields {unknown}" if unknown else "no text"))
+                req = TTSJob(**req)
+            elif not isinstance(req, TTSJob):
+                raise ValueError(f"request {r}: a TTSJob or a dict with its fields is expected, not {type(req).__name__}")
+            reqs[r] = req
+            if req.voice not in voices:
+                raise ValueError(f"request {r}: unknown voice {req.voice!r} (stored: {sorted(voices)})")
+            if not isinstance(req.text, str) or not req.text.strip():
+                raise ValueError(f"request {r}: empty text")
+            voice = voices[req.voice]
+            given = {k: getattr(req, k) for k in ("nfe_step", "cfg_strength", "sway_sampling_coef", "speed", "fix_duration", "cross_fade_duration",
+                                                  "use_duration_predictor")}
+            if given["speed"] is None:
+                given["speed"] = voice.get("speed")  # add_voice(speed=)
+            settings = types.SimpleNamespace(**{k: v if v is not None else getattr(self, k) for k, v in given.items()})
+            if int(settings.nfe_step) < 1:
+                raise ValueError(f"request {r}: nfe_step {settings.nfe_step} < 1")
+            plans.append((settings, voice))
+        jobs, job_voices, job_req, job_kw, seg_sizes = [], [], [], [], []
+        for r, (settings, voice) in enumerate(plans):
+            piece_jobs = self._plan_piece(voice, reqs[r].text, settings, settings.speed)
+            if not piece_jobs:
+                raise ValueError(f"request {r}: the text gives no chunk to speak")
+            jobs += piece_jobs
+            job_voices += [voice] * len(piece_jobs)
+            job_req += [r] * len(piece_jobs)
+            job_kw += [dict(steps=settings.nfe_step, cfg_strength=settings.cfg_strength, sway_sampling_coef=settings.sway_sampling_coef)] * len(piece_jobs)
+            seg_sizes.append(len(piece_jobs))
+
+        # the noise of every job, in flat order, with the shapes sample() draws (model/cfm.py): nothing below can change what a request hears
+        frames = self._generated_frames(jobs, job_voices)
+        mel_dim, dtype = self.model.num_channels, next(self.model.parameters()).dtype
+        ndev = self.model.noise_device or self.model.device
+        own, y0s = {}, []
+        for k, (n, v) in enumerate(zip(frames, job_voices)):
+            r = job_req[k]
+            kw = {}
+            if reqs[r].seed is not None:
+                if r not in own:
+                    own[r] = torch.Generator(device=ndev).manual_seed(int(reqs[r].seed))
+                kw["generator"] = own[r]
+            y0s.append(torch.randn(n + v["ref_audio_len"], mel_dim, device=ndev, dtype=dtype, **kw).to(self.model.device))
+
+        keys = [(int(kw["steps"]), None if kw["sway_sampling_coef"] is None else float(kw["sway_sampling_coef"]), float(kw["cfg_strength"]) >= 1e-5)
+                for kw in job_kw]
+        keys = [key if key[2] else key + (r,) for key, r in zip(keys, job_req)]  # (an unguided request keeps generate()'s own groups)
+        groups = plan_request_groups(keys, [d for _, d in jobs], int(self.ragged_chunks))
+        mels = self._sample_jobs(jobs, job_voices, None, groups=groups, job_kw=job_kw, y0s=y0s)
+
+        first = [0]
+        for g in seg_sizes:
+            first.append(first[-1] + g)
+        results = [None] * len(reqs)
+        skips = [v["ref_audio_len"] for v in job_voices]
+        want_float = not return_pcm16 or any(q.remove_silence for q in reqs)
+        with torch.inference_mode():
+            kind = device_tail_kind(self.vocoder, *mels)
+            on_device = (kind is not None and (kind == "vocos") == (self.mel_spec_type == "vocos")
+                         and min(int(m.shape[1]) - k for m, k in zip(mels, skips)) >= 2)
+            by_fade = {}  # distinct cross-fade lengths in order of first appearance -> their requests
+            for r, (settings, _) in enumerate(plans):
+                by_fade.setdefault(float(settings.cross_fade_duration), []).append(r)
+            if on_device:
+                rows, row_start, got = mel_rows_of(mels, skips)
+                wave_buf, samples = decode_utterances(self.vocoder, kind, rows, row_start, got)
+                waves = torch.split(wave_buf, samples)
+            for fade, members in by_fade.items() if on_device else ():
+                idx = [k for r in members for k in range(first[r], first[r + 1])]
+                sizes = [seg_sizes[r] for r in members]
+                buf = wave_buf if len(idx) == len(jobs) else torch.cat([waves[k] for k in idx])
+                lengths = [samples[k] for k in idx]
+                done = finish_waves(buf, lengths, want_float=want_float, want_pcm16=return_pcm16,
+                                    **self._tail_kw(types.SimpleNamespace(cross_fade_duration=fade), [job_voices[k] for k in idx], sizes))
+                if done is None:
+                    continue  # (joints that chain: these requests take the host functions below)
+                plan = plan_wave_tail_segments(lengths, sizes, fade, self.target_sample_rate)
+                starts, at = [], 0
+                for g in sizes:
+                    starts.append(plan["out_offsets"][at])
+                    at += g
+                starts.append(plan["total"])
+                signal, pcm = done
+                for j, r in enumerate(members):
+                    wave = signal[starts[j]: starts[j + 1]] if signal is not None else None
+                    if wave is not None and sizes[j] == 1 and wave.dtype == torch.float64:
+                        wave = wave.to(torch.float32)  # (its fp32 values widened by the buffer's promotion: the cast back is exact)
+                    part = pcm[starts[j]: starts[j + 1]] if pcm is not None else None
+                    if reqs[r].remove_silence:
+                        wave, part = self._silence_step(wave, part)
+                    out = (part if return_pcm16 else wave).cpu().numpy()
+                    if return_spectrogram:
+                        spec = np.concatenate([rows[row_start[k]: row_start[k] + got[k]].t().cpu().numpy() for k in range(first[r], first[r + 1])], axis=1)
+                        results[r] = (out, self.target_sample_rate, spec)
+                    else:
+                        results[r] = (out, self.target_sample_rate)
+        for r, (settings, _) in enumerate(plans):  # the host tails, per request: exactly what its generate() call does behind the sampler
+            if results[r] is None:
+                span = slice(first[r], first[r + 1])
+                results[r] = self._deliver(mels[span], settings, job_voices[span], [seg_sizes[r]], None, True, return_spectrogram, return_pcm16,
+                                           reqs[r].remove_silence)
+        return results
+
     def _plan_jobs(self, text, tagged=False, nfe_step=None, cfg_strength=None, sway_sampling_coef=None, speed=None, fix_duration=None,
                    cross_fade_duration=None, use_duration_predictor=None):
         """The host work before any sampling: ``(settings, jobs, voices, seg_sizes)`` -- the arguments every entry point takes as one value,
@@ -312,46 +480,55 @@ class F5TTSWrapper:
         given = dict(nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration,
                      cross_fade_duration=cross_fade_duration, use_duration_predictor=use_duration_predictor)
         settings = types.SimpleNamespace(**{k: v if v is not None else getattr(self, k) for k, v in given.items()})
-        can_use_predictor = settings.use_duration_predictor and self.has_duration_predictor
         jobs, job_voices, seg_sizes = [], [], []
         for name, piece in split_voice_script(text, voices) if tagged else [("main", text)]:
             if tagged:
                 print(f"Voice: {name}")
             voice = voices[name]
-            ref_text, ref_audio_len = voice["ref_text"], voice["ref_audio_len"]
-            audio_len = voice["audio"].shape[-1] / self.target_sample_rate
-            max_chars = int(len(ref_text.encode("utf-8")) / audio_len * (22 - audio_len))
-            text_batches = chunk_text(piece, max_chars=max_chars)
-            for i, text_batch in enumerate(text_batches):
-                print(f"Text batch {i}: {text_batch}")
-            print("\n")
-
-            for text_batch in text_batches:  # host work of the reference's loop (:476-510)
-                local_speed = 0.3 if len(text_batch.encode("utf-8")) < 10 else settings.speed
-                final_text_list = convert_char_to_pinyin([ref_text + text_batch])
-                if settings.fix_duration is not None:
-                    duration = int(settings.fix_duration * self.target_sample_rate / self.hop_length)
-                    print(f"Using fixed duration: {settings.fix_duration}s ({duration} frames)")
-                elif can_use_predictor:
-                    if isinstance(final_text_list[0], str):
-                        text_tokens = list_str_to_idx(final_text_list, self.vocab_char_map).to(self.device)
-                    else:
-                        text_tokens = torch.tensor(final_text_list, device=self.device)
-                    text_lengths = torch.tensor([len(t) for t in final_text_list], device=self.device)
-                    with self._voice_installed(voice):  # (the reference's public method reads self.ref_audio_len)
-                        duration = self.calculate_duration_with_predictor(text_tokens, text_lengths, local_speed)
-                    print(f"Duration predictor output: {duration} frames")
-                else:
-                    ref_text_len, gen_text_len = len(ref_text.encode("utf-8")), len(text_batch.encode("utf-8"))
-                    duration = ref_audio_len + int(ref_audio_len / ref_text_len * gen_text_len / local_speed)
-                    print(f"Calculated duration based on text ratio: {duration} frames")
-                jobs.append((final_text_list, int(duration)))
-                job_voices.append(voice)
-            if text_batches:
-                seg_sizes.append(len(text_batches))
+            own_speed = voice.get("speed") if speed is None else None  # add_voice(speed=): used where the call names none
+            piece_jobs = self._plan_piece(voice, piece, settings, settings.speed if own_speed is None else own_speed)
+            jobs += piece_jobs
+            job_voices += [voice] * len(piece_jobs)
+            if piece_jobs:
+                seg_sizes.append(len(piece_jobs))
         if not jobs:
             raise RuntimeError("No audio generated")
         return settings, jobs, job_voices, seg_sizes
+
+    def _plan_piece(self, voice, piece, settings, speed):
+        """The jobs ``(token list, frames asked for)`` of one piece of text in one voice, as generate() plans them with that voice's prompt in the
+        main fields: the chunks of `chunk_text` under the prompt's byte budget, each with the duration rule (or the predictor) at ``speed``."""
+        can_use_predictor = settings.use_duration_predictor and self.has_duration_predictor
+        ref_text, ref_audio_len = voice["ref_text"], voice["ref_audio_len"]
+        audio_len = voice["audio"].shape[-1] / self.target_sample_rate
+        max_chars = int(len(ref_text.encode("utf-8")) / audio_len * (22 - audio_len))
+        text_batches = chunk_text(piece, max_chars=max_chars)
+        for i, text_batch in enumerate(text_batches):
+            print(f"Text batch {i}: {text_batch}")
+        print("\n")
+
+        jobs = []
+        for text_batch in text_batches:  # host work of the reference's loop (:476-510)
+            local_speed = 0.3 if len(text_batch.encode("utf-8")) < 10 else speed
+            final_text_list = convert_char_to_pinyin([ref_text + text_batch])
+            if settings.fix_duration is not None:
+                duration = int(settings.fix_duration * self.target_sample_rate / self.hop_length)
+                print(f"Using fixed duration: {settings.fix_duration}s ({duration} frames)")
+            elif can_use_predictor:
+                if isinstance(final_text_list[0], str):
+                    text_tokens = list_str_to_idx(final_text_list, self.vocab_char_map).to(self.device)
+                else:
+                    text_tokens = torch.tensor(final_text_list, device=self.device)
+                text_lengths = torch.tensor([len(t) for t in final_text_list], device=self.device)
+                with self._voice_installed(voice):  # (the reference's public method reads self.ref_audio_len)
+                    duration = self.calculate_duration_with_predictor(text_tokens, text_lengths, local_speed)
+                print(f"Duration predictor output: {duration} frames")
+            else:
+                ref_text_len, gen_text_len = len(ref_text.encode("utf-8")), len(text_batch.encode("utf-8"))
+                duration = ref_audio_len + int(ref_audio_len / ref_text_len * gen_text_len / local_speed)
+                print(f"Calculated duration based on text ratio: {duration} frames")
+            jobs.append((final_text_list, int(duration)))
+        return jobs
 
     def _generated_frames(self, jobs, voices):
         """Frames each job's sample() call generates behind its voice's prompt, from the host values alone: the sampler raises the frames asked
@@ -359,7 +536,7 @@ class F5TTSWrapper:
         return [min(max(max(len(tokens[0]), int(v["mel"].shape[1])) + 1, duration), 4096) - v["ref_audio_len"]
                 for (tokens, duration), v in zip(jobs, voices)]
 
-    def _sample_jobs(self, jobs, voices, settings):
+    def _sample_jobs(self, jobs, voices, settings, *, groups=None, job_kw=None, y0s=None):
         """The mels of these jobs, in order, each over its own voice's prompt mel (``voices``: one field dict per job).  The text chunks of one
         call are independent (the reference samples them one after the other, :476-533), and a single-utterance sample() fills a fraction
         of the 256 CUs, so they run together, either way with the arithmetic of their own batch-1 calls and the noise drawn in chunk order
@@ -367,31 +544,54 @@ class F5TTSWrapper:
           * ragged -- the backbone is the DiT and there are at least 2 jobs, all of at least 256 frames (the row count from which a batch-1
             call takes the tuned kernels too) and at most 4096: ONE ragged batch per group of chunks (`chunk_groups`), the utterances
             concatenated along the token axis without padding, one prompt per utterance zero-padded to the longest, with ``lens``;
-          * otherwise sample() per job, up to `chunk_streams` of them in flight, each on a HIP stream (and a libf5hip plan) of its own."""
+          * otherwise sample() per job, up to `chunk_streams` of them in flight, each on a HIP stream (and a libf5hip plan) of its own.
+        `generate_batch` hands over jobs of independent requests: ``groups`` (`utils_infer.plan_request_groups`: index lists, every group of
+        one step count and time grid) replaces the rule's one list -- each group that meets the rule above is ONE ragged call with its jobs'
+        guidance strengths as a vector, the jobs of every other group take sample(); ``job_kw`` holds each job's ``steps`` / ``cfg_strength`` /
+        ``sway_sampling_coef`` and ``y0s`` its initial noise ([n, mel], drawn by the caller), so the grouping cannot change a bit."""
         transformer = getattr(self.model, "transformer", None)
-        sample_kw = dict(steps=settings.nfe_step, cfg_strength=settings.cfg_strength, sway_sampling_coef=settings.sway_sampling_coef)
-        ragged = (int(self.ragged_chunks) >= 2 and len(jobs) >= 2 and torch.cuda.is_available() and hasattr(transformer, "native_sample_ragged")
-                  and getattr(transformer, "BACKBONE", None) == 0 and min(d for _, d in jobs) >= 256 and max(d for _, d in jobs) <= 4096)
-        if ragged:
-            mels = []
-            with torch.inference_mode():
-                for idx in chunk_groups([d for _, d in jobs], 0, int(self.ragged_chunks)):
-                    prompts = [voices[i]["mel"][0] for i in idx]
-                    lens = torch.tensor([int(m.shape[0]) for m in prompts], device=prompts[0].device, dtype=torch.long)
-                    cond = torch.nn.utils.rnn.pad_sequence(prompts, batch_first=True, padding_value=0.0)
-                    mels += self.model.sample_ragged(cond, [jobs[i][0][0] for i in idx], [jobs[i][1] for i in idx], lens=lens, **sample_kw)
+        sample_kw = dict(steps=settings.nfe_step, cfg_strength=settings.cfg_strength, sway_sampling_coef=settings.sway_sampling_coef) if settings else None
+        can_ragged = (int(self.ragged_chunks) >= 2 and torch.cuda.is_available() and hasattr(transformer, "native_sample_ragged")
+                      and getattr(transformer, "BACKBONE", None) == 0)
+
+        def fits(idx):  # the ragged rule over these jobs
+            return can_ragged and len(idx) >= 2 and min(jobs[i][1] for i in idx) >= 256 and max(jobs[i][1] for i in idx) <= 4096
+
+        if groups is None:
+            ragged_groups = chunk_groups([d for _, d in jobs], 0, int(self.ragged_chunks)) if fits(range(len(jobs))) else []
+            singles = [] if ragged_groups else list(range(len(jobs)))
+        else:
+            ragged_groups = [list(g) for g in groups if fits(g)]
+            singles = [i for g in groups if not fits(g) for i in g]
+        mels = [None] * len(jobs)
+        with torch.inference_mode():
+            for idx in ragged_groups:
+                prompts = [voices[i]["mel"][0] for i in idx]
+                lens = torch.tensor([int(m.shape[0]) for m in prompts], device=prompts[0].device, dtype=torch.long)
+                cond = torch.nn.utils.rnn.pad_sequence(prompts, batch_first=True, padding_value=0.0)
+                kw = sample_kw
+                if job_kw is not None:  # one step count and time grid per group (the planner's key), a guidance strength per utterance
+                    kw = dict(job_kw[idx[0]], cfg_strength=[float(job_kw[i]["cfg_strength"]) for i in idx])
+                if y0s is not None:
+                    kw = dict(kw, y0s=[y0s[i] for i in idx])
+                for i, mel in zip(idx, self.model.sample_ragged(cond, [jobs[i][0][0] for i in idx], [jobs[i][1] for i in idx], lens=lens, **kw)):
+                    mels[i] = mel
+        if not singles:
             return mels
         n_streams = 1
         if torch.cuda.is_available() and hasattr(transformer, "finish_pending"):
-            n_streams = max(1, min(len(jobs), int(self.chunk_streams)))
+            n_streams = max(1, min(len(singles), int(self.chunk_streams)))
         main, streams = (torch.cuda.current_stream(), self._chunk_stream_pool(n_streams)) if n_streams > 1 else (None, [])
         for st in streams:
             st.wait_stream(main)  # the prompts' mels were produced on the caller's stream
-        mels = []
-        for i, ((tokens, duration), v) in enumerate(zip(jobs, voices)):
-            with torch.inference_mode(), torch.cuda.stream(streams[i % n_streams]) if streams else contextlib.nullcontext():
-                mels.append(self.model.sample(cond=v["mel"], text=tokens, duration=duration, return_trajectory=False, **sample_kw,
-                                              **({"defer_guard": True} if streams else {}))[0])
+        for k, i in enumerate(singles):
+            (tokens, duration), v = jobs[i], voices[i]
+            kw = sample_kw if job_kw is None else job_kw[i]
+            if y0s is not None:
+                kw = dict(kw, y0=y0s[i].unsqueeze(0))
+            with torch.inference_mode(), torch.cuda.stream(streams[k % n_streams]) if streams else contextlib.nullcontext():
+                mels[i] = self.model.sample(cond=v["mel"], text=tokens, duration=duration, return_trajectory=False, **kw,
+                                            **({"defer_guard": True} if streams else {}))[0]
         if not streams:
             return mels
         transformer.finish_pending()  # reads every chunk's fp16 range-guard flag (and lets the library redo a chunk whose guard fired)
@@ -401,8 +601,8 @@ class F5TTSWrapper:
         for st in streams:
             main.wait_stream(st)
         with torch.inference_mode():
-            for generated in mels:
-                generated.record_stream(main)
+            for i in singles:
+                mels[i].record_stream(main)
         return mels
 
     def _silence_step(self, signal, pcm16=None):
@@ -431,7 +631,12 @@ class F5TTSWrapper:
                     remove_silence=False):
         """Sampler, mel -> wave (`utils_infer.waves_of_mels`: on the device where the vocoder is one of ours), and delivery in the three return
         shapes of generate()."""
-        mels = self._sample_jobs(jobs, voices, settings)
+        return self._deliver(self._sample_jobs(jobs, voices, settings), settings, voices, seg_sizes, output_path, return_numpy, return_spectrogram,
+                             return_pcm16, remove_silence)
+
+    def _deliver(self, mels, settings, voices, seg_sizes, output_path=None, return_numpy=False, return_spectrogram=False, return_pcm16=False,
+                 remove_silence=False):
+        """`_synthesize` behind the sampler: these mels -> what generate() returns."""
         want_float = not return_pcm16 or output_path is not None
         want_spec = return_spectrogram or output_path is not None
         with torch.inference_mode():

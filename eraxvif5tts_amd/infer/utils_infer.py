@@ -371,6 +371,22 @@ def chunk_groups(durations, first=0, group_max=8, max_rows=16384):
     return groups
 
 
+def plan_request_groups(keys, durations, group_max=8, max_rows=16384):
+    """The sampler calls of `F5TTSWrapper.generate_batch`: jobs ``0 .. len(keys) - 1`` (the chunks of all requests, in flat order) cut into groups
+    of indices.  ``keys[i]`` is job i's ``(nfe_step, sway_sampling_coef, cfg_strength >= 1e-5)`` -- what one sampler call must share: the step
+    count, the time grid and the branch of cfm.py:167 -- and ``durations[i]`` its frame count.  Jobs of one key keep their flat order and go
+    through `chunk_groups` (at most ``group_max`` jobs and ``max_rows`` frames per group); the keys are visited in order of first appearance,
+    so a request mix that recurs meets the same time grids in the same order.  A pure function of its arguments."""
+    assert len(keys) == len(durations)
+    by_key = {}
+    for i, key in enumerate(keys):
+        by_key.setdefault(key, []).append(i)
+    groups = []
+    for members in by_key.values():
+        groups += [[members[j] for j in g] for g in chunk_groups([durations[i] for i in members], 0, group_max, max_rows)]
+    return groups
+
+
 def stream_emitted_counts(lengths, group_sizes, cross_fade_duration, sample_rate=target_sample_rate, segments=None):
     """Output samples each push of a `WaveStream` over waves of these ``lengths`` emits when the list is pushed in consecutive groups of
     ``group_sizes`` utterances: a push that ends before the last utterance emits up to where the next utterance's first sample lands

@@ -358,15 +358,26 @@ class DiT(nn.Module):
         self._report_fallback(lib, plan)
         return out, traj
 
-    def native_sample_ragged(self, cond_cat, text, lens, frames, y0_cat, tgrid, steps, cfg_strength, method="euler", use_graph="auto"):
+    def native_sample_ragged(self, cond_cat, text, lens, frames, y0_cat, tgrid, steps, cfg_strength, method="euler", use_graph="auto", *,
+                             cond_mask=None):
         """Utterances of different frame counts in ONE set of launches (include/f5hip.h: f5_sample_ragged).  cond_cat / y0_cat f32
         [sum(frames), mel] (the utterances one after the other), text int [B, nt] (-1 padded), lens int [B], frames list of ints.
-        Returns out_cat [sum(frames), mel]; every utterance's rows equal its own batch-1 native_sample()."""
+        Returns out_cat [sum(frames), mel]; every utterance's rows equal its own batch-1 native_sample().
+        ``cfg_strength``: a number, or one float per utterance (f5_sample_ragged_ex: independent requests in one batch; values below and at
+        or above 1e-5 in one vector raise ``ValueError`` -- the reference's single-pass branch cannot share a doubled batch).  ``cond_mask``:
+        bool / u8 [sum(frames)], the per-frame condition masks of the utterances one after the other (speech editing), or None."""
         lib = _lib.load()
         if self.BACKBONE != _lib.F5_BACKBONE_DIT:
             raise NotImplementedError("ragged sampling is built for the DiT backbone")
         meth = _ode_code(method)
         B = len(frames)
+        cfg_vec = None
+        if not isinstance(cfg_strength, (int, float)):
+            cfg_vec = [float(c) for c in (cfg_strength.tolist() if torch.is_tensor(cfg_strength) else cfg_strength)]
+            if len(cfg_vec) != B:
+                raise ValueError(f"cfg_strength holds {len(cfg_vec)} values for {B} utterances")
+            if len({c >= 1e-5 for c in cfg_vec}) > 1:
+                raise ValueError("cfg_strength mixes values below 1e-5 (single pass, cfm.py:167) with guided ones: sample them in separate calls")
         evals = steps * lib.f5_ode_evals_per_step(meth)
         # the plan must hold T = sum(round_up(n_i + 16, 16)) rows per CFG half and (B + 1) text rows: size it by total rows, not by the longest
         # utterance (seq is capped at 4096 by plan(), so utterances near that length need a larger batch dimension)
@@ -385,14 +396,28 @@ class DiT(nn.Module):
         _lib.check(lib.f5_plan_set_option(plan, b"residual_guard", 1), "plan_set_option")
         # a list of frame counts that recurs (batch inference over fixed buckets, a server's chunk pattern) replays its hipGraph from the second
         # call on; one-off shapes run eagerly (capturing costs about one small sample())
-        key = ("ragged", tuple(int(f) for f in frames), int(text.shape[1]), steps, method, float(cfg_strength))
+        key = ("ragged", tuple(int(f) for f in frames), int(text.shape[1]), steps, method, float(cfg_strength) if cfg_vec is None else "vector")
+        if cond_mask is not None:
+            key += ("masked",)
         seen = self._seen_shapes.get(key, 0)
         self._seen_shapes[key] = seen + 1
         graph = seen >= 1 if use_graph == "auto" else bool(use_graph)
         _lib.check(lib.f5_plan_set_option(plan, b"ragged_graph", int(graph)), "plan_set_option")
-        _lib.check(lib.f5_sample_ragged(plan, B, C.c_void_p(fr.data_ptr()), _lib.ptr(cond_cat), _lib.ptr(ids), ids.shape[1], _lib.ptr(lens32),
-                                        _lib.ptr(y0_cat), C.c_void_p(tg.data_ptr()), steps, float(cfg_strength), meth, _lib.ptr(out),
-                                        _lib.stream_ptr()), "sample_ragged")
+        if cfg_vec is None and cond_mask is None:
+            _lib.check(lib.f5_sample_ragged(plan, B, C.c_void_p(fr.data_ptr()), _lib.ptr(cond_cat), _lib.ptr(ids), ids.shape[1], _lib.ptr(lens32),
+                                            _lib.ptr(y0_cat), C.c_void_p(tg.data_ptr()), steps, float(cfg_strength), meth, _lib.ptr(out),
+                                            _lib.stream_ptr()), "sample_ragged")
+        else:
+            cm = None
+            if cond_mask is not None:
+                cm = cond_mask.to(device=dev, dtype=torch.uint8).contiguous()
+                assert tuple(cm.shape) == (cond_cat.shape[0],), (tuple(cm.shape), cond_cat.shape[0])
+            cv = torch.tensor(cfg_vec, dtype=torch.float32) if cfg_vec is not None else None
+            _lib.check(lib.f5_sample_ragged_ex(plan, B, C.c_void_p(fr.data_ptr()), _lib.ptr(cond_cat), _lib.ptr(ids), ids.shape[1], _lib.ptr(lens32),
+                                               _lib.ptr(cm), _lib.ptr(y0_cat), C.c_void_p(tg.data_ptr()), steps,
+                                               float(cfg_strength) if cfg_vec is None else cfg_vec[0],
+                                               C.c_void_p(cv.data_ptr()) if cv is not None else None, meth, _lib.ptr(out), _lib.stream_ptr()),
+                       "sample_ragged_ex")
         self._report_fallback(lib, plan)
         return out
 

@@ -323,18 +323,31 @@ class CFM(nn.Module):
 
     @torch.no_grad()
     def sample_ragged(self, cond, texts, durations, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None, seed=None,
-                      max_duration=4096, y0s=None, noise_device=None, use_graph="auto"):
+                      max_duration=4096, y0s=None, noise_device=None, use_graph="auto", edit_masks=None):
         """``sample()`` for several texts over ONE prompt, each with its own duration, in one set of kernel launches without padding the
         utterances to a common length (libf5hip ``f5_sample_ragged``).  Equivalent to ``[sample(cond, [t], d)[0] for t, d in zip(texts,
         durations)]`` -- the reference's batch-1 arithmetic per utterance (cfm.py:82-208 with batch = 1: no key mask), noise drawn in the
         same order -- and returns that list ([1, N_i, mel] each).  cond: mel [1, nc, mel] or raw wave [1, nw] (one prompt for every text), or
         [B, nc, mel] with ``lens`` (a prompt per utterance, zero-padded to a common nc as for ``sample()``); texts: list of str / list of token
-        lists / id tensor; durations: list of ints."""
+        lists / id tensor; durations: list of ints.
+        Independent requests in one batch (libf5hip ``f5_sample_ragged_ex``): ``cfg_strength`` may be a sequence with one float per utterance
+        -- utterance i then equals ``sample(..., cfg_strength=cfg_strength[i])``; a sequence that mixes values below 1e-5 (the reference's
+        single-pass branch, cfm.py:167) with guided ones raises ``ValueError`` before any library call.  ``edit_masks``: one bool tensor
+        ([n] or [1, n]) or None per utterance, combined with the prompt prefix as ``sample(edit_mask=...)`` does.  ``y0s``: explicit noise
+        per utterance; an entry that is None is drawn here, in order."""
         method = ode_method(self.odeint_kwargs)
         self.eval()
         native = getattr(self.transformer, "native_sample_ragged", None)
         if native is None:
             raise NotImplementedError("the backbone has no ragged sampler")
+        if not isinstance(cfg_strength, (int, float)):
+            cfg_strength = [float(c) for c in (cfg_strength.tolist() if torch.is_tensor(cfg_strength) else cfg_strength)]
+            if len(cfg_strength) != len(texts):
+                raise ValueError(f"cfg_strength holds {len(cfg_strength)} values for {len(texts)} utterances")
+            if len({c >= 1e-5 for c in cfg_strength}) > 1:
+                raise ValueError("cfg_strength mixes values below 1e-5 (single pass, cfm.py:167) with guided ones: sample them in separate calls")
+        if edit_masks is not None and len(edit_masks) != len(texts):
+            raise ValueError(f"edit_masks holds {len(edit_masks)} entries for {len(texts)} utterances")
         if cond.ndim == 2:  # raw wave
             cond = self.mel_spec(cond).permute(0, 2, 1)
         cond = cond.to(next(self.parameters()).dtype)
@@ -358,7 +371,7 @@ class CFM(nn.Module):
         ndev = default(default(noise_device, self.noise_device), self.device)
         for i, n in enumerate(frames):
             conds.append(F.pad(cond[i if cond.shape[0] > 1 else 0], (0, 0, 0, n - cond_seq_len), value=0.0))
-            if y0s is not None:
+            if y0s is not None and y0s[i] is not None:
                 noises.append(y0s[i].reshape(n, self.num_channels).to(device=device, dtype=cond.dtype))
             else:
                 if exists(seed):
@@ -367,8 +380,19 @@ class CFM(nn.Module):
         t = torch.linspace(0, 1, steps + 1, device=self.device, dtype=cond.dtype)
         if sway_sampling_coef is not None:
             t = t + sway_sampling_coef * (torch.cos(torch.pi / 2 * t) - 1 + t)
+        extra = {}
+        if edit_masks is not None and any(m is not None for m in edit_masks):
+            # cond_mask of sample(): lens_to_mask(lens) & edit_mask, False-padded to the utterance's frames -- per utterance, back to back
+            rows = []
+            for i, n in enumerate(frames):
+                prefix = torch.arange(n, device=device) < lens[i]
+                if edit_masks[i] is not None:
+                    em = edit_masks[i].reshape(-1).to(device=device, dtype=torch.bool)
+                    prefix = prefix & F.pad(em[:n], (0, max(0, n - em.numel())), value=False)
+                rows.append(prefix)
+            extra["cond_mask"] = torch.cat(rows)
         out = native(torch.cat(conds), text, lens, frames, torch.cat(noises), t, steps, cfg_strength, method=method,
-                     use_graph=use_graph)
+                     use_graph=use_graph, **extra)
         self.transformer.clear_cache()
         return [o.unsqueeze(0).to(cond.dtype) for o in torch.split(out, frames)]
 

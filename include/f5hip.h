@@ -180,6 +180,22 @@ F5_API int f5_sample_finish(f5_plan_t p, f5_stream_t stream);
 F5_API int f5_sample_ragged(f5_plan_t p, int B, const int32_t* frames_host, const float* cond, const int32_t* text, int nt, const int32_t* lens,
                      const float* y0, const float* tgrid_host, int steps, float cfg_strength, int ode_method, float* out, f5_stream_t stream);
 
+/* f5_sample_ragged for INDEPENDENT requests (F5TTSWrapper.generate_batch): a guidance strength and a per-frame condition mask of its own
+ * for every utterance.  Detected by symbol, like the round-5 entries.  f5_sample_ragged(...) is this call with both pointers NULL.
+ *   cfg_host   host f32 [B] or NULL (= cfg_strength for every utterance).  Utterance u is combined as pred + (pred - null_pred) * cfg_host[u]
+ *              (cfm.py:173) with the operations of the scalar form, so its rows are bit-identical to its own batch-1 f5_sample call with
+ *              cfg_strength = cfg_host[u].  The reference takes its single-pass branch below 1e-5 (cfm.py:167) and one doubled batch cannot
+ *              hold both branches: a vector with values on both sides of 1e-5 (or a NaN) is refused with F5_EINVAL before anything is
+ *              staged or launched -- keep such requests in different calls.  A vector below 1e-5 throughout runs the single pass.
+ *              The values are staged as device data per call, outside the captured region: with plan option "ragged_graph" = 1 a replayed
+ *              capture combines with the CURRENT call's vector (the capture key holds only whether a vector was given).  The fp16 range
+ *              guard's fp32 rerun reads the same staged values.
+ *   cond_mask  dev u8 [sum(frames)] or NULL (= frame < lens[u]): the condition mask of f5_sample_masked, utterance after utterance; rows
+ *              bit-identical to the batch-1 f5_sample_masked call of each utterance. */
+F5_API int f5_sample_ragged_ex(f5_plan_t p, int B, const int32_t* frames_host, const float* cond, const int32_t* text, int nt,
+                        const int32_t* lens, const uint8_t* cond_mask, const float* y0, const float* tgrid_host, int steps,
+                        float cfg_strength, const float* cfg_host, int ode_method, float* out, f5_stream_t stream);
+
 /* TextEmbedding.forward (dit.py:49-79): text ids [B, nt] (-1 padded) -> dev f32 [B, N, text_dim] */
 F5_API int f5_text_embed(f5_plan_t p, int B, int N, const int32_t* text, int nt, int drop_text, float* out, f5_stream_t stream);
 
