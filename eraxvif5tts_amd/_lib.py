@@ -86,6 +86,11 @@ _PROTOS = {
     "f5_cfm_noise": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "f5_cfm_loss_workspace": (C.c_int64, [_I, _I, _I]),
     "f5_cfm_loss": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_align_similarity": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_align_workspace": (C.c_int64, [_I, _I, _I]),
+    "f5_align_viterbi": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    "f5_align_window": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    "f5_duration_loss": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f5_plan_timing_begin": (_I, [_P, _I]),
     "f5_plan_timing_end": (_I, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int), _P]),
     "f5_plan_timing_site": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_int)]),

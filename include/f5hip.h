@@ -231,6 +231,48 @@ F5_API int64_t f5_cfm_loss_workspace(int B, int N, int mel);
 F5_API int f5_cfm_loss(int B, int N, int mel, const float* pred, const float* x1, const float* x0, const uint8_t* span, double* sums,
                        int64_t* counts, float* loss, void* workspace, f5_stream_t stream);
 
+/* ------------------------------------------------------------------ duration validation (Trainer.calculate_duration_loss, trainer.py:829-1068)
+ * The training target of the duration predictor and its loss, forward only, for judging a duration_predictor_*.pt checkpoint: the phoneme x
+ * mel similarity, the monotonic alignment search (alignment_utils.py:337-355: "viterbi" and "window"; "progressive" is not built: the trainer's
+ * AlignmentMethodManager never selects it), the durations of the alignment and the masked loss.  Detected by symbol.  All tensors dev f32 in
+ * PyTorch layouts unless said otherwise; nothing synchronises; the same input gives the same bits on every run (no atomics).
+ * Shapes: 1 <= nt <= 1024 (one lane per phoneme row), 1 <= T <= 65536, 1 <= B <= 65535; anything else is F5_EINVAL with a message.  nt and T
+ * are those of the PADDED batch, exactly as in the reference, with a consequence that is kept, not repaired: an utterance with fewer
+ * phonemes than nt has all -inf in its last rows, the viterbi backtrack finds no positive gradient there, and the last padded row takes the
+ * utterance's whole length (durations [0, ..., 0, T]).
+ *
+ * Similarity (trainer.py:925-970): embed [rows, K]; ids dev i32 [B, nt], used raw (no +1; an id outside [0, rows) reads nothing and stands for
+ * a zero row); phoneme_lens, mel_lens dev i32 [B]; melspec [B, T, mel]; proj [mel, K]; sim [B, nt, T].  K <= 768.
+ *   e = embed[id] / (|embed[id]| + 1e-8);  m = (melspec @ proj) / (|melspec @ proj| + 1e-8);  sim = e . m  (fp32 FMA dot products)
+ *   + 3.0 on columns [max(0, c - w), min(m_len, c + w)) of row p < p_len, c = (p * m_len) / p_len in integers (the reference's int(p * m_len /
+ *     p_len) in float64 is the same integer for operands below 2^26), w = max(3, m_len / 10), where p_len > 0 and m_len > 0  (:949-962)
+ *   -inf on rows >= p_len and columns >= m_len  (:965-970) */
+F5_API int f5_align_similarity(int B, int nt, int T, int mel, int K, int rows, const float* embed, const int32_t* ids,
+                               const int32_t* phoneme_lens, const float* melspec, const int32_t* mel_lens, const float* proj, float* sim,
+                               f5_stream_t stream);
+/* bytes of workspace the two searches take for a [B, nt, T] problem (one i32 per cell), or the negative F5_* code of a refused shape */
+F5_API int64_t f5_align_workspace(int B, int nt, int T);
+/* "viterbi" (alignment_utils.py:154-212).  sim [B, nt, T] -> durations [B, nt] = frames per row; alignment [B, nt, T] of 0 / 1, or NULL for
+ * durations alone.  Forward, every add ONE fp32 add in this association, so P has the reference's bits (row 0 is a serial running sum):
+ *   P[0,0] = s[0,0];  P[n,0] = P[n-1,0] + s[n,0];  P[0,t] = P[0,t-1] + s[0,t];  P[n,t] = s[n,t] + max(P[n-1,t], P[n,t-1])
+ * as an anti-diagonal wavefront, one workgroup per utterance, nt + T - 1 dependent steps.  Backtrack (:184-210): curr = T - 1; for n = nt-1 .. 0:
+ * boundary = the last t in [0, curr-1] with P[n,t+1] - P[n,t] > 0 in fp32 (NaN from -inf - -inf compares false), 0 if there is none or n = 0;
+ * row n takes columns boundary..curr; curr = boundary - 1; stop when curr < 0 (rows above keep duration 0).  Every column belongs to one row.
+ * workspace: dev, 4-byte aligned, f5_align_workspace bytes: per cell the index of the last positive gradient at or before it, which is all
+ * the backtrack asks of P. */
+F5_API int f5_align_viterbi(int B, int nt, int T, const float* sim, float* durations, float* alignment, void* workspace, f5_stream_t stream);
+/* "window" (alignment_utils.py:214-258), same arguments (workspace is not used and may be NULL).  frames_per_phone = T / nt in double; row n <
+ * nt - 1 ends at the first maximum of sim[n] (torch.argmax) over [max(start, e - w), min(T - 1, e + w)], e = (int)((n + 1) * frames_per_phone),
+ * w = max(2, (int)(T * 0.2)); the next row starts behind it; stop when start >= T; the last row takes the rest.  Where that window is empty
+ * (start > e + w: possible only when nt > T; the reference raises there) the row takes the single frame `start`. */
+F5_API int f5_align_window(int B, int nt, int T, const float* sim, float* durations, float* alignment, void* workspace, f5_stream_t stream);
+/* The loss (trainer.py:984-1025) over the elements n < phoneme_lens[b] (clamped to [0, nt]).  logw, durations [B, nt]; per element, in fp64 from
+ * the fp32 inputs:  d = max(dur, 0.1);  sq = (logw - log(d + 1e-6))^2;  ab = |exp(clamp(logw, -10, 10)) - d|.  sq_sums, abs_sums dev f64 [B],
+ * counts dev i64 [B] (8-byte aligned), added in a fixed order; loss_mae dev f32 [2] = (sum sq, sum ab) / (sum counts + 1e-8) over the batch, as
+ * the trainer logs them.  An utterance of length 0 gives 0, 0, 0. */
+F5_API int f5_duration_loss(int B, int nt, const float* logw, const float* durations, const int32_t* phoneme_lens, double* sq_sums,
+                            double* abs_sums, int64_t* counts, float* loss_mae, f5_stream_t stream);
+
 /* debug/parity taps: after the next f5_dit_forward / f5_sample evaluation, copy the named internal stage
  * (converted to f32, row-major [rows, cols]) into `dst` (dev f32).  Names: "t_emb", "input_embed",
  * "blk<i>.n1", "blk<i>.attn", "blk<i>.out", "final_norm".  Pass dst = NULL to clear all taps. */
