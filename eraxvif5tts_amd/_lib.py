@@ -61,6 +61,17 @@ class TileGemm(C.Structure):  # struct f5_tile_gemm (f5_op_tile_gemm: the refere
                                          "ldadd", "add2_f16", "ldo", "ldof", "out_rows")]
 
 
+class ReferenceRule(C.Structure):  # struct f5_reference_rule
+    _fields_ = [(n, C.c_int32) for n in ("clip_short", "min_silence_len_1", "threshold_floor_1", "min_silence_len_2", "threshold_floor_2",
+                                         "keep_silence", "seek_step", "soft_limit_ms", "hard_limit_ms", "r_lead", "r_trail", "lead_chunk_ms",
+                                         "pad_ms")] + [("target_rms", C.c_float)]
+
+
+# f5_reference_*: the words of counts_dev (include/f5hip.h: F5_REF_*)
+REF_WORDS = ("kept", "parts", "clip", "lead_ms", "trail_ms", "sumsq", "boost", "gathered", "gathered_ms", "lead_frame", "edge_frames", "edge_ms",
+             "out_frames", "rms_bits", "pass2")
+F5_REF_WORDS = 16
+
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 _PROTOS = {
     "f5_last_error": (C.c_char_p, []),
@@ -148,6 +159,10 @@ _PROTOS = {
     "f5_wave_remove_silence_workspace": (C.c_int64, [C.c_int64, _I, _I, _I]),
     "f5_wave_remove_silence": (_I, [_P, _I, C.c_int64, _I, C.c_int64, _I, _I, _I, _I, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "f5_op_silence_ranges": (_I, [_P, _I, C.c_int64, _I, C.c_int64, _I, _I, _I, _I, _P, C.c_int64, _P, _P, _P, _P]),
+    "f5_reference_prepare_workspace": (C.c_int64, [C.c_int64, _I, _I, C.POINTER(ReferenceRule)]),
+    "f5_reference_table_rows": (C.c_int64, [C.c_int64, _I, _I, C.POINTER(ReferenceRule)]),
+    "f5_reference_prepare": (_I, [_P, C.c_int64, _I, _I, C.POINTER(ReferenceRule), _I, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
+    "f5_op_reference_plan": (_I, [_P, C.c_int64, _I, _I, C.POINTER(ReferenceRule), _P, C.c_int64, _P, _P, _P]),
     "f5_bigvgan_create": (_I, [C.POINTER(BigVGANConfig), C.POINTER(_P)]),
     "f5_bigvgan_set_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
     "f5_bigvgan_has_tensor": (_I, [_P, C.c_char_p, C.POINTER(C.c_int64)]),

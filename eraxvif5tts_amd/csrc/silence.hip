@@ -11,12 +11,14 @@
 //           which needs n < 2^22)
 //   ranges  one workgroup: prefix scan, window flags, then one wave walks the flags 64 at a time (a ballot; runs of consecutive silent starts merge
 //           by the rule itself), inverts the silent ranges, pads by keep_silence with the midpoint rule and writes the segment table
+//           (silence_rule.h, which reference.hip includes too)
 //   gather  one thread per output sample and a binary search in the table, as wave_finish_kernel does
 // Stores to device memory are plain C++; no atomics: one workgroup owns the table and the counts.
 #include <cmath>
 
 #include "kernels.h"
 #include "runtime.h"
+#include "silence_rule.h"
 
 __device__ __forceinline__ int pcm_rint(double x) {  // what audio.write_wav stores for x
 #pragma clang fp contract(off)
@@ -24,11 +26,6 @@ __device__ __forceinline__ int pcm_rint(double x) {  // what audio.write_wav sto
     if (r >= 32767.0) return 32767;
     if (r <= -32768.0) return -32768;
     return r == r ? (int)r : 0;
-}
-
-__device__ __forceinline__ int64_t ms_frame(int64_t ms, double spm, int64_t n) {  // Segment._frame, then numpy's slice clamp
-    const int64_t f = (int64_t)((double)ms * spm);
-    return f < n ? f : n;
 }
 
 static constexpr int SIL_TILE = 8192;  // samples staged per pass (uint32 squares: 32 KiB of LDS)
@@ -82,122 +79,20 @@ __global__ __launch_bounds__(256) void silence_cells_kernel(const T* __restrict_
     if (mine) sums[c + 1] = acc;
 }
 
-struct SilenceParams {
-    int64_t n, n_ms;  // samples, milliseconds (Segment.__len__)
-    double spm;       // rate / 1000.0
-    int64_t L, step, keep;
-    int64_t lim;      // (R + 1)^2
-    int64_t W_reg;    // window starts 0, step, .. <= last
-    int64_t W;        // W_reg, + 1 when last % step != 0
-    int cap;          // table entries
-};
-
 // One workgroup: (1) sums[k] becomes the sum of the cells below k, (2) flags[w] = window w is silent, (3) wave 0 turns the flags into the table
-// (in_start, in_end, out_start) of the parts split_on_silence returns, in samples, and counts = (kept samples, parts).
+// (in_start, in_end, out_start) of the parts split_on_silence returns, in samples, and counts = (kept samples, parts).  (silence_rule.h)
 __global__ __launch_bounds__(1024) void silence_ranges_kernel(const SilenceParams q, int64_t* __restrict__ sums, uint8_t* __restrict__ flags,
                                                               int32_t* __restrict__ table, int64_t* __restrict__ counts) {
     __shared__ int64_t part[1024];
-    const int tid = threadIdx.x;
-    // (1) each thread owns `chunk` consecutive cells; the threads' totals are scanned in LDS
-    const int64_t chunk = (q.n_ms + 1023) / 1024;
-    int64_t a = 1 + tid * chunk, b = a + chunk;
-    if (a > q.n_ms + 1) a = q.n_ms + 1;
-    if (b > q.n_ms + 1) b = q.n_ms + 1;
-    int64_t tot = 0;
-    for (int64_t k = a; k < b; ++k) tot += sums[k];
-    part[tid] = tot;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int64_t add = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    int64_t run = part[tid] - tot;  // the sum of everything before this thread's cells
-    for (int64_t k = a; k < b; ++k) {
-        run += sums[k];
-        sums[k] = run;
-    }
-    if (tid == 0) sums[0] = 0;
-    __syncthreads();
-    // (2)
-    const int64_t last = q.n_ms - q.L;
-    for (int64_t w = tid; w < q.W; w += 1024) {
-        const int64_t i = w < q.W_reg ? w * q.step : last;
-        const int64_t cnt = ms_frame(i + q.L, q.spm, q.n) - ms_frame(i, q.spm, q.n);
-        const int64_t S = sums[i + q.L] - sums[i];
-        flags[w] = (cnt <= 0 || S < q.lim * cnt) ? 1 : 0;  // (an empty slice has rms 0)
-    }
-    __syncthreads();
-    if (tid >= 64) return;
-    // (3) every lane of wave 0 carries the same state; lane 0 stores
-    bool have = false, pend = false;
-    int64_t cur = 0, prev = 0, prev_end = 0, pend_s = 0, pend_e = 0, out_pos = 0;
-    int nseg = 0;
-    auto flush = [&](int64_t s, int64_t e) {  // one part: clamp, slice_ms, append
-        const int64_t s_ms = s > 0 ? s : 0, e_ms = e < q.n_ms ? e : q.n_ms;
-        const int64_t i0 = ms_frame(s_ms, q.spm, q.n);
-        int64_t i1 = ms_frame(e_ms, q.spm, q.n);
-        if (i1 < i0) i1 = i0;
-        if (tid == 0 && nseg < q.cap) {
-            table[3 * nseg] = (int32_t)i0;
-            table[3 * nseg + 1] = (int32_t)i1;
-            table[3 * nseg + 2] = (int32_t)out_pos;
-        }
-        out_pos += i1 - i0;
-        ++nseg;
-    };
-    auto nonsilent = [&](int64_t s, int64_t e) {  // a range of detect_nonsilent: pad it, meet the one before at the midpoint
-        int64_t ps = s - q.keep;
-        const int64_t pe = e + q.keep;
-        if (pend) {
-            if (ps < pend_e) {
-                pend_e = (pend_e + ps) / 2;  // (a non-negative sum: Python's // and this division agree)
-                ps = pend_e;
-            }
-            flush(pend_s, pend_e);
-        }
-        pend = true;
-        pend_s = ps;
-        pend_e = pe;
-    };
-    auto silent_range = [&](int64_t s, int64_t e) {  // a range of detect_silence
-        if (!(prev_end == 0 && s == 0 && !pend)) nonsilent(prev_end, s);  // (the leading [0, 0] is popped)
-        prev_end = e;
-    };
-    auto silent_start = [&](int64_t i) {
-        if (!have) {
-            have = true;
-            cur = i;
-        } else if (i != prev + q.step && i > prev + q.L) {
-            silent_range(cur, prev + q.L);
-            cur = i;
-        }
-        prev = i;
-    };
-    for (int64_t base = 0; base < q.W_reg; base += 64) {
-        const int64_t w = base + tid;
-        unsigned long long mask = __ballot(w < q.W_reg && flags[w] != 0);
-        while (mask) {  // a run of consecutive starts: its first start is judged by the rule, every other one is `prev + step` and merges
-            const int lo = __builtin_ctzll(mask);
-            const unsigned long long inv = ~(mask >> lo);
-            const int len = inv ? __builtin_ctzll(inv) : 64;
-            silent_start((base + lo) * q.step);
-            prev = (base + lo + len - 1) * q.step;
-            mask = lo + len >= 64 ? 0ull : mask & ~((1ull << (lo + len)) - 1ull);
-        }
-    }
-    if (q.W > q.W_reg && flags[q.W - 1] != 0) silent_start(last);
-    if (!have) {
-        nonsilent(0, q.n_ms);  // no silence, or shorter than one window
-    } else {
-        silent_range(cur, prev + q.L);
-        if (prev_end != q.n_ms) nonsilent(prev_end, q.n_ms);
-    }
-    if (pend) flush(pend_s, pend_e);
-    if (tid == 0) {
-        counts[0] = out_pos;
-        counts[1] = nseg;
+    silence_scan(q.n_ms, sums, part);
+    silence_flags(q, sums, flags);
+    if (threadIdx.x >= 64) return;
+    int64_t kept;
+    int parts;
+    silence_table(q, flags, table, &kept, &parts);
+    if (threadIdx.x == 0) {
+        counts[0] = kept;
+        counts[1] = parts;
     }
 }
 
@@ -252,14 +147,8 @@ static int silence_plan(const void* wave, int is_f64, int64_t n_samples, int sam
     q.keep = keep_silence;
     const int64_t R = threshold_floor < 32768 ? threshold_floor : 32768;  // an rms never exceeds 32768
     q.lim = (R + 1) * (R + 1);
-    if (n_ms < q.L) {
-        q.W_reg = q.W = 0;
-    } else {
-        const int64_t last = n_ms - q.L;
-        q.W_reg = last / q.step + 1;
-        q.W = q.W_reg + (last % q.step ? 1 : 0);
-    }
-    q.cap = (int)(n_ms / q.L + 2);
+    q.cmul = 1;
+    silence_set_windows(q);
     int cpb = (int)(SIL_TILE / (spm + 1.0));
     out->cells_per_block = cpb < 1 ? 1 : (cpb > 256 ? 256 : cpb);
     out->off_table = (size_t)round_up((n_ms + 1) * 8, 16);

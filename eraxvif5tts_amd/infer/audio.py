@@ -8,6 +8,7 @@ restatements (the packages are absent from the reference tree); o
 """
 from __future__ import annotations
 
+import functools
 import math
 import struct
 
@@ -242,6 +243,76 @@ def clip_reference(seg, show_info=print):
         wave = wave.slice_ms(0, 12000)
         show_info("Audio is over 12s, clipping short. (3)")
     return wave
+
+
+@functools.lru_cache(maxsize=None)
+def edge_threshold_integers(silence_threshold, amplitude=32768):
+    """``(r_lead, r_trail)``: the smallest integer rms in ``[0, amplitude]`` for which ``dBFS < silence_threshold`` is false, and the smallest
+    for which ``dBFS > silence_threshold`` is true (``amplitude + 1`` when there is none) -- the two comparisons of `detect_leading_silence` /
+    `remove_silence_edges` as integers.  ``Segment.rms`` is an integer and the float predicate is monotone in it (tests/test_reference_host.py
+    checks every value), so over n < 2^22 samples with the sum of squares S: ``dBFS < T`` <=> ``S < r_lead^2 n`` and ``dBFS > T`` <=>
+    ``S >= r_trail^2 n``.  261 / 261 at -42 dB."""
+    def dbfs(r):
+        return -float("inf") if r == 0 else 20.0 * math.log10(r / float(amplitude))
+    r_lead = next((r for r in range(amplitude + 1) if not dbfs(r) < silence_threshold), amplitude + 1)
+    r_trail = next((r for r in range(amplitude + 1) if dbfs(r) > silence_threshold), amplitude + 1)
+    return r_lead, r_trail
+
+
+def trailing_cut_ms(n_samples, frame_rate, silent_ms):
+    """`remove_silence_edges`' ``int(end * 1000)`` after ``silent_ms`` trailing milliseconds were judged silent (the float loop itself)"""
+    end = n_samples / frame_rate
+    for _ in range(silent_ms):
+        end -= 0.001
+    return int(end * 1000)
+
+
+def cut_sample_ranges(ranges, first, count):
+    """samples ``[first, first + count)`` of the concatenation of ``ranges``, as ranges again (empty ones dropped)"""
+    out, pos = [], 0
+    for a, b in ranges:
+        lo, hi = max(first - pos, 0), min(first + count - pos, b - a)
+        if hi > lo:
+            out.append((a + lo, a + hi))
+        pos += b - a
+    return out
+
+
+def reference_sample_ranges(seg, clip_short=True, silence_threshold=-42):
+    """``(ranges, messages)``: the ``(first, end)`` sample ranges of ``seg`` whose concatenation is ``remove_silence_edges(clip_reference(seg))``'
+    samples, and the messages `clip_reference` shows on the way -- the reference-voice rule as a table (what the device route,
+    csrc/reference.hip, is compared with).  The edges are judged on the concatenation, as the host route does: where a millisecond is no whole
+    number of samples its grid is not the original's."""
+    rate, messages = seg.frame_rate, []
+    ranges = [(0, seg.samples.shape[0])]
+    if clip_short:
+        def ms(samples):
+            return int(round(1000.0 * samples / rate))
+
+        def gather(min_len, thresh):
+            out, count = [], 0
+            for a, b in split_sample_ranges(seg, min_silence_len=min_len, silence_thresh=thresh, keep_silence=1000, seek_step=10):
+                if ms(count) > 6000 and ms(count + b - a) > 12000:
+                    return out, count, True
+                out.append((a, b))
+                count += b - a
+            return out, count, False
+
+        ranges, count, clipped = gather(1000, -50)
+        if clipped:
+            messages.append("Audio is over 12s, clipping short. (1)")
+        if ms(count) > 12000:
+            ranges, count, clipped = gather(100, -40)
+            if clipped:
+                messages.append("Audio is over 12s, clipping short. (2)")
+        if ms(count) > 12000:
+            ranges = cut_sample_ranges(ranges, 0, seg._frame(12000))
+            messages.append("Audio is over 12s, clipping short. (3)")
+    gathered = Segment(np.concatenate([seg.samples[a:b] for a, b in ranges]) if ranges else seg.samples[:0], rate, seg.sample_width)
+    count = gathered.samples.shape[0]
+    first = min(gathered._frame(detect_leading_silence(gathered, silence_threshold)), count)
+    kept = remove_silence_edges(gathered, silence_threshold).samples.shape[0]
+    return cut_sample_ranges(ranges, first, kept), messages
 
 
 def segment_to_float(seg):

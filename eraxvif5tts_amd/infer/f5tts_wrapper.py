@@ -128,6 +128,10 @@ class F5TTSWrapper:
         self.ref_audio_len = None
         self._voices = {}  # add_voice(): name -> the fields of one more reference voice ("main" is the three fields above)
         self.target_rms = 0.1
+        # the clip / trim / boost steps of preprocess_reference() and add_voice() on the GPU (infer/reference.py) when a call does not say
+        # (on_device=None); off by default: the host steps, as before.  `last_reference_route` is "device" or "host" after each voice
+        self.reference_on_device = os.environ.get("F5HIP_REFERENCE_DEVICE", "0").strip().lower() in ("1", "true", "yes", "on")
+        self.last_reference_route = None
         self.cross_fade_duration = 0.15
         # text chunks of one generate() call sampled concurrently (HIP streams); 1 = one after the other as the reference does.  Not a
         # constructor argument (the reference's signature is kept); set the attribute or F5HIP_CHUNK_STREAMS
@@ -158,21 +162,32 @@ class F5TTSWrapper:
         return load_checkpoint(model, ckpt_path, self.device, dtype=dtype, use_ema=use_ema)
 
     # ------------------------------------------------------------------ reference voice
-    def preprocess_reference(self, ref_audio_path: str, ref_text: str = "", clip_short: bool = True):
-        audio, ref_text = self._preprocess_voice(ref_audio_path, ref_text, clip_short)
+    def preprocess_reference(self, ref_audio_path: str, ref_text: str = "", clip_short: bool = True, on_device: Optional[bool] = None):
+        """``on_device``: True runs the clip / trim / pad / mono / boost steps on the GPU (`infer.reference.prepare_reference_device`: the same
+        samples; the boost divides by the exact rms, see there), False on the host, None as ``self.reference_on_device`` says.  A file the device
+        route does not take (a sample width other than 16 bits, more than two channels) goes the host's way; ``self.last_reference_route`` tells
+        which ran."""
+        audio, ref_text = self._preprocess_voice(ref_audio_path, ref_text, clip_short, on_device)
         self.ref_audio_processed = audio
         self.ref_text = ref_text
         self.ref_audio_len = audio.shape[-1] // self.hop_length
         return audio, ref_text
 
-    def _preprocess_voice(self, ref_audio_path, ref_text, clip_short):
+    def _preprocess_voice(self, ref_audio_path, ref_text, clip_short, on_device=None):
         """The steps of preprocess_reference() / add_voice(): ``(audio on the device, ref_text as it is used)``."""
+        from . import reference as _reference
         print("Converting audio...")
         aseg = _audio.Segment.from_file(ref_audio_path)
-        if clip_short:
-            aseg = _audio.clip_reference(aseg)
-        aseg = self._remove_silence_edges(aseg)
-        aseg = aseg + aseg.silent_like(50)
+        on_device = getattr(self, "reference_on_device", False) if on_device is None else on_device
+        on_device = bool(on_device) and _reference.device_route_takes(aseg)
+        self.last_reference_route = "device" if on_device else "host"
+        if on_device:
+            audio, sr, _ = _reference.prepare_reference_device(aseg, clip_short, self.target_rms, device=self.device)
+        else:
+            if clip_short:
+                aseg = _audio.clip_reference(aseg)
+            aseg = self._remove_silence_edges(aseg)
+            aseg = aseg + aseg.silent_like(50)
         if not ref_text.strip():
             raise RuntimeError("No reference text provided: automatic transcription (Whisper) needs a network model download; pass ref_text")
         print("Using custom reference text...")
@@ -180,30 +195,32 @@ class F5TTSWrapper:
             ref_text += " " if ref_text.endswith(".") else ". "
         print("\nReference text:", ref_text)
 
-        audio, sr = _audio.segment_to_float(aseg), aseg.frame_rate
-        if audio.shape[0] > 1:
-            audio = torch.mean(audio, dim=0, keepdim=True)
-        rms = torch.sqrt(torch.mean(torch.square(audio)))
-        if rms < self.target_rms:  # boosted only when quieter than the target (reference :334-336)
-            audio = audio * self.target_rms / rms
-        audio = audio.to(self.device)
+        if not on_device:
+            audio, sr = _audio.segment_to_float(aseg), aseg.frame_rate
+            if audio.shape[0] > 1:
+                audio = torch.mean(audio, dim=0, keepdim=True)
+            rms = torch.sqrt(torch.mean(torch.square(audio)))
+            if rms < self.target_rms:  # boosted only when quieter than the target (reference :334-336)
+                audio = audio * self.target_rms / rms
+            audio = audio.to(self.device)
         if sr != self.target_sample_rate:
             audio = _audio.resample(audio, sr, self.target_sample_rate)  # on the device (f5_frontend_resample)
         return audio, ref_text
 
     # ------------------------------------------------------------------ further voices (generate_multi)
-    def add_voice(self, name: str, ref_audio_path: str, ref_text: str = "", clip_short: bool = True, speed: Optional[float] = None):
+    def add_voice(self, name: str, ref_audio_path: str, ref_text: str = "", clip_short: bool = True, speed: Optional[float] = None,
+                  on_device: Optional[bool] = None):
         """One more reference voice for `generate_multi`, under ``name`` (a ``\\w+`` word other than "main", which is the voice
         `preprocess_reference` stored): exactly the steps of `preprocess_reference`, with the prompt's mel and its rms computed once.  The main
         fields are not touched.  Returns ``(audio, ref_text)`` as `preprocess_reference` does.
         ``speed`` (the reference's per-voice ``speed`` of infer_cli's voice table): kept in the voice's fields and used for this voice's pieces
         where a call (`generate_multi`, `generate_multi_stream`) or a request (`generate_batch`) gives no ``speed`` of its own; None: the
-        wrapper's ``speed``, as before."""
+        wrapper's ``speed``, as before.  ``on_device``: as in `preprocess_reference`."""
         if speed is not None and not float(speed) > 0:
             raise ValueError(f"voice {name!r}: speed {speed!r} is not a positive number")
         if not isinstance(name, str) or not re.fullmatch(r"\w+", name) or name == "main":
             raise ValueError(f"voice name {name!r}: a name is one \\w+ word (what a [name] tag can hold) and \"main\" is the voice of preprocess_reference()")
-        audio, ref_text = self._preprocess_voice(ref_audio_path, ref_text, clip_short)
+        audio, ref_text = self._preprocess_voice(ref_audio_path, ref_text, clip_short, on_device)
         self._voices[name] = self._voice_fields(audio, ref_text)
         if speed is not None:
             self._voices[name]["speed"] = float(speed)

@@ -648,6 +648,66 @@ F5_API int f5_wave_remove_silence(const void* wave, int is_f64, int64_t n_sample
 F5_API int f5_op_silence_ranges(const void* wave, int is_f64, int64_t n_samples, int sample_rate, int64_t n_ms, int min_silence_len,
                                 int threshold_floor, int keep_silence, int seek_step, void* workspace, int64_t workspace_bytes,
                                 uint8_t* flags_out, int32_t* table_out, int64_t* counts_dev, f5_stream_t stream);
+/* The reference-voice front-end on the device: the host steps of F5TTSWrapper._preprocess_voice (the reference's f5tts_wrapper.py:256-379) by the
+ * rule of this package's stand-in for pydub, infer/audio.py clip_reference / remove_silence_edges / Segment.silent_like / segment_to_float, bit
+ * for bit up to the rms (below), detected by symbol.
+ *   pcm        dev int16 [n_frames, channels] interleaved, channels 1 or 2, n_frames * channels < 2^31, sample_rate >= 1000
+ *   lengths    len(x) = rint(1000 frames / sample_rate), half to even; millisecond m is frame F(m) = min(int(m * (sample_rate / 1000.0)), frames),
+ *              a double product, truncated; an rms is over the interleaved samples of all channels
+ *   clip       (clip_short != 0; otherwise the one part [0, n_frames)) pass 1 = the split_on_silence of f5_wave_remove_silence above with
+ *              (min_silence_len_1, threshold_floor_1, keep_silence, seek_step) over the clip; its parts are appended while not
+ *              (len(out) > soft_limit_ms and len(out + part) > hard_limit_ms), which sets clip bit 0 ("(1)").  If len(out) > hard_limit_ms, pass 2
+ *              does the same over the ORIGINAL clip with (min_silence_len_2, threshold_floor_2) and replaces out (bit 1, "(2)").  If still
+ *              len(out) > hard_limit_ms, out = its first int(hard_limit_ms * (sample_rate / 1000.0)) frames (bit 2, "(3)")
+ *   edges      over the gathered frames out (their own millisecond grid, K frames, n_ms = len(out)): trim = 0; while trim < n_ms and the chunk
+ *              [trim, min(trim + lead_chunk_ms, n_ms)) is empty or has S < r_lead^2 n: trim += lead_chunk_ms; lead = min(trim, n_ms).  The segment
+ *              is re-sliced to frames [F(lead), F(n_ms)) -- K2 frames, n2 = len of them, its millisecond grid restarting there -- and milliseconds
+ *              n2 - 1, n2 - 2, .. count as silent until one has n > 0 and S >= r_trail^2 n.  S = the int64 sum of squares of a slice's n
+ *              interleaved samples; r_lead / r_trail are the caller's integers (audio.edge_threshold_integers: the smallest rms whose dBFS is not
+ *              below / is above the threshold); equal to the host's float comparison while n < 2^22.  No pow, log or sqrt in a decision
+ *   cut        the host's part: end = K2 / sample_rate; `end -= 0.001` once per silent millisecond; cut_ms = int(end * 1000).  The result keeps
+ *              slice_ms(0, cut_ms) of the re-sliced segment (Python's rule: a negative cut_ms counts from n2; clamped to [0, n2]), then
+ *              int(pad_ms * (sample_rate / 1000.0)) zero frames
+ *   wave       out_wave[i] = fp32(sum of frame i's channels) / (32768 channels): exactly the mean over channels of int / 32768 in fp32.
+ *              S = the int64 sum of the squared channel sums, pad included; rms32 = fp32(sqrt(fp64(S) / (channels^2 32768^2 out frames))), the
+ *              division and the root in fp64, rounded once more to fp32.  When rms32 < target_rms every sample becomes
+ *              (x * target_rms) / rms32: two fp32 operations, each correctly rounded.  (The host route's rms is torch's fp32 reduction, whose
+ *              summation order is its own: the contract here is rms32.)
+ *   counts_dev dev int64 [F5_REF_WORDS], indexed by F5_REF_*.  The decision stores PARTS, CLIP, GATHERED (K), GATHERED_MS, PASS2 (1: pass 2 ran),
+ *              LEAD_MS, TRAIL_MS (silent milliseconds at the end), LEAD_FRAME (F(lead)), EDGE_FRAMES (K2), EDGE_MS (n2); the rest is stored by
+ *              f5_reference_prepare: KEPT (frames before the pad), OUT_FRAMES, SUMSQ (S), BOOST (1: applied), RMS_BITS (rms32's bits)
+ *   table_out  dev int32 [3 rows], rows = what the _table_rows entry answers: per part (first frame, end frame, position among the gathered
+ *              frames) of the original clip; the PARTS rows concatenated are the K gathered frames (before the edges)
+ *   workspace  dev, 16-byte aligned, at least the bytes the _workspace entry answers for the same arguments.  Nothing is allocated here
+ *   prepare    planned = 0: the decision, then the wave.  planned != 0: workspace, table_out and counts_dev are as f5_op_reference_plan left them
+ *              for the same arguments on the same stream (the caller read TRAIL_MS and EDGE_FRAMES in between to form cut_ms) and only the wave is
+ *              made.  out_frames = the frames the caller expects (KEPT + the pad; at most n_frames + the pad): nothing is stored behind it;
+ *              out_wave dev f32 [out_frames]; out_pcm (may be NULL) dev int16 [out_frames, channels]: the integers out_wave was made from
+ *   refusals   F5_EINVAL with the argument's name, before any launch: channels other than 1 / 2, 2^31 samples or more, sample_rate < 1000, a
+ *              window (either min_silence_len or lead_chunk_ms) of 2^22 samples or more, a length below 1, a negative keep_silence, floor, limit
+ *              or pad, soft_limit_ms > hard_limit_ms, r_lead / r_trail outside 0 .. 32768, a short or misaligned workspace, a null pointer
+ * Nothing synchronises.  f5_op_reference_plan stops behind the decision (tables and counts only). */
+typedef struct f5_reference_rule {
+    int32_t clip_short;
+    int32_t min_silence_len_1, threshold_floor_1; /* 1000, floor(10^(-50 / 20) * 32768) = 103 */
+    int32_t min_silence_len_2, threshold_floor_2; /* 100, 327 (-40 dB) */
+    int32_t keep_silence, seek_step;              /* 1000, 10 */
+    int32_t soft_limit_ms, hard_limit_ms;         /* 6000, 12000 */
+    int32_t r_lead, r_trail;                      /* 261, 261 (-42 dB) */
+    int32_t lead_chunk_ms, pad_ms;                /* 10, 50 */
+    float target_rms;                             /* 0.1 */
+} f5_reference_rule;
+enum {
+    F5_REF_KEPT = 0, F5_REF_PARTS, F5_REF_CLIP, F5_REF_LEAD_MS, F5_REF_TRAIL_MS, F5_REF_SUMSQ, F5_REF_BOOST, F5_REF_GATHERED, F5_REF_GATHERED_MS,
+    F5_REF_LEAD_FRAME, F5_REF_EDGE_FRAMES, F5_REF_EDGE_MS, F5_REF_OUT_FRAMES, F5_REF_RMS_BITS, F5_REF_PASS2, F5_REF_WORDS = 16
+};
+F5_API int64_t f5_reference_prepare_workspace(int64_t n_frames, int channels, int sample_rate, const f5_reference_rule* rule);
+F5_API int64_t f5_reference_table_rows(int64_t n_frames, int channels, int sample_rate, const f5_reference_rule* rule);
+F5_API int f5_reference_prepare(const int16_t* pcm, int64_t n_frames, int channels, int sample_rate, const f5_reference_rule* rule, int planned,
+                                int64_t cut_ms, void* workspace, int64_t workspace_bytes, int32_t* table_out, int64_t* counts_dev,
+                                int64_t out_frames, float* out_wave, int16_t* out_pcm, f5_stream_t stream);
+F5_API int f5_op_reference_plan(const int16_t* pcm, int64_t n_frames, int channels, int sample_rate, const f5_reference_rule* rule, void* workspace,
+                                int64_t workspace_bytes, int32_t* table_out, int64_t* counts_dev, f5_stream_t stream);
 /* ISTFT head alone (for the roofline measurement): spec dev f32 [B, T, n_fft+2] (head.out activations:
  * log-magnitude | phase) -> wave dev f32 [B, (T-1)*hop] */
 F5_API int f5_vocoder_istft_head(f5_vocoder_t v, int B, int T, const float* head_out, float* wave, f5_stream_t stream);
