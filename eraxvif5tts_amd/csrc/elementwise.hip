@@ -991,41 +991,37 @@ int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, 
 // ----------------------------------------------------------------------------- CFG combine + fixed-grid ODE step
 // one element of the step; both kernels below are this body, so a row's arithmetic does not depend on where its guidance strength came from
 __device__ __forceinline__ void cfg_step_elem(const float* __restrict__ x_base, const float* __restrict__ vc, const float* __restrict__ vu, int ldv, int mel,
-                                              float cfg, const float* __restrict__ coef, float* __restrict__ x_out, float* __restrict__ x_out2, size_t i,
-                                              int r, int c) {
+                                              float cfg, const float* __restrict__ coef, float* __restrict__ x_out, size_t i, int r, int c) {
     const float pc = vc[(size_t)r * ldv + c];
     float f = pc;
     if (vu) f = pc + (pc - vu[(size_t)r * ldv + c]) * cfg;  // pred + (pred - null_pred) * cfg_strength (cfm.py:173)
-    const float y = x_base[i] + coef[0] * f;
-    x_out[i] = y;
-    if (x_out2) x_out2[i] = y;
+    x_out[i] = x_base[i] + coef[0] * f;
 }
 __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ x_base, const float* __restrict__ vc, const float* __restrict__ vu, int ldv,
-                                                       int rows, int mel, float cfg, const float* __restrict__ coef, float* __restrict__ x_out,
-                                                       float* __restrict__ x_out2) {
+                                                       int rows, int mel, float cfg, const float* __restrict__ coef, float* __restrict__ x_out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)rows * mel) return;
     const int r = (int)(i / mel), c = (int)(i % mel);
-    cfg_step_elem(x_base, vc, vu, ldv, mel, cfg, coef, x_out, x_out2, i, r, c);
+    cfg_step_elem(x_base, vc, vu, ldv, mel, cfg, coef, x_out, i, r, c);
 }
 // the guidance strength of row r is cfg_rows[r] (f5_sample_ragged_ex: one value per utterance, spread over its rows)
 __global__ __launch_bounds__(256) void cfg_step_rows_kernel(const float* __restrict__ x_base, const float* __restrict__ vc, const float* __restrict__ vu,
                                                             int ldv, int rows, int mel, const float* __restrict__ cfg_rows,
-                                                            const float* __restrict__ coef, float* __restrict__ x_out, float* __restrict__ x_out2) {
+                                                            const float* __restrict__ coef, float* __restrict__ x_out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)rows * mel) return;
     const int r = (int)(i / mel), c = (int)(i % mel);
-    cfg_step_elem(x_base, vc, vu, ldv, mel, cfg_rows[r], coef, x_out, x_out2, i, r, c);
+    cfg_step_elem(x_base, vc, vu, ldv, mel, cfg_rows[r], coef, x_out, i, r, c);
 }
 int launch_cfg_step(const float* x_base, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* coef,
-                    float* x_out, float* x_out2, hipStream_t stream, const float* cfg_rows) {
+                    float* x_out, hipStream_t stream, const float* cfg_rows) {
     if (rows <= 0) return 0;
     const size_t total = (size_t)rows * mel;
     const dim3 grid((unsigned)((total + 255) / 256));
     if (cfg_rows && vu)
-        hipLaunchKernelGGL(cfg_step_rows_kernel, grid, dim3(256), 0, stream, x_base, vc, vu, ldv, rows, mel, cfg_rows, coef, x_out, x_out2);
+        hipLaunchKernelGGL(cfg_step_rows_kernel, grid, dim3(256), 0, stream, x_base, vc, vu, ldv, rows, mel, cfg_rows, coef, x_out);
     else
-        hipLaunchKernelGGL(cfg_step_kernel, grid, dim3(256), 0, stream, x_base, vc, vu, ldv, rows, mel, cfg, coef, x_out, x_out2);
+        hipLaunchKernelGGL(cfg_step_kernel, grid, dim3(256), 0, stream, x_base, vc, vu, ldv, rows, mel, cfg, coef, x_out);
     F5_LAUNCH_CHECK();
     return 0;
 }

@@ -1,6 +1,7 @@
 // kernels.h -- launchers of the non-GEMM kernels (all enqueue on `stream`, never synchronise).
 #pragma once
 #include "common.h"
+#include "ode_methods.h"
 
 // ---- attention.hip
 // qkv: [B*N, 3*H*64] (q | k | v, token-major), mask u8 [B, N] or null, out [B*N, H*64]; activation dtype by precision.
@@ -134,16 +135,11 @@ int launch_pack_base(int precision_out, const float* cond, const int32_t* lens, 
 // x_out = x_base + coef[0] * (vc + (vc - vu) * cfg)   (cfm.py:173 + torchdiffeq step); vu == null -> x_base + coef * vc
 // cfg_rows (dev f32 [rows], or null): row r takes cfg_rows[r] in place of cfg, with the same operations (f5_sample_ragged_ex)
 int launch_cfg_step(const float* x_base, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* coef,
-                    float* x_out, float* x_out2 /*or null*/, hipStream_t stream, const float* cfg_rows = nullptr);
-// One stage of an explicit Runge-Kutta step (rk4 / heun2 / heun3, sampler.hip: the method table).  With f = vc + (vc - vu) * cfg (vu == null
-// -> vc) and the slopes k_j = slots + j * slot_stride (j < nk) of the step's earlier stages:
+                    float* x_out, hipStream_t stream, const float* cfg_rows = nullptr);
+// One stage of an explicit Runge-Kutta step (rk4 / heun2 / heun3, ode_methods.h: the method table and RkStage).  With f = vc + (vc - vu) * cfg
+// (vu == null -> vc) and the slopes k_j = slots + j * slot_stride (j < nk) of the step's earlier stages:
 //   kst (or null) = f;   out = y0 + (dt[0] * (wk[0] k_0 + .. + wk[nk-1] k_{nk-1} + wf f)) * post
 // as a left-to-right FMA chain (elementwise.hip).  out is the next stage's input, or y1 after the last stage.
-struct RkStage {
-    float wk[3];
-    float wf, post;
-    int nk;
-};
 int launch_rk_stage(const float* y0, const float* vc, const float* vu, int ldv, int rows, int mel, float cfg, const float* dt, const RkStage& sg,
                     const float* slots, size_t slot_stride, float* kst /*or null*/, float* out, hipStream_t stream,
                     const float* cfg_rows = nullptr /* as for launch_cfg_step */);

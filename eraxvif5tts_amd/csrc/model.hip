@@ -577,10 +577,7 @@ extern "C" int f5_plan_create(f5_model_t m, int max_batch, int max_seq, int max_
 
 extern "C" int f5_plan_destroy(f5_plan_t p) {
     if (!p) return 0;
-    for (auto& g : p->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
+    plan_drop_graphs(p);
     if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
     if (p->fold) --p->fold->users;
     for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);

@@ -4,7 +4,8 @@
 //   dit_eval.hip     one DiT evaluation (dit.py:185-233, modules.py:301-336,610-641)
 //   unett_eval.hip   one UNetT evaluation (backbones/unett.py:185-253)
 //   mmdit_eval.hip   one MMDiT evaluation (backbones/mmdit.py:146-190)
-//   sampler.hip      CFM.sample: ODE loop, hipGraph replay, fp16 range guard, LayerNorm-fold tables, ragged sampler (cfm.py:82-208)
+//   sampler.hip      CFM.sample: the step loop over ode_methods.h's solver table (uniform and ragged calls), the hipGraph cache keyed by the
+//                    call (GraphKey below), fp16 range guard, LayerNorm-fold tables (cfm.py:82-208)
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -89,23 +90,40 @@ struct f5_model_s {
     ~f5_model_s();
 };
 
-struct GraphEntry {
-    int B, N, nt, steps, method, cfg_on, mask_on;
-    float cfg;
-    int epoch;
-    uint64_t fold_id = 0;  // the FoldTable whose addresses the capture baked (0 = none)
-    int cmask_on = 0;      // captured with the staged per-frame condition mask (f5_sample_masked)
-    std::vector<int> rn;   // ragged sample(): the utterances' frame counts (empty: a uniform batch)
-    int cfg_rows = 0;      // captured with the per-row guidance strengths of p->cfg_rows (the VALUES are read at replay, not baked)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-};
-
+// what one sample loop bakes into its launches.  Every member is part of a captured graph's key: a new one goes into operator== here, nowhere else.
 struct SampleArgs {
     int B, N, nt, steps, method, cfg_on, mask_on;
     float cfg;
     int cmask_on = 0;  // the condition mask is the staged cmask_in (f5_sample_masked), not the lens prefix
-    int cfg_rows = 0;  // f5_sample_ragged_ex with cfg_host: row r is combined with p->cfg_rows[r], not with cfg
+    int cfg_rows = 0;  // f5_sample_ragged_ex with cfg_host: row r is combined with p->cfg_rows[r], not with cfg (the VALUES are read at replay)
+    bool operator==(const SampleArgs& o) const {  // (cfg by value: a NaN strength never finds its capture again)
+        return B == o.B && N == o.N && nt == o.nt && steps == o.steps && method == o.method && cfg_on == o.cfg_on && mask_on == o.mask_on &&
+               cfg == o.cfg && cmask_on == o.cmask_on && cfg_rows == o.cfg_rows;
+    }
+};
+
+// a captured sample loop: the call it was captured for and what else its nodes bake
+struct GraphKey {
+    SampleArgs a;
+    int epoch;             // g_tuning_epoch: the kernel choices of the knobs in force
+    uint64_t fold_id;      // the FoldTable whose addresses the capture baked (0 = none)
+    std::vector<int> rn;   // ragged sample(): the utterances' frame counts (empty: a uniform batch)
+    bool operator==(const GraphKey& o) const { return a == o.a && epoch == o.epoch && fold_id == o.fold_id && rn == o.rn; }
+};
+struct GraphEntry {  // owns its handles: erasing an entry from f5_plan_s::graphs destroys them
+    GraphKey key;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    explicit GraphEntry(GraphKey k) : key(std::move(k)) {}
+    GraphEntry(GraphEntry&& o) noexcept : key(std::move(o.key)), graph(o.graph), exec(o.exec) { o.graph = nullptr, o.exec = nullptr; }
+    GraphEntry& operator=(GraphEntry&& o) noexcept {
+        std::swap(key, o.key), std::swap(graph, o.graph), std::swap(exec, o.exec);
+        return *this;
+    }
+    ~GraphEntry() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
 };
 // f5_sample_ragged: utterances of different frame counts concatenated along the token axis.  One CFG half holds utterance i at rows
 // [off[i], off[i] + n[i]) followed by at least RAGGED_GAP rows that are kept ZERO wherever the position conv reads them, so the conv's own
@@ -237,7 +255,7 @@ template <typename F> static int timed(f5_plan_s* p, int site, hipStream_t st, F
     return rc;
 }
 
-void plan_drop_graphs(f5_plan_s* p);  // destroys every captured graph of the plan (sampler.hip)
+inline void plan_drop_graphs(f5_plan_s* p) { p->graphs.clear(); }  // destroys every captured graph of the plan
 int finish_if_pending(f5_plan_s* p);  // completes a deferred sample() before the plan's buffers are reused (sampler.hip)
 
 

@@ -1,87 +1,37 @@
-// sampler.hip -- CFM.sample on the device (reference model/cfm.py:82-208): the fixed-grid ODE loop over network evaluations with CFG doubling,
-// hipGraph capture / replay, the fp16 range guard and its fp32 fallback, the LayerNorm-fold tables of a time grid, and the ragged sampler.
+// sampler.hip -- CFM.sample on the device (reference model/cfm.py:82-208): the fixed-grid ODE loop over network evaluations with CFG doubling
+// -- one step loop over the solver table of ode_methods.h, behind the prologue of a uniform or of a ragged call --, hipGraph capture / replay
+// keyed by the call, the fp16 range guard and its fp32 fallback, the LayerNorm-fold tables of a time grid, and the two families of entry points.
+#include <algorithm>
+
 #include "model_internal.h"
 
-// ----------------------------------------------------------------------------- fixed-grid solvers
-// torchdiffeq's fixed-grid family, chosen by odeint_kwargs["method"] (cfm.py:197).  Evaluation j of step s has the evaluation index
-// evals * s + j (its AdaLN rows, fold-table entry and p->coefs word) and runs at t0 + c[j] * dt in fp32, as torchdiffeq computes it; rk4's
-// last evaluation is at t1 itself.  Euler and midpoint update with launch_cfg_step; the Runge-Kutta methods launch launch_rk_stage after
-// every evaluation with stage[j]: the slopes it combines, the slot its own slope is kept in (slot[j], -1: not needed later) and its output
-// (the next stage's input p->xmid, or y1 = traj[s + 1] after the last stage).  Their p->coefs word is dt.  The combinations restate
-// torchdiffeq's step functions (heun2 / heun3 tableaux, rk4 = rk4_alt_step_func, the 3/8 rule):
-//   rk4    x2 = y0 + dt k1 (1/3)    x3 = y0 + dt (k2 - k1 (1/3))    x4 = y0 + dt (k1 - k2 + k3)    y1 = y0 + dt (k1 + 3 k2 + 3 k3 + k4) / 8
-//   heun2  x2 = y0 + dt k1                                                                        y1 = y0 + dt (k1 / 2 + k2 / 2)
-//   heun3  x2 = y0 + dt k1 (1/3)    x3 = y0 + dt k2 (2/3)                                         y1 = y0 + dt (k1 / 4 + 3 k3 / 4)
-// (the kernel forms each of them as one FMA chain; torchdiffeq's rk4 groups the last one as (k1 + 3 (k2 + k3) + k4) * dt * 0.125).
-// Slope slots live in the tail of p->traj, past the steps + 1 states of the trajectory: a method with E evaluations per step keeps at most
-// E - 1 slopes, and E * steps <= max_evals with steps >= 1 gives steps + 1 + (E - 1) <= max_evals + 1 states, which is what traj holds.
-struct OdeMethod {
-    int evals;       // network evaluations per step
-    float c[4];      // evaluation times t0 + c[j] * dt
-    bool last_at_t1; // the last evaluation runs at t1 (rk4_alt_step_func: k4 = f(t1, ...))
-    RkStage stage[4];
-    int slot[4];
-};
-static const float ODE_THIRD = 1.0f / 3.0f, ODE_TWO_THIRDS = 2.0f / 3.0f;
-static const OdeMethod ODE_METHODS[] = {
-    /* F5_ODE_EULER */ {1, {0.f}, false, {}, {-1, -1, -1, -1}},
-    /* F5_ODE_MIDPOINT */ {2, {0.f, 0.5f}, false, {}, {-1, -1, -1, -1}},
-    /* F5_ODE_RK4 */
-    {4, {0.f, ODE_THIRD, ODE_TWO_THIRDS, 1.f}, true,
-     {{{0.f, 0.f, 0.f}, 1.f, ODE_THIRD, 0}, {{-ODE_THIRD, 0.f, 0.f}, 1.f, 1.f, 1}, {{1.f, -1.f, 0.f}, 1.f, 1.f, 2}, {{1.f, 3.f, 3.f}, 1.f, 0.125f, 3}},
-     {0, 1, 2, -1}},
-    /* F5_ODE_HEUN2 */ {2, {0.f, 1.f}, false, {{{0.f, 0.f, 0.f}, 1.f, 1.f, 0}, {{0.5f, 0.f, 0.f}, 0.5f, 1.f, 1}}, {0, -1, -1, -1}},
-    /* F5_ODE_HEUN3 */
-    {3, {0.f, ODE_THIRD, ODE_TWO_THIRDS}, false,
-     {{{0.f, 0.f, 0.f}, 1.f, ODE_THIRD, 0}, {{0.f, 0.f, 0.f}, 1.f, ODE_TWO_THIRDS, 0}, {{0.25f, 0.f, 0.f}, 0.75f, 1.f, 1}},
-     {0, -1, -1, -1}},
-};
-static const OdeMethod* ode_method_of(int ode_method) {
-    return ode_method >= 0 && ode_method < (int)(sizeof(ODE_METHODS) / sizeof(ODE_METHODS[0])) ? &ODE_METHODS[ode_method] : nullptr;
-}
+static_assert(F5_ODE_EULER == 0 && F5_ODE_MIDPOINT == 1 && F5_ODE_RK4 == 2 && F5_ODE_HEUN2 == 3 && F5_ODE_HEUN3 == 4 &&
+                  sizeof(ODE_METHODS) / sizeof(ODE_METHODS[0]) == 5,
+              "ODE_METHODS (ode_methods.h) is indexed by the F5_ODE_* constants");
 
 extern "C" int f5_ode_evals_per_step(int ode_method) {
     const OdeMethod* om = ode_method_of(ode_method);
     return om ? om->evals : f5_fail(F5_EINVAL, "bad ode_method %d", ode_method);
 }
-
-// the evaluations of one Runge-Kutta step from xs = traj[s] to xn = traj[s + 1] (rows: token rows of one CFG half)
-static int rk_step(f5_plan_s* p, const SampleArgs& a, int s, const float* xs, float* xn, int rows, int nb, int N, const uint8_t* mask, hipStream_t st) {
-    const OdeMethod& om = *ode_method_of(a.method);
-    const int mel = p->m->cfg.mel_dim;
-    const size_t state = (size_t)rows * mel;
-    float* slots = p->traj + (size_t)(a.steps + 1) * state;  // (see the slot invariant above)
-    const float* vu = a.cfg_on ? p->vout + (size_t)rows * MELP : nullptr;
-    const float* cfgr = a.cfg_rows ? p->cfg_rows : nullptr;
-    for (int j = 0; j < om.evals; ++j) {
-        const int ev = om.evals * s + j;
-        F5_TRY(net_eval(p, j == 0 ? xs : p->xmid, rows, nb, N, ev, 0, mask, st));
-        F5_TRY(launch_rk_stage(xs, p->vout, vu, MELP, rows, mel, a.cfg, p->coefs + ev, om.stage[j], slots, state,
-                               om.slot[j] >= 0 ? slots + (size_t)om.slot[j] * state : nullptr, j == om.evals - 1 ? xn : p->xmid, st, cfgr));
-    }
+// what both entry points refuse before any work: an unknown method, a grid the plan's per-evaluation buffers do not hold
+static int check_method_and_evals(const f5_plan_s* p, int ode_method, int steps) {
+    const OdeMethod* om = ode_method_of(ode_method);
+    if (!om) return f5_fail(F5_EINVAL, "bad ode_method %d", ode_method);
+    const int nev = om->evals * steps;
+    if (nev > p->maxE) return f5_fail(F5_EINVAL, "%d evaluations exceed the plan's max_evals=%d", nev, p->maxE);
     return 0;
 }
 
-// ----------------------------------------------------------------------------- public: sample
-
-// everything between the staged inputs and the final state traj[steps]; capturable (no syncs, no allocations)
-static int sample_body_ragged(f5_plan_s* p, const SampleArgs& a, hipStream_t st);
+// ----------------------------------------------------------------------------- the sample loop
 // attention dropout: call words one sample loop consumes (evaluations x blocks)
 static uint32_t sample_call_words(const f5_plan_s* p, const SampleArgs& a) {
     return (uint32_t)(ode_method_of(a.method)->evals * a.steps) * (uint32_t)p->m->cfg.depth;
 }
 
-static int sample_body(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
-    if (p->rg) return sample_body_ragged(p, a, st);
-    f5_model_s* m = p->m;
-    const f5_dit_config& c = m->cfg;
-    const int B = a.B, N = a.N, mel = c.mel_dim, bn = B * N;
-    const size_t state = (size_t)bn * mel;
-    // range guard of the fp16 residual stream: cleared by a KERNEL node of the graph, so every replay starts clean.  (Not hipMemsetAsync: on
-    // ROCm 7.2 the 32-byte memset node captured here cleared the words on the first launch of the instantiated graph and filled them with
-    // two stale host pointers on every replay -- gpurun_out/r3g: [512..519] = {0xf5dffab8, 0x78fe, 0xea66b000, 0x7909} x 2 -- which read as
-    // a raised flag and sent the second sample() of every process through the fp32 fallback.)
-    F5_TRY(launch_fill_f32(reinterpret_cast<float*>(p->sat_flag), 8, 0.0f, st));
+// Prologue of a uniform batch [B, N]: text embeddings, the hoisted half of the input embedding, the key mask of the durations, the MMDiT text
+// rows.  -> the key mask of the evaluations (null: none)
+static int uniform_prologue(f5_plan_s* p, const SampleArgs& a, const uint8_t** mask, hipStream_t st) {
+    const int B = a.B, N = a.N, bn = B * N;
     // (the AdaLN modulation rows of all evaluation times are already in p->mod: f5_sample keeps them across calls)
     // text embeddings are constants of the whole sample() (the reference caches them per branch, dit.py:202-210)
     F5_TRY(compute_text_embed(p, p->text_in, a.nt, B, N, 0, p->te[0], st));
@@ -91,95 +41,116 @@ static int sample_body(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
         F5_TRY(compute_text_embed(p, p->text_in, a.nt, B, N, 1, p->te[1], st));
         F5_TRY(compute_base(p, p->cond_in, p->lens_in, p->te[1], B, N, 1, (size_t)bn, st, cmask));
     }
-    const uint8_t* mask = nullptr;
+    *mask = nullptr;
     if (a.mask_on) {
         F5_TRY(launch_len_mask(p->dur_in, B, N, p->mask, st));
         if (a.cfg_on) F5_HIP(hipMemcpyAsync(p->mask + bn, p->mask, bn, hipMemcpyDeviceToDevice, st));
-        mask = p->mask;
-        F5_TRY(launch_rowbits(mask, (a.cfg_on ? 2 : 1) * (int)bn, p->rowbits, st));
-        p->rowbits_src = mask;
+        *mask = p->mask;
+        F5_TRY(launch_rowbits(p->mask, (a.cfg_on ? 2 : 1) * (int)bn, p->rowbits, st));
+        p->rowbits_src = p->mask;
     }
-    const int nb = a.cfg_on ? 2 * B : B;
-    if (c.backbone == F5_BACKBONE_MMDIT) {  // the text stream restarts from these rows at every evaluation (mmdit.py:163-173: the cached embeddings)
+    if (p->m->cfg.backbone == F5_BACKBONE_MMDIT) {  // the text stream restarts from these rows at every evaluation (mmdit.py:163-173: the cached embeddings)
         p->c_src[0] = p->te[0];
         p->c_src[1] = a.cfg_on ? p->te[1] : nullptr;
         p->c_nt = a.nt;
         p->c_rows_each = B * a.nt;
     }
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (g_sync_evals) (void)hipStreamIsCapturing(st, &capturing);
-    for (int s = 0; s < a.steps; ++s) {
-        if (g_sync_evals && capturing == hipStreamCaptureStatusNone && s > 0) F5_HIP(hipStreamSynchronize(st));
-        float* xs = p->traj + (size_t)s * state;
-        float* xn = p->traj + (size_t)(s + 1) * state;
-        const float* vu = a.cfg_on ? p->vout + (size_t)bn * MELP : nullptr;
-        if (a.method == F5_ODE_EULER) {
-            F5_TRY(net_eval(p, xs, bn, nb, N, s, 0, mask, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, bn, mel, a.cfg, p->coefs + s, xn, nullptr, st));
-        } else if (a.method == F5_ODE_MIDPOINT) {
-            F5_TRY(net_eval(p, xs, bn, nb, N, 2 * s, 0, mask, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, bn, mel, a.cfg, p->coefs + 2 * s, p->xmid, nullptr, st));
-            F5_TRY(net_eval(p, p->xmid, bn, nb, N, 2 * s + 1, 0, mask, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, bn, mel, a.cfg, p->coefs + 2 * s + 1, xn, nullptr, st));
-        } else {
-            F5_TRY(rk_step(p, a, s, xs, xn, bn, nb, N, mask, st));
+    return 0;
+}
+
+// Prologue of a ragged call (p->rg; see "public: ragged sample"): text embedding and the hoisted half of the input embedding per utterance,
+// each at its row offset
+static int ragged_prologue(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
+    const Ragged& rg = *p->rg;
+    const int B = a.B, T = rg.T, mel = p->m->cfg.mel_dim, td = p->m->cfg.text_dim;
+    for (int br = 0; br < (a.cfg_on ? 2 : 1); ++br)
+        for (int u = 0; u < B; ++u) {
+            const int nu = rg.n[u], nt_eff = a.nt < nu ? a.nt : nu;  // tokens beyond the frame count are curtailed (dit.py:51)
+            float* te = p->te[br] + (size_t)rg.off[u] * td;
+            F5_HIP(hipMemcpy2DAsync(p->text_in + (size_t)B * a.nt, (size_t)nt_eff * 4, p->text_in + (size_t)u * a.nt, (size_t)a.nt * 4, (size_t)nt_eff * 4, 1,
+                                    hipMemcpyDeviceToDevice, st));
+            F5_TRY(compute_text_embed(p, p->text_in + (size_t)B * a.nt, nt_eff, 1, nu, br, te, st));
+            // (the staged per-frame condition mask, utterance u's slice at its row offset: a replay sees the current call's mask)
+            F5_TRY(compute_base(p, p->cond_in + (size_t)rg.off[u] * mel, p->lens_in + u, te, 1, nu, br, (size_t)br * T + rg.off[u], st,
+                                a.cmask_on ? p->cmask_in + rg.off[u] : nullptr));
         }
+    return 0;
+}
+
+// The steps of a call over `rows` token rows per CFG half (nb batch items of N rows in all, key mask `mask` or null).  Evaluation j of step
+// s reads xs = traj[s] (j = 0) or p->xmid, and the method's update kernel behind it writes p->xmid, or xn = traj[s + 1] after the last one.
+// sync: diagnostic knob "sync_evals" -- the stream is synchronised between steps (never while capturing).
+static int sample_steps(f5_plan_s* p, const SampleArgs& a, int rows, int nb, int N, const uint8_t* mask, bool sync, hipStream_t st) {
+    const OdeMethod& om = *ode_method_of(a.method);
+    const int mel = p->m->cfg.mel_dim;
+    const size_t state = (size_t)rows * mel;
+    float* slots = p->traj + (size_t)(a.steps + 1) * state;  // (ode_methods.h: the slot invariant)
+    const float* vu = a.cfg_on ? p->vout + (size_t)rows * MELP : nullptr;
+    const float* cfgr = a.cfg_rows ? p->cfg_rows : nullptr;  // (read at run time: a replay honours the vector staged by the current call)
+    for (int s = 0; s < a.steps; ++s) {
+        if (sync && s > 0) F5_HIP(hipStreamSynchronize(st));
+        const float* xs = p->traj + (size_t)s * state;
+        float* xn = p->traj + (size_t)(s + 1) * state;
+        for (int j = 0; j < om.evals; ++j) {
+            const int ev = om.evals * s + j;
+            float* xo = j == om.evals - 1 ? xn : p->xmid;
+            F5_TRY(net_eval(p, j == 0 ? xs : p->xmid, rows, nb, N, ev, 0, mask, st));
+            if (om.rk_stage)
+                F5_TRY(launch_rk_stage(xs, p->vout, vu, MELP, rows, mel, a.cfg, p->coefs + ev, om.stage[j], slots, state,
+                                       om.slot[j] >= 0 ? slots + (size_t)om.slot[j] * state : nullptr, xo, st, cfgr));
+            else
+                F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, rows, mel, a.cfg, p->coefs + ev, xo, st, cfgr));
+        }
+    }
+    return 0;
+}
+
+// everything between the staged inputs and the final state traj[steps]; capturable (no syncs, no allocations)
+static int sample_body(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
+    // range guard of the fp16 residual stream: cleared by a KERNEL node of the graph, so every replay starts clean.  (Not hipMemsetAsync: on
+    // ROCm 7.2 the 32-byte memset node captured here cleared the words on the first launch of the instantiated graph and filled them with
+    // two stale host pointers on every replay -- gpurun_out/r3g: [512..519] = {0xf5dffab8, 0x78fe, 0xea66b000, 0x7909} x 2 -- which read as
+    // a raised flag and sent the second sample() of every process through the fp32 fallback.)
+    F5_TRY(launch_fill_f32(reinterpret_cast<float*>(p->sat_flag), 8, 0.0f, st));
+    if (p->rg) {  // one batch item per CFG half: the concatenation of the utterances, T rows; no key mask
+        F5_TRY(ragged_prologue(p, a, st));
+        F5_TRY(sample_steps(p, a, p->rg->T, a.cfg_on ? 2 : 1, p->rg->T, nullptr, false, st));
+    } else {
+        const uint8_t* mask = nullptr;
+        F5_TRY(uniform_prologue(p, a, &mask, st));
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (g_sync_evals) (void)hipStreamIsCapturing(st, &capturing);
+        F5_TRY(sample_steps(p, a, a.B * a.N, a.cfg_on ? 2 * a.B : a.B, a.N, mask, g_sync_evals && capturing == hipStreamCaptureStatusNone, st));
     }
     return plan_attn_dropout_advance(p, sample_call_words(p, a), st);  // (the loop's last node: a replay advances the base as an eager call does)
 }
 
-void plan_drop_graphs(f5_plan_s* p) {
-    for (auto& g : p->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    p->graphs.clear();
+// ----------------------------------------------------------------------------- the graph cache
+template <typename Pred> static void drop_graphs_where(f5_plan_s* p, Pred stale) {
+    p->graphs.erase(std::remove_if(p->graphs.begin(), p->graphs.end(), stale), p->graphs.end());
 }
 
 // the ODE loop of one sample() on the staged inputs: replay of the hipGraph captured for this exact problem, or eager launches
 static int run_sample_loop(f5_plan_s* p, const SampleArgs& a, int use_graph, hipStream_t st) {
     if (use_graph && p->taps.empty() && !p->timing) {
-        GraphEntry* ge = nullptr;
-        for (size_t i = 0; i < p->graphs.size();) {  // a tuning knob changed since the capture: the graph baked the old kernel choice
-            if (p->graphs[i].epoch != g_tuning_epoch) {
-                (void)hipGraphExecDestroy(p->graphs[i].exec);
-                (void)hipGraphDestroy(p->graphs[i].graph);
-                p->graphs.erase(p->graphs.begin() + i);
-            } else {
-                ++i;
-            }
-        }
-        for (auto& g : p->graphs)
-            if (g.B == a.B && g.N == a.N && g.nt == a.nt && g.steps == a.steps && g.method == a.method && g.cfg_on == a.cfg_on &&
-                g.mask_on == a.mask_on && g.cmask_on == a.cmask_on && g.cfg_rows == a.cfg_rows && g.cfg == a.cfg && g.fold_id == (p->fold && g_ln_fold ? p->fold->id : 0) &&
-                g.rn == (p->rg ? p->rg->n : std::vector<int>()))
-                ge = &g;
-        if (!ge) {
-            GraphEntry g{a.B, a.N, a.nt, a.steps, a.method, a.cfg_on, a.mask_on, a.cfg, g_tuning_epoch, (p->fold && g_ln_fold) ? p->fold->id : 0};
-            g.cmask_on = a.cmask_on;
-            g.cfg_rows = a.cfg_rows;
-            if (p->rg) g.rn = p->rg->n;
+        // a tuning knob changed since the capture: the graph baked the old kernel choice
+        drop_graphs_where(p, [](const GraphEntry& g) { return g.key.epoch != g_tuning_epoch; });
+        const GraphKey key{a, g_tuning_epoch, p->fold && g_ln_fold ? p->fold->id : 0, p->rg ? p->rg->n : std::vector<int>()};
+        auto ge = std::find_if(p->graphs.begin(), p->graphs.end(), [&](const GraphEntry& g) { return g.key == key; });
+        if (ge == p->graphs.end()) {
+            GraphEntry g(key);  // (leaving early destroys what it holds by then)
             if (!p->cap_stream) F5_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
             F5_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed));
             int rc = sample_body(p, a, p->cap_stream);
             hipError_t e = hipStreamEndCapture(p->cap_stream, &g.graph);
-            if (rc != 0) {
-                if (g.graph) (void)hipGraphDestroy(g.graph);
-                return rc;
-            }
+            F5_TRY(rc);
             if (e != hipSuccess) return f5_fail(F5_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
             e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
-            if (e != hipSuccess) {
-                (void)hipGraphDestroy(g.graph);
-                return f5_fail(F5_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-            }
-            if (p->graphs.size() >= 32) {  // small LRU-less cache: drop the oldest bucket (32: batch inference over length buckets meets a few dozen shapes)
-                (void)hipGraphExecDestroy(p->graphs[0].exec);
-                (void)hipGraphDestroy(p->graphs[0].graph);
-                p->graphs.erase(p->graphs.begin());
-            }
-            p->graphs.push_back(g);
-            ge = &p->graphs.back();
+            if (e != hipSuccess) return f5_fail(F5_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+            // small LRU-less cache: drop the oldest bucket (32: batch inference over length buckets meets a few dozen shapes)
+            if (p->graphs.size() >= 32) p->graphs.erase(p->graphs.begin());
+            p->graphs.push_back(std::move(g));
+            ge = p->graphs.end() - 1;
         }
         F5_HIP(hipGraphLaunch(ge->exec, st));
     } else {
@@ -270,45 +241,19 @@ static int acquire_fold(f5_plan_s* p, const std::vector<float>& tv, hipStream_t 
         if (p->fold) --p->fold->users;
         p->fold = want;
         if (want) ++want->users;
-        for (size_t i = 0; i < p->graphs.size();) {  // captures that baked another table's addresses
-            if (p->graphs[i].fold_id != (want ? want->id : 0)) {
-                (void)hipGraphExecDestroy(p->graphs[i].exec);
-                (void)hipGraphDestroy(p->graphs[i].graph);
-                p->graphs.erase(p->graphs.begin() + i);
-            } else {
-                ++i;
-            }
-        }
+        const uint64_t id = want ? want->id : 0;  // captures that baked another table's addresses
+        drop_graphs_where(p, [id](const GraphEntry& g) { return g.key.fold_id != id; });
     }
     return 0;
 }
 
-// evaluation times / step coefficients of a fixed grid (fp32 op order of torchdiffeq's fixed-grid solvers) -> p->tvals / p->coefs, and the
-// AdaLN rows of every evaluation time -> p->mod (kept across calls with the same grid on the same stream)
+// evaluation times / coefficient words of a fixed grid (ode_methods.h: ode_time_grid) -> p->tvals / p->coefs, and the AdaLN rows of every
+// evaluation time -> p->mod (kept across calls with the same grid on the same stream)
 static int stage_time_grid(f5_plan_s* p, const float* tgrid_host, int steps, int ode_method, hipStream_t st) {
-#pragma clang fp contract(off)  // t0 + dt * c rounded twice, as torchdiffeq's fp32 tensors compute it
     const OdeMethod& om = *ode_method_of(ode_method);
-    const int E = om.evals, nev = E * steps;
+    const int nev = om.evals * steps;
     std::vector<float> tv(nev), cf(nev);
-    for (int s = 0; s < steps; ++s) {
-        const float t0 = tgrid_host[s], t1 = tgrid_host[s + 1];
-        const float dt = t1 - t0;
-        if (ode_method == F5_ODE_EULER) {
-            tv[s] = t0;
-            cf[s] = dt;
-        } else if (ode_method == F5_ODE_MIDPOINT) {
-            const float half = 0.5f * dt;
-            tv[2 * s] = t0;
-            cf[2 * s] = half;
-            tv[2 * s + 1] = t0 + half;
-            cf[2 * s + 1] = dt;
-        } else {
-            for (int j = 0; j < E; ++j) {
-                tv[E * s + j] = j == 0 ? t0 : (j == E - 1 && om.last_at_t1) ? t1 : t0 + dt * om.c[j];
-                cf[E * s + j] = dt;
-            }
-        }
-    }
+    ode_time_grid(om, tgrid_host, steps, tv.data(), cf.data());
     // The time MLP and every AdaLN row depend only on the evaluation times: a server calls sample() with the same grid every time,
     // so the 0.56 GB weight pass is done once per grid and kept (1.7 ms per call; 3 % of a single-utterance sample()).
     if (p->mod_tv != tv || p->mod_stream != st) {  // the rows are ordered only behind the stream they were computed on
@@ -325,7 +270,6 @@ static int stage_time_grid(f5_plan_s* p, const float* tgrid_host, int steps, int
 // A plan holds ONE deferred sample(): its staged inputs and the device flag words would be overwritten by the next call.  Every entry point
 // that reuses the plan's buffers completes the deferred call first (on the stream it was enqueued on), so a raised range-guard flag is never
 // lost when a caller round-robins more chunks than it has streams.
-extern "C" int f5_sample_finish(f5_plan_t p, f5_stream_t stream);
 int finish_if_pending(f5_plan_s* p) {
     if (p && p->pending.valid) return f5_sample_finish(p, (f5_stream_t)p->pending.stream);
     return 0;
@@ -338,10 +282,7 @@ static int sample_impl(f5_plan_t p, int B, int N, const float* cond, const int32
     F5_TRY(check_plan_shape(p, B, N));
     if (!cond || !text || !lens || !y0 || !tgrid_host || !out) return f5_fail(F5_EINVAL, "null argument");
     if (steps <= 0 || nt <= 0) return f5_fail(F5_EINVAL, "steps and nt must be positive");
-    const OdeMethod* om = ode_method_of(ode_method);
-    if (!om) return f5_fail(F5_EINVAL, "bad ode_method %d", ode_method);
-    const int nev = om->evals * steps;
-    if (nev > p->maxE) return f5_fail(F5_EINVAL, "%d evaluations exceed the plan's max_evals=%d", nev, p->maxE);
+    F5_TRY(check_method_and_evals(p, ode_method, steps));
     F5_TRY(finish_if_pending(p));
     hipStream_t st = (hipStream_t)stream;
     f5_model_s* m = p->m;
@@ -406,46 +347,9 @@ extern "C" int f5_sample_finish(f5_plan_t p, f5_stream_t stream) {
 // infer/f5tts_wrapper.py:476-533; a batch-1 sample() has mask = None, cfm.py:152-155).  Every per-row kernel (GEMMs, LayerNorm, CFG step) runs
 // over the concatenation; the three places where a token sees its neighbours are handled so that each utterance gets exactly the arithmetic
 // of its own batch-1 call: the position conv reads zero gap rows where it would read its zero padding, RoPE takes a per-row position table,
-// attention is launched per utterance on its rows.  Text embedding and the hoisted half of the input embedding are computed per utterance.
-static int sample_body_ragged(f5_plan_s* p, const SampleArgs& a, hipStream_t st) {
-    f5_model_s* m = p->m;
-    const f5_dit_config& c = m->cfg;
-    const Ragged& rg = *p->rg;
-    const int B = a.B, T = rg.T, mel = c.mel_dim, td = c.text_dim;
-    const size_t state = (size_t)T * mel;
-    F5_TRY(launch_fill_f32(reinterpret_cast<float*>(p->sat_flag), 8, 0.0f, st));
-    for (int br = 0; br < (a.cfg_on ? 2 : 1); ++br)
-        for (int u = 0; u < B; ++u) {
-            const int nu = rg.n[u], nt_eff = a.nt < nu ? a.nt : nu;  // tokens beyond the frame count are curtailed (dit.py:51)
-            float* te = p->te[br] + (size_t)rg.off[u] * td;
-            F5_HIP(hipMemcpy2DAsync(p->text_in + (size_t)B * a.nt, (size_t)nt_eff * 4, p->text_in + (size_t)u * a.nt, (size_t)a.nt * 4, (size_t)nt_eff * 4, 1,
-                                    hipMemcpyDeviceToDevice, st));
-            F5_TRY(compute_text_embed(p, p->text_in + (size_t)B * a.nt, nt_eff, 1, nu, br, te, st));
-            // (the staged per-frame condition mask, utterance u's slice at its row offset: a replay sees the current call's mask)
-            F5_TRY(compute_base(p, p->cond_in + (size_t)rg.off[u] * mel, p->lens_in + u, te, 1, nu, br, (size_t)br * T + rg.off[u], st,
-                                a.cmask_on ? p->cmask_in + rg.off[u] : nullptr));
-        }
-    const int nb = a.cfg_on ? 2 : 1;
-    const float* cfgr = a.cfg_rows ? p->cfg_rows : nullptr;  // (read at run time: a replay honours the vector staged by the current call)
-    for (int s = 0; s < a.steps; ++s) {
-        float* xs = p->traj + (size_t)s * state;
-        float* xn = p->traj + (size_t)(s + 1) * state;
-        const float* vu = a.cfg_on ? p->vout + (size_t)T * MELP : nullptr;
-        if (a.method == F5_ODE_EULER) {
-            F5_TRY(net_eval(p, xs, T, nb, T, s, 0, nullptr, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + s, xn, nullptr, st, cfgr));
-        } else if (a.method == F5_ODE_MIDPOINT) {
-            F5_TRY(net_eval(p, xs, T, nb, T, 2 * s, 0, nullptr, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + 2 * s, p->xmid, nullptr, st, cfgr));
-            F5_TRY(net_eval(p, p->xmid, T, nb, T, 2 * s + 1, 0, nullptr, st));
-            F5_TRY(launch_cfg_step(xs, p->vout, vu, MELP, T, mel, a.cfg, p->coefs + 2 * s + 1, xn, nullptr, st, cfgr));
-        } else {
-            F5_TRY(rk_step(p, a, s, xs, xn, T, nb, T, nullptr, st));
-        }
-    }
-    return plan_attn_dropout_advance(p, sample_call_words(p, a), st);
-}
-
+// attention is launched per utterance on its rows.  Text embedding and the hoisted half of the input embedding are computed per utterance
+// (ragged_prologue); the steps are sample_steps over the T rows of a half.
+//
 // f5_sample_ragged and f5_sample_ragged_ex: cond_mask (dev u8 [sum(frames)]) or null = the lens prefix of every utterance; cfg_host (host
 // f32 [B]) or null = cfg_strength for all of them
 static int sample_ragged_impl(f5_plan_t p, int B, const int32_t* frames_host, const float* cond, const int32_t* text, int nt, const int32_t* lens,
@@ -457,10 +361,7 @@ static int sample_ragged_impl(f5_plan_t p, int B, const int32_t* frames_host, co
     f5_model_s* m = p->m;
     if (m->cfg.backbone != F5_BACKBONE_DIT) return f5_fail(F5_ENOTSUP, "f5_sample_ragged: DiT backbone only");
     if (B <= 0 || B > p->maxB || steps <= 0 || nt <= 0 || nt > p->maxN) return f5_fail(F5_EINVAL, "bad B / steps / nt for this plan");
-    const OdeMethod* om = ode_method_of(ode_method);
-    if (!om) return f5_fail(F5_EINVAL, "bad ode_method %d", ode_method);
-    const int nev = om->evals * steps;
-    if (nev > p->maxE) return f5_fail(F5_EINVAL, "%d evaluations exceed the plan's max_evals=%d", nev, p->maxE);
+    F5_TRY(check_method_and_evals(p, ode_method, steps));
     if (!p->taps.empty() || p->timing) return f5_fail(F5_ESTATE, "f5_sample_ragged: stage taps / in-situ timing are not available here");
     // One doubled batch cannot hold utterances of both branches of cfm.py:167 (below 1e-5 the reference makes ONE pass, and its bits are
     // those of an undoubled batch): refused before anything is staged or launched; the caller keeps such requests in different calls.
@@ -475,12 +376,10 @@ static int sample_ragged_impl(f5_plan_t p, int B, const int32_t* frames_host, co
     }
     const bool cfg_vec = cfg_host && cfg_on;  // (below 1e-5 no combine runs: the vector has nothing to say)
     Ragged rg;
-    size_t total = 0;
     for (int u = 0; u < B; ++u) {
         if (frames_host[u] <= 0 || frames_host[u] > p->maxN) return f5_fail(F5_EINVAL, "utterance %d: %d frames outside 1 .. %d", u, frames_host[u], p->maxN);
         rg.off.push_back(rg.T);
         rg.n.push_back(frames_host[u]);
-        total += (size_t)frames_host[u];
         rg.T = (int)round_up((size_t)rg.T + frames_host[u] + RAGGED_GAP, 16);
     }
     const size_t bn_cap = (size_t)p->maxB * p->maxN;
@@ -541,7 +440,6 @@ static int sample_ragged_impl(f5_plan_t p, int B, const int32_t* frames_host, co
                                   out + src * mel, st));
         src += (size_t)rg.n[u];
     }
-    (void)total;
     return 0;
 }
 

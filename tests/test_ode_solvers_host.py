@@ -1,6 +1,6 @@
 """The Runge-Kutta members of torchdiffeq's fixed-grid family (rk4 = rk4_alt_step_func, heun2, heun3) on the host: CFM.sample over a CPU
 backbone against an independent restatement of the step functions, their convergence order on a linear ODE, the methods that stay refused,
-and the C ABI declaration.  No GPU needed; tests/test_gpu_ode_solvers.py runs the same methods on the fused sampler."""
+the C ABI declaration, and the solver table's time grid (csrc/ode_methods.h, compiled with g++) against the per-method rules.  No GPU needed; tests/test_gpu_ode_solvers.py runs the same methods on the fused sampler."""
 import math
 import os
 import re
@@ -181,3 +181,95 @@ def test_rk_solvers_are_declared_and_exported():
     if nm:
         syms = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
         assert re.search(r"\bT f5_ode_evals_per_step$", syms, re.M)
+
+
+_GRID_PROGRAM = r"""
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <vector>
+#include "ode_methods.h"
+/* stdin: "method steps" and the steps + 1 grid words in hex, per case; stdout: the tv words, then the cf words of the case */
+int main() {
+    int method, steps;
+    while (scanf("%d %d", &method, &steps) == 2) {
+        const OdeMethod* om = ode_method_of(method);
+        if (!om) return 2;
+        std::vector<float> grid(steps + 1), tv(om->evals * steps), cf(om->evals * steps);
+        for (float& g : grid) {
+            uint32_t w;
+            if (scanf("%x", &w) != 1) return 3;
+            memcpy(&g, &w, 4);
+        }
+        ode_time_grid(*om, grid.data(), steps, tv.data(), cf.data());
+        for (const std::vector<float>* v : {&tv, &cf}) {
+            for (float f : *v) {
+                uint32_t w;
+                memcpy(&w, &f, 4);
+                printf("%08x ", w);
+            }
+            printf("\n");
+        }
+    }
+    return ode_method_of(5) || ode_method_of(-1);
+}
+"""
+
+
+def _restated_grid(method, t):
+    """(tv, cf) of the float32 grid `t`: the evaluation times and step coefficients of torchdiffeq's fixed-grid rules, one float32 rounding per
+    operation (numpy float32 scalars), written out per method."""
+    import numpy as np
+    f = np.float32
+    third, two_thirds, half = f(1 / 3), f(2 / 3), f(0.5)
+    tv, cf = [], []
+    for t0, t1 in zip(t[:-1], t[1:]):
+        dt = t1 - t0
+        if method == "euler":
+            tv += [t0]
+            cf += [dt]
+        elif method == "midpoint":
+            tv += [t0, t0 + dt * half]
+            cf += [half * dt, dt]
+        elif method == "rk4":
+            tv += [t0, t0 + dt * third, t0 + dt * two_thirds, t1]
+            cf += [dt] * 4
+        elif method == "heun2":
+            tv += [t0, t0 + dt]
+            cf += [dt] * 2
+        else:
+            tv += [t0, t0 + dt * third, t0 + dt * two_thirds]
+            cf += [dt] * 3
+    assert all(type(v) is np.float32 for v in tv + cf)
+    return np.array(tv, dtype=f), np.array(cf, dtype=f)
+
+
+def test_time_grid_header_compiled_with_gxx_equals_the_restated_rules(tmp_path):
+    """csrc/ode_methods.h is plain host C++ (g++ -Wall -Werror, contraction off) and its table-driven ode_time_grid gives, bit for bit, the
+    evaluation times and coefficient words of the per-method rules: five methods x steps 1, 2, 7, 32 x the linear grid and the grid swayed with -1."""
+    import numpy as np
+    from eraxvif5tts_amd import _lib
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed: ode_methods.h must compile as plain host C++"
+    src, exe = tmp_path / "ode_grid.cpp", tmp_path / "ode_grid"
+    src.write_text(_GRID_PROGRAM)
+    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-ffp-contract=off", "-I", os.path.join(ROOT, "eraxvif5tts_amd", "csrc"), str(src),
+                    "-o", str(exe)], check=True)
+    cases, lines = [], []
+    for method in ("euler", "midpoint", "rk4", "heun2", "heun3"):
+        for steps in (1, 2, 7, 32):
+            for sway in (None, -1.0):
+                t = cpu_ref.time_grid(steps, sway).float().numpy()
+                assert t.dtype == np.float32 and t.shape == (steps + 1,)
+                cases.append((method, steps, sway, t))
+                lines.append(f"{_lib.ODE_METHODS[method]} {steps} " + " ".join(f"{int(w):08x}" for w in t.view(np.uint32)))
+    out = subprocess.run([str(exe)], input="\n".join(lines) + "\n", check=True, capture_output=True, text=True).stdout.split("\n")
+    assert len(out) == 2 * len(cases) + 1
+    words = 0
+    for i, (method, steps, sway, t) in enumerate(cases):
+        tv, cf = _restated_grid(method, t)
+        for name, want, line in (("tv", tv, out[2 * i]), ("cf", cf, out[2 * i + 1])):
+            got = np.array([int(w, 16) for w in line.split()], dtype=np.uint32)
+            assert got.shape == want.shape and (got == want.view(np.uint32)).all(), (method, steps, sway, name)
+            words += got.size
+    assert words == 2 * 2 * (1 + 2 + 4 + 2 + 3) * (1 + 2 + 7 + 32)
