@@ -97,7 +97,11 @@ _PROTOS = {
     "f5_cfm_noise": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "f5_cfm_loss_workspace": (C.c_int64, [_I, _I, _I]),
     "f5_cfm_loss": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "f5_align_similarity": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_distill_loss_workspace": (C.c_int64, [_I, _I, _I]),
+    "f5_distill_loss": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_plan_set_blocks": (_I, [_P, _P, _I]),
+    "f5_plan_get_blocks": (_I, [_P, _P, _I]),
+    "f5_align_similarity":(_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f5_align_workspace": (C.c_int64, [_I, _I, _I]),
     "f5_align_viterbi": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
     "f5_align_window": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),

@@ -96,8 +96,9 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     // them: every other kernel works on `rows`, attention on the utterances' own rows.
     const int rows_g = (rmw && g_gemm_pad_rows && rows >= 3584 /* from here on the fused projection takes the 256-wide persistent tile */ && rows % 256 != 0 && (size_t)((rows + 255) / 256 * 256) <= p->rows_cap) ? (rows + 255) / 256 * 256 : rows;
     const FoldTable* ft = p->fold;
+    // (not under a block subset: the table and block 0's second weight copy are laid out for the full depth -- no fold, q as projected)
     const bool lnf = rmw && g_ln_fold && ft && p->lnf_stats && p->fold_eval >= 0 && p->fold_eval < (int)ft->tv.size() && p->gemm_kernel != 0 &&
-                     (p->gemm_kernel == 1 || rows >= 512) && D % 64 == 0 && inner % 64 == 0 && ff % 64 == 0;
+                     (p->gemm_kernel == 1 || rows >= 512) && D % 64 == 0 && inner % 64 == 0 && ff % 64 == 0 && p->sub.empty();
     // pre-scaled q: the table's q rows and block 0's second weight copy carry the softmax scale, the attention kernels apply none
     const bool qs = lnf && ft->qscaled && plan_attn_prescale(p);
     if (lnf && ft->qscaled && !qs) return f5_fail(F5_ESTATE, "dit_eval: the fold table holds pre-scaled q rows, the plan runs without them");
@@ -135,10 +136,16 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         }
         return 0;
     };
-    for (int l = 0; l < c.depth; ++l) {
+    // Block subset (f5_plan_set_blocks): position j of the walk runs model block l = sub[j] -- its weights, its AdaLN rows, its prefetch sets --
+    // and everything that speaks of the first, the previous or the last block (the position-conv branch, the long-skip copy, tap names, guard
+    // tags, the dropout call word) keys on j: the evaluation of the model whose blocks are the subset renumbered.  No subset: l = j.
+    const int nblk = plan_depth(p);
+    auto block_at = [&](int j) { return p->sub.empty() ? j : p->sub[j]; };
+    for (int j = 0; j < nblk; ++j) {
+        const int l = block_at(j);
         const BlockW& b = m->blocks[l];
         const float* ml = modp + (size_t)l * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp (modules.py:312)
-        const std::string tn = "blk" + std::to_string(l);
+        const std::string tn = "blk" + std::to_string(j);
         const bool in16 = r16;
         const void* xin = in16 ? p->xres16 : (const void*)p->xres;
         void* xout = r16 ? p->xres16 : (void*)p->xres;
@@ -151,7 +158,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         const bool wpf = r16 && g_w_prefetch && rows <= g_w_prefetch;
         const size_t wes = f5_elem_size(P);
         PrefetchSet pf1{{b.w_o, b.w_ff1, nullptr, nullptr}, {(unsigned)(D * inner * wes), (unsigned)(ff * D * wes), 0u, 0u}};
-        PrefetchSet pf2{{b.w_ff2, l + 1 < c.depth ? m->blocks[l + 1].w_qkv : nullptr, nullptr, nullptr},
+        PrefetchSet pf2{{b.w_ff2, j + 1 < nblk ? m->blocks[block_at(j + 1)].w_qkv : nullptr, nullptr, nullptr},
                         {(unsigned)(D * ff * wes), (unsigned)(3 * inner * D * wes), 0u, 0u}};
         // (LayerNorm fold: the statistics kernels sit where the passes sat and prefetch what runs behind THEM -- the one behind the out-projection
         //  this block's W' rows of ff.0.0 and the FF2 weight, the one behind FF2 the next block's W' rows of q|k|v and its out-projection weight)
@@ -168,15 +175,15 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         const float *fc1 = lnf ? ft->c1 + frow0 + (size_t)l * fR : nullptr, *fc2 = lnf ? ft->c2 + frow0 + (size_t)l * fR : nullptr;
         if (!lnf1) F5_TRY(timed(p, F5_SITE_LN1, st, [&] {
             if (rmw)
-                return launch_layernorm_res(P, xin, 1, xout, 1, D, rows, D, l == 0 ? p->yT : nullptr, D, nullptr, 1, ml + D, ml, mod_bstride, N, 1, p->hT, D, st,
-                                            wpf ? &pf1 : nullptr, sat, 1 | (l << 4));
+                return launch_layernorm_res(P, xin, 1, xout, 1, D, rows, D, j == 0 ? p->yT : nullptr, D, nullptr, 1, ml + D, ml, mod_bstride, N, 1, p->hT, D, st,
+                                            wpf ? &pf1 : nullptr, sat, 1 | (j << 4));
             return launch_layernorm_res(P, xin, in16, xout, r16, D, rows, D, p->yT, D, nullptr, defer ? 2 : 1, ml + D, ml, mod_bstride, N, 1, p->hT, D, st,
-                                        wpf ? &pf1 : nullptr, sat, 1 | (l << 4));
+                                        wpf ? &pf1 : nullptr, sat, 1 | (j << 4));
         }));
-        if (l == 0) F5_TRY(tap_f32(p, "input_embed", p->xres, D, rows, D, st));
-        if (l == 0 && c.long_skip)  // residual = x  (dit.py:217-218)
+        if (j == 0) F5_TRY(tap_f32(p, "input_embed", p->xres, D, rows, D, st));
+        if (j == 0 && c.long_skip)  // residual = x  (dit.py:217-218)
             F5_HIP(hipMemcpyAsync(p->skips[0], p->xres, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (l > 0) F5_TRY(tap_f32(p, "blk" + std::to_string(l - 1) + ".out", p->xres, D, rows, D, st));
+        if (j > 0) F5_TRY(tap_f32(p, "blk" + std::to_string(j - 1) + ".out", p->xres, D, rows, D, st));
         F5_TRY(tap_t(p, tn + ".n1", p->hT, D, rows, D, st));
         g = gp_zero();
         const void* const wqkv = (qs && b.w_qkv_qs) ? b.w_qkv_qs : b.w_qkv;  // (block 0: the only unfolded projection of a folded evaluation)
@@ -230,13 +237,13 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         }
         if (rg) {  // every utterance gets the computation of the launch its own batch-1 sample() makes, on its rows of both halves; the ones
                    // that launch would give to the pipelined kernel share launches (grid.z = utterance x branch, 12 utterances per table)
-            const AttnDropout drop = plan_attn_dropout(p, l, 0, (uint32_t)rg->n.size());  // batch word = branch * B + u
+            const AttnDropout drop = plan_attn_dropout(p, j, 0, (uint32_t)rg->n.size());  // batch word = branch * B + u
             F5_TRY(launch_attention_ragged_all(P, p->attn_kernel, nb, (int)rg->n.size(), rg->off.data(), rg->n.data(), c.heads, p->qkv, 3 * inner, p->cT, inner,
                                                st, N, qs, &drop));
         } else {
             int kind = 0;
             if (p->attn_kernel != 0 && attention_fast_supported(P, N, c.heads)) kind = 1;
-            const AttnDropout drop = plan_attn_dropout(p, l);  // batch word = row of the (CFG-doubled) batch
+            const AttnDropout drop = plan_attn_dropout(p, j);  // batch word = row of the (CFG-doubled) batch
             F5_TRY(timed(p, F5_SITE_ATTN, st, [&] { return launch_attention(P, kind, nb, N, c.heads, p->qkv, 3 * inner, mask, p->cT, inner, st, 0, qs, &drop); }));
         }
         if (float* d = tap_dst(p, tn + ".attn")) {  // Attention module output before gating (extra GEMM, debug only)
@@ -264,9 +271,9 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         if (!lnf) F5_TRY(timed(p, F5_SITE_LN2, st, [&] {
             if (rmw)
                 return launch_layernorm_res(P, xin, 1, xout, 1, D, rows, D, nullptr, D, nullptr, 1, ml + 4 * D, ml + 3 * D, mod_bstride, N, 1, p->hT, D, st,
-                                            wpf ? &pf2 : nullptr, sat, 2 | (l << 4));
+                                            wpf ? &pf2 : nullptr, sat, 2 | (j << 4));
             return launch_layernorm_res(P, xin, in16, xout, r16, D, rows, D, p->yT, D, defer ? p->yA : nullptr, defer ? 3 : 1, ml + 4 * D, ml + 3 * D,
-                                        mod_bstride, N, 1, p->hT, D, st, wpf ? &pf2 : nullptr, sat, 2 | (l << 4));
+                                        mod_bstride, N, 1, p->hT, D, st, wpf ? &pf2 : nullptr, sat, 2 | (j << 4));
         }));
         g = gp_zero();
         g.A = p->hT; g.lda = D; g.W = b.w_ff1; g.ldw = D; g.M = rows_g; g.N = ff; g.K = D;
@@ -299,7 +306,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     else
         F5_TRY(launch_layernorm_res(P, r16 ? p->xres16 : (const void*)p->xres, r16, r16 ? p->xres16 : (void*)p->xres, r16, D, rows, D, p->yT, D, nullptr,
                                     defer ? 2 : 1, mf, mf + D, mod_bstride, N, 1, p->hT, D, st, nullptr, sat, 3));
-    F5_TRY(tap_f32(p, "blk" + std::to_string(c.depth - 1) + ".out", p->xres, D, rows, D, st));
+    F5_TRY(tap_f32(p, "blk" + std::to_string(nblk - 1) + ".out", p->xres, D, rows, D, st));
     if (c.long_skip) {  // x = long_skip_connection(cat(x, residual))  (dit.py:227-228), then the final AdaLN on it
         const size_t es = f5_elem_size(P);
         F5_TRY(launch_convert_pad(P, p->xres, D, rows, D, D, p->catT, 2 * D, st));

@@ -18,7 +18,7 @@ AttnDropout plan_attn_dropout(const f5_plan_s* p, int l, uint32_t bw0, uint32_t 
     d.prob = p->drop_p;
     d.seed = p->drop_seed;
     d.base = p->drop_base;
-    d.offset = (uint32_t)p->drop_eval * (uint32_t)p->m->cfg.depth + (uint32_t)l;
+    d.offset = (uint32_t)p->drop_eval * (uint32_t)plan_depth(p) + (uint32_t)l;
     d.bw0 = bw0;
     d.bw_step = bw_step;
     return d;
@@ -163,8 +163,8 @@ extern "C" int f5_dit_forward(f5_plan_t p, int B, int N, const float* x, const f
     F5_TRY(compute_modulation(p, time, B, st));
     F5_TRY(compute_base(p, cond, nullptr, text_embed, B, N, drop_audio_cond, 0, st));
     F5_TRY(net_eval(p, x, B * N, B, N, 0, 1, mask, st));
-    F5_TRY(plan_attn_dropout_advance(p, (uint32_t)m->cfg.depth, st));
-    p->drop_base_host += p->drop_p > 0.0 ? (uint32_t)m->cfg.depth : 0u;
+    F5_TRY(plan_attn_dropout_advance(p, (uint32_t)plan_depth(p), st));
+    p->drop_base_host += p->drop_p > 0.0 ? (uint32_t)plan_depth(p) : 0u;
     return launch_convert_back(F5_PREC_FP32, p->vout, MELP, B * N, m->cfg.mel_dim, out, m->cfg.mel_dim, st);
 }
 

@@ -634,6 +634,45 @@ extern "C" int f5_plan_set_attn_dropout(f5_plan_t p, float prob, uint64_t seed) 
     return 0;
 }
 
+// Block subset: every check comes before any change.  Captured graphs baked the previous walk; the attention-dropout call
+// words of a call are evaluations x plan_depth, so the host mirror stays valid (the base word itself does not move).
+extern "C" int f5_plan_set_blocks(f5_plan_t p, const int32_t* blocks_host, int count) {
+    if (!p) return f5_fail(F5_EINVAL, "null plan");
+    const f5_dit_config& c = p->m->cfg;
+    const bool clear = blocks_host == nullptr && count == 0;
+    if (!clear) {
+        if (c.backbone == F5_BACKBONE_UNETT)
+            return f5_fail(F5_ENOTSUP, "f5_plan_set_blocks: UNetT pairs its layers through skip connections, a subset of them is not a model");
+        if (c.backbone == F5_BACKBONE_MMDIT)
+            return f5_fail(F5_ENOTSUP, "f5_plan_set_blocks: block subsets are built for the DiT backbone, not for MMDiT");
+        if (!blocks_host || count < 1) return f5_fail(F5_EINVAL, "f5_plan_set_blocks: the block list is empty");
+        if (count > c.depth) return f5_fail(F5_EINVAL, "f5_plan_set_blocks: %d blocks listed, the model has %d", count, c.depth);
+        for (int i = 0; i < count; ++i) {
+            if (blocks_host[i] < 0 || blocks_host[i] >= c.depth)
+                return f5_fail(F5_EINVAL, "f5_plan_set_blocks: block %d is outside [0, %d)", (int)blocks_host[i], c.depth);
+            if (i > 0 && blocks_host[i] <= blocks_host[i - 1])
+                return f5_fail(F5_EINVAL, "f5_plan_set_blocks: the block list must be strictly increasing (%d follows %d)", (int)blocks_host[i],
+                               (int)blocks_host[i - 1]);
+        }
+    }
+    F5_TRY(finish_if_pending(p));  // a deferred sample() still owns the plan: its fp32 rerun must walk the blocks it walked
+    F5_HIP(hipDeviceSynchronize());
+    if (clear)
+        p->sub.clear();
+    else
+        p->sub.assign(blocks_host, blocks_host + count);
+    plan_drop_graphs(p);
+    return 0;
+}
+
+// the subset read back: returns the number of blocks of the subset (0 = none set: all blocks) and writes min(count, cap) of them
+extern "C" int f5_plan_get_blocks(f5_plan_t p, int32_t* blocks_host, int cap) {
+    if (!p) return f5_fail(F5_EINVAL, "null plan");
+    if (cap < 0 || (cap > 0 && !blocks_host)) return f5_fail(F5_EINVAL, "f5_plan_get_blocks: null buffer");
+    for (int i = 0; i < cap && i < (int)p->sub.size(); ++i) blocks_host[i] = p->sub[i];
+    return (int)p->sub.size();
+}
+
 extern "C" int f5_plan_get_option(f5_plan_t p, const char* key, int* value) {
     if (!p || !key || !value) return f5_fail(F5_EINVAL, "null argument");
     if (strcmp(key, "gemm_kernel") == 0)

@@ -208,6 +208,9 @@ struct f5_plan_s {
     FoldTable* fold = nullptr;
     float *lnf_stats = nullptr, *lnf_stats2 = nullptr, *lnf_partial = nullptr;  // (two statistics tables: a site's pivots are the previous site's means)
     int fold_eval = -1;  // evaluation index of the running net_eval (-1: no table row applies, e.g. f5_dit_forward's per-sample times)
+    // Block subset (f5_plan_set_blocks): the model blocks an evaluation runs, strictly increasing; empty = all of them.  The
+    // plan then behaves as a plan of the model whose blocks are these renumbered 0 .. size - 1 (plan_depth); the LayerNorm fold is off under one.
+    std::vector<int> sub;
     std::map<std::string, float*> taps;
     std::vector<float> mod_tv;  // evaluation times the AdaLN rows in `mod` were computed for (empty = stale); see f5_sample
     hipStream_t mod_stream = nullptr;  // ... and the stream they were computed on (a call on another stream recomputes them)
@@ -255,6 +258,8 @@ template <typename F> static int timed(f5_plan_s* p, int site, hipStream_t st, F
     return rc;
 }
 
+// blocks one evaluation of the plan runs: the model's depth, or the size of its block subset
+inline int plan_depth(const f5_plan_s* p) { return p->sub.empty() ? p->m->cfg.depth : (int)p->sub.size(); }
 inline void plan_drop_graphs(f5_plan_s* p) { p->graphs.clear(); }  // destroys every captured graph of the plan
 int finish_if_pending(f5_plan_s* p);  // completes a deferred sample() before the plan's buffers are reused (sampler.hip)
 
@@ -262,7 +267,7 @@ int finish_if_pending(f5_plan_s* p);  // completes a deferred sample() before th
 // ---- eval_common.hip
 bool plan_res_f16(const f5_plan_s* p);
 bool plan_attn_prescale(const f5_plan_s* p);  // pre-scaled q wanted and possible for this plan (what its fold table is built for)
-// the dropout descriptor of block l's attention call in the running evaluation (prob 0 when the mode is off)
+// the dropout descriptor of the attention call of the block at position l (of plan_depth) in the running evaluation (prob 0 when the mode is off)
 AttnDropout plan_attn_dropout(const f5_plan_s* p, int l, uint32_t bw0 = 0, uint32_t bw_step = 1);
 int plan_attn_dropout_advance(f5_plan_s* p, uint32_t by, hipStream_t st);  // no-op when the mode is off
 GemmParams gp_zero();

@@ -25,7 +25,7 @@ static int check_method_and_evals(const f5_plan_s* p, int ode_method, int steps)
 // ----------------------------------------------------------------------------- the sample loop
 // attention dropout: call words one sample loop consumes (evaluations x blocks)
 static uint32_t sample_call_words(const f5_plan_s* p, const SampleArgs& a) {
-    return (uint32_t)(ode_method_of(a.method)->evals * a.steps) * (uint32_t)p->m->cfg.depth;
+    return (uint32_t)(ode_method_of(a.method)->evals * a.steps) * (uint32_t)plan_depth(p);
 }
 
 // Prologue of a uniform batch [B, N]: text embeddings, the hoisted half of the input embedding, the key mask of the durations, the MMDiT text
@@ -201,7 +201,7 @@ static int acquire_fold(f5_plan_s* p, const std::vector<float>& tv, hipStream_t 
     f5_model_s* m = p->m;
     const int nev = (int)tv.size();
     FoldTable* want = nullptr;
-    if (m->w_fold && g_ln_fold && p->lnf_stats && nev > 0 && nev <= F5_FOLD_MAX_EVALS) {
+    if (m->w_fold && g_ln_fold && p->lnf_stats && nev > 0 && nev <= F5_FOLD_MAX_EVALS && p->sub.empty() /* the table is laid out for the full depth */) {
         const bool qs = plan_attn_prescale(p);
         for (FoldTable* t : m->folds)
             if (t->tv == tv && t->qscaled == qs) want = t;

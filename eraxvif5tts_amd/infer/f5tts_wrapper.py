@@ -161,6 +161,12 @@ class F5TTSWrapper:
     def _load_checkpoint(self, model, ckpt_path, dtype=None, use_ema=True):
         return load_checkpoint(model, ckpt_path, self.device, dtype=dtype, use_ema=use_ema)
 
+    def set_active_blocks(self, blocks=None):
+        """Speak with a subset of the backbone's blocks (``DiT.set_active_blocks``): generate(), generate_stream(), generate_multi() and
+        generate_batch() then run the pruned model on the weights already loaded -- a pruning choice can be listened to before any checkpoint
+        is written (``eval.prune.prune_checkpoint``).  None restores all blocks."""
+        self.model.transformer.set_active_blocks(blocks)
+
     # ------------------------------------------------------------------ reference voice
     def preprocess_reference(self, ref_audio_path: str, ref_text: str = "", clip_short: bool = True, on_device: Optional[bool] = None):
         """``on_device``: True runs the clip / trim / pad / mono / boost steps on the GPU (`infer.reference.prepare_reference_device`: the same

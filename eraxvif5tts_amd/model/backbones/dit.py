@@ -143,6 +143,8 @@ class DiT(nn.Module):
         self._fallbacks_seen = {}
         self._pending = {}  # plan handle -> stream of a sample() whose range-guard check was deferred (finish_pending)
         self._attn_dropout = None  # (p, seed, plans numbered so far) while the attention-dropout mode is on (set_attn_dropout)
+        self._active_blocks = None  # the block subset every plan runs (set_active_blocks); None = all blocks
+        self._residual_f16 = None  # residual-stream storage asked of every plan (set_residual_f16); None = the library's choice
         self.register_load_state_dict_post_hook(lambda module, _keys: module._drop_native())
 
     # ------------------------------------------------------------------ native handle management
@@ -227,7 +229,78 @@ class DiT(nn.Module):
         self._plans.append(((stream, batch, seq_cap, max(evals, 1)), h))
         if self._attn_dropout is not None:
             self._apply_attn_dropout(h)
+        if self._active_blocks is not None:
+            self._apply_active_blocks(h)
+        if self._residual_f16 is not None:
+            _lib.check(lib.f5_plan_set_option(h, b"residual_f16", int(self._residual_f16)), "plan_set_option")
         return h
+
+    @property
+    def residual_f16(self):
+        """The residual-stream storage asked of every plan (set_residual_f16): True / False, or None = the library's choice."""
+        return self._residual_f16
+
+    def set_residual_f16(self, value=None):
+        """Residual-stream storage of the 16-bit modes (plan option "residual_f16"): True = saturating fp16 (the production default), False =
+        fp32, None = the library's choice again.  The arithmetic and the branch dtypes do not change.  fp16 storage rounds the stream once per
+        block, so two models that differ by a block rounding differently even where that block adds exact zeros: measurements that compare
+        two models (eval.distill) run with fp32 storage.  Applies to the live plans (their captured graphs are dropped) and to later ones."""
+        self._residual_f16 = None if value is None else bool(value)
+        for _, h in self._plans:
+            self._finish_plan(h)
+            _lib.check(_lib.load().f5_plan_set_option(h, b"residual_f16", -1 if value is None else int(bool(value))), "plan_set_option")
+
+    # the library's refusals (csrc/model.hip: f5_plan_set_blocks), raised here before any plan exists
+    _SUBSET_REFUSALS = {_lib.F5_BACKBONE_UNETT: "f5_plan_set_blocks: UNetT pairs its layers through skip connections, a subset of them is not a model",
+                        _lib.F5_BACKBONE_MMDIT: "f5_plan_set_blocks: block subsets are built for the DiT backbone, not for MMDiT"}
+
+    @property
+    def active_blocks(self):
+        """The block subset in force (a tuple of block indices), or None: all blocks."""
+        return self._active_blocks
+
+    def set_active_blocks(self, blocks=None):
+        """Run only ``blocks`` (strictly increasing indices in [0, depth)) of this model, on the weights already in HBM -- layer pruning
+        auditioned before any checkpoint is written (reference src/model_pruning).  forward(), sample() and the ragged sampler then compute what
+        ``self.pruned(blocks)`` computes (include/f5hip.h: f5_plan_set_blocks; the LayerNorm fold is off under a subset, so against a pruned
+        model that runs folded the agreement is to rounding, not to the bit).  None restores all blocks: every bit and launch as before.  It
+        applies to the live plans and to plans created later, and survives refresh_native() and load_state_dict().  UNetT and MMDiT raise
+        NotImplementedError with the library's message; a bad list raises ValueError; nothing changes in either case."""
+        if blocks is None:
+            self._active_blocks = None
+            for _, h in self._plans:
+                self._finish_plan(h)
+                _lib.check(_lib.load().f5_plan_set_blocks(h, None, 0), "plan_set_blocks")
+            return
+        if self.BACKBONE in self._SUBSET_REFUSALS:
+            raise NotImplementedError(self._SUBSET_REFUSALS[self.BACKBONE])
+        from ...eval.prune import check_blocks
+        self._active_blocks = tuple(check_blocks(blocks, self.depth))
+        for _, h in self._plans:
+            self._apply_active_blocks(h)
+
+    def _apply_active_blocks(self, h):
+        self._finish_plan(h)
+        arr = (C.c_int32 * len(self._active_blocks))(*self._active_blocks)
+        _lib.check(_lib.load().f5_plan_set_blocks(h, arr, len(arr)), "plan_set_blocks")
+
+    def pruned(self, blocks):
+        """A new DiT of depth ``len(blocks)`` whose parameters are copies of the kept blocks' and of everything outside the blocks
+        (``eval.prune.prune_state_dict`` of this model's state dict): the model a pruned checkpoint loads into."""
+        if self.BACKBONE in self._SUBSET_REFUSALS:
+            raise NotImplementedError(self._SUBSET_REFUSALS[self.BACKBONE])
+        from ...eval.prune import check_blocks, prune_state_dict
+        blocks = check_blocks(blocks, self.depth)
+        names = {v: k for k, v in _lib.PRECISIONS.items()}
+        layouts = {_lib.F5_ROPE_ADJACENT: "adjacent", _lib.F5_ROPE_HALF_SPLIT: "half_split"}
+        new = type(self)(dim=self.dim, depth=len(blocks), heads=self.heads, dim_head=self.dim_head, ff_mult=(self.ff_inner + 0.5) / self.dim,  # (int(dim * ff_mult) gives ff_inner back whatever the division rounds to)
+                         mel_dim=self.mel_dim, text_num_embeds=self.text_num_embeds, text_dim=self.text_dim,
+                         text_mask_padding=self.text_mask_padding, qk_norm=self.qk_norm, conv_layers=self.conv_layers,
+                         pe_attn_head=self.pe_attn_head, long_skip_connection=self.long_skip, precision=names[self.precision],
+                         rope_layout=layouts[self.rope_layout])
+        assert new.ff_inner == self.ff_inner, (new.ff_inner, self.ff_inner)
+        new.load_state_dict(prune_state_dict(self.state_dict(), blocks))
+        return new
 
     def set_attn_dropout(self, p, seed=None):
         """Opt-in attention dropout: the reference's F.scaled_dot_product_attention(dropout_p=0.1) stays live under model.eval()

@@ -33,7 +33,7 @@ extern "C" {
 /* the library is built with -fvisibility=hidden: only the entry points declared here are exported */
 #define F5_API __attribute__((visibility("default")))
 
-#define F5HIP_VERSION 400 /* 0.4.0 (round 4; round 5 adds f5_vocoder_decode_ragged, f5_wave_finish and f5_bigvgan_decode_ragged (+ tuning key "bigvgan_group_frames") under the same number, which tests/test_host_logic.py pins: detect them by symbol): + the BigVGAN entry points and mel front-end, f5_op_ln_fold, bounded timing ring; plan options "ln_fold_active", "gemm_w4"; tuning keys "ln_fold", "gemm_w4"; 0.3.2: + f5_sample_ragged, f5_mmdit_forward, f5_duration_predict_g */
+#define F5HIP_VERSION 400 /* 0.4.0 (round 4; round 5 adds f5_vocoder_decode_ragged, f5_wave_finish and f5_bigvgan_decode_ragged (+ tuning key "bigvgan_group_frames") under the same number, which tests/test_host_logic.py pins: detect them by symbol -- as f5_plan_set_blocks, f5_plan_get_blocks and f5_distill_loss after them): + the BigVGAN entry points and mel front-end, f5_op_ln_fold, bounded timing ring; plan options "ln_fold_active", "gemm_w4"; tuning keys "ln_fold", "gemm_w4"; 0.3.2: + f5_sample_ragged, f5_mmdit_forward, f5_duration_predict_g */
 
 /* error codes */
 #define F5_OK 0
@@ -231,6 +231,25 @@ F5_API int64_t f5_cfm_loss_workspace(int B, int N, int mel);
 F5_API int f5_cfm_loss(int B, int N, int mel, const float* pred, const float* x1, const float* x0, const uint8_t* span, double* sums,
                        int64_t* counts, float* loss, void* workspace, f5_stream_t stream);
 
+/* ------------------------------------------------------------------ distillation losses (train/distil_reload.py:1070-1097; forward only)
+ * The losses the reference's teacher-to-student distillation script logs per update, for judging a pruned model against the model it was cut
+ * from: no gradient of anything here exists.  Detected by symbol.  student, teacher (the two backbones' predictions on the same phi and cond),
+ * x1, x0 dev f32 [B, N, mel]; span dev u8 [B, N].  One pass forms, per element of a row where span is set, with every fp32 step rounded on its own,
+ *   flow = x1 - x0;   term 0 = (student - flow)^2;   term 1 = (teacher - flow)^2;   term 2 = (student - teacher)^2;   term 3 = |student - teacher|
+ * -- the values F.mse_loss / F.l1_loss(reduction = "none") form -- and sums each in fp64 in the fixed order of the flow-matching loss above (per-workgroup
+ * partials in `workspace`, added by index, no atomics: the same input gives the same bits).  Rows outside the span are not read.
+ *   sums   dev f64 [B, 4]   per utterance and term
+ *   frames dev i64 [B]      selected FRAMES, not frames x mel: the script divides by rand_span_mask.sum() (:1072, :1093), so its losses are mel
+ *                           times a mean.  The quirk is kept.
+ *   batch  dev f32 [4]      each term summed over the utterances in order and divided by max(total frames, 1): the script's clamp(min = 1)
+ *                           makes an empty span give 0, not NaN (unlike the flow-matching loss above)
+ * workspace: dev, 8-byte aligned, at least the bytes the _workspace entry answers (a negative F5_* code for a shape it refuses).  Shape limits
+ * and refusals as for the flow-matching loss: F5_EINVAL with a message for a null pointer or B, N or mel below 1.  16-byte loads when mel % 4 == 0
+ * and the four tensors are 16-byte aligned, element loads otherwise.  Nothing synchronises. */
+F5_API int64_t f5_distill_loss_workspace(int B, int N, int mel);
+F5_API int f5_distill_loss(int B, int N, int mel, const float* student, const float* teacher, const float* x1, const float* x0,
+                           const uint8_t* span, double* sums, int64_t* frames, float* batch, void* workspace, f5_stream_t stream);
+
 /* ------------------------------------------------------------------ duration validation (Trainer.calculate_duration_loss, trainer.py:829-1068)
  * The training target of the duration predictor and its loss, forward only, for judging a duration_predictor_*.pt checkpoint: the phoneme x
  * mel similarity, the monotonic alignment search (alignment_utils.py:337-355: "viterbi" and "window"; "progressive" is not built: the trainer's
@@ -328,6 +347,18 @@ F5_API int f5_plan_get_option(f5_plan_t p, const char* key, int* value);
  * ("attn_prescale_active" reads 0) and a ragged sample() is not bit-equal to its batch-1 calls.  f5_plan_get_option keys:
  * "attn_dropout_on", "attn_dropout_base" (host mirror of base).  prob > 0 on an F5_PREC_FP16 plan: F5_ENOTSUP (the dropout kernel is bf16 / fp32). */
 F5_API int f5_plan_set_attn_dropout(f5_plan_t p, float prob, uint64_t seed);
+/* Block subset (layer pruning, reference src/model_pruning): the plan runs only the listed blocks of its DiT, on the weights
+ * already in HBM.  blocks_host: host i32 [count], strictly increasing, each in [0, depth), count >= 1; NULL with count 0 restores all blocks
+ * (every launch and bit as before the first call).  Detected by symbol.  A plan with subset S behaves as a plan of the model whose blocks are S
+ * renumbered 0 .. |S| - 1: position j of the walk takes the weights, AdaLN rows and prefetch sets of block S[j], and whatever speaks of the
+ * first, previous or last block (the position-conv branch, the long-skip copy, the tap names "blk<j>.*", the range-guard tags, the dropout
+ * call word base + e * |S| + j) speaks of positions.  f5_dit_forward and every f5_sample* entry honour it.  The LayerNorm fold and pre-scaled q
+ * are off under a subset -- a list of ALL blocks included -- since the fold table and block 0's second weight copy are laid out for the full
+ * depth; no table is built or held for such a call.  Refused before anything changes: F5_ENOTSUP for UNetT (skip connections pair its layers)
+ * and MMDiT, F5_EINVAL for an empty, out-of-range or non-increasing list.  Completes a deferred sample() first and drops captured graphs. */
+F5_API int f5_plan_set_blocks(f5_plan_t p, const int32_t* blocks_host, int count);
+/* reads the subset back: returns its size (0 = none set) and writes the first min(size, cap) entries to blocks_host (may be NULL when cap = 0) */
+F5_API int f5_plan_get_blocks(f5_plan_t p, int32_t* blocks_host, int cap);
 
 /* ------------------------------------------------------------------ duration predictor
  * Replaces DurationPredictor.forward / .phoneme_forward (reference model/duration_predictor.py:28-46 / :48-68) as called from
