@@ -163,6 +163,11 @@ _PROTOS = {
     "f5_wave_remove_silence_workspace": (C.c_int64, [C.c_int64, _I, _I, _I]),
     "f5_wave_remove_silence": (_I, [_P, _I, C.c_int64, _I, C.c_int64, _I, _I, _I, _I, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "f5_op_silence_ranges": (_I, [_P, _I, C.c_int64, _I, C.c_int64, _I, _I, _I, _I, _P, C.c_int64, _P, _P, _P, _P]),
+    "f5_op_g711_encode": (_I, [C.c_int64, _P, _I, _P, _P]),
+    "f5_wave_convert": (_I, [_P, _I, C.c_int64, _I, _I, _P, _I, _P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "f5_wave_convert_stream_create": (_I, [_I, _I, _P, _I, _I, C.POINTER(_P)]),
+    "f5_wave_convert_stream_push": (_I, [_P, _P, C.c_int64, _I, _P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "f5_wave_convert_stream_destroy": (_I, [_P]),
     "f5_reference_prepare_workspace": (C.c_int64, [C.c_int64, _I, _I, C.POINTER(ReferenceRule)]),
     "f5_reference_table_rows": (C.c_int64, [C.c_int64, _I, _I, C.POINTER(ReferenceRule)]),
     "f5_reference_prepare": (_I, [_P, C.c_int64, _I, _I, C.POINTER(ReferenceRule), _I, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),

@@ -77,6 +77,33 @@ def write_wav_pcm16(path, samples, sample_rate):
         f.write(b"data" + struct.pack("<I", len(pcm)) + pcm)
 
 
+G711_FORMAT_TAGS = {0: 7, 1: 6}  # law (0 mu-law, 1 A-law) -> WAVE_FORMAT_MULAW / WAVE_FORMAT_ALAW
+
+
+def g711_wav_header(sample_rate, law, n_samples=0):
+    """The 58 bytes in front of the samples of a mono G.711 WAV file: RIFF/WAVE, an 18-byte ``fmt `` chunk (format tag 7 for mu-law, 6 for A-law,
+    1 channel, byte rate = sample rate, block align 1, 8 bits, cbSize 0), a ``fact`` chunk with the sample count, and the ``data`` chunk's header.
+    ``law``: "mulaw" / 0 or "alaw" / 1.  With ``n_samples = 0`` the counts say "unknown" (a stream: players read until it ends)."""
+    law = {"mulaw": 0, "alaw": 1}.get(law, law)
+    if law not in G711_FORMAT_TAGS:
+        raise ValueError(f"law {law!r}: \"mulaw\" / 0 or \"alaw\" / 1")
+    n, rate = int(n_samples), int(sample_rate)
+    return (b"RIFF" + struct.pack("<I", 50 + n + (n & 1)) + b"WAVE"
+            + b"fmt " + struct.pack("<IHHIIHHH", 18, G711_FORMAT_TAGS[law], 1, rate, rate, 1, 8, 0)
+            + b"fact" + struct.pack("<II", 4, n)
+            + b"data" + struct.pack("<I", n))
+
+
+def write_wav_g711(path, codes, sample_rate, law):
+    """uint8 G.711 codes [n] -> a mono mu-law / A-law WAV file (`g711_wav_header`, then the codes; a pad byte behind an odd count, as RIFF asks)"""
+    a = np.asarray(codes).reshape(-1)
+    if a.dtype != np.uint8:
+        raise ValueError(f"G.711 codes are uint8, not {a.dtype}")
+    data = a.tobytes()
+    with open(path, "wb") as f:
+        f.write(g711_wav_header(sample_rate, law, len(data)) + data + (b"\x00" if len(data) & 1 else b""))
+
+
 # ----------------------------------------------------------------------------- pydub-like segment on int samples
 class Segment:
     """Minimal stand-in for pydub.AudioSegment: int samples [n, ch], millisecond indexing, rms / dBFS."""

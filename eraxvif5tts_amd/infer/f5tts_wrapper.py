@@ -157,6 +157,42 @@ class F5TTSWrapper:
         self.sway_sampling_coef = -1.0
         self.speed = 1.0
         self.fix_duration = None
+        self._output_format = None  # set_output_format(): None, or (output rate, "pcm16" | "mulaw" | "alaw")
+
+    # ------------------------------------------------------------------ output format
+    def set_output_format(self, sample_rate: Optional[int] = None, encoding: Optional[str] = None):
+        """The format every synthesis entry point delivers in -- a setting of the wrapper, not a per-call argument.  ``sample_rate``: None (the
+        native ``target_sample_rate``; passing that rate means the same) or a positive int; ``encoding``: None / "pcm16" (the same), "mulaw" or
+        "alaw" (G.711).  Anything else raises ValueError and changes nothing.  With both unset every entry point behaves as it always has.
+        With a format set the conversion is the last step behind the wave tail (and behind silence removal), on the device
+        (`infer.deliver.convert_wave`: torchaudio's sinc_interp_hann resampler, its sums in ordered fp64): the returned sample rate is the output
+        rate; a float return is float32 at that rate; ``return_pcm16=True`` returns int16 -- ``trunc(float32 * 32767)``, saturating -- or the
+        uint8 G.711 codes of that int16; ``output_path`` is written at the output rate, as a mu-law / A-law WAV file under a G.711 encoding
+        (`audio.write_wav_g711`).  At the native rate nothing is resampled: the float is the tail's, the int16 the tail's own, the codes
+        `infer.deliver.g711_encode` of it.  Spectrograms are untouched.  The streamed entry points push each group's tail output into a
+        `infer.deliver.ConvertStream`: their pieces, concatenated, are byte for byte the one-shot result under the same format and seed."""
+        from .deliver import check_output_format
+        self._output_format = check_output_format(sample_rate, encoding, self.target_sample_rate)
+
+    @property
+    def output_format(self):
+        """None while no format is set, else ``(sample_rate, encoding)`` with the output rate and "pcm16", "mulaw" or "alaw"."""
+        return getattr(self, "_output_format", None)
+
+    def _format_step(self, signal, pcm16, want_float, want_codes):
+        """The last step of delivery under `output_format`: ``(signal, codes)`` of a finished signal and its truncating PCM (device tensors from
+        the device tail, arrays from the host tails; None where there is none).  At another rate both come from `convert_wave` of the signal
+        (a host array is uploaded once: there is no CPU resampler); at the native rate the PCM is encoded where the encoding is G.711."""
+        fmt = self.output_format
+        if fmt is None:
+            return signal, pcm16
+        from .deliver import LAWS, convert_wave, g711_encode, g711_encode_device
+        rate, encoding = fmt
+        if rate != self.target_sample_rate:
+            return convert_wave(signal, self.target_sample_rate, rate, encoding, want_float=want_float, want_codes=want_codes)
+        if encoding in LAWS and pcm16 is not None:
+            pcm16 = g711_encode_device(pcm16, encoding) if torch.is_tensor(pcm16) and pcm16.is_cuda else g711_encode(np.asarray(pcm16), encoding)
+        return signal, pcm16
 
     def _load_checkpoint(self, model, ckpt_path, dtype=None, use_ema=True):
         return load_checkpoint(model, ckpt_path, self.device, dtype=dtype, use_ema=use_ema)
@@ -443,7 +479,9 @@ class F5TTSWrapper:
             first.append(first[-1] + g)
         results = [None] * len(reqs)
         skips = [v["ref_audio_len"] for v in job_voices]
-        want_float = not return_pcm16 or any(q.remove_silence for q in reqs)
+        fmt = self.output_format  # (each request's finished wave is converted, behind its silence removal)
+        rate = fmt[0] if fmt else self.target_sample_rate
+        want_float = not return_pcm16 or any(q.remove_silence for q in reqs) or rate != self.target_sample_rate
         with torch.inference_mode():
             kind = device_tail_kind(self.vocoder, *mels)
             on_device = (kind is not None and (kind == "vocos") == (self.mel_spec_type == "vocos")
@@ -478,12 +516,14 @@ class F5TTSWrapper:
                     part = pcm[starts[j]: starts[j + 1]] if pcm is not None else None
                     if reqs[r].remove_silence:
                         wave, part = self._silence_step(wave, part)
+                    if fmt is not None:
+                        wave, part = self._format_step(wave, part, not return_pcm16, return_pcm16)
                     out = (part if return_pcm16 else wave).cpu().numpy()
                     if return_spectrogram:
                         spec = np.concatenate([rows[row_start[k]: row_start[k] + got[k]].t().cpu().numpy() for k in range(first[r], first[r + 1])], axis=1)
-                        results[r] = (out, self.target_sample_rate, spec)
+                        results[r] = (out, rate, spec)
                     else:
-                        results[r] = (out, self.target_sample_rate)
+                        results[r] = (out, rate)
         for r, (settings, _) in enumerate(plans):  # the host tails, per request: exactly what its generate() call does behind the sampler
             if results[r] is None:
                 span = slice(first[r], first[r + 1])
@@ -659,35 +699,50 @@ class F5TTSWrapper:
 
     def _deliver(self, mels, settings, voices, seg_sizes, output_path=None, return_numpy=False, return_spectrogram=False, return_pcm16=False,
                  remove_silence=False):
-        """`_synthesize` behind the sampler: these mels -> what generate() returns."""
-        want_float = not return_pcm16 or output_path is not None
+        """`_synthesize` behind the sampler: these mels -> what generate() returns, in the wrapper's `output_format` where one is set."""
+        fmt = self.output_format
+        rate = fmt[0] if fmt else self.target_sample_rate
+        resamples = rate != self.target_sample_rate  # (then float and codes both come from the converted signal: the tail's PCM is not asked for)
+        g711 = fmt is not None and fmt[1] != "pcm16"
+        want_codes = return_pcm16 or (output_path is not None and g711)  # (a G.711 file holds the codes, a PCM file the rounded float)
+        want_float = not return_pcm16 or (output_path is not None and not g711)
         want_spec = return_spectrogram or output_path is not None
+        tail_pcm = want_codes and not resamples
         with torch.inference_mode():
             done, generated_waves, spectrograms = waves_of_mels(
-                self.vocoder, self.mel_spec_type, mels, [v["ref_audio_len"] for v in voices], want_spec=want_spec, want_pcm16=return_pcm16,
-                want_float=want_float or remove_silence, **self._tail_kw(settings, voices, seg_sizes))  # (the float wave is what is judged)
+                self.vocoder, self.mel_spec_type, mels, [v["ref_audio_len"] for v in voices], want_spec=want_spec, want_pcm16=tail_pcm,
+                want_float=want_float or remove_silence or resamples, **self._tail_kw(settings, voices, seg_sizes))  # (the float wave is what is judged)
             if done is not None and remove_silence:
                 done, remove_silence = self._silence_step(*done), False
+            if done is not None and fmt is not None:
+                done = self._format_step(*done, want_float, want_codes)
         if done is not None:
             final_wave = done[0].cpu().numpy() if want_float else None
-            final_pcm = done[1].cpu().numpy() if return_pcm16 else None
+            final_pcm = done[1].cpu().numpy() if want_codes else None
         else:  # the host tail: cross_fade_concat per segment, np.concatenate of the segments
             pieces, k = [], 0
             for g in seg_sizes:
                 pieces.append(cross_fade_concat(generated_waves[k: k + g], settings.cross_fade_duration, self.target_sample_rate))
                 k += g
             final_wave, final_pcm = np.concatenate(pieces), None
-            if return_pcm16:  # (each segment's int16 from its own dtype, as its generate() call forms it)
+            if tail_pcm:  # (each segment's int16 from its own dtype, as its generate() call forms it)
                 from ..streaming.wire import pcm16_bytes
                 final_pcm = np.concatenate([np.frombuffer(pcm16_bytes(p), dtype=np.int16) for p in pieces])
         if remove_silence:  # the host tails (a foreign vocoder, or joints that chain): the same rule by the host functions
             final_wave, final_pcm = self._silence_step(final_wave, final_pcm)
+        if done is None and fmt is not None:  # the host tails under a format: the signal is uploaded once and converted on the device
+            with torch.inference_mode():
+                final_wave, final_pcm = (None if x is None else x.cpu().numpy() if torch.is_tensor(x) else x
+                                         for x in self._format_step(final_wave, final_pcm, want_float, want_codes))
         combined_spectrogram = np.concatenate(spectrograms, axis=1) if spectrograms else None
         if output_path is not None:
             output_dir = os.path.dirname(output_path)
             if output_dir and not os.path.exists(output_dir):
                 os.makedirs(output_dir)
-            _audio.write_wav(output_path, final_wave, self.target_sample_rate)
+            if g711:
+                _audio.write_wav_g711(output_path, final_pcm, rate, fmt[1])
+            else:
+                _audio.write_wav(output_path, final_wave, rate)
             if return_spectrogram:
                 np.save(os.path.splitext(output_path)[0] + "_spec.npy", combined_spectrogram)  # matplotlib is not in the image
             if not return_numpy:
@@ -695,24 +750,29 @@ class F5TTSWrapper:
         if return_pcm16:
             final_wave = final_pcm
         if return_spectrogram:
-            return final_wave, self.target_sample_rate, combined_spectrogram
-        return final_wave, self.target_sample_rate
+            return final_wave, rate, combined_spectrogram
+        return final_wave, rate
 
     def _synthesize_stream(self, settings, jobs, voices, seg_sizes, return_pcm16):
         """`_synthesize` group by group, as a generator of ``(piece, sample_rate)``; where the streamed tail does not apply, its result once."""
         frames = self._generated_frames(jobs, voices)
         kind = device_tail_kind(self.vocoder, *[v["audio"] for v in voices])
-        session = None
+        fmt = self.output_format
+        rate = fmt[0] if fmt else self.target_sample_rate
+        resamples = rate != self.target_sample_rate  # (the tail then hands its float signal to a ConvertStream, which forms float and codes)
+        session = converter = None
         if kind is not None and kind == self.mel_spec_type and min(frames) >= 2:
             samples = [(t - 1) * self.hop_length for t in frames] if kind == "vocos" else [t * self.vocoder._total_up() for t in frames]
             with torch.inference_mode():
-                session = WaveStream(samples, want_float=not return_pcm16, want_pcm16=return_pcm16, **self._tail_kw(settings, voices, seg_sizes))
+                session = WaveStream(samples, want_float=not return_pcm16 or resamples, want_pcm16=return_pcm16 and not resamples,
+                                     **self._tail_kw(settings, voices, seg_sizes))
         if session is None or not session.ok:
             yield self._synthesize(settings, jobs, voices, seg_sizes, return_numpy=True, return_pcm16=return_pcm16)
             return
         try:
             first = 0
-            for group in chunk_groups([d for _, d in jobs], int(self.stream_first_chunks), int(self.ragged_chunks)):
+            groups = chunk_groups([d for _, d in jobs], int(self.stream_first_chunks), int(self.ragged_chunks))
+            for g, group in enumerate(groups):
                 mels = self._sample_jobs([jobs[i] for i in group], [voices[i] for i in group], settings)
                 with torch.inference_mode():
                     rows, row_start, got = mel_rows_of(mels, [voices[i]["ref_audio_len"] for i in group])
@@ -720,11 +780,21 @@ class F5TTSWrapper:
                         raise RuntimeError(f"the sampler returned {got} generated frames where {frames[first: first + len(group)]} were planned")
                     wave_buf, counts = decode_utterances(self.vocoder, kind, rows, row_start, got)
                     signal, pcm = session.push(wave_buf, counts)
+                    if resamples:
+                        if converter is None:
+                            from .deliver import ConvertStream
+                            converter = ConvertStream(self.target_sample_rate, rate, fmt[1], is_f64=session.mixed, want_float=not return_pcm16,
+                                                      want_codes=return_pcm16, device=wave_buf.device)
+                        signal, pcm = converter.push(signal, last=g == len(groups) - 1)
+                    elif fmt is not None:
+                        signal, pcm = self._format_step(signal, pcm, not return_pcm16, return_pcm16)
                     piece = (pcm if return_pcm16 else signal).cpu().numpy()
                 first += len(group)
-                yield piece, self.target_sample_rate
+                yield piece, rate
         finally:
             session.close()
+            if converter is not None:
+                converter.close()
 
     def _chunk_stream_pool(self, n):
         pool = getattr(self, "_chunk_streams_pool", None) or []

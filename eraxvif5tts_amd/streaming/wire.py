@@ -35,6 +35,23 @@ def pcm16_bytes(audio: np.ndarray) -> bytes:
     return (np.asarray(audio) * 32767).astype(np.int16).tobytes()
 
 
+def create_stream_header(sample_rate, encoding=None) -> bytes:
+    """The header `stream_audio` sends for a model with an output format (``F5TTSWrapper.set_output_format``): for PCM16 (``encoding`` None or
+    "pcm16") exactly ``create_wave_header(sample_rate)``; for "mulaw" / "alaw" the 58-byte G.711 header of ``infer.audio.g711_wav_header`` with
+    unknown sizes."""
+    if encoding in (None, "pcm16"):
+        return create_wave_header(sample_rate)
+    if encoding not in ("mulaw", "alaw"):
+        raise ValueError(f"encoding {encoding!r}: one of None, 'pcm16', 'mulaw', 'alaw'")
+    from ..infer.audio import g711_wav_header
+    return g711_wav_header(sample_rate, encoding, 0)
+
+
+def _sample_bytes(pcm) -> bytes:
+    """what a model hands back for ``return_pcm16=True``, as it goes on the wire: uint8 G.711 codes as they are, anything else as int16"""
+    return np.ascontiguousarray(pcm, dtype=np.uint8 if getattr(pcm, "dtype", None) == np.uint8 else np.int16).tobytes()
+
+
 class ReferenceCache:
     """speaker id -> processed reference, with the reference server's entry layout and status strings."""
 
@@ -83,7 +100,7 @@ def process_chunk(chunk_text: str, model, **gen_kwargs) -> Optional[bytes]:
         pcm, _sr = model.generate(text=chunk_text, return_numpy=True, return_pcm16=True, **gen_kwargs)
         if pcm is None or np.size(pcm) == 0:
             return None
-        return np.ascontiguousarray(pcm, dtype=np.int16).tobytes()
+        return _sample_bytes(pcm)
     audio, _sr = model.generate(text=chunk_text, return_numpy=True, **gen_kwargs)
     if audio is None or np.size(audio) == 0:
         return None
@@ -114,7 +131,7 @@ def process_chunk_pieces(chunk_text: str, model, **gen_kwargs) -> Iterator[bytes
     try:
         for pcm, _sr in pieces:
             if pcm is not None and np.size(pcm):
-                yield np.ascontiguousarray(pcm, dtype=np.int16).tobytes()
+                yield _sample_bytes(pcm)
     finally:
         pieces.close()
 
@@ -122,10 +139,13 @@ def process_chunk_pieces(chunk_text: str, model, **gen_kwargs) -> Iterator[bytes
 def stream_audio(model, cache: ReferenceCache, speaker: str, text_chunks: Iterable[str], stream_groups: bool = False, **gen_kwargs) -> Iterator[bytes]:
     """WAV header (unknown size) then one PCM block per synthesised chunk; the wrapper's reference state is always cleared.
     ``stream_groups=True`` with a model that has ``generate_stream`` (duck-typed): each text chunk's pieces are sent as they come -- the same
-    bytes in more blocks, the first of them after one utterance's work.  Any other model keeps the one block per text chunk."""
+    bytes in more blocks, the first of them after one utterance's work.  Any other model keeps the one block per text chunk.
+    A model whose ``output_format`` (duck-typed: ``(sample_rate, encoding)``, or None) is set gets that format's header
+    (`create_stream_header`) and its pieces -- int16 at that rate, or uint8 G.711 codes -- are forwarded as they are."""
     cache.install(model, speaker)
     try:
-        yield create_wave_header(sample_rate=model.target_sample_rate, data_size=0)
+        fmt = getattr(model, "output_format", None)
+        yield create_stream_header(*fmt) if fmt else create_wave_header(sample_rate=model.target_sample_rate, data_size=0)
         grouped = stream_groups and callable(getattr(model, "generate_stream", None))
         for chunk in text_chunks:
             if grouped:

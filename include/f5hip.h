@@ -679,6 +679,43 @@ F5_API int f5_wave_remove_silence(const void* wave, int is_f64, int64_t n_sample
 F5_API int f5_op_silence_ranges(const void* wave, int is_f64, int64_t n_samples, int sample_rate, int64_t n_ms, int min_silence_len,
                                 int threshold_floor, int keep_silence, int seek_step, void* workspace, int64_t workspace_bytes,
                                 uint8_t* flags_out, int32_t* table_out, int64_t* counts_dev, f5_stream_t stream);
+/* The delivery stage behind the wave tail, on the device: the finished signal at another sample rate, as float32, as the truncating int16 PCM of
+ * f5_wave_finish and as G.711, detected by symbol like the entries above.
+ *   resample   torchaudio's sinc_interp_hann at its defaults (lowpass_filter_width 6, rolloff 0.99), the definition of f5_frontend_resample:
+ *              g = gcd(in_rate, out_rate), orig = in_rate / g, nw = out_rate / g, base = min(orig, nw) * 0.99, width = ceil(6 orig / base),
+ *              kw = 2 width + orig, target = ceil(nw n / orig); output j = blk * nw + ph is sum_k taps[ph][k] * x[blk * orig - width + k] over
+ *              k = 0 .. kw - 1
+ *   taps       dev f64 [nw][kw], the CALLER's table (as w_down / w_up are for the cross-fade): the formula in float64, cast to fp32 and back, as
+ *              torchaudio casts its kernel to the waveform's dtype.  It must outlive a stream session
+ *   arithmetic x widened to fp64; fp64 products; ONE fp64 accumulator from 0.0 over ascending k; multiply and add never contracted; a tap whose
+ *              sample lies outside [0, n) is skipped, not added as zero.  So the result does not depend on how the work is cut
+ *   wave       dev f32 (is_f64 = 0) or f64 (1), n > 0 mono samples, aligned to its element
+ *   outputs    each may be NULL, each with room for target elements: out_f32 = (float)acc; out_pcm16 = trunc(out_f32 * 32767.0f), the product in
+ *              fp32, saturating at or beyond +-32768, NaN -> 0 (the wave tail's rule); out_g711 = the G.711 code of that int16 under law.
+ *              *out_samples (host) = target; with all three outputs NULL that is all the call does
+ *   G.711      law 0 = mu-law, 1 = A-law, as CPython's audioop.lin2ulaw / lin2alaw give them for 16-bit input, with integer arithmetic only:
+ *              mu-law  v = s >> 2, m = min(|v|, 8158) + 33, seg = floor(log2 m) - 5, code = seg << 4 | ((m >> (seg + 1)) & 15),
+ *                      code ^ 0x7F for v < 0, code ^ 0xFF otherwise
+ *              A-law   v = s >> 3, m = v for v >= 0 and -v - 1 for v < 0, seg = 0 for m < 32 and floor(log2 m) - 4 otherwise,
+ *                      code = seg << 4 | ((seg < 2 ? m >> 1 : m >> seg) & 15), code ^ 0x55 for v < 0, code ^ 0xD5 otherwise
+ *              The op-level entry encodes dev int16 [n] -> dev uint8 [n] on its own (the native rate: the wave tail's PCM16 is encoded as it is)
+ *   refusals   F5_EINVAL before any launch: n <= 0 or >= 2^31, a rate that is not positive, in_rate == out_rate (nothing to resample: the caller
+ *              keeps its signal), nw * kw above 2^20 table entries, a law other than 0 / 1, a null or misaligned wave or table
+ * In pushes: a session is created with the rates, the table, is_f64 and law -- properties of the whole stream -- and a push hands over the next
+ * n_k > 0 input samples and whether it is the last.  After a non-final push that brings the input to N samples, nw * max(0, (N - width) / orig)
+ * samples (integer division) are out in all: the blocks whose whole support has arrived, so a push may emit none; the last push emits up to target
+ * of the whole input.  The session keeps the input later blocks still need (fewer than kw samples) in a buffer of its own: the caller may free
+ * its buffer in stream order.  For EVERY way of cutting a signal into pushes the pieces, concatenated, are byte for byte the one-shot result --
+ * float, int16 and G.711.  With all three outputs NULL a push answers *emitted and leaves the session as it was.  F5_EINVAL, the session unchanged:
+ * a push after the last one, n_k <= 0, 2^31 samples or more in all.  Nothing synchronises. */
+typedef struct f5_convert_stream_s* f5_convert_stream_t;
+F5_API int f5_op_g711_encode(int64_t n, const int16_t* pcm16, int law, uint8_t* out, f5_stream_t stream);
+F5_API int f5_wave_convert(const void* wave, int is_f64, int64_t n, int in_rate, int out_rate, const double* taps, int law, float* out_f32,
+                           int16_t* out_pcm16, uint8_t* out_g711, int64_t* out_samples, f5_stream_t stream);
+F5_API int f5_wave_convert_stream_create(int in_rate, int out_rate, const double* taps, int is_f64, int law, f5_convert_stream_t* out);
+F5_API int f5_wave_convert_stream_push(f5_convert_stream_t s, const void* wave, int64_t n_k, int last, float* out_f32, int16_t* out_pcm16,
+                                       uint8_t* out_g711, int64_t* emitted, f5_stream_t stream);
+F5_API int f5_wave_convert_stream_destroy(f5_convert_stream_t s);
 /* The reference-voice front-end on the device: the host steps of F5TTSWrapper._preprocess_voice (the reference's f5tts_wrapper.py:256-379) by the
  * rule of this package's stand-in for pydub, infer/audio.py clip_reference / remove_silence_edges / Segment.silent_like / segment_to_float, bit
  * for bit up to the rms (below), detected by symbol.
