@@ -19,6 +19,7 @@
 #include <numeric>
 
 #include "kernels.h"
+#include "pcm_rule.h"
 #include "runtime.h"
 
 static constexpr int DLV_SPAN = 4096;                    // doubles of LDS per workgroup (32 KiB)
@@ -38,12 +39,6 @@ __device__ __forceinline__ uint8_t deliver_g711(int s, int law) {
     const int seg = m < 32 ? 0 : 27 - __clz(m);  // floor(log2 m) - 4, m in 32 .. 4095
     const int code = (seg << 4) | ((seg < 2 ? m >> 1 : m >> seg) & 15);
     return (uint8_t)(code ^ (v < 0 ? 0x55 : 0xD5));
-}
-
-__device__ __forceinline__ int16_t deliver_pcm(float p) {  // truncation toward zero inside int16, saturation outside, NaN -> 0
-    if (p >= 32767.0f) return (int16_t)32767;
-    if (p <= -32768.0f) return (int16_t)-32768;
-    return p == p ? (int16_t)(int)p : (int16_t)0;
 }
 
 __global__ __launch_bounds__(256) void deliver_g711_kernel(const int16_t* __restrict__ pcm, int64_t n, int law, uint8_t* __restrict__ out) {
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(256) void deliver_convert_kernel(const DeliverSourc
     const float f = (float)acc;
     if (out_f32) out_f32[rel] = f;
     if (out_pcm || out_g711) {
-        const int16_t s = deliver_pcm(f * 32767.0f);
+        const int16_t s = pcm_sat((double)(f * 32767.0f));  // (the product in fp32)
         if (out_pcm) out_pcm[rel] = s;
         if (out_g711) out_g711[rel] = deliver_g711((int)s, law);
     }

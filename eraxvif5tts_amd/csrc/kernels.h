@@ -184,15 +184,13 @@ struct WaveTable {
 // nj[k] samples, is the cross-fade with utterance k-1's tail (nj[0] = 0 in a table that starts the list).  f64: a joint mixed, so the whole signal
 // is double (numpy's promotion) and the PCM product is taken in double; otherwise fp32.  rms_dev (or null): device vector, utterance k takes
 // g = rms_dev[ridx[k]] and the gain applies when g < target.
-int launch_wave_finish(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, const double* w_down, const double* w_up,
-                       const float* rms_dev, float target, int gain_div, bool f64, float* out_f32, double* out_f64, int16_t* out_pcm, hipStream_t stream);
-// One push of a wave stream (f5_wave_stream_push): the same arithmetic with positions local to the push.  carry_in (given exactly when nj[0] > 0 in
-// the push's first table): nj[0] gained fp32 samples, the tail of the utterance before the table's utterance 0, which that utterance's first samples
-// are cross-faded with; carry_out (or null): receives the last n_carry samples of the table's last utterance, gained, from n_carry extra threads
-// behind pos_end -- another buffer than carry_in.
-int launch_wave_stream(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n_carry, const double* w_down, const double* w_up,
-                       const float* rms_dev, float target, int gain_div, bool f64, const float* carry_in, float* carry_out, float* out_f32,
-                       double* out_f64, int16_t* out_pcm, hipStream_t stream);
+// In a push of a wave stream the positions are local to the push.  carry_in (given exactly when nj[0] > 0 in the push's first table): nj[0] gained
+// fp32 samples, the tail of the utterance before the table's utterance 0, which that utterance's first samples are cross-faded with; carry_out (or
+// null): receives the last n_carry samples of the table's last utterance, gained, from n_carry extra threads behind pos_end -- another buffer than
+// carry_in.  A one-shot call carries nothing: n_carry = 0 and both null.
+int launch_wave_tail(const float* wave, const WaveTable& tb, int first, int pos0, int pos_end, int n_carry, const double* w_down, const double* w_up,
+                     const float* rms_dev, float target, int gain_div, bool f64, const float* carry_in, float* carry_out, float* out_f32,
+                     double* out_f64, int16_t* out_pcm, hipStream_t stream);
 
 // ---- LayerNorm fold (lnfold.hip; gemm.h)
 // per-evaluation-time projection weights W' = fp16(W (1 + scale)) and column constants c1 = rowsum W', c2 = b + W . shift for `evals` times x `depth`

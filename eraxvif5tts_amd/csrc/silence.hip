@@ -12,7 +12,7 @@
 //   ranges  one workgroup: prefix scan, window flags, then one wave walks the flags 64 at a time (a ballot; runs of consecutive silent starts merge
 //           by the rule itself), inverts the silent ranges, pads by keep_silence with the midpoint rule and writes the segment table
 //           (silence_rule.h, which reference.hip includes too)
-//   gather  one thread per output sample and a binary search in the table, as wave_finish_kernel does
+//   gather  one thread per output sample and a binary search in the table, as wave_tail_kernel does
 // Stores to device memory are plain C++; no atomics: one workgroup owns the table and the counts.
 #include <cmath>
 

@@ -329,242 +329,3 @@ extern "C" int f5_vocoder_decode_ragged(f5_vocoder_t v, int B, const int32_t* ro
     F5_TRY(ensure_work(v, (size_t)rows));
     return decode_rows(v, 0, 0, &rg, (int)rows, mel, ld, wave, (hipStream_t)stream);
 }
-
-// See f5hip.h.  Only calls whose joints do not chain are taken: inside a segment the first and the last utterance hold at least n = xfade_samples
-// samples and every one between them 2 n, so that each joint mixes n untouched samples of either side (cross_fade_concat then takes n =
-// xfade_samples at every joint of the segment).  Shorter utterances make the reference mix an already mixed region in sequence: F5_ENOTSUP, the
-// caller takes the host functions.  Segments are joined without a fade (np.concatenate), so a one-utterance segment has no constraint.
-namespace {
-inline bool continues_segment(const uint8_t* seg_start, int g) { return g > 0 && !(seg_start && seg_start[g]); }
-
-// n of the whole list: xfade_samples when some utterance continues a segment (then the result is float64 throughout), else 0
-int segments_n(int total, const uint8_t* seg_start, int xfade_samples) {
-    if (xfade_samples <= 0) return 0;
-    for (int g = 1; g < total; ++g)
-        if (continues_segment(seg_start, g)) return xfade_samples;
-    return 0;
-}
-
-// samples utterance g of a list of `total` must hold: n per joint it takes part in
-inline int chain_need(int total, const uint8_t* seg_start, int g, int n) {
-    return n * ((continues_segment(seg_start, g) ? 1 : 0) + ((g + 1 < total && continues_segment(seg_start, g + 1)) ? 1 : 0));
-}
-
-// pcm_f32[g] asks for the fp32 PCM product of a call over utterance g alone: only an utterance that is a segment of its own mixes nothing
-int check_pcm_f32(int total, const uint8_t* seg_start, const uint8_t* pcm_f32) {
-    for (int g = 0; pcm_f32 && g < total; ++g)
-        if (pcm_f32[g] && (continues_segment(seg_start, g) || (g + 1 < total && continues_segment(seg_start, g + 1))))
-            return f5_fail(F5_EINVAL, "utterance %d: pcm_f32 is for a segment of one utterance", g);
-    return 0;
-}
-
-int check_rms_index(int B, const float* rms_dev, int n_rms, const int32_t* rms_index) {
-    if (!rms_dev) return 0;
-    if (n_rms < 1) return f5_fail(F5_EINVAL, "rms_dev needs n_rms >= 1 values");
-    for (int u = 0; rms_index && u < B; ++u)
-        if (rms_index[u] < 0 || rms_index[u] >= n_rms) return f5_fail(F5_EINVAL, "utterance %d: rms_index %d outside the %d rms values", u, rms_index[u], n_rms);
-    return 0;
-}
-}  // namespace
-
-extern "C" int f5_wave_finish_segments(int B, const float* wave, const int32_t* samples_host, const uint8_t* seg_start_host, const float* gain_host,
-                                       const uint8_t* apply_host, const float* rms_dev, int n_rms, const int32_t* rms_index_host, float target_rms,
-                                       int gain_div, int xfade_samples, const double* w_down, const double* w_up, const uint8_t* pcm_f32_host,
-                                       float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* total_samples_out, f5_stream_t stream) {
-    if (!wave || !samples_host || B <= 0) return f5_fail(F5_EINVAL, "null argument or B <= 0");
-    if (gain_host && !apply_host) return f5_fail(F5_EINVAL, "gain_host needs apply_host");
-    if (gain_host && rms_dev) return f5_fail(F5_EINVAL, "give the rms either as host gains or as device values");
-    if ((gain_host || rms_dev) && !(target_rms > 0.f)) return f5_fail(F5_EINVAL, "target_rms must be positive");
-    F5_TRY(check_rms_index(B, rms_dev, n_rms, rms_index_host));
-    F5_TRY(check_pcm_f32(B, seg_start_host, pcm_f32_host));
-    F5_TRY(f5_check_device());
-    const int n = segments_n(B, seg_start_host, xfade_samples);
-    const bool f64 = n > 0;  // a mixed joint is float64 and np.concatenate promotes the whole signal
-    if (f64 && (!w_down || !w_up)) return f5_fail(F5_EINVAL, "a cross-fade needs the w_down / w_up tables");
-    int64_t in0 = 0, out0 = 0;
-    std::vector<int> vin(B), vout(B), vn(B);
-    for (int u = 0; u < B; ++u) {
-        const int len = samples_host[u];
-        if (len <= 0) return f5_fail(F5_EINVAL, "utterance %d: no samples", u);
-        if (len < chain_need(B, seg_start_host, u, n))
-            return f5_fail(F5_ENOTSUP, "utterance %d (%d samples) is shorter than its cross-fades (%d samples each): the joints chain", u, len, n);
-        vn[u] = continues_segment(seg_start_host, u) ? n : 0;
-        out0 -= vn[u];
-        vin[u] = (int)in0;
-        vout[u] = (int)out0;
-        in0 += len;
-        out0 += len;
-        if (in0 >= (int64_t)1 << 31) return f5_fail(F5_EINVAL, "more than 2^31 samples");
-    }
-    if (total_samples_out) *total_samples_out = out0;
-    // (the extents are judged first: a caller may ask "can you take this call" before it allocates the outputs)
-    if (f64 ? out_f32 != nullptr : out_f64 != nullptr) return f5_fail(F5_EINVAL, "the float result is float64 exactly when a joint mixed (out_f32 / out_f64)");
-    if (!out_f32 && !out_f64 && !out_pcm16) return f5_fail(F5_EINVAL, "no output");
-    hipStream_t st = (hipStream_t)stream;
-    // tables of MAXU utterances that overlap by one: a joint needs its left neighbour
-    for (int a = 0; a < B; a += WaveTable::MAXU - 1) {
-        WaveTable tb;
-        const int b = a + WaveTable::MAXU < B ? a + WaveTable::MAXU : B;
-        tb.cnt = b - a;
-        for (int k = a; k < b; ++k) {
-            tb.in0[k - a] = vin[k];
-            tb.len[k - a] = samples_host[k];
-            tb.out0[k - a] = vout[k];
-            tb.nj[k - a] = vn[k];
-            tb.ridx[k - a] = (rms_dev && rms_index_host) ? rms_index_host[k] : 0;
-            tb.gain[k - a] = gain_host ? gain_host[k] : 0.f;
-            tb.apply[k - a] = gain_host ? (apply_host[k] != 0) : 0;
-            tb.pcm32[k - a] = (pcm_f32_host && pcm_f32_host[k]) ? 1 : 0;
-        }
-        const int first = a == 0 ? 0 : 1;
-        if (first >= tb.cnt) break;
-        const int pos0 = vout[a + first], pos_end = b < B ? vout[b] : (int)out0;
-        F5_TRY(launch_wave_finish(wave, tb, first, pos0, pos_end, w_down, w_up, rms_dev, target_rms, gain_div, f64, out_f32, out_f64, out_pcm16, st));
-        if (b == B) break;
-    }
-    return 0;
-}
-
-extern "C" int f5_wave_finish(int B, const float* wave, const int32_t* samples_host, const float* gain_host, const uint8_t* apply_host,
-                              const float* rms_dev, float target_rms, int gain_div, int xfade_samples, const double* w_down, const double* w_up,
-                              float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* total_samples_out, f5_stream_t stream) {
-    return f5_wave_finish_segments(B, wave, samples_host, nullptr, gain_host, apply_host, rms_dev, 1, nullptr, target_rms, gain_div, xfade_samples,
-                                   w_down, w_up, nullptr, out_f32, out_f64, out_pcm16, total_samples_out, stream);
-}
-
-// ---- f5_wave_finish in consecutive pushes (see f5hip.h).  The session holds what one call's wave buffer held for the next joint: the last n samples
-// of the utterance to the left, with their gain applied, in one of two buffers used in alternation (a push reads one and writes the other in the
-// same launch).  Whether the signal is float64 is decided by the whole list (its segments, n), so every push of a stream answers in one dtype.
-// A push whose last utterance ends a segment carries nothing, and the next push's first utterance reads no carry.
-struct f5_wave_stream_s {
-    int total = 0, n = 0, done = 0, cur = 0;  // utterances of the whole list / taken so far; carry[cur] holds the tail of utterance done - 1
-    int64_t in_total = 0;                     // input samples taken so far (the 2^31 bound is the one-shot call's, over the whole list)
-    bool f64 = false;
-    const double *w_down = nullptr, *w_up = nullptr;
-    const float* rms_dev = nullptr;
-    float target = 0.f;
-    int gain_div = 0;
-    std::vector<uint8_t> seg_start;  // of the whole list (entry 0 unused: it always begins a segment)
-    std::vector<int32_t> rms_index;  // of the whole list
-    std::vector<uint8_t> pcm32;      // of the whole list
-    float* carry[2] = {nullptr, nullptr};
-    DevArena arena;
-};
-
-extern "C" int f5_wave_stream_create_segments(int total_utterances, const uint8_t* seg_start_host, int xfade_samples, const double* w_down,
-                                              const double* w_up, const float* rms_dev, int n_rms, const int32_t* rms_index_host, float target_rms,
-                                              int gain_div, const uint8_t* pcm_f32_host, f5_wave_stream_t* out) {
-    if (!out) return f5_fail(F5_EINVAL, "null argument");
-    *out = nullptr;
-    if (total_utterances <= 0 || xfade_samples < 0) return f5_fail(F5_EINVAL, "need total_utterances >= 1 and xfade_samples >= 0");
-    if (rms_dev && !(target_rms > 0.f)) return f5_fail(F5_EINVAL, "target_rms must be positive");
-    F5_TRY(check_rms_index(total_utterances, rms_dev, n_rms, rms_index_host));
-    F5_TRY(check_pcm_f32(total_utterances, seg_start_host, pcm_f32_host));
-    F5_TRY(f5_check_device());
-    const int n = segments_n(total_utterances, seg_start_host, xfade_samples);
-    if (n > 0 && (!w_down || !w_up)) return f5_fail(F5_EINVAL, "a cross-fade needs the w_down / w_up tables");
-    f5_wave_stream_s* s = new f5_wave_stream_s();
-    s->total = total_utterances;
-    s->n = n;
-    s->f64 = n > 0;
-    s->w_down = w_down;
-    s->w_up = w_up;
-    s->rms_dev = rms_dev;
-    s->target = target_rms;
-    s->gain_div = gain_div;
-    s->seg_start.assign(total_utterances, 0);
-    s->rms_index.assign(total_utterances, 0);
-    s->pcm32.assign(total_utterances, 0);
-    for (int g = 0; g < total_utterances; ++g) {
-        s->seg_start[g] = (g == 0 || (seg_start_host && seg_start_host[g])) ? 1 : 0;
-        if (rms_dev && rms_index_host) s->rms_index[g] = rms_index_host[g];
-        if (pcm_f32_host && pcm_f32_host[g]) s->pcm32[g] = 1;
-    }
-    if (n > 0) {
-        float* both = nullptr;
-        const int rc = s->arena.alloc_t(&both, (size_t)2 * n);
-        if (rc != 0) {
-            delete s;
-            return rc;
-        }
-        s->carry[0] = both;
-        s->carry[1] = both + n;
-    }
-    *out = s;
-    return 0;
-}
-
-extern "C" int f5_wave_stream_create(int total_utterances, int xfade_samples, const double* w_down, const double* w_up, const float* rms_dev,
-                                     float target_rms, int gain_div, f5_wave_stream_t* out) {
-    return f5_wave_stream_create_segments(total_utterances, nullptr, xfade_samples, w_down, w_up, rms_dev, 1, nullptr, target_rms, gain_div, nullptr, out);
-}
-
-extern "C" int f5_wave_stream_destroy(f5_wave_stream_t s) {
-    delete s;  // (the arena's hipFree waits for the pushes still in flight)
-    return 0;
-}
-
-extern "C" int f5_wave_stream_push(f5_wave_stream_t s, int B, const float* wave, const int32_t* samples_host, const float* gain_host,
-                                   const uint8_t* apply_host, float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* emitted,
-                                   f5_stream_t stream) {
-    if (!s || !samples_host || B <= 0) return f5_fail(F5_EINVAL, "null argument or B <= 0");
-    if (B > s->total - s->done) return f5_fail(F5_EINVAL, "%d utterances pushed where %d of the stream's %d are left", B, s->total - s->done, s->total);
-    if (gain_host && !apply_host) return f5_fail(F5_EINVAL, "gain_host needs apply_host");
-    if (gain_host && s->rms_dev) return f5_fail(F5_EINVAL, "give the rms either as host gains or as device values");
-    if (gain_host && !(s->target > 0.f)) return f5_fail(F5_EINVAL, "target_rms must be positive");
-    const int n = s->n;
-    const uint8_t* seg = s->seg_start.data();
-    // the joint with the previous push / with the next one: only inside a segment
-    const bool joins = n > 0 && continues_segment(seg, s->done);
-    const bool carries = n > 0 && s->done + B < s->total && continues_segment(seg, s->done + B);
-    int64_t in0 = 0, out0 = 0;
-    std::vector<int> vin(B), vout(B), vn(B);
-    for (int u = 0; u < B; ++u) {
-        const int len = samples_host[u], g = s->done + u;
-        if (len <= 0) return f5_fail(F5_EINVAL, "utterance %d: no samples", g);
-        if (len < chain_need(s->total, seg, g, n))
-            return f5_fail(F5_ENOTSUP, "utterance %d (%d samples) is shorter than its cross-fades (%d samples each): the joints chain", g, len, n);
-        vn[u] = continues_segment(seg, g) ? n : 0;
-        if (u > 0) out0 -= vn[u];  // (the joint with the carry lands on this push's first samples: nothing before it to take back)
-        vin[u] = (int)in0;
-        vout[u] = (int)out0;
-        in0 += len;
-        out0 += len;
-        if (s->in_total + in0 >= (int64_t)1 << 31) return f5_fail(F5_EINVAL, "more than 2^31 samples");
-    }
-    if (carries) out0 -= n;
-    if (emitted) *emitted = out0;
-    if (!out_f32 && !out_f64 && !out_pcm16) return 0;  // "how many would this push emit": nothing is enqueued, the session stays as it is
-    if (!wave) return f5_fail(F5_EINVAL, "null wave");
-    if (s->f64 ? out_f32 != nullptr : out_f64 != nullptr)
-        return f5_fail(F5_EINVAL, "the float result is float64 exactly when the stream cross-fades (out_f32 / out_f64)");
-    F5_TRY(f5_check_device());
-    hipStream_t st = (hipStream_t)stream;
-    const float* carry_in = joins ? s->carry[s->cur] : nullptr;
-    float* carry_out = carries ? s->carry[s->cur ^ 1] : nullptr;
-    for (int a = 0; a < B; a += WaveTable::MAXU - 1) {
-        WaveTable tb;
-        const int b = a + WaveTable::MAXU < B ? a + WaveTable::MAXU : B;
-        tb.cnt = b - a;
-        for (int k = a; k < b; ++k) {
-            tb.in0[k - a] = vin[k];
-            tb.len[k - a] = samples_host[k];
-            tb.out0[k - a] = vout[k];
-            tb.nj[k - a] = vn[k];
-            tb.ridx[k - a] = s->rms_dev ? s->rms_index[s->done + k] : 0;
-            tb.gain[k - a] = gain_host ? gain_host[k] : 0.f;
-            tb.apply[k - a] = gain_host ? (apply_host[k] != 0) : 0;
-            tb.pcm32[k - a] = s->pcm32[s->done + k];
-        }
-        const int first = a == 0 ? 0 : 1;
-        if (first >= tb.cnt) break;
-        const int pos0 = vout[a + first], pos_end = b < B ? vout[b] : (int)out0;
-        F5_TRY(launch_wave_stream(wave, tb, first, pos0, pos_end, n, s->w_down, s->w_up, s->rms_dev, s->target, s->gain_div, s->f64,
-                                  a == 0 ? carry_in : nullptr, b == B ? carry_out : nullptr, out_f32, out_f64, out_pcm16, st));
-        if (b == B) break;
-    }
-    s->done += B;
-    s->in_total += in0;
-    if (carry_out) s->cur ^= 1;
-    return 0;
-}

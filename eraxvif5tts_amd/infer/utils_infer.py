@@ -300,6 +300,29 @@ def _rms_forms(rms, B, target_rms, rms_index=None):
     return gain_host, apply_host, rms_dev
 
 
+class _TailList:
+    """One utterance list as the library takes it, for `finish_waves` and `WaveStream` alike (both call the ``_segments`` entry points: a list
+    without segments is one segment with rms index 0): the plan, ``n`` / ``mixed``, the rms rule in its forms (`_rms_forms`) and the ctypes
+    arrays ``seg_start`` / ``rms_index`` / ``pcm_f32`` over the whole list (None where the library takes NULL)."""
+
+    def __init__(self, samples, cross_fade_duration, sample_rate, rms, target_rms, gain_divide, segments, rms_index, pcm_f32):
+        import ctypes as C
+        self.samples = [int(x) for x in samples]
+        B = len(self.samples)
+        self.plan = plan_wave_tail_segments(self.samples, [B] if segments is None else segments, cross_fade_duration, sample_rate)
+        self.n, self.mixed = self.plan["n"], self.plan["n"] > 0
+        self.gain_host, self.apply_host, self.rms_dev = _rms_forms(rms, B, target_rms, rms_index)
+        self.n_rms = int(self.rms_dev.numel()) if self.rms_dev is not None else 0
+        self.seg_start = (C.c_uint8 * B)(*self.plan["seg_start"])
+        self.rms_index = (C.c_int32 * B)(*[int(i) for i in rms_index]) if rms_index is not None and self.rms_dev is not None else None
+        self.pcm_f32 = (C.c_uint8 * B)(*[1 if f else 0 for f in pcm_f32]) if pcm_f32 is not None else None
+        self.target_rms, self.gain_div = float(target_rms), 1 if gain_divide else 0
+
+    def weights(self, dev):
+        """the cross-fade tables on ``dev`` (None, None when nothing mixes)"""
+        return _xfade_weights(self.n, dev) if self.mixed else (None, None)
+
+
 def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_sample_rate, rms=None, target_rms=target_rms, want_float=True,
                  want_pcm16=False, gain_divide=False, segments=None, rms_index=None, pcm_f32=None):
     """``f5_wave_finish`` over the utterances held back to back in ``wave`` (fp32, on the GPU; ``samples[i]`` each): the rms rule, the linear
@@ -318,31 +341,22 @@ def finish_waves(wave, samples, cross_fade_duration=0.0, sample_rate=target_samp
     import ctypes as C
 
     from .. import _lib
-    lib = _lib.load()
     B = len(samples)
     assert wave.is_cuda and wave.dtype == torch.float32 and wave.is_contiguous() and wave.numel() == sum(samples) and B >= 1
-    segmented = segments is not None or rms_index is not None or pcm_f32 is not None
-    plan = plan_wave_tail_segments(samples, [B] if segments is None else segments, cross_fade_duration, sample_rate)
-    n, mixed = plan["n"], plan["n"] > 0
-    total = sum(samples) - n * (B - sum(plan["seg_start"]))
-    gain_host, apply_host, rms_dev = _rms_forms(rms, B, target_rms, rms_index)
-    w_down, w_up = _xfade_weights(n, wave.device) if mixed else (None, None)
-    if total <= 0 or not plan["device_ok"]:
+    t = _TailList(samples, cross_fade_duration, sample_rate, rms, target_rms, gain_divide, segments, rms_index, pcm_f32)
+    n, mixed = t.n, t.mixed
+    total = sum(samples) - n * (B - sum(t.plan["seg_start"]))
+    w_down, w_up = t.weights(wave.device)
+    if total <= 0 or not t.plan["device_ok"]:
         out = pcm = None  # the library decides (and says why); nothing is allocated for a call it will refuse
     else:
         out = torch.empty(total, device=wave.device, dtype=torch.float64 if mixed else torch.float32) if want_float else None
         pcm = torch.empty(total, device=wave.device, dtype=torch.int16) if want_pcm16 else None
     got = C.c_int64(0)
-    head = (float(target_rms), 1 if gain_divide else 0, int(n), _lib.ptr(w_down), _lib.ptr(w_up))
-    tail = (_lib.ptr(out) if not mixed else None, _lib.ptr(out) if mixed else None, _lib.ptr(pcm), C.byref(got), _lib.stream_ptr())
-    arr = (C.c_int32 * B)(*[int(x) for x in samples])
-    if segmented:
-        index = (C.c_int32 * B)(*[int(i) for i in rms_index]) if rms_index is not None and rms_dev is not None else None
-        rc = lib.f5_wave_finish_segments(B, _lib.ptr(wave), arr, (C.c_uint8 * B)(*plan["seg_start"]), gain_host, apply_host, _lib.ptr(rms_dev),
-                                         int(rms_dev.numel()) if rms_dev is not None else 0, index, *head,
-                                         (C.c_uint8 * B)(*[1 if f else 0 for f in pcm_f32]) if pcm_f32 is not None else None, *tail)
-    else:
-        rc = lib.f5_wave_finish(B, _lib.ptr(wave), arr, gain_host, apply_host, _lib.ptr(rms_dev), *head, *tail)
+    rc = _lib.load().f5_wave_finish_segments(B, _lib.ptr(wave), (C.c_int32 * B)(*t.samples), t.seg_start, t.gain_host, t.apply_host,
+                                             _lib.ptr(t.rms_dev), t.n_rms, t.rms_index, t.target_rms, t.gain_div, int(n), _lib.ptr(w_down),
+                                             _lib.ptr(w_up), t.pcm_f32, _lib.ptr(out) if not mixed else None, _lib.ptr(out) if mixed else None,
+                                             _lib.ptr(pcm), C.byref(got), _lib.stream_ptr())
     if rc == _lib.F5_ENOTSUP:
         return None
     _lib.check(rc, "wave_finish")
@@ -417,31 +431,19 @@ class WaveStream:
         import ctypes as C
 
         from .. import _lib
-        self.samples = [int(x) for x in samples]
-        segmented = segments is not None or rms_index is not None or pcm_f32 is not None
-        self.plan = plan_wave_tail_segments(self.samples, [len(self.samples)] if segments is None else segments, cross_fade_duration, sample_rate)
-        self.n, self.mixed = self.plan["n"], self.plan["n"] > 0
-        self.ok = bool(self.plan["device_ok"]) and min(self.samples) > 0
         assert want_float or want_pcm16
+        t = _TailList(samples, cross_fade_duration, sample_rate, rms, target_rms, gain_divide, segments, rms_index, pcm_f32)
+        self.samples, self.plan, self.n, self.mixed = t.samples, t.plan, t.n, t.mixed
+        self.ok = bool(self.plan["device_ok"]) and min(self.samples) > 0
         self.want_float, self.want_pcm16, self.done, self._handle = want_float, want_pcm16, 0, None
-        self._gain_host, self._apply_host, self._rms_dev = _rms_forms(rms, len(self.samples), target_rms, rms_index)
+        self._gain_host, self._apply_host, self._rms_dev = t.gain_host, t.apply_host, t.rms_dev
         if not self.ok:
             return
-        dev = torch.device("cuda", torch.cuda.current_device())
-        self._tables = _xfade_weights(self.n, dev) if self.mixed else (None, None)  # (kept alive with the session, which reads them in every push)
+        self._tables = t.weights(torch.device("cuda", torch.cuda.current_device()))  # (kept alive with the session, which reads them in every push)
         handle = C.c_void_p()
-        B = len(self.samples)
-        if segmented:
-            index = (C.c_int32 * B)(*[int(i) for i in rms_index]) if rms_index is not None and self._rms_dev is not None else None
-            rc = _lib.load().f5_wave_stream_create_segments(B, (C.c_uint8 * B)(*self.plan["seg_start"]), int(self.n), _lib.ptr(self._tables[0]),
-                                                            _lib.ptr(self._tables[1]), _lib.ptr(self._rms_dev),
-                                                            int(self._rms_dev.numel()) if self._rms_dev is not None else 0, index,
-                                                            float(target_rms), 1 if gain_divide else 0,
-                                                            (C.c_uint8 * B)(*[1 if f else 0 for f in pcm_f32]) if pcm_f32 is not None else None,
-                                                            C.byref(handle))
-        else:
-            rc = _lib.load().f5_wave_stream_create(B, int(self.n), _lib.ptr(self._tables[0]), _lib.ptr(self._tables[1]), _lib.ptr(self._rms_dev),
-                                                   float(target_rms), 1 if gain_divide else 0, C.byref(handle))
+        rc = _lib.load().f5_wave_stream_create_segments(len(self.samples), t.seg_start, int(self.n), _lib.ptr(self._tables[0]),
+                                                        _lib.ptr(self._tables[1]), _lib.ptr(self._rms_dev), t.n_rms, t.rms_index, t.target_rms,
+                                                        t.gain_div, t.pcm_f32, C.byref(handle))
         _lib.check(rc, "wave_stream_create")
         self._handle = handle
 

@@ -583,7 +583,8 @@ F5_API int f5_wave_finish(int B, const float* wave, const int32_t* samples_host,
                           float* out_f32, double* out_f64, int16_t* out_pcm16, int64_t* total_samples_out, f5_stream_t stream);
 /* f5_wave_finish in consecutive pushes: a caller that decodes its utterances group by group gets every output sample as soon as it is final.
  * For EVERY way of cutting an utterance list into consecutive pushes, the emitted pieces, concatenated, are byte-identical to one f5_wave_finish
- * over the whole list (float and PCM): the same kernel arithmetic, tables and saturation rule.
+ * over the whole list (float and PCM): it is the same kernel and the same host path (csrc/wave_tail.hip), the one-shot call being the push that
+ * holds the whole list, reads no carry and writes none.
  *   create   total_utterances = length of the whole list, known up front; xfade_samples, w_down / w_up, rms_dev, target_rms, gain_div as for
  *            f5_wave_finish.  The device arrays (w_down, w_up, rms_dev) are read by every push and stay the caller's: keep them alive until destroy.
  *            n = xfade_samples when total_utterances >= 2, else 0.  float64 or float32 is a property of the WHOLE STREAM, not of a push: with

@@ -160,6 +160,29 @@ def _raw_finish(buf, lengths, seg_start, n, rms_dev=None, n_rms=0, index=None, p
     return rc, got.value, out
 
 
+def _raw_finish_plain(buf, lengths, n, rms):
+    """`f5_wave_finish` itself, the entry point without segments -> (signal, pcm); ``rms``: None, a 0-dim fp32 GPU tensor, or one host value per
+    utterance (the decision taken as `_oracle` takes it)"""
+    from eraxvif5tts_amd import _lib
+    from eraxvif5tts_amd.infer.utils_infer import _xfade_weights
+    B, mixed = len(lengths), n > 0
+    down, up = _xfade_weights(n, buf.device) if mixed else (None, None)
+    gains = applies = rms_dev = None
+    if torch.is_tensor(rms):
+        rms_dev = rms
+    elif rms is not None:
+        gains, applies = (C.c_float * B)(*rms), (C.c_uint8 * B)(*[1 if r < TARGET else 0 for r in rms])
+    total = sum(lengths) - n * (B - 1)
+    out = torch.zeros(total, device="cuda", dtype=torch.float64 if mixed else torch.float32)
+    pcm = torch.zeros(total, device="cuda", dtype=torch.int16)
+    got = C.c_int64(-1)
+    rc = _lib.load().f5_wave_finish(B, _lib.ptr(buf), (C.c_int32 * B)(*lengths), gains, applies, _lib.ptr(rms_dev), TARGET, 0, n, _lib.ptr(down),
+                                    _lib.ptr(up), None if mixed else _lib.ptr(out), _lib.ptr(out) if mixed else None, _lib.ptr(pcm),
+                                    C.byref(got), _lib.stream_ptr())
+    assert rc == 0 and got.value == total
+    return out, pcm
+
+
 def test_refusals():
     from eraxvif5tts_amd import _lib
     from eraxvif5tts_amd.infer.utils_infer import finish_waves, plan_wave_tail_segments
@@ -191,7 +214,7 @@ def test_one_segment_is_the_existing_entry_point():
     buf = _waves(lengths, 10)
     for d in (D, 0.0):
         for rms in (None, torch.tensor(0.07, device="cuda"), [0.05, 0.2, 0.0999, 0.1, 0.03]):
-            old = finish_waves(buf, lengths, d, SR, rms=rms, target_rms=TARGET, want_pcm16=True)
+            old = _raw_finish_plain(buf, lengths, int(d * SR), rms)  # (`finish_waves` always takes the segmented entry point)
             new = finish_waves(buf, lengths, d, SR, rms=rms, target_rms=TARGET, want_pcm16=True, segments=[5])
             assert old[0].dtype == new[0].dtype and torch.equal(old[0], new[0]) and torch.equal(old[1], new[1])
     rc, total, out = _raw_finish(buf, lengths, None, N)  # no array at all: one segment

@@ -8,7 +8,8 @@ import pytest
 import torch
 
 from test_generate_stream_host import compositions
-from test_gpu_wave_tail import DURATIONS, HOST_RMS, LENGTHS, SR
+from test_gpu_wave_segments import D as D16, _lengths as _seg_lengths  # a cross-fade of 16 samples, lengths from {16 .. 257} within the rule
+from test_gpu_wave_tail import DURATIONS, HOST_RMS, LENGTHS, SR, _host_tail
 
 pytestmark = pytest.mark.gpu
 F5_EINVAL, F5_ENOTSUP = -1, -5  # include/f5hip.h
@@ -70,6 +71,36 @@ def test_every_cut_gives_the_one_shot_bytes(dname, gain):
         got = np.concatenate(sigs)
         assert got.dtype == want_sig.dtype and np.array_equal(got, want_sig), sizes
         assert np.concatenate(pcms).tobytes() == want_pcm.tobytes(), sizes
+
+
+def test_streamed_pieces_equal_the_host_functions_byte_for_byte():
+    """The one-shot call runs the kernel and the host path of a push, so this cut is compared with the host functions themselves: torch's gain
+    per wave, numpy's `cross_fade_concat`, `pcm16_bytes` of that array.  Every product lies inside int16, so numpy's cast is defined for every
+    sample and all of them are compared."""
+    from eraxvif5tts_amd.streaming.wire import pcm16_bytes
+    d = DURATIONS["default"]
+    buf = _waves(LENGTHS, seed=71)
+    ref = _host_tail(list(torch.split(buf, LENGTHS)), d, HOST_RMS, TARGET)
+    assert ref.dtype == np.float64 and len(ref) == sum(LENGTHS) - 4 * int(d * SR)
+    assert (np.abs(ref * 32767) < 32767).all()
+    sigs, pcms = _push_all(buf, LENGTHS, [2, 2, 1], d, HOST_RMS, poison=True)
+    got = np.concatenate(sigs)
+    assert got.dtype == np.float64 and got.tobytes() == ref.tobytes()
+    assert np.concatenate(pcms).tobytes() == pcm16_bytes(ref)
+
+
+def test_a_push_with_both_carries_across_a_table_split():
+    """70 utterances in one segment, pushed as 3, 66 and 1: the middle push reads a carry, spans two kernel tables (64, and 3 that overlap by one)
+    and writes a carry"""
+    from eraxvif5tts_amd.infer.utils_infer import finish_waves
+    lengths = _seg_lengths([70], 70)
+    buf = _waves(lengths, seed=70)
+    rms = torch.tensor(0.07, device="cuda")
+    want_sig, want_pcm = finish_waves(buf, lengths, D16, SR, rms=rms, target_rms=TARGET, want_pcm16=True)
+    assert want_sig.dtype == torch.float64 and want_sig.numel() == sum(lengths) - 16 * 69
+    sigs, pcms = _push_all(buf, lengths, [3, 66, 1], D16, rms, poison=True)
+    assert torch.equal(torch.from_numpy(np.concatenate(sigs)), want_sig.cpu())
+    assert torch.equal(torch.from_numpy(np.concatenate(pcms)), want_pcm.cpu())
 
 
 def test_the_first_push_alone_decides_nothing_about_the_dtype():
