@@ -45,6 +45,10 @@ class BigVGANConfig(C.Structure):  # struct f5_bigvgan_config
                 ("use_bias_at_final", C.c_int32)]
 
 
+class SpeakerConfig(C.Structure):  # struct f5_speaker_config
+    _fields_ = [(n, C.c_int32) for n in ("feat_dim", "channels", "emb_dim", "layers", "cat_channels", "se_bottleneck", "attention_channels", "scale")]
+
+
 class MelConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_fft", "hop", "win", "n_mels", "sample_rate", "mel_type")]
 
@@ -185,6 +189,18 @@ _PROTOS = {
     "f5_frontend_destroy": (_I, [_P]),
     "f5_frontend_mel": (_I, [_P, _I, _I, _P, _P, _P]),
     "f5_frontend_resample": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "f5_speaker_create": (_I, [C.POINTER(SpeakerConfig), C.POINTER(_P)]),
+    "f5_speaker_set_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
+    "f5_speaker_has_tensor": (_I, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
+    "f5_speaker_finalize": (_I, [_P]),
+    "f5_speaker_destroy": (_I, [_P]),
+    "f5_speaker_embed_ragged": (_I, [_P, _I, C.POINTER(C.c_int32), _P, _P, _P]),
+    "f5_speaker_set_tap": (_I, [_P, C.c_char_p, _P]),
+    "f5_op_speaker_featnorm": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P]),
+    "f5_op_speaker_conv_relu_bn": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
+    "f5_op_speaker_res2": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
+    "f5_op_speaker_se": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_op_speaker_pool": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 

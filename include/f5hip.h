@@ -855,6 +855,66 @@ F5_API int f5_frontend_destroy(f5_frontend_t h);
 F5_API int f5_frontend_mel(f5_frontend_t h, int B, int nw, const float* wave, float* mel, f5_stream_t stream);
 F5_API int f5_frontend_resample(f5_frontend_t h, int B, int n, int orig_freq, int new_freq, const float* wave, float* out, f5_stream_t stream);
 
+/* ------------------------------------------------------------------ speaker-similarity head (ECAPA-TDNN, the "SIM" figure)
+ * Everything of the reference's eval/ecapa_tdnn.py behind `self.feature_extract(...)` (ECAPA_TDNN.get_feat / forward, :283-309) with
+ * global_context_att = False, as ECAPA_TDNN_SMALL and utils_eval.run_sim use it: forward only, eval mode, fp32 storage.  The feature extractor
+ * (WavLM-large from s3prl in the reference) is NOT part of this library: the caller hands in its hidden states.
+ *   x = sum_l softmax(feature_weight)[l] hs[l] + 1e-6 -> InstanceNorm1d per utterance (biased variance, eps 1e-5) -> layer1 Conv1dReluBn(k 5)
+ *   -> three SE_Res2Blocks (dilation 2, 3, 4; Res2 scale `scale`) -> cat -> Conv1d(3C -> cat_channels) + ReLU -> AttentiveStatsPool
+ *   -> BatchNorm1d(2 cat_channels) -> Linear(-> emb_dim)
+ * Tensor names are the reference state_dict()'s: feature_weight, layer1.conv.*, layer1.bn.*, layer{2,3,4}.Conv1dReluBn{1,2}.{conv,bn}.*,
+ * layer{2,3,4}.Res2Conv1dReluBn.{convs,bns}.{0..scale-2}.*, layer{2,3,4}.SE_Connect.linear{1,2}.*, conv.*, pooling.linear{1,2}.*, bn.*, linear.*
+ * (bn: weight, bias, running_mean, running_var).  has_tensor answers 0 for feature_extract.* and num_batches_tracked; finalize names the first
+ * missing tensor.  A pooling.linear1.weight with 3 * cat_channels input channels (global_context_att = True) is refused by set_tensor with
+ * F5_ENOTSUP: that model is another function, not an approximation of this one.
+ * Per-channel statistics over time (instance norm, the SE mean, the pool's softmax denominator, its two weighted sums and the subtraction
+ * E[x^2] - mean^2) are accumulated in fp64 in a fixed order; no sum uses atomics. */
+typedef struct f5_speaker_s* f5_speaker_t;
+typedef struct f5_speaker_config {
+    int32_t feat_dim;           /* 1024 (WavLM-large); a multiple of 32 */
+    int32_t channels;           /* 512; a multiple of 8 * scale */
+    int32_t emb_dim;            /* 256 */
+    int32_t layers;             /* 25 hidden-state layers */
+    int32_t cat_channels;       /* 1536; a multiple of 32 */
+    int32_t se_bottleneck;      /* 128 */
+    int32_t attention_channels; /* 128; a multiple of 32 */
+    int32_t scale;              /* 8 */
+} f5_speaker_config;
+F5_API int f5_speaker_create(const f5_speaker_config* cfg, f5_speaker_t* out);
+F5_API int f5_speaker_set_tensor(f5_speaker_t h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+F5_API int f5_speaker_has_tensor(f5_speaker_t h, const char* name, int64_t* numel);
+F5_API int f5_speaker_finalize(f5_speaker_t h);
+F5_API int f5_speaker_destroy(f5_speaker_t h);
+/* B utterances of DIFFERENT frame counts through one set of launches.  hs: dev f32 [layers, sum(frames), feat_dim], the utterances back to back
+ * along the row axis; frames_host: host int32 [B], read before the call returns; emb: dev f32 [B, emb_dim].  Every kernel that looks across rows
+ * stops at the utterance's own first and last frame (a Conv1d tap outside reads zero), so an utterance's embedding has the same bits whatever
+ * shares the call with it and in every call.  Lists of more than 64 utterances (or 32768 frames: 64 utterances of 10 s) are cut, in order, into several launch sets,
+ * which changes no bit.  F5_EINVAL before any launch: B <= 0, a frame count below 2 (InstanceNorm1d has no variance there; the reference
+ * raises too), rows beyond 32-bit indexing.  Nothing synchronises (workspace growth aside). */
+F5_API int f5_speaker_embed_ragged(f5_speaker_t h, int B, const int32_t* frames_host, const float* hs, float* emb, f5_stream_t stream);
+/* Test hook: the next embed calls also copy an intermediate tensor, time-major [sum(frames), width] (pooling: [B, 2 cat_channels]), into `dev`
+ * (NULL: stop).  Names: instance_norm (feat_dim), layer1 .. layer4 (channels), conv (cat_channels), pooling. */
+F5_API int f5_speaker_set_tap(f5_speaker_t h, const char* name, float* dev);
+/* Test-only: the pieces of the head one by one, launched as the head launches them, over cnt utterances back to back (frames_host as above).
+ * Activations x / out: dev f32, time-major [sum(frames), channels].  Parameters are HOST arrays in PyTorch's layouts; every op stages them on the
+ * device itself and synchronises the stream before it returns.  bn_host: [4][channels] = weight, bias, running_mean, running_var.
+ *   featnorm       hs dev [L, rows, F], feature_weight_host [L] (before the softmax) -> out [rows, F]
+ *   conv_relu_bn   bn(relu(Conv1d(cin -> cout, k odd, dilation dil, padding dil (k - 1) / 2)(x))); w_host [cout][cin][k]
+ *   res2           Res2Conv1dReluBn(C, k 3, dilation dil, scale): w_host [scale - 1][C / scale][C / scale][3], b_host [scale - 1][C / scale],
+ *                  bn_host [scale - 1][4][C / scale]
+ *   se             x * sigmoid(linear2(relu(linear1(mean_t x)))) + resid (resid NULL: no add); w1_host [bott][C], w2_host [C][bott]
+ *   pool           AttentiveStatsPool(C, att) -> out [cnt, 2 C] (mean | std); w1_host [att][C], w2_host [C][att] */
+F5_API int f5_op_speaker_featnorm(int cnt, const int32_t* frames_host, int L, int F, const float* hs, const float* feature_weight_host, float* out,
+                                  f5_stream_t stream);
+F5_API int f5_op_speaker_conv_relu_bn(int cnt, const int32_t* frames_host, int cin, int cout, int k, int dil, const float* x, const float* w_host,
+                                      const float* b_host, const float* bn_host, float eps, float* out, f5_stream_t stream);
+F5_API int f5_op_speaker_res2(int cnt, const int32_t* frames_host, int C, int scale, int dil, const float* x, const float* w_host,
+                              const float* b_host, const float* bn_host, float eps, float* out, f5_stream_t stream);
+F5_API int f5_op_speaker_se(int cnt, const int32_t* frames_host, int C, int bott, const float* x, const float* resid, const float* w1_host,
+                            const float* b1_host, const float* w2_host, const float* b2_host, float* out, f5_stream_t stream);
+F5_API int f5_op_speaker_pool(int cnt, const int32_t* frames_host, int C, int att, const float* x, const float* w1_host, const float* b1_host,
+                              const float* w2_host, const float* b2_host, float* out, f5_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
