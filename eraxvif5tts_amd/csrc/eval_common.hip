@@ -23,6 +23,9 @@ AttnDropout plan_attn_dropout(const f5_plan_s* p, int l, uint32_t bw0, uint32_t 
     d.bw_step = bw_step;
     return d;
 }
+int plan_attn_kind(const f5_plan_s* p, int S) {  // launch_attention's kernel for sequences of S tokens: 1 = the tuned kernels where they support S
+    return p->attn_kernel != 0 && attention_fast_supported(p->m->cfg.precision, S, p->m->cfg.heads) ? 1 : 0;
+}
 int plan_attn_dropout_advance(f5_plan_s* p, uint32_t by, hipStream_t st) {
     if (!(p->drop_p > 0.0)) return 0;
     return launch_attn_dropout_advance(p->drop_base, by, st);
@@ -46,6 +49,89 @@ int run_gemm(f5_plan_s* p, const GemmParams& g, int mode, int epi, hipStream_t s
     if (p->gemm_kernel != 0 && gemm_fast_supported(g, prec, mode, epi) && (p->gemm_kernel == 1 || g.M >= 512)) kind = 1;
     return launch_gemm(g, prec, mode, epi, kind, st);
 }
+// ---- call-site builders: the GemmParams of the linears every backbone shares.  `site`: the launch is one of the DiT block's four call sites of the
+// per-site tile-walk knobs (GemmParams::site = 1 .. 4); the other backbones' linears carry none.
+GemmParams gp_linear(const void* A, const void* W, const float* bias, int M, int N, int K) {  // A [M, K] . W [N, K]^T + bias, destination left to the caller
+    GemmParams g = gp_zero();
+    g.A = A; g.lda = K; g.W = W; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = bias;
+    return g;
+}
+// input x-projection (EPI_ADD2): h = W_x . x + base -> p->hT and the stream `res`; res16: `res` and the addend (p->base16) hold fp16 elements
+GemmParams gp_x_proj(const f5_plan_s* p, int xrows, int rows, void* res, bool res16) {
+    GemmParams g = gp_linear(p->xin, p->m->w_x, nullptr, rows, p->m->cfg.dim, MELP);
+    g.a_row_mod = xrows < rows ? xrows : 0;
+    g.addend = res16 ? reinterpret_cast<const float*>(p->base16) : p->base; g.ldadd = g.N; g.out_t = p->hT; g.ldo = g.N;
+    g.out_f = reinterpret_cast<float*>(res); g.ldof = g.N; g.add2_f16 = res16;
+    return g;
+}
+GemmParams gp_pos_conv(const f5_plan_s* p, int li, int rows, int N) {  // position conv li (GEMM_CONV31): hT -> cT (EPI_STORE_T), cT -> yT (EPI_GATE_T)
+    const f5_model_s* m = p->m;
+    const int D = m->cfg.dim;
+    GemmParams g = gp_zero();
+    g.A = li == 0 ? p->hT : p->cT; g.lda = D; g.W = m->w_conv[li]; g.M = rows; g.N = D; g.K = 31 * m->conv_win;
+    g.bias = m->b_conv[li]; g.act = ACT_MISH; g.rows_per_batch = N; g.conv_cg = m->conv_cg; g.conv_win = m->conv_win;
+    g.out_t = li == 0 ? p->cT : p->yT; g.ldo = D;
+    return g;
+}
+GemmParams gp_qkv(const f5_plan_s* p, const void* W, const float* bias, int M, int rpb, const float* rope, bool site) {  // hT -> q|k|v with RoPE (EPI_ROPE_T)
+    GemmParams g = gp_linear(p->hT, W, bias, M, 3 * p->m->inner, p->m->cfg.dim);
+    g.out_t = p->qkv; g.ldo = g.N; g.rows_per_batch = rpb; g.site = site ? 1 : 0;
+    g.rope = rope; g.rope_inner = p->m->inner; g.rope_heads = p->m->rope_heads;
+    return g;
+}
+// out-projection: gate * to_out(cT), 0 where rowmask is 0, as a stored branch `out_t` (EPI_GATE_T) -- or into a stream (gp_resid_stream)
+GemmParams gp_out_proj(const f5_plan_s* p, const void* W, const float* bias, int M, int rpb, const float* gate, int gate_bstride, const uint8_t* rowmask,
+                       void* out_t, bool site) {
+    GemmParams g = gp_linear(p->cT, W, bias, M, p->m->cfg.dim, p->m->inner);
+    g.out_t = out_t; g.ldo = out_t ? g.N : 0; g.gate = gate; g.gate_bstride = gate_bstride; g.rows_per_batch = rpb; g.rowmask = rowmask; g.site = site ? 2 : 0;
+    return g;
+}
+GemmParams gp_ff1(const f5_plan_s* p, const void* W, const float* bias, int M, bool site) {  // hT -> gelu(ff.0.0) -> ffh (EPI_STORE_T)
+    GemmParams g = gp_linear(p->hT, W, bias, M, p->m->cfg.ff_inner, p->m->cfg.dim);
+    g.act = ACT_GELU_TANH; g.out_t = p->ffh; g.ldo = g.N; g.site = site ? 3 : 0;
+    return g;
+}
+GemmParams gp_ff2(const f5_plan_s* p, const void* W, const float* bias, int M, int rpb, const float* gate, int gate_bstride, void* out_t, bool site) {  // as gp_out_proj, from ffh
+    GemmParams g = gp_linear(p->ffh, W, bias, M, p->m->cfg.dim, p->m->cfg.ff_inner);
+    g.out_t = out_t; g.ldo = out_t ? g.N : 0; g.gate = gate; g.gate_bstride = gate_bstride; g.rows_per_batch = rpb; g.site = site ? 4 : 0;
+    return g;
+}
+GemmParams gp_linear_f32(const void* A, const void* W, const float* bias, int M, int N, int K, float* out) {  // ... stored as fp32 to out [M, N] (EPI_STORE_F32)
+    GemmParams g = gp_linear(A, W, bias, M, N, K);
+    g.out_f = out; g.ldof = N;
+    return g;
+}
+GemmParams gp_proj_out(const f5_plan_s* p, int M, float* out) { return gp_linear_f32(p->hT, p->m->w_out, p->m->b_out, M, MELP, p->m->cfg.dim, out); }
+// points an EPI_RESID site (out-projection, FF2) at the residual stream it updates in place: fp32, or the fp16 stream of the bf16 / fp16 modes
+GemmParams gp_resid_stream(GemmParams g, void* stream, bool f16) {
+    g.out_t = nullptr; g.out_f = reinterpret_cast<float*>(stream); g.ldof = g.N; g.add2_f16 = f16;
+    return g;
+}
+// a QKV or FF1 site in its LayerNorm-fold form: A = the fp16 stream itself, W' = fp16(W (1 + scale)), c1 = rowsum W', c2 = b + W . shift (gemm.h)
+GemmParams gp_folded(GemmParams g, const void* stream16, const void* Wf, const float* c1, const float* c2) {
+    g.A = stream16; g.W = Wf; g.bias = nullptr; g.lnf_c1 = c1; g.lnf_c2 = c2;
+    return g;
+}
+
+// Input embedding of every backbone (dit.py:88-96, mmdit.py:69-79, unett.py:88-98; the cond / text half of the linear is hoisted into `base`):
+// h = W_x . x + base -> p->hT and the stream `res` [rows, D]; then mish(conv(mish(conv(h)))) -> p->yT.  The second conv only STORES its branch
+// (activation dtype); every fp32 residual add of the network is fused into the pass that follows it (coalesced streaming RMW, store-only GEMM
+// epilogues).  tm: the launches are in-situ timing sites (DiT).  Ragged sample() (DiT): the gap rows of what the convs read are zeroed.
+int input_embed(f5_plan_s* p, const float* x, int xrows, int rows, int N, void* res, bool res16, bool tm, hipStream_t st) {
+    const f5_dit_config& c = p->m->cfg;
+    const int P = c.precision;
+    const size_t row_bytes = (size_t)c.dim * f5_elem_size(P);
+    auto run = [&](int site, const GemmParams& g, int mode, int epi) {
+        return tm ? timed(p, site, st, [&] { return run_gemm(p, g, mode, epi, st); }) : run_gemm(p, g, mode, epi, st);
+    };
+    F5_TRY(launch_convert_pad(P, x, c.mel_dim, xrows, c.mel_dim, MELP, p->xin, MELP, st));
+    F5_TRY(run(F5_SITE_INPUT, gp_x_proj(p, xrows, rows, res, res16), GEMM_DENSE, EPI_ADD2));
+    if (p->rg) F5_TRY(launch_zero_rows(p->hT, row_bytes, rows, p->gapflag, st));
+    F5_TRY(run(F5_SITE_CONV, gp_pos_conv(p, 0, rows, N), GEMM_CONV31, EPI_STORE_T));
+    if (p->rg) F5_TRY(launch_zero_rows(p->cT, row_bytes, rows, p->gapflag, st));
+    return run(F5_SITE_CONV, gp_pos_conv(p, 1, rows, N), GEMM_CONV31, EPI_GATE_T);
+}
+
 float* tap_dst(f5_plan_s* p, const std::string& name) {
     auto it = p->taps.find(name);
     return it == p->taps.end() ? nullptr : it->second;
@@ -93,14 +179,12 @@ int compute_text_embed(f5_plan_s* p, const int32_t* text, int nt, int B, int N, 
     for (int i = 0; i < c.conv_layers; ++i) {
         const TextBlockW& t = m->tblocks[i];
         F5_TRY(launch_dwconv7_ln(P, out, B, N, td, t.dw_wt, t.dw_b, t.ln_w, t.ln_b, p->teT, td, st));
-        GemmParams g = gp_zero();
-        g.A = p->teT; g.lda = td; g.W = t.w1; g.ldw = td; g.M = rows; g.N = 2 * td; g.K = td;
-        g.bias = t.b1; g.act = ACT_GELU_ERF; g.out_t = p->te_h; g.ldo = 2 * td;
+        GemmParams g = gp_linear(p->teT, t.w1, t.b1, rows, 2 * td, td);
+        g.act = ACT_GELU_ERF; g.out_t = p->te_h; g.ldo = 2 * td;
         F5_TRY(run_gemm(p, g, GEMM_DENSE, EPI_STORE_T, st));
         F5_TRY(launch_grn(P, p->te_h, B, N, 2 * td, t.gamma, t.beta, p->grn_scratch, st));
-        g = gp_zero();
-        g.A = p->te_h; g.lda = 2 * td; g.W = t.w2; g.ldw = 2 * td; g.M = rows; g.N = td; g.K = 2 * td;
-        g.bias = t.b2; g.act = ACT_NONE; g.out_f = out; g.ldof = td; g.rows_per_batch = N;
+        g = gp_linear(p->te_h, t.w2, t.b2, rows, td, 2 * td);
+        g.act = ACT_NONE; g.out_f = out; g.ldof = td; g.rows_per_batch = N;
         F5_TRY(run_gemm(p, g, GEMM_DENSE, EPI_RESID, st));
         if (mp) F5_TRY(launch_mask_rows(out, rows, td, p->filler, st));
     }
@@ -116,10 +200,7 @@ int compute_base(f5_plan_s* p, const float* cond, const int32_t* lens, const flo
     const size_t es = f5_elem_size(P);
     void* ab = (char*)p->abase + row0 * kct * es;
     F5_TRY(launch_pack_base(P, cond, lens, cmask, te, nb, N, c.mel_dim, MELP, td, zero_cond, ab, kct, st));
-    GemmParams g = gp_zero();
-    g.A = ab; g.lda = kct; g.W = m->w_ct; g.ldw = kct; g.M = nb * N; g.N = D; g.K = kct;
-    g.bias = m->b_in; g.out_f = p->base + row0 * D; g.ldof = D;
-    F5_TRY(run_gemm(p, g, GEMM_DENSE, EPI_STORE_F32, st));
+    F5_TRY(run_gemm(p, gp_linear_f32(ab, m->w_ct, m->b_in, nb * N, D, kct, p->base + row0 * D), GEMM_DENSE, EPI_STORE_F32, st));
     if (p->base16) F5_TRY(launch_f32_to_f16(p->base + row0 * D, (char*)p->base16 + row0 * D * 2, (size_t)nb * N * D, st, plan_res_f16(p) ? p->sat_flag : nullptr));
     return 0;
 }

@@ -1,7 +1,9 @@
 // model_internal.h -- shared by the translation units of the model path (round 4: csrc/model.hip split per concern, no launch changed):
 //   model.hip        weights in HBM (f5_model_*), plans / workspaces / options / in-situ timing (f5_plan_*)
-//   eval_common.hip  tuning knobs, GEMM dispatch, stage taps, AdaLN table, text embedding, hoisted input embedding, net_eval, f5_dit_forward
-//   dit_eval.hip     one DiT evaluation (dit.py:185-233, modules.py:301-336,610-641)
+//   eval_common.hip  GEMM dispatch, the call-site builders (gp_*) and the input embedding of every backbone, stage taps, AdaLN table, text
+//                    embedding, hoisted input embedding, net_eval, f5_dit_forward
+//   dit_eval.hip     one DiT evaluation (dit.py:185-233, modules.py:301-336,610-641): its modes (DitEvalModes, f5_debug_eval_modes), the LayerNorm
+//                    and LayerNorm-fold sites, the attention and feed-forward halves of a block
 //   unett_eval.hip   one UNetT evaluation (backbones/unett.py:185-253)
 //   mmdit_eval.hip   one MMDiT evaluation (backbones/mmdit.py:146-190)
 //   sampler.hip      CFM.sample: the step loop over ode_methods.h's solver table (uniform and ragged calls), the hipGraph cache keyed by the
@@ -270,8 +272,24 @@ bool plan_attn_prescale(const f5_plan_s* p);  // pre-scaled q wanted and possibl
 // the dropout descriptor of the attention call of the block at position l (of plan_depth) in the running evaluation (prob 0 when the mode is off)
 AttnDropout plan_attn_dropout(const f5_plan_s* p, int l, uint32_t bw0 = 0, uint32_t bw_step = 1);
 int plan_attn_dropout_advance(f5_plan_s* p, uint32_t by, hipStream_t st);  // no-op when the mode is off
+int plan_attn_kind(const f5_plan_s* p, int S);  // launch_attention's kernel kind for sequences of S tokens
 GemmParams gp_zero();
 int run_gemm(f5_plan_s* p, const GemmParams& g, int mode, int epi, hipStream_t st);
+// call-site builders: each returns the complete GemmParams of one linear (site: one of the DiT block's four GemmParams::site call sites)
+GemmParams gp_linear(const void* A, const void* W, const float* bias, int M, int N, int K);
+GemmParams gp_linear_f32(const void* A, const void* W, const float* bias, int M, int N, int K, float* out);
+GemmParams gp_x_proj(const f5_plan_s* p, int xrows, int rows, void* res, bool res16);
+GemmParams gp_pos_conv(const f5_plan_s* p, int li, int rows, int N);
+GemmParams gp_qkv(const f5_plan_s* p, const void* W, const float* bias, int M, int rpb, const float* rope, bool site);
+GemmParams gp_out_proj(const f5_plan_s* p, const void* W, const float* bias, int M, int rpb, const float* gate, int gate_bstride, const uint8_t* rowmask,
+                       void* out_t, bool site);
+GemmParams gp_ff1(const f5_plan_s* p, const void* W, const float* bias, int M, bool site);
+GemmParams gp_ff2(const f5_plan_s* p, const void* W, const float* bias, int M, int rpb, const float* gate, int gate_bstride, void* out_t, bool site);
+GemmParams gp_proj_out(const f5_plan_s* p, int M, float* out);
+GemmParams gp_resid_stream(GemmParams g, void* stream, bool f16);  // an EPI_RESID site updates `stream` in place (fp32, or fp16 elements)
+GemmParams gp_folded(GemmParams g, const void* stream16, const void* Wf, const float* c1, const float* c2);  // a QKV / FF1 site in its LayerNorm-fold form
+// convert_pad, x-projection into p->hT and the stream `res` (fp16 elements: res16), the two position convs -> p->yT; tm: in-situ timing sites
+int input_embed(f5_plan_s* p, const float* x, int xrows, int rows, int N, void* res, bool res16, bool tm, hipStream_t st);
 float* tap_dst(f5_plan_s* p, const std::string& name);
 int tap_f32(f5_plan_s* p, const std::string& name, const float* src, int ld, int rows, int cols, hipStream_t st);
 int tap_t(f5_plan_s* p, const std::string& name, const void* src, int ld, int rows, int cols, hipStream_t st);
@@ -283,6 +301,22 @@ int compute_base(f5_plan_s* p, const float* cond, const int32_t* lens, const flo
 int net_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, int time_row, int per_batch_rows, const uint8_t* mask, hipStream_t st);
 int check_plan_shape(f5_plan_s* p, int B, int N);
 // ---- one evaluation per backbone
+// The modes of one DiT evaluation: every switch between its launch forms, decided once by dit_eval_modes from the plan's state, the knobs and the
+// call's shape (the conditions and their reasons: dit_eval.hip).  dit_eval and f5_debug_eval_modes (f5hip.h: same order) read it.
+struct DitEvalModes {
+    int rows, rows_g;  // token rows; rows the four block GEMMs run over (rounded up to the 256-row tile, or = rows)
+    bool defer;        // the fp32 / fp16 stream is written once per block
+    bool r16;          // fp16 residual stream (plan_res_f16)
+    bool rmw;          // in-place residual epilogues on the fp16 stream
+    bool lnf;          // LayerNorm fold (per block: lnf1 = lnf && l > 0, lnf_next = lnf && l + 1 < depth)
+    bool qs;           // pre-scaled q
+    bool wpf;          // the LayerNorm passes / statistics launches prefetch weights
+    bool ink_qkv, ink_ff1;  // the folded projection finishes its row statistics inside its kernel (no stats_finalize launch in front)
+    bool split_v;      // the tile arithmetic would project v apart from q|k (the launch adds: not fp32, tuned kernel, fused projection not on gemm_w4)
+    size_t frow0;      // first row of this evaluation time in the fold table
+};
+// F5_ESTATE where the plan cannot run the fold table it holds (pre-scaled q rows)
+int dit_eval_modes(const f5_plan_s* p, int nb, int N, int mod_bstride, DitEvalModes* out);
 int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float* modp, int mod_bstride, const uint8_t* mask, hipStream_t st);
 int unett_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float* temb, int temb_bstride, const uint8_t* mask, hipStream_t st);
 int mmdit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float* modp, int mod_bstride, const uint8_t* mask, hipStream_t st);

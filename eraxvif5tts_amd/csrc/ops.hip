@@ -4,6 +4,7 @@
 
 #include "gemm.h"
 #include "kernels.h"
+#include "model_internal.h"
 #include "runtime.h"
 #include "tuning.h"
 
@@ -71,10 +72,7 @@ extern "C" int f5_op_linear_fused_p(int precision, int kernel, int epi, int M, i
         g.bias = bias; g.act = act; g.out_t = Ot; g.ldo = N; g.rows_per_batch = seq > 0 ? seq : M;
         if (epi == EPI_RESID) {  // in-place update of the fp16 residual stream: `out` is read (rounded to fp16), updated and written back
             if ((rc = launch_f32_to_f16(out, Ot, (size_t)M * N, st))) break;
-            g.out_t = nullptr;
-            g.out_f = reinterpret_cast<float*>(Ot);
-            g.ldof = N;
-            g.add2_f16 = 1;
+            g = gp_resid_stream(g, Ot, true);
         }
         if (epi == EPI_GATE_T || epi == EPI_RESID) {
             g.gate = gate;

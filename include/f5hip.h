@@ -526,6 +526,15 @@ F5_API int f5_debug_gemm_clock(void* dev_buf);
  * feature tile (conv31: tokens per workgroup x 64); schedule 0 = plain ring, 1 = staggered wave groups, 2 = persistent grid; flags: 1 = fp16
  * elements, 4 = fp32 elements (neither: bf16), 2 = LayerNorm-fold build, 8 = grouped conv as an implicit GEMM. */
 F5_API int f5_debug_last_gemm(int* family, int* bm, int* bn, int* schedule, int* flags);
+/* Which launch forms one DiT evaluation of nb x N token rows takes in the plan's present state (its options, stage taps, block subset, the fold
+ * table and evaluation index its last call left, the tuning knobs in force); per_batch_rows != 0: per-sample times, as f5_dit_forward evaluates.
+ * The function the evaluation itself decides with, called alone: no launch, no side effect.  out[F5_EVAL_MODES_N] = rows, rows_g (rows the block
+ * GEMMs run over), defer, r16 (fp16 stream), rmw (in-place residual epilogues), lnf (LayerNorm fold), qs (pre-scaled q), wpf (weight prefetch),
+ * ink_qkv, ink_ff1 (the folded projection finishes its row statistics in its own kernel), split_v (the tile arithmetic projects v apart from
+ * q|k; the launch further needs a 16-bit mode, the tuned kernel and a fused projection the one-wave-per-SIMD kernel does not take), frow0 (first
+ * fold-table row of the evaluation time).  F5_ENOTSUP on the other backbones; F5_ESTATE as the evaluation itself would refuse. */
+#define F5_EVAL_MODES_N 12
+F5_API int f5_debug_eval_modes(f5_plan_t plan, int nb, int N, int per_batch_rows, int32_t* out);
 /* process-wide kernel tuning knobs for A/B measurements ("gemm_variant": main-loop schedule of the tuned GEMM) */
 F5_API int f5_tuning_set(const char* key, int value);
 /* The value a knob holds now (no side effect; F5_EINVAL for a null argument or an unknown key), and the key of knob `index` in the library's

@@ -170,6 +170,17 @@ def last_gemm():
     return tuple(t.value for t in v)
 
 
+# f5_debug_eval_modes (include/f5hip.h): the fields of csrc/model_internal.h's DitEvalModes, in its order
+EVAL_MODE_FIELDS = ("rows", "rows_g", "defer", "r16", "rmw", "lnf", "qs", "wpf", "ink_qkv", "ink_ff1", "split_v", "frow0")
+
+
+def eval_modes(plan, nb, N, per_batch_rows=False):
+    """The launch forms one DiT evaluation of nb x N token rows takes in the plan's present state (nb counts the CFG-doubled batch), as a dict."""
+    v = (C.c_int32 * len(EVAL_MODE_FIELDS))()
+    _lib.check(_lib.load().f5_debug_eval_modes(plan, nb, N, int(bool(per_batch_rows)), v), "f5_debug_eval_modes")
+    return dict(zip(EVAL_MODE_FIELDS, v))
+
+
 # ----------------------------------------------------------------------------- element-wise comparison of the 16-bit GEMM / conv kernels
 P_BF16, P_FP32, P_FP16 = 0, 1, 2
 PREC_NAMES = {P_BF16: "bf16", P_FP32: "fp32", P_FP16: "fp16"}
