@@ -124,6 +124,7 @@ _PROTOS = {
     "f5_op_ln_fold": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "f5_op_linear_fused_p": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "f5_op_ln_fold_p": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "f5_op_resid_stats_p": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f5_op_layernorm_modulate": (_I, [_I, _I, _P, _P, _P, _P, _P]),
     "f5_op_attention": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "f5_op_attention_dropout": (_I, [_I, _I, _I, _I, _I, _P, _P, _F, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),

@@ -50,6 +50,8 @@ struct GemmParams {
                              // sets it now: every launch starts at row 0
     const uint8_t* rowmask;  // [M] or null
     const uint8_t* rowbits;  // optional transposed form of rowmask for the tuned kernel's epilogue (launch_rowbits): byte [m/128][m%16], bit (m%128)/16
+                             // (4-byte aligned: the whole-line in-place epilogue of gemm_w4.hip reads the bytes 4 q .. 4 q + 3 of a group as one dword;
+                             //  every buffer launch_rowbits fills is a hipMalloc allocation of its own)
     const float* rope;       // [N_seq][32][2] (cos, sin)
     int rope_inner;          // heads * 64
     int rope_heads;          // heads that receive RoPE

@@ -27,8 +27,13 @@
 //     lane's eight accumulators over the feature fragments are eight consecutive features of one token: one 16-byte store, 16 adjacent lanes write 256
 //     contiguous bytes, an instruction 8 whole lines instead of 64 separate 16-byte pieces (store_wave_impl; no cross-lane instruction).  Same products,
 //     same K order, same epilogue operations per element: same bits.  Probe (tools/gemm_w4_probe.hip schedules 70 - 73,
-//     profiles/w4_whole_line_epilogue_probe.txt): - 15 .. - 20 us at the QKV and FF1 shapes; the in-place residual epilogue gained less than a third
-//     of its read-modify-write cost there and keeps the map above, as do the 128-row tiles (not measured);
+//     profiles/w4_whole_line_epilogue_probe.txt): - 15 .. - 20 us at the QKV and FF1 shapes;
+//   * the in-place residual builds on 256-row tiles (out-projection, FF2; RL below) use the same operand roles and weight-row permutation: one 16-byte
+//     load and one 16-byte store of the fp16 stream per lane, token tile and component, no cross-lane instruction around the arithmetic.  The
+//     LayerNorm fold's partial row statistics keep their lane map and summation tree -- the values just stored reach it through a 4-KiB patch of
+//     LDS per wave (resid_tile_wl) --, so stream and statistics keep their bits (tests/test_gpu_w4_resid_whole_line.py; probe schedules 80 / 81,
+//     profiles/w4_resid_whole_line_ab.md: - 2 us at the out-projection shape, - 11 us at FF2's, C2 step - 1.3 %).  The 128-row tiles keep the map
+//     above (not measured);
 //   * a second tile height (template parameter MI = 4: 128 x 256, 64 x 128 per wave) for small batches; there the folded projections also finish the
 //     LayerNorm fold's row statistics themselves (finish_stats) and the kernel touches the weights of the launches behind it.
 // Launch conditions (gemm_w4_ok): bf16 / fp16-fold operands, M % 128 == 0, N % 256 == 0, K % 128 == 0, K >= 256, the lean operand forms of the
@@ -63,7 +68,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // 16 j + 4 fq + r of feature 8 fc + i in acc[i][j][r]: for a fixed (j, r) its eight accumulators over i are 16 consecutive output bytes, and
     // the 16 lanes of a row write 256 contiguous bytes.  Same products in the same K order: the same bits as the other operand order.
     constexpr bool WL = MI == 8 && EPI != EPI_RESID;
-    __shared__ __attribute__((aligned(1024))) char smem[EPI_LDS + EPI_BYTES];
+    // RL: the same operand roles and weight-row permutation for the in-place residual epilogue of the 256-row builds (resid_tile_wl below): one 16-byte
+    // load and one 16-byte store of the stream per lane, (token tile, component), 16 lanes = one 256-byte run of a stream row.  The partial row statistics
+    // keep their lane map: the values just stored travel through a 4-KiB patch of LDS per wave (behind the bias | gate image) into it.
+    constexpr bool RL = MI == 8 && EPI == EPI_RESID;
+    constexpr bool SWP = WL || RL;  // tokens on the MFMA's row index, weight rows permuted
+    constexpr int PATCH = EPI_LDS + EPI_BYTES, PATCH_BYTES = RL ? 4 * 4096 : 0;
+    __shared__ __attribute__((aligned(4096))) char smem[EPI_LDS + EPI_BYTES + PATCH_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
@@ -107,7 +118,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int jj = 0; jj < 8; ++jj) {
         const int row = (wave * 8 + jj) * 8 + (lane >> 3);
         const int logical = (lane & 7) ^ ((row >> 1) & 7);  // (keyed on the LDS row, also under WL)
-        const int wrow = WL ? (row & ~127) + 8 * (row & 15) + ((row & 127) >> 4) : row;
+        const int wrow = SWP ? (row & ~127) + 8 * (row & 15) + ((row & 127) >> 4) : row;
         voffW[jj] = (unsigned)(wrow * p.ldw * 2 + logical * 16);
     }
 #pragma unroll
@@ -192,7 +203,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             (void)acc; (void)fw; (void)fa; (void)voffA; (void)voffW; (void)baseA; (void)baseW;
             constexpr int n = decltype(nc)::value;
             constexpr int s = n / (8 * MI), i = (n % (8 * MI)) / MI, j = n % MI;
-            if constexpr (WL) {  // tokens on the row index
+            if constexpr (SWP) {  // tokens on the row index
                 if constexpr (LNF || Elem<EL>::F16)
                     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fa[s][j]), "v"(fw[s][i]));
                 else
@@ -286,9 +297,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         }
     };
-    constexpr int NBS = WL ? 2 : 8;  // registers of a tile's accumulator start.  WL: the lane's eight features' bias, 8 fc .. 8 fc + 7
+    constexpr int NBS = SWP ? 2 : 8;  // registers of a tile's accumulator start.  WL: the lane's eight features' bias, 8 fc .. 8 fc + 7
     auto load_bias = [&](int tn0, f32x4 (&dst)[NBS]) {
-        if constexpr (WL) {
+        if constexpr (SWP) {
             dst[0] = *reinterpret_cast<const f32x4*>(p.bias + tn0 + wn * 128 + 8 * fr);
             dst[1] = *reinterpret_cast<const f32x4*>(p.bias + tn0 + wn * 128 + 8 * fr + 4);
         } else {
@@ -300,7 +311,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         static_for<8>([&](auto ic) {
             static_for<MI>([&](auto jc) {
                 constexpr int i = decltype(ic)::value;
-                if constexpr (WL) {
+                if constexpr (SWP) {
                     const float b = b4[i >> 2][i & 3];  // (one feature per fragment i, four tokens)
                     acc[i][decltype(jc)::value] = f32x4{b, b, b, b};
                 } else {
@@ -485,7 +496,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // the next tile's first fragments are read behind the epilogue: the registers go to the stream tile's loads in flight.
     [[maybe_unused]] const float* const lds_bias = reinterpret_cast<const float*>(smem + EPI_LDS);
     [[maybe_unused]] const float* const lds_gate = lds_bias + p.N;
-    [[maybe_unused]] auto emit_stats = [&](int nb, int m /* row inside the wave's 128 */, float pivot, const f32x4& h0, const f32x4& h1, const f32x4& h2, const f32x4& h3) {
+    [[maybe_unused]] auto emit_stats = [&](int fq /* the caller's opaque copy */, int nb, int m /* row inside the wave's 128 */, float pivot, const f32x4& h0, const f32x4& h1, const f32x4& h2, const f32x4& h3) {
         const f32x4 npv{-pivot, -pivot, -pivot, -pivot};  // (h + (-pivot) == h - pivot bit for bit; the add form packs into v_pk_add_f32)
         const f32x4 d0 = h0 + npv, d1 = h1 + npv, d2 = h2 + npv, d3 = h3 + npv;
         const f32x4 a = (d0 + d1) + (d2 + d3);
@@ -582,8 +593,139 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 const f16x4_t h0 = to_h16(v0), h1 = to_h16(v1), h2 = to_h16(v2), h3 = to_h16(v3);
                 *reinterpret_cast<u32x4*>(sbase + offj[j] + h * 128) = pair_swap(__builtin_bit_cast(bf16x4, h0), __builtin_bit_cast(bf16x4, h1));
                 *reinterpret_cast<u32x4*>(sbase + offj[j] + h * 128 + 64) = pair_swap(__builtin_bit_cast(bf16x4, h2), __builtin_bit_cast(bf16x4, h3));
-                if (p.stats_out) emit_stats(nb, fr + 16 * j, piv[j], h_f32(h0), h_f32(h1), h_f32(h2), h_f32(h3));
+                if (p.stats_out) emit_stats(fq, nb, fr + 16 * j, piv[j], h_f32(h0), h_f32(h1), h_f32(h2), h_f32(h3));
                 if constexpr (decltype(sc)::value + AHEAD < 2 * MI) load_step(std::integral_constant<int, decltype(sc)::value + AHEAD>{});
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        };
+        if (all_kept)
+            steps(std::true_type{});
+        else
+            steps(std::false_type{});
+    };
+
+    // ---- RL: the same update in the whole-line map.  Lane (fq, fc) holds features 8 fc .. 8 fc + 7 of token 16 j + 4 fq + r in acc[0..7][j][r]: per
+    // (token tile j, component r) ONE 16-byte load and ONE 16-byte store of the stream, 16 adjacent lanes one 256-byte run of a row, and no cross-lane
+    // instruction on the way (the map above undoes and redoes pair_swap around the arithmetic).  Per element the same operations in the same order.
+    // The partial row statistics are NOT re-derived in this map: their summation tree is per lane of the old map (lane (fr, fq): features
+    // 16 ii + 4 fq + e of token fr + 16 j per 64-feature half).  The packed fp16 values of a token tile -- 16 tokens x 128 features, 4 KiB -- go
+    // token-major into this wave's patch of LDS (ds_write_b128) and come back as the old map's 8-byte pieces (ds_read_b64), into the emit_stats of
+    // the map above: same values, same tree, same addresses.  Patch image: token row t (256 bytes), logical 16-byte chunk c at physical chunk
+    // c ^ t: the eight lanes of a write group cover one 128-byte half row, the 32 lanes of a read group -- 16 rows x one logical chunk x two
+    // halves -- all 16 chunks (tests/test_w4_resid_map_host.py).  Only this wave touches its patch, and a wave's LDS operations execute in
+    // order: tile j's read-back is issued in front of tile j + 1's arithmetic (whose writes it therefore precedes) and consumed behind it.
+    [[maybe_unused]] auto resid_tile_wl = [&]() {
+        // (the lane's indices from the lane counter, behind an opaque asm: nothing per lane is kept across the main loop for them -- resid_tile above
+        //  says why.  One scalar base per token tile + four 32-bit lane offsets, one per component)
+        int lid = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(lid));
+        const int fc = lid & 15, fq = lid >> 4;
+        // (two scalar bases that walk the token tiles, each step through an opaque asm: the 2 x 8 tile bases are otherwise all formed up front, for both
+        //  builds of the loop below.  Typed as global pointers -- an address that has been through an asm is a flat one to the compiler otherwise,
+        //  and flat accesses also count on lgkmcnt)
+        typedef __attribute__((address_space(1))) char gchar;
+        typedef __attribute__((address_space(1))) u32x4 gu32x4;
+        gchar* sst = (gchar*)(reinterpret_cast<char*>(p.out_f) + ((size_t)(m0 + wm * WROWS) * p.ldof + n0 + wn * 128) * 2);  // stores
+        const gchar* sld = sst;                                                                                             // loads: AHEAD / 4 token tiles ahead
+        const size_t jstride = (size_t)p.ldof * 32;
+        unsigned offr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) offr[r] = (unsigned)(((4 * fq + r) * p.ldof + 8 * fc) * 2);
+        // masked rows: byte r of kb4 = the eight token tiles' bits of token row 4 fq + r (rowbits: byte [m / 128][m % 16], bit (m % 128) / 16; one
+        // dword per lane, so the base is 4-byte aligned: gemm.h)
+        unsigned kb4 = 0xffffffffu;
+        if (p.rowmask && p.rowbits) kb4 = *reinterpret_cast<const unsigned*>(p.rowbits + ((m0 + wm * WROWS) >> 7) * 16 + 4 * fq);
+        // The statistics part of a step has NO branch on p.stats_out: a launch without statistics (the last block's FF2) computes them all the same
+        // and stores none -- its lanes pass emit_stats a quarter index that stores nothing.  (Read-back and use under two tests of one flag: the
+        // compiler's wait bookkeeping, which does not know that they agree, carries the reads as pending out of the epilogue and waits for them
+        // in the middle of the next main-loop iteration.)
+        const int fq_st = p.stats_out ? fq : 4;
+        float piv[MI];  // (old map: token fc + 16 j)
+#pragma unroll
+        for (int j = 0; j < MI; ++j) piv[j] = 0.0f;
+        if (p.stats_out && p.stats_pivot) {
+            const char* pbase = reinterpret_cast<const char*>(p.stats_pivot + (size_t)(m0 + wm * WROWS) * 2);
+#pragma unroll
+            for (int j = 0; j < MI; ++j) piv[j] = *reinterpret_cast<const float*>(pbase + (unsigned)((fc + 16 * j) * 8));
+        }
+        char* const patch = smem + PATCH + wave * 4096;
+        const unsigned wof = (unsigned)(4 * fq * 256 + ((fc ^ (4 * fq)) * 16));  // component r: (wof ^ 16 r) + 256 r
+        const unsigned rof = (unsigned)(fc * 256 + ((fc >> 1) & 7) * 32 + (((fq >> 1) ^ (fc & 1)) * 16) + (fq & 1) * 8);  // piece (h, ii): rof ^ 32 (4 h + ii)
+        // the stream tile is requested AHEAD (token tile, component) steps ahead of its use, the first AHEAD before the first store: six 16-byte loads
+        // in flight (eight, the bytes the map above keeps in flight, spill 20 registers; four measured 0.4 % slower on the C2 step)
+        constexpr int AHEAD = 6;
+        u32x4 xs[4 * MI];
+        auto load_step = [&](auto sc) __attribute__((always_inline)) {
+            constexpr int r = decltype(sc)::value % 4;
+            xs[decltype(sc)::value] = *(const gu32x4*)(sld + offr[r]);
+            if constexpr (r == 3) {
+                sld += jstride;
+                asm volatile("" : "+s"(sld));
+            }
+        };
+        // the lane's eight gate values, once per tile
+        const f32x4 g0 = *reinterpret_cast<const f32x4*>(lds_gate + n0 + wn * 128 + 8 * fc), g1 = *reinterpret_cast<const f32x4*>(lds_gate + n0 + wn * 128 + 8 * fc + 4);
+        static_for<AHEAD>([&](auto sc) { load_step(sc); });
+        __builtin_amdgcn_sched_barrier(0);
+        // (waited for where the compiler sees it, as the accumulator start in the prologue: its wait bookkeeping otherwise carries the pending read
+        //  over the loop's back edge into the middle of an iteration)
+        asm volatile("" ::"v"(g0), "v"(g1));
+        const bool all_kept = __builtin_amdgcn_ballot_w64(kb4 != 0xffffffffu) == 0ull;  // wave-uniform: no masked row in this wave's 128 token rows
+        auto widen_h = [](unsigned lo, unsigned hi) __attribute__((always_inline)) {
+            const f16x4_t hv = __builtin_bit_cast(f16x4_t, u32x2{lo, hi});
+            return f32x4{(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]};
+        };
+        auto to_h16 = [](const f32x4& v) __attribute__((always_inline)) {  // saturating fp16 store form
+            f16x4_t hv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hv[e] = (_Float16)__builtin_amdgcn_fmed3f(v[e], -65504.0f, 65504.0f);
+            return hv;
+        };
+        u32x2 rb[8];  // a token tile's stored values in the old map: [half * 4 + feature tile]
+        auto read_back = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int hi = 0; hi < 8; ++hi) rb[hi] = *reinterpret_cast<const u32x2*>(patch + (rof ^ (unsigned)(hi * 32)));
+        };
+        auto stats_of = [&](int j) __attribute__((always_inline)) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                emit_stats(fq_st, n0 + wn * 128 + h * 64, fc + 16 * j, piv[j], widen_h(rb[h * 4][0], rb[h * 4][1]), widen_h(rb[h * 4 + 1][0], rb[h * 4 + 1][1]),
+                           widen_h(rb[h * 4 + 2][0], rb[h * 4 + 2][1]), widen_h(rb[h * 4 + 3][0], rb[h * 4 + 3][1]));
+        };
+        auto steps = [&](auto keptc) __attribute__((always_inline)) {
+            constexpr bool ALL = decltype(keptc)::value;
+            static_for<MI>([&](auto jc) __attribute__((always_inline)) {
+                constexpr int j = decltype(jc)::value;
+                __builtin_amdgcn_sched_barrier(0);
+                // (the lane offsets through an opaque asm in every step: their zero-extension then happens in the basic block of the accesses,
+                //  where instruction selection folds it into the scalar-base address form; hoisted out, each access gets a 64-bit lane address)
+                asm volatile("" : "+v"(offr[0]), "+v"(offr[1]), "+v"(offr[2]), "+v"(offr[3]));
+                f32x4 a[8];
+                static_for<8>([&](auto ic) { a[decltype(ic)::value] = W4_ACC(decltype(ic)::value, j); });
+                static_for<4>([&](auto rc) __attribute__((always_inline)) {
+                    constexpr int r = decltype(rc)::value, s = 4 * j + r;
+                    const u32x4 x = xs[s];
+                    const f32x4 x0 = widen_h(x[0], x[1]), x1 = widen_h(x[2], x[3]);
+                    f32x4 v0 = epi_axpy4(f32x4{a[0][r], a[1][r], a[2][r], a[3][r]}, g0, x0), v1 = epi_axpy4(f32x4{a[4][r], a[5][r], a[6][r], a[7][r]}, g1, x1);
+                    if constexpr (!ALL) {  // masked query rows keep their value
+                        const bool keep = (kb4 >> (8 * r + j)) & 1u;
+                        v0 = keep ? v0 : x0;
+                        v1 = keep ? v1 : x1;
+                    }
+                    const u32x2 q0 = __builtin_bit_cast(u32x2, to_h16(v0)), q1 = __builtin_bit_cast(u32x2, to_h16(v1));
+                    const u32x4 q{q0[0], q0[1], q1[0], q1[1]};
+                    *(gu32x4*)(sst + offr[r]) = q;
+                    *reinterpret_cast<u32x4*>(patch + (wof ^ (unsigned)(16 * r)) + 256 * r) = q;
+                    if constexpr (s + AHEAD < 4 * MI) load_step(std::integral_constant<int, s + AHEAD>{});
+                });
+                sst += jstride;
+                asm volatile("" : "+s"(sst));
+                __builtin_amdgcn_sched_barrier(0);
+                // the statistics of the tile BEFORE this one, whose read-back flew under this tile's arithmetic, then this tile's read-back
+                if constexpr (j > 0) stats_of(j - 1);
+                __builtin_amdgcn_sched_barrier(0);
+                read_back();
+                if constexpr (j == MI - 1) stats_of(j);
                 __builtin_amdgcn_sched_barrier(0);
             });
         };
@@ -620,7 +762,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         load_bias(n0, bstart);
         // (waited for where the compiler sees it: left pending into the tile loop, its own wait bookkeeping puts a vmcnt(0) in front of the first
         //  instruction that reuses these registers -- a fragment read in the middle of an iteration)
-        if constexpr (WL) {
+        if constexpr (SWP) {
 #pragma unroll
             for (int i = 0; i < NBS; ++i) asm volatile("" ::"v"(bstart[i]));
         }
@@ -648,11 +790,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if constexpr (EPI == EPI_RESID) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stages requested ahead have landed: from here on only the epilogue's own traffic
             __builtin_amdgcn_sched_barrier(0);
-            resid_tile();
+            if constexpr (RL)
+                resid_tile_wl();
+            else
+                resid_tile();
             __builtin_amdgcn_sched_barrier(0);
-            f32x4 bn[8];  // the next tile's accumulator start: its features' bias, from LDS
+            f32x4 bn[NBS];  // the next tile's accumulator start: its features' bias, from LDS
+            if constexpr (RL) {
+                int fc = lane & 15;  // (opaque, as inside the epilogue: the address is otherwise kept across the main loop)
+                asm volatile("" : "+v"(fc));
+                bn[0] = *reinterpret_cast<const f32x4*>(lds_bias + nn0 + wn * 128 + 8 * fc);
+                bn[1] = *reinterpret_cast<const f32x4*>(lds_bias + nn0 + wn * 128 + 8 * fc + 4);
+                asm volatile("" ::"v"(bn[0]), "v"(bn[1]));  // (waited for where the compiler sees it, as in the prologue)
+            } else {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) bn[i] = *reinterpret_cast<const f32x4*>(lds_bias + nn0 + wn * 128 + i * 16 + 4 * fq);
+                for (int i = 0; i < NBS; ++i) bn[i] = *reinterpret_cast<const f32x4*>(lds_bias + nn0 + wn * 128 + i * 16 + 4 * fq);
+            }
             acc_from(bn);
         } else {
             // the NEXT tile's accumulator start is requested before the stores and waited for while only loads are in flight (loads and stores

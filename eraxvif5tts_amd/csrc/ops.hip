@@ -156,6 +156,57 @@ extern "C" int f5_op_ln_fold(int epi, int M, int D, int N, int Kb, float* x, con
     return f5_op_ln_fold_p(F5_PREC_BF16, epi, M, D, N, Kb, x, A, Wo, bo, gate, pivot, W, bias, scale, shift, act, rope, rope_heads, seq, stats, out, stream);
 }
 
+// The producer half of a LayerNorm-fold site on its own, with everything it writes handed back (parity tests of the in-place epilogue's lane maps):
+// x [M, N] (the fp16 residual stream as f32) += gate * (A . W^T + bias) where rowmask[m] != 0, `planes` [N / 64][M][2] = the partial row sums
+// (sum (h - pivot), sum (h - pivot)^2 per 64-feature plane, pivot = column 0 of `pivot` [M][2] or 0) as the GEMM stored them, `stats` [M][2] =
+// stats_finalize's (mean, rstd), `guard` = the six words of the fp16 range guard (zeroed here, raised by the finalize) or NULL.
+extern "C" int f5_op_resid_stats_p(int precision, int M, int N, int K, float* x, const float* A, const float* W, const float* bias, const float* gate,
+                                   const uint8_t* rowmask, const float* pivot, float* planes, float* stats, unsigned* guard, f5_stream_t stream) {
+    F5_TRY(f5_check_device());
+    if (precision != F5_PREC_BF16 && precision != F5_PREC_FP16) return f5_fail(F5_EINVAL, "f5_op_resid_stats_p: a 16-bit precision mode (bf16 0, fp16 2), got %d", precision);
+    if (M <= 0 || N <= 0 || K <= 0 || !x || !A || !W || !bias || !planes || !stats) return f5_fail(F5_EINVAL, "bad argument");
+    if (N % 128 != 0 || K % 32 != 0) return f5_fail(F5_EINVAL, "f5_op_resid_stats_p: N % 128, K % 32");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Mp = round_up(M, 256) + 256;
+    DevArena a;
+    void *At = nullptr, *Wt = nullptr, *xs = nullptr;
+    float *partial = nullptr, *st2 = nullptr;
+    unsigned* sat = nullptr;
+    uint8_t* bits = nullptr;
+    int rc = 0;
+    do {
+        if ((rc = a.alloc(&At, Mp * K * 2))) break;
+        if ((rc = a.alloc(&Wt, (size_t)round_up(N, 256) * K * 2))) break;
+        if ((rc = a.alloc(&xs, Mp * N * 2))) break;
+        if ((rc = a.alloc_t(&partial, (size_t)(N / 64) * Mp * 2))) break;
+        if ((rc = a.alloc_t(&st2, Mp * 2))) break;
+        if ((rc = a.alloc_t(&sat, (size_t)8))) break;
+        if ((rc = a.alloc_t(&bits, (size_t)(Mp / 128 + 1) * 16))) break;
+        if ((rc = launch_convert_pad(precision, A, K, M, K, K, At, K, st))) break;
+        if ((rc = launch_convert_pad(precision, W, K, N, K, K, Wt, K, st))) break;
+        if ((rc = launch_f32_to_f16(x, xs, (size_t)M * N, st))) break;
+        F5_HIP(hipMemsetAsync(partial, 0, (size_t)(N / 64) * Mp * 2 * sizeof(float), st));
+        F5_HIP(hipMemsetAsync(sat, 0, 8 * sizeof(unsigned), st));
+        if (pivot) F5_HIP(hipMemcpyAsync(st2, pivot, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        GemmParams g;
+        memset(&g, 0, sizeof(g));
+        g.A = At; g.lda = K; g.W = Wt; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = bias; g.rows_per_batch = M;
+        g.out_f = reinterpret_cast<float*>(xs); g.ldof = N; g.add2_f16 = 1; g.gate = gate;
+        g.stats_out = partial; g.stats_ld = (int)Mp; g.stats_pivot = pivot ? st2 : nullptr;
+        if (rowmask) {
+            if ((rc = launch_rowbits(rowmask, M, bits, st))) break;
+            g.rowmask = rowmask; g.rowbits = bits;
+        }
+        if ((rc = launch_gemm(g, precision, GEMM_DENSE, EPI_RESID, 1, st))) break;
+        if ((rc = launch_stats_finalize(partial, (int)Mp, N / 64, M, N, pivot ? st2 : nullptr, st2, sat, 0, st))) break;
+        if ((rc = launch_f16_to_f32(xs, x, (size_t)M * N, st))) break;
+        F5_HIP(hipMemcpy2DAsync(planes, (size_t)M * 2 * sizeof(float), partial, Mp * 2 * sizeof(float), (size_t)M * 2 * sizeof(float), N / 64, hipMemcpyDeviceToDevice, st));
+        F5_HIP(hipMemcpyAsync(stats, st2, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (guard) F5_HIP(hipMemcpyAsync(guard, sat, 6 * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
+    } while (0);
+    return sync_and_release(a, st, rc);
+}
+
 extern "C" int f5_op_layernorm_modulate(int rows, int dim, const float* x, const float* scale, const float* shift, float* out,
                                         f5_stream_t stream) {
     F5_TRY(f5_check_device());

@@ -416,6 +416,12 @@ F5_API int f5_op_ln_fold(int epi, int M, int D, int N, int Kb, float* x, const f
 F5_API int f5_op_ln_fold_p(int precision, int epi, int M, int D, int N, int Kb, float* x, const float* A, const float* Wo, const float* bo,
                            const float* gate, const float* pivot, const float* W, const float* bias, const float* scale, const float* shift, int act,
                            const float* rope, int rope_heads, int seq, float* stats, float* out, f5_stream_t stream);
+/* The producer half of a LayerNorm-fold site on its own (parity tests of the in-place epilogue): x [M, N] (the fp16 residual stream as f32) +=
+ * gate * (A . W^T + bias) on the rows where rowmask[m] != 0 (NULL: all), by the tuned GEMM's EPI_RESID epilogue in the 16-bit mode `precision`;
+ * planes [N / 64][M][2] = its partial row sums per 64-feature plane (pivot = column 0 of `pivot` [M][2], or NULL), stats [M][2] = the (mean, rstd)
+ * stats_finalize makes of them, guard = the six words of the fp16 range guard after the finalize (NULL: not returned).  N % 128 == 0, K % 32 == 0. */
+F5_API int f5_op_resid_stats_p(int precision, int M, int N, int K, float* x, const float* A, const float* W, const float* bias, const float* gate,
+                               const uint8_t* rowmask, const float* pivot, float* planes, float* stats, unsigned* guard, f5_stream_t stream);
 /* LayerNorm(eps 1e-6, no affine) * (1 + scale) + shift ; x f32 [rows, dim]; scale/shift f32 [dim] */
 F5_API int f5_op_layernorm_modulate(int rows, int dim, const float* x, const float* scale, const float* shift, float* out,
                              f5_stream_t stream);

@@ -20,6 +20,13 @@
 //             (LDS row 16 i + c of a wave's 128 <- weight row 8 c + i), so that a lane's eight accumulators over i are eight consecutive features of
 //             one token and 16 adjacent lanes write 256 contiguous bytes per store.  70: on schedule 46; 71: on schedule 1; 72 / 73: the
 //             read-modify-write forms of 30 / 33 in that map (on schedule 1, as they are; 72 loads four token tiles ahead, not all eight)
+//   80, 81    the library's in-place residual epilogue IN FULL on schedule 46: C is the fp16 residual stream, x += gate[n] * (acc + bias[n]) with the
+//             saturating fp16 pack, bias | gate in LDS, the accumulators started from the bias, the next tile's first fragments read again behind
+//             the epilogue, and the LayerNorm fold's partial row statistics (sum (h - pivot), sum (h - pivot)^2 per 64-feature plane) of the values
+//             just stored.  80: the library's lane map (resid_tile + emit_stats of csrc/gemm_w4.hip); 81: the whole-line map of 70 for the stream
+//             (one 16-byte load and store per lane, token tile and component), the statistics fed in the OLD map through a 4-KiB patch of LDS per
+//             wave (ds_write_b128 token-major, chunk c of row t at chunk c ^ t; ds_read_b64 back).  Both produce real values: the error column
+//             is against the fp64-free host form of the update on sampled rows, and the statistics of those rows are checked too.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +40,7 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 
 template <int N, int I = 0, typename F> __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) {
@@ -56,8 +64,14 @@ constexpr int OPB = 32768;
 template <int SCHED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void w4_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
                                                                                            bf16_t* __restrict__ C, int M, int N, int K, int lda,
-                                                                                           int ldw, int ldc, int tiles_n, int nblocks, int group) {
-    __shared__ __attribute__((aligned(1024))) char smem[4 * OPB];
+                                                                                           int ldw, int ldc, int tiles_n, int nblocks, int group,
+                                                                                           const float* __restrict__ bias, const float* __restrict__ gate,
+                                                                                           float* __restrict__ stats, const float* __restrict__ pivot, int stats_ld) {
+    constexpr bool RESID = SCHED == 80 || SCHED == 81;                  // the library's in-place epilogue in full
+    constexpr bool WLM = (SCHED >= 70 && SCHED <= 73) || SCHED == 81;   // whole-line map: operand roles swapped, weight rows permuted
+    constexpr bool L46 = SCHED == 46 || SCHED == 50 || SCHED == 60 || SCHED == 70 || RESID;  // the library's main-loop schedule
+    constexpr int EPI_LDS = 4 * OPB, PATCH = EPI_LDS + 16384;           // RESID: bias[N] | gate[N] (N <= 2048), then a 4-KiB patch per wave
+    __shared__ __attribute__((aligned(4096))) char smem[4 * OPB + (RESID ? 16384 + 16384 : 0)];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
@@ -89,7 +103,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int logical = (lane & 7) ^ ((row >> 1) & 7);
         voffA[jj] = (unsigned)(row * lda * 2 + logical * 16);
         // whole-line epilogue: LDS row 16 i + c of a wave's 128 features receives weight row 8 c + i (the swizzle stays keyed on the LDS row)
-        const int wrow = (SCHED >= 70 && SCHED <= 73) ? (row & ~127) + 8 * (row & 15) + ((row & 127) >> 4) : row;
+        const int wrow = WLM ? (row & ~127) + 8 * (row & 15) + ((row & 127) >> 4) : row;
         voffW[jj] = (unsigned)(wrow * ldw * 2 + logical * 16);
     }
     const char* baseA;  // DMA front: tile row / feature base at the front's K position
@@ -166,14 +180,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // with that start skew; 20: schedule 1 without the stores
         constexpr bool NO_DMA = SCHED == 10 || SCHED == 12 || SCHED == 13 || SCHED == 17 || SCHED == 18, NO_RD = SCHED == 11 || NO_DMA && SCHED != 10, NO_BAR = SCHED == 13 || SCHED == 14 || SCHED == 17 || SCHED == 18;
         constexpr bool M0E = SCHED == 40 || SCHED == 41;
-        constexpr bool S42 = (SCHED >= 42 && SCHED <= 47) || SCHED == 50 || SCHED == 51 || SCHED == 60 || SCHED == 70;  // family of schedule 42: reads of sub-step 1 in the first 16 slots, requests spread wide
-        constexpr int R1S = SCHED == 0 ? 3 : (S42 ? 1 : 2), B1P = SCHED == 0 ? 49 : (S42 ? ((SCHED == 46 || SCHED == 50 || SCHED == 60 || SCHED == 70) ? 20 : 24) : 40), D0 = SCHED == 0 ? 50 : (S42 ? ((SCHED == 46 || SCHED == 50 || SCHED == 60 || SCHED == 70) ? 22 : 26) : 42), DS = (SCHED == 2 || SCHED == 4 || SCHED == 41) ? 2 : (SCHED == 43 ? 5 : (SCHED == 44 || SCHED == 46 || SCHED == 50 || SCHED == 60 || SCHED == 70 ? 6 : (S42 ? 4 : 3)));
+        constexpr bool S42 = (SCHED >= 42 && SCHED <= 47) || SCHED == 50 || SCHED == 51 || SCHED == 60 || SCHED == 70 || RESID;  // family of schedule 42: reads of sub-step 1 in the first 16 slots, requests spread wide
+        constexpr int R1S = SCHED == 0 ? 3 : (S42 ? 1 : 2), B1P = SCHED == 0 ? 49 : (S42 ? (L46 ? 20 : 24) : 40), D0 = SCHED == 0 ? 50 : (S42 ? (L46 ? 22 : 26) : 42), DS = (SCHED == 2 || SCHED == 4 || SCHED == 41) ? 2 : (SCHED == 43 ? 5 : (SCHED == 44 || L46 ? 6 : (S42 ? 4 : 3)));
         constexpr int B2P = SCHED == 0 ? 100 : (SCHED == 3 || SCHED == 4 ? 78 : (SCHED == 45 ? 104 : (SCHED == 47 ? 94 : 86))), R0 = B2P + 2, R0S = SCHED == 0 ? 0 : (SCHED == 45 ? 1 : 2);
         static_for<128>([&](auto nc) {
             (void)acc; (void)fw; (void)fa;
             constexpr int n = decltype(nc)::value;
             constexpr int s = n / 64, i = (n % 64) / 8, j = n % 8;
-            if constexpr (SCHED >= 70 && SCHED <= 73)  // tokens on the row index: a lane holds tokens 4 fq + r of the feature its LDS row carries
+            if constexpr (WLM)  // tokens on the row index: a lane holds tokens 4 fq + r of the feature its LDS row carries
                 asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fa[s][j]), "v"(fw[s][i]));
             else
                 asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fw[s][i]), "v"(fa[s][j]));
@@ -240,18 +254,220 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if ((blockIdx.x >> 3) & 1)
             for (int i = 0; i < K / 340; ++i) __builtin_amdgcn_s_sleep(127);  // 64 x 127 cycles each: about half a tile at K = 1024
     }
+    if constexpr (RESID) {  // bias[N] | gate[N] of the launch into LDS (visible to every wave behind the prologue's barrier)
+        float* lb = reinterpret_cast<float*>(smem + EPI_LDS);
+        for (int i = tid; i < N; i += 256) {
+            lb[i] = bias[i];
+            lb[N + i] = gate[i];
+        }
+    }
     issue_all(0);
     front_advance();
     issue_all(1);
     front_advance();
+    if constexpr (RESID) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");
     static_for<16>([&](auto ec) { rd(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, ec); });
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    zero_acc();
 
     int m0, n0;
     tile_mn(blockIdx.x, m0, n0);
+    [[maybe_unused]] const float* const lds_bias = reinterpret_cast<const float*>(smem + EPI_LDS);
+    [[maybe_unused]] const float* const lds_gate = lds_bias + N;
+    // RESID: every accumulator starts from its feature's bias, read from the LDS image (lane indices through an opaque asm: the address is
+    // otherwise kept across the main loop)
+    auto start_acc = [&](int tn0) {
+        if constexpr (!RESID) {
+            zero_acc();
+        } else {
+            int lid = lane;
+            asm volatile("" : "+v"(lid));
+            if constexpr (SCHED == 81) {
+                const f32x4 b0 = *reinterpret_cast<const f32x4*>(lds_bias + tn0 + wn * 128 + 8 * (lid & 15));
+                const f32x4 b1 = *reinterpret_cast<const f32x4*>(lds_bias + tn0 + wn * 128 + 8 * (lid & 15) + 4);
+                asm volatile("" ::"v"(b0), "v"(b1));
+                static_for<8>([&](auto ic) {
+                    static_for<8>([&](auto jc) {
+                        constexpr int i = decltype(ic)::value;
+                        const float b = i < 4 ? b0[i & 3] : b1[i & 3];
+                        acc[i][decltype(jc)::value] = f32x4{b, b, b, b};
+                    });
+                });
+            } else {
+                f32x4 bn[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) bn[i] = *reinterpret_cast<const f32x4*>(lds_bias + tn0 + wn * 128 + i * 16 + 4 * (lid >> 4));
+                static_for<8>([&](auto ic) {
+                    static_for<8>([&](auto jc) { acc[decltype(ic)::value][decltype(jc)::value] = bn[decltype(ic)::value]; });
+                });
+            }
+        }
+    };
+    start_acc(n0);
+#define W4_ACC(i, j)                                                                         \
+    ([&]() -> f32x4 {                                                                        \
+        float c0_, c1_, c2_, c3_;                                                            \
+        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(c0_) : "a"(acc[i][j][0]));           \
+        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(c1_) : "a"(acc[i][j][1]));           \
+        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(c2_) : "a"(acc[i][j][2]));           \
+        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(c3_) : "a"(acc[i][j][3]));           \
+        return f32x4{c0_, c1_, c2_, c3_};                                                    \
+    }())
+    // ---- schedules 80 / 81: the in-place epilogues of csrc/gemm_w4.hip (resid_tile / resid_tile_wl there; no row mask here)
+    [[maybe_unused]] auto widen_h = [](unsigned lo, unsigned hi) __attribute__((always_inline)) {
+        const f16x4_t hv = __builtin_bit_cast(f16x4_t, u32x2{lo, hi});
+        return f32x4{(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]};
+    };
+    [[maybe_unused]] auto to_h16 = [](const f32x4& v) __attribute__((always_inline)) {  // saturating fp16 store form
+        f16x4_t hv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) hv[e] = (_Float16)__builtin_amdgcn_fmed3f(v[e], -65504.0f, 65504.0f);
+        return hv;
+    };
+    [[maybe_unused]] auto emit_stats = [&](int fq, int nb, int m /* row inside the wave's 128 */, float pv, const f32x4& h0, const f32x4& h1, const f32x4& h2, const f32x4& h3) {
+        const f32x4 npv{-pv, -pv, -pv, -pv};
+        const f32x4 d0 = h0 + npv, d1 = h1 + npv, d2 = h2 + npv, d3 = h3 + npv;
+        const f32x4 a = (d0 + d1) + (d2 + d3);
+        const f32x4 q = __builtin_elementwise_fma(d3, d3, __builtin_elementwise_fma(d2, d2, __builtin_elementwise_fma(d1, d1, d0 * d0)));
+        const float s1 = (a[0] + a[1]) + (a[2] + a[3]), s2 = (q[0] + q[1]) + (q[2] + q[3]);
+        float a0 = s1, b0 = s2;
+        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a0), "+v"(b0));
+        float t = a0 + b0, z = 0.0f;
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(t), "+v"(z));
+        const float tot = t + z;
+        if (fq < 2) {
+            char* sb = reinterpret_cast<char*>(stats + ((size_t)(nb >> 6) * stats_ld + (m0 + wm * 128)) * 2);  // (scalar base + 32-bit lane offset)
+            *reinterpret_cast<float*>(sb + (unsigned)((m * 2 + fq) * 4)) = tot;
+        }
+    };
+    [[maybe_unused]] auto resid_old = [&]() {  // schedule 80
+        int fr = lane & 15, fq = lane >> 4;
+        asm volatile("" : "+v"(fr), "+v"(fq));
+        char* const sbase = reinterpret_cast<char*>(C) + ((size_t)(m0 + wm * 128) * ldc + n0 + wn * 128) * 2;
+        unsigned offj[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) offj[j] = (unsigned)(((fr + 16 * j) * ldc + 16 * (fq & 1) + 8 * (fq >> 1)) * 2);
+        float piv[8];
+        const float* pbase = pivot + (size_t)(m0 + wm * 128) * 2;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) piv[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(pbase) + (unsigned)((fr + 16 * j) * 8));
+        u32x4 xs[2][8][2];
+        auto load_step = [&](auto sc) __attribute__((always_inline)) {
+            constexpr int h = decltype(sc)::value / 8, j = decltype(sc)::value % 8;
+            xs[h][j][0] = *reinterpret_cast<const u32x4*>(sbase + offj[j] + h * 128);
+            xs[h][j][1] = *reinterpret_cast<const u32x4*>(sbase + offj[j] + h * 128 + 64);
+        };
+        constexpr int AHEAD = 4;
+        static_for<AHEAD>([&](auto sc) { load_step(sc); });
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 g4[4];
+        static_for<16>([&](auto sc) __attribute__((always_inline)) {
+            constexpr int h = decltype(sc)::value / 8, j = decltype(sc)::value % 8;
+            const int nb = n0 + wn * 128 + h * 64;
+            if constexpr (j == 0) {
+#pragma unroll
+                for (int ii = 0; ii < 4; ++ii) g4[ii] = *reinterpret_cast<const f32x4*>(lds_gate + nb + ii * 16 + 4 * fq);
+            }
+            f32x4 x0, x1, x2, x3;
+            {
+                const u32x4 q = xs[h][j][0];
+                const u32x2 s0 = __builtin_amdgcn_permlane16_swap(q[0], q[2], false, false);
+                const u32x2 s1 = __builtin_amdgcn_permlane16_swap(q[1], q[3], false, false);
+                x0 = widen_h(s0[0], s1[0]);
+                x1 = widen_h(s0[1], s1[1]);
+            }
+            {
+                const u32x4 q = xs[h][j][1];
+                const u32x2 s0 = __builtin_amdgcn_permlane16_swap(q[0], q[2], false, false);
+                const u32x2 s1 = __builtin_amdgcn_permlane16_swap(q[1], q[3], false, false);
+                x2 = widen_h(s0[0], s1[0]);
+                x3 = widen_h(s0[1], s1[1]);
+            }
+            const f32x4 a0 = W4_ACC(h * 4 + 0, j), a1 = W4_ACC(h * 4 + 1, j), a2 = W4_ACC(h * 4 + 2, j), a3 = W4_ACC(h * 4 + 3, j);
+            const f32x4 v0 = __builtin_elementwise_fma(a0, g4[0], x0), v1 = __builtin_elementwise_fma(a1, g4[1], x1), v2 = __builtin_elementwise_fma(a2, g4[2], x2),
+                        v3 = __builtin_elementwise_fma(a3, g4[3], x3);
+            const f16x4_t h0 = to_h16(v0), h1 = to_h16(v1), h2 = to_h16(v2), h3 = to_h16(v3);
+            *reinterpret_cast<u32x4*>(sbase + offj[j] + h * 128) = pair_swap(__builtin_bit_cast(bf16x4, h0), __builtin_bit_cast(bf16x4, h1));
+            *reinterpret_cast<u32x4*>(sbase + offj[j] + h * 128 + 64) = pair_swap(__builtin_bit_cast(bf16x4, h2), __builtin_bit_cast(bf16x4, h3));
+            auto h_f32 = [](const f16x4_t& hv) __attribute__((always_inline)) { return f32x4{(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]}; };
+            emit_stats(fq, nb, fr + 16 * j, piv[j], h_f32(h0), h_f32(h1), h_f32(h2), h_f32(h3));
+            if constexpr (decltype(sc)::value + AHEAD < 16) load_step(std::integral_constant<int, decltype(sc)::value + AHEAD>{});
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    };
+    [[maybe_unused]] auto resid_wl = [&]() {  // schedule 81
+        int lid = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(lid));
+        const int fc = lid & 15, fq = lid >> 4;
+        typedef __attribute__((address_space(1))) char gchar;
+        typedef __attribute__((address_space(1))) u32x4 gu32x4;
+        gchar* sst = (gchar*)(reinterpret_cast<char*>(C) + ((size_t)(m0 + wm * 128) * ldc + n0 + wn * 128) * 2);
+        const gchar* sld = sst;
+        const size_t jstride = (size_t)ldc * 32;
+        unsigned offr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) offr[r] = (unsigned)(((4 * fq + r) * ldc + 8 * fc) * 2);
+        float piv[8];
+        const char* pbase = reinterpret_cast<const char*>(pivot + (size_t)(m0 + wm * 128) * 2);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) piv[j] = *reinterpret_cast<const float*>(pbase + (unsigned)((fc + 16 * j) * 8));
+        char* const patch = smem + PATCH + wave * 4096;
+        const unsigned wof = (unsigned)(4 * fq * 256 + ((fc ^ (4 * fq)) * 16));
+        const unsigned rof = (unsigned)(fc * 256 + ((fc >> 1) & 7) * 32 + (((fq >> 1) ^ (fc & 1)) * 16) + (fq & 1) * 8);
+        constexpr int AHEAD = 6;
+        u32x4 xs[32];
+        auto load_step = [&](auto sc) __attribute__((always_inline)) {
+            constexpr int r = decltype(sc)::value % 4;
+            xs[decltype(sc)::value] = *(const gu32x4*)(sld + offr[r]);
+            if constexpr (r == 3) {
+                sld += jstride;
+                asm volatile("" : "+s"(sld));
+            }
+        };
+        const f32x4 g0 = *reinterpret_cast<const f32x4*>(lds_gate + n0 + wn * 128 + 8 * fc), g1 = *reinterpret_cast<const f32x4*>(lds_gate + n0 + wn * 128 + 8 * fc + 4);
+        static_for<AHEAD>([&](auto sc) { load_step(sc); });
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::"v"(g0), "v"(g1));
+        u32x2 rb[8];
+        auto read_back = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int hi = 0; hi < 8; ++hi) rb[hi] = *reinterpret_cast<const u32x2*>(patch + (rof ^ (unsigned)(hi * 32)));
+        };
+        auto stats_of = [&](int j) __attribute__((always_inline)) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                emit_stats(fq, n0 + wn * 128 + h * 64, fc + 16 * j, piv[j], widen_h(rb[h * 4][0], rb[h * 4][1]), widen_h(rb[h * 4 + 1][0], rb[h * 4 + 1][1]),
+                           widen_h(rb[h * 4 + 2][0], rb[h * 4 + 2][1]), widen_h(rb[h * 4 + 3][0], rb[h * 4 + 3][1]));
+        };
+        static_for<8>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = decltype(jc)::value;
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("" : "+v"(offr[0]), "+v"(offr[1]), "+v"(offr[2]), "+v"(offr[3]));
+            f32x4 a[8];
+            static_for<8>([&](auto ic) { a[decltype(ic)::value] = W4_ACC(decltype(ic)::value, j); });
+            static_for<4>([&](auto rc) __attribute__((always_inline)) {
+                constexpr int r = decltype(rc)::value, s = 4 * j + r;
+                const u32x4 x = xs[s];
+                const f32x4 x0 = widen_h(x[0], x[1]), x1 = widen_h(x[2], x[3]);
+                const f32x4 v0 = __builtin_elementwise_fma(f32x4{a[0][r], a[1][r], a[2][r], a[3][r]}, g0, x0),
+                            v1 = __builtin_elementwise_fma(f32x4{a[4][r], a[5][r], a[6][r], a[7][r]}, g1, x1);
+                const u32x2 q0 = __builtin_bit_cast(u32x2, to_h16(v0)), q1 = __builtin_bit_cast(u32x2, to_h16(v1));
+                const u32x4 q{q0[0], q0[1], q1[0], q1[1]};
+                *(gu32x4*)(sst + offr[r]) = q;
+                *reinterpret_cast<u32x4*>(patch + (wof ^ (unsigned)(16 * r)) + 256 * r) = q;
+                if constexpr (s + AHEAD < 32) load_step(std::integral_constant<int, s + AHEAD>{});
+            });
+            sst += jstride;
+            asm volatile("" : "+s"(sst));
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (j > 0) stats_of(j - 1);
+            __builtin_amdgcn_sched_barrier(0);
+            read_back();
+            if constexpr (j == 7) stats_of(j);
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    };
     auto epilogue = [&]() {
         bf16_t* orow = C + (size_t)(m0 + wm * 128 + fr) * ldc + n0 + wn * 128 + 16 * (fq & 1) + 8 * (fq >> 1);
         if constexpr (SCHED == 50 || SCHED == 51) {
@@ -273,6 +489,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             dbase = reinterpret_cast<const char*>(C + (size_t)(m0 + wm * 128) * ldc + n0 + wn * 128);
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) doff[jj] = (unsigned)(((fr + 16 * (jj + 4)) * ldc + 16 * (fq & 1) + 8 * (fq >> 1)) * 2);
+            return;
+        }
+        if constexpr (SCHED == 80) {
+            resid_old();
+            return;
+        }
+        if constexpr (SCHED == 81) {
+            resid_wl();
             return;
         }
         if constexpr (SCHED >= 70 && SCHED <= 73) {
@@ -430,10 +654,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             body(X1{}, F{}, T{}, N1{});
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stages requested ahead have landed; only stores follow
+        if constexpr (RESID) __builtin_amdgcn_sched_barrier(0);
         epilogue();
-        zero_acc();
+        if constexpr (RESID) __builtin_amdgcn_sched_barrier(0);
         if (!last) tile_mn(blockIdx.x + (t + 1) * G, m0, n0);
+        start_acc(n0);
+        if constexpr (RESID) {  // as the library: the next tile's first fragments are read AGAIN behind the epilogue, which frees their registers inside it
+            if (!last) {
+                static_for<16>([&](auto ec) { rd(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, ec); });
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+        }
     }
+#undef W4_ACC
 }
 
 __global__ void ref_rows(const bf16_t* A, const bf16_t* W, float* out, const int* rows, int nrows, int N, int K, int lda, int ldw) {
@@ -451,9 +684,11 @@ __global__ void ref_rows(const bf16_t* A, const bf16_t* W, float* out, const int
 static float bf2f(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
 static uint16_t f2bf(float f) { uint32_t u; memcpy(&u, &f, 4); u += 0x7fff + ((u >> 16) & 1); return (uint16_t)(u >> 16); }
 
+struct ResidArgs { const float* bias; const float* gate; float* stats; const float* pivot; int stats_ld; };  // schedules 80 / 81
+static ResidArgs g_resid = {nullptr, nullptr, nullptr, nullptr, 0};
 static void launch(int sched, dim3 grid, const bf16_t* dA, const bf16_t* dW, bf16_t* dC, int M, int N, int K, int tiles_n, int nblocks) {
-#define W4_CASE(S) case S: hipLaunchKernelGGL(w4_kernel<S>, grid, dim3(256), 0, 0, dA, dW, dC, M, N, K, K, K, N, tiles_n, nblocks, 8); break;
-    switch (sched) { W4_CASE(0) W4_CASE(1) W4_CASE(3) W4_CASE(10) W4_CASE(11) W4_CASE(12) W4_CASE(13) W4_CASE(14) W4_CASE(17) W4_CASE(18) W4_CASE(19) W4_CASE(20) W4_CASE(21) W4_CASE(22) W4_CASE(23) W4_CASE(30) W4_CASE(31) W4_CASE(32) W4_CASE(33) W4_CASE(40) W4_CASE(41) W4_CASE(42) W4_CASE(43) W4_CASE(44) W4_CASE(45) W4_CASE(46) W4_CASE(47) W4_CASE(50) W4_CASE(60) W4_CASE(70) W4_CASE(71) W4_CASE(72) W4_CASE(73) }
+#define W4_CASE(S) case S: hipLaunchKernelGGL(w4_kernel<S>, grid, dim3(256), 0, 0, dA, dW, dC, M, N, K, K, K, N, tiles_n, nblocks, 8, g_resid.bias, g_resid.gate, g_resid.stats, g_resid.pivot, g_resid.stats_ld); break;
+    switch (sched) { W4_CASE(0) W4_CASE(1) W4_CASE(3) W4_CASE(10) W4_CASE(11) W4_CASE(12) W4_CASE(13) W4_CASE(14) W4_CASE(17) W4_CASE(18) W4_CASE(19) W4_CASE(20) W4_CASE(21) W4_CASE(22) W4_CASE(23) W4_CASE(30) W4_CASE(31) W4_CASE(32) W4_CASE(33) W4_CASE(40) W4_CASE(41) W4_CASE(42) W4_CASE(43) W4_CASE(44) W4_CASE(45) W4_CASE(46) W4_CASE(47) W4_CASE(50) W4_CASE(60) W4_CASE(70) W4_CASE(71) W4_CASE(72) W4_CASE(73) W4_CASE(80) W4_CASE(81) }
 }
 
 int main(int argc, char** argv) {
@@ -463,9 +698,17 @@ int main(int argc, char** argv) {
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, 0));
     ncu = prop.multiProcessorCount & ~7;
-    for (int sched : {1, 20, 46, 70, 71, 30, 33, 72, 73, 1, 20, 70, 71})
+    // (a list of schedules on the command line replaces the default one)
+    std::vector<int> scheds = {1, 20, 46, 70, 71, 30, 33, 72, 73, 1, 20, 70, 71, 80, 81, 80, 81};
+    if (argc > 1) {
+        scheds.clear();
+        for (int i = 1; i < argc; ++i) scheds.push_back(atoi(argv[i]));
+    }
+    for (int sched : scheds)
     for (const Shape& sh : shapes) {
         const int M = sh.M, N = sh.N, K = sh.K;
+        const bool resid = sched == 80 || sched == 81;
+        if (resid && N > 2048) continue;  // (bias | gate live in 16 KiB of LDS; the in-place call sites have N = 1024)
         std::vector<uint16_t> hA((size_t)M * K), hW((size_t)N * K);
         uint32_t st = 12345u;
         auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xffff) / 65536.0f - 0.5f; };
@@ -478,6 +721,27 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(dA, hA.data(), hA.size() * 2, hipMemcpyHostToDevice));
         CK(hipMemcpy(dW, hW.data(), hW.size() * 2, hipMemcpyHostToDevice));
         CK(hipMemset(dC, 0xff, (size_t)M * N * 2));
+        // schedules 80 / 81: C is the fp16 stream x0[m][n] = ((131 m + 7 n) % 1024 - 512) / 64 (exact in fp16), bias / gate per feature, a pivot per row
+        float *dBias = nullptr, *dGate = nullptr, *dStats = nullptr, *dPivot = nullptr;
+        auto x0_of = [](long long m, int n) { return (float)((131 * m + 7 * n) % 1024 - 512) / 64.0f; };
+        auto bias_of = [](int n) { return (float)(n % 13 - 6) * 0.125f; };
+        auto gate_of = [](int n) { return (float)(n % 7 - 3) * 0.25f; };
+        auto pivot_of = [](int m) { return (float)(m % 5 - 2) * 0.5f; };
+        if (resid) {
+            std::vector<_Float16> hx((size_t)M * N);
+            for (int m = 0; m < M; ++m)
+                for (int n = 0; n < N; ++n) hx[(size_t)m * N + n] = (_Float16)x0_of(m, n);
+            CK(hipMemcpy(dC, hx.data(), hx.size() * 2, hipMemcpyHostToDevice));
+            std::vector<float> hb(N), hg(N), hp((size_t)M * 2);
+            for (int n = 0; n < N; ++n) { hb[n] = bias_of(n); hg[n] = gate_of(n); }
+            for (int m = 0; m < M; ++m) { hp[2 * m] = pivot_of(m); hp[2 * m + 1] = 1.0f; }
+            CK(hipMalloc(&dBias, N * 4)); CK(hipMalloc(&dGate, N * 4)); CK(hipMalloc(&dPivot, (size_t)M * 8)); CK(hipMalloc(&dStats, (size_t)(N / 64) * M * 8));
+            CK(hipMemcpy(dBias, hb.data(), N * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(dGate, hg.data(), N * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(dPivot, hp.data(), (size_t)M * 8, hipMemcpyHostToDevice));
+            CK(hipMemset(dStats, 0xff, (size_t)(N / 64) * M * 8));
+            g_resid = ResidArgs{dBias, dGate, dStats, dPivot, M};
+        }
         const int tiles_m = M / 256, tiles_n = N / 256, nblocks = tiles_m * tiles_n;
         const int grid = nblocks < ncu ? nblocks : ncu;
         launch(sched, dim3(grid), dA, dW, dC, M, N, K, tiles_n, nblocks);
@@ -497,15 +761,35 @@ int main(int argc, char** argv) {
         std::vector<float> ref((size_t)nrows * N);
         std::vector<uint16_t> got(N);
         CK(hipMemcpy(ref.data(), dRef, ref.size() * 4, hipMemcpyDeviceToHost));
-        double maxerr = 0, maxref = 0;
+        double maxerr = 0, maxref = 0, staterr = 0;
         for (int r = 0; r < nrows; ++r) {
             CK(hipMemcpy(got.data(), (uint16_t*)dC + (size_t)rows[r] * N, N * 2, hipMemcpyDeviceToHost));
+            if (resid) {  // the stream against x0 + gate (A . W + bias); the statistics against the sums of the STORED values
+                std::vector<float> st((size_t)(N / 64) * 2);
+                for (int pl = 0; pl < N / 64; ++pl) CK(hipMemcpy(&st[2 * pl], dStats + ((size_t)pl * M + rows[r]) * 2, 8, hipMemcpyDeviceToHost));
+                for (int pl = 0; pl < N / 64; ++pl) {
+                    double s1 = 0, s2 = 0;
+                    for (int n = 64 * pl; n < 64 * pl + 64; ++n) {
+                        _Float16 hv; memcpy(&hv, &got[n], 2);
+                        const double v = (double)(float)hv, want = (double)x0_of(rows[r], n) + (double)gate_of(n) * ((double)ref[(size_t)r * N + n] + bias_of(n));
+                        const double e = fabs(v - want);
+                        if (!(e <= maxerr)) maxerr = e;
+                        if (fabs(want) > maxref) maxref = fabs(want);
+                        s1 += v - pivot_of(rows[r]); s2 += (v - pivot_of(rows[r])) * (v - pivot_of(rows[r]));
+                    }
+                    const double e1 = fabs(st[2 * pl] - s1) / (1 + fabs(s1)), e2 = fabs(st[2 * pl + 1] - s2) / (1 + fabs(s2));
+                    if (!(e1 <= staterr)) staterr = e1;
+                    if (!(e2 <= staterr)) staterr = e2;
+                }
+                continue;
+            }
             for (int n = 0; n < N; ++n) {
                 const double e = fabs((double)bf2f(got[n]) - ref[(size_t)r * N + n]);
                 if (!(e <= maxerr)) maxerr = e;
                 if (fabs(ref[(size_t)r * N + n]) > maxref) maxref = fabs(ref[(size_t)r * N + n]);
             }
         }
+        if (resid) printf("[sched %d] %s: statistics of the sampled rows, max rel err %.3g%s\n", sched, sh.name, staterr, staterr <= 1e-4 ? "" : "  <-- MISMATCH");
         // timing
         hipEvent_t e0, e1;
         CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
@@ -522,6 +806,7 @@ int main(int argc, char** argv) {
                ((sched >= 10 && sched != 22 && sched < 40) || sched == 72 || sched == 73) ? "  (timing only)" : (maxerr <= 0.02 * maxref + 1e-3 ? "" : "  <-- MISMATCH"));
         fflush(stdout);
         (void)hipFree(dA); (void)hipFree(dW); (void)hipFree(dC); (void)hipFree(dRows); (void)hipFree(dRef);
+        if (resid) { (void)hipFree(dBias); (void)hipFree(dGate); (void)hipFree(dStats); (void)hipFree(dPivot); g_resid = ResidArgs{nullptr, nullptr, nullptr, nullptr, 0}; }
     }
     return 0;
 }
