@@ -810,12 +810,15 @@ int launch_grn(int precision, void* h, int B, int N, int C, const float* gamma, 
 
 // ----------------------------------------------------------------------------- text embedding gather (dit.py:49-68)
 __global__ __launch_bounds__(256) void text_gather_kernel(const int32_t* __restrict__ text, int nt, int B, int N, int td,
-                                                          const float* __restrict__ table, const float* __restrict__ pos_table, int pos_rows,
-                                                          int drop_text, float* __restrict__ out, uint8_t* __restrict__ filler) {
+                                                          const float* __restrict__ table, int table_rows, const float* __restrict__ pos_table,
+                                                          int pos_rows, int drop_text, float* __restrict__ out, uint8_t* __restrict__ filler) {
     const int row = blockIdx.x;  // b * N + p
     const int b = row / N, p = row % N;
     int tok = 0;
-    if (p < nt) tok = text[(size_t)b * nt + p] + 1;  // +1: 0 is the filler token; batch padding -1 -> 0
+    if (p < nt) {
+        const int id = text[(size_t)b * nt + p];  // ids outside [-1, vocab) are clamped into the table, as duration.hip's gather does
+        tok = id < 0 ? 0 : id >= table_rows - 1 ? table_rows - 1 : id + 1;  // +1: 0 is the filler token; batch padding -1 -> 0
+    }
     if (threadIdx.x == 0 && filler) filler[row] = tok == 0;
     if (drop_text) tok = 0;
     const int pp = p < pos_rows ? p : pos_rows - 1;  // get_pos_embed_indices clamps at precompute_max_pos (modules.py:218; 4096 dit.py:41, 1024 mmdit.py:37)
@@ -825,10 +828,12 @@ __global__ __launch_bounds__(256) void text_gather_kernel(const int32_t* __restr
         out[(size_t)row * td + c] = v;
     }
 }
-int launch_text_gather(const int32_t* text, int nt, int B, int N, int td, const float* table, const float* pos_table, int pos_rows, int drop_text,
-                       float* out, uint8_t* filler, hipStream_t stream) {
+int launch_text_gather(const int32_t* text, int nt, int B, int N, int td, const float* table, int table_rows, const float* pos_table, int pos_rows,
+                       int drop_text, float* out, uint8_t* filler, hipStream_t stream) {
     if (B * N <= 0) return 0;
-    hipLaunchKernelGGL(text_gather_kernel, dim3(B * N), dim3(256), 0, stream, text, nt, B, N, td, table, pos_table, pos_rows, drop_text, out, filler);
+    if (table_rows <= 0) return f5_fail(F5_EINVAL, "text_gather: empty table");
+    hipLaunchKernelGGL(text_gather_kernel, dim3(B * N), dim3(256), 0, stream, text, nt, B, N, td, table, table_rows, pos_table, pos_rows, drop_text, out,
+                       filler);
     F5_LAUNCH_CHECK();
     return 0;
 }

@@ -152,11 +152,13 @@ int compute_modulation(f5_plan_s* p, const float* tvals_dev, int n, hipStream_t 
     f5_model_s* m = p->m;
     const int D = m->cfg.dim;
     F5_TRY(launch_time_sinus(tvals_dev, n, p->tsin, st));
+    F5_TRY(tap_f32(p, "t_sin", p->tsin, 256, n, 256, st));
     F5_TRY(launch_gemv_rows(p->tsin, 256, n, m->w_t0, m->b_t0, D, 256, 0, 1, p->thid, D, st));  // Linear -> SiLU
     F5_TRY(launch_gemv_rows(p->thid, D, n, m->w_t2, m->b_t2, D, D, 0, 0, p->temb, D, st));      // Linear
     F5_TRY(tap_f32(p, "t_emb", p->temb, D, n, D, st));
     // every AdaLN: Linear(SiLU(t_emb))  (modules.py:311,332); UNetT has none: its layers see the time as a token (unett.py:211-213)
     if (m->modrow > 0) F5_TRY(launch_gemv_rows(p->temb, D, n, m->w_adaln, m->b_adaln, m->modrow, D, 1, 0, p->mod, m->modrow, st));
+    if (m->modrow > 0) F5_TRY(tap_f32(p, "adaln", p->mod, m->modrow, n, m->modrow, st));
     return 0;
 }
 
@@ -166,13 +168,14 @@ int compute_text_embed(f5_plan_s* p, const int32_t* text, int nt, int B, int N, 
     const f5_dit_config& c = m->cfg;
     const int td = c.text_dim, P = c.precision;
     if (c.backbone == F5_BACKBONE_MMDIT) {  // mmdit.py:40-61: [B, nt, dim], not padded to the frame count; table of 1024 positions
-        F5_TRY(launch_text_gather(text, nt, B, nt, td, m->text_table, m->text_pos, m->text_pos_rows, drop_text, out, p->filler, st));
+        F5_TRY(launch_text_gather(text, nt, B, nt, td, m->text_table, c.text_num_embeds + 1, m->text_pos, m->text_pos_rows, drop_text, out, p->filler, st));
         if (c.text_mask_padding) F5_TRY(launch_mask_rows(out, B * nt, td, p->filler, st));
         return 0;
     }
     const int rows = B * N;
     const bool extra = c.conv_layers > 0;
-    F5_TRY(launch_text_gather(text, nt, B, N, td, m->text_table, extra ? m->text_pos : nullptr, m->text_pos_rows, drop_text, out, p->filler, st));
+    F5_TRY(launch_text_gather(text, nt, B, N, td, m->text_table, c.text_num_embeds + 1, extra ? m->text_pos : nullptr, m->text_pos_rows, drop_text, out,
+                              p->filler, st));
     if (!extra) return 0;
     const bool mp = c.text_mask_padding != 0;
     if (mp) F5_TRY(launch_mask_rows(out, rows, td, p->filler, st));
@@ -229,6 +232,8 @@ int check_plan_shape(f5_plan_s* p, int B, int N) {
 extern "C" int f5_text_embed(f5_plan_t p, int B, int N, const int32_t* text, int nt, int drop_text, float* out, f5_stream_t stream) {
     F5_TRY(check_plan_shape(p, B, N));
     if (!text || !out || nt <= 0) return f5_fail(F5_EINVAL, "null/empty text");
+    if (p->m->cfg.backbone == F5_BACKBONE_MMDIT && nt > p->maxN)  // (its B * nt rows use the plan's per-row buffers, as f5_mmdit_forward's do)
+        return f5_fail(F5_EINVAL, "text length %d outside 1 .. the plan's max_seq %d", nt, p->maxN);
     return compute_text_embed(p, text, nt, B, N, drop_text, out, (hipStream_t)stream);
 }
 

@@ -116,9 +116,10 @@ int launch_dwconv7_ln_ragged(const float* x, const UttExtents& ext, int C, const
 // GRN (modules.py:225-234) in place on h [B*N, C] (activation dtype): h = gamma * (h * Nx) + beta + h
 int launch_grn(int precision, void* h, int B, int N, int C, const float* gamma, const float* beta, float* scratch /*[B*C + B]*/,
                hipStream_t stream);
-// text ids -> embedding rows (+ abs-pos table) ; also writes filler flags [B*N] (1 where the id is the filler 0)
-int launch_text_gather(const int32_t* text, int nt, int B, int N, int td, const float* table, const float* pos_table /*or null*/, int pos_rows,
-                       int drop_text, float* out, uint8_t* filler, hipStream_t stream);
+// text ids -> embedding rows (+ abs-pos table) ; also writes filler flags [B*N] (1 where the id is the filler 0).  table [table_rows, td],
+// table_rows = text_num_embeds + 1: an id outside [-1, table_rows - 1) is clamped into it (and is the filler when it clamps to row 0)
+int launch_text_gather(const int32_t* text, int nt, int B, int N, int td, const float* table, int table_rows, const float* pos_table /*or null*/,
+                       int pos_rows, int drop_text, float* out, uint8_t* filler, hipStream_t stream);
 int launch_mask_rows(float* x, int rows, int cols, const uint8_t* zero_flags, hipStream_t stream);
 // sinusoidal timestep embedding (modules.py:149-161): t [n] -> out [n, 256]
 int launch_time_sinus(const float* t, int n, float* out, hipStream_t stream);

@@ -196,7 +196,8 @@ F5_API int f5_sample_ragged_ex(f5_plan_t p, int B, const int32_t* frames_host, c
                         const int32_t* lens, const uint8_t* cond_mask, const float* y0, const float* tgrid_host, int steps,
                         float cfg_strength, const float* cfg_host, int ode_method, float* out, f5_stream_t stream);
 
-/* TextEmbedding.forward (dit.py:49-79): text ids [B, nt] (-1 padded) -> dev f32 [B, N, text_dim] */
+/* TextEmbedding.forward (dit.py:49-79): text ids [B, nt] (-1 padded) -> dev f32 [B, N, text_dim].  An id outside [-1, text_num_embeds) is
+ * clamped to the nearer end of that range (-1 is the filler) instead of being read outside the embedding table. */
 F5_API int f5_text_embed(f5_plan_t p, int B, int N, const int32_t* text, int nt, int drop_text, float* out, f5_stream_t stream);
 
 /* DiT.forward (dit.py:185-233) for one branch:
@@ -293,8 +294,9 @@ F5_API int f5_duration_loss(int B, int nt, const float* logw, const float* durat
                             double* abs_sums, int64_t* counts, float* loss_mae, f5_stream_t stream);
 
 /* debug/parity taps: after the next f5_dit_forward / f5_sample evaluation, copy the named internal stage
- * (converted to f32, row-major [rows, cols]) into `dst` (dev f32).  Names: "t_emb", "input_embed",
- * "blk<i>.n1", "blk<i>.attn", "blk<i>.out", "final_norm".  Pass dst = NULL to clear all taps. */
+ * (converted to f32, row-major [rows, cols]) into `dst` (dev f32).  Names: "t_sin" (the 256 sinusoid features of every time), "t_emb",
+ * "adaln" (the AdaLN modulation rows of every block and the final norm, [times, the model's modulation width]; DiT and MMDiT),
+ * "input_embed", "blk<i>.n1", "blk<i>.attn", "blk<i>.out", "final_norm".  Pass dst = NULL to clear all taps. */
 F5_API int f5_plan_set_tap(f5_plan_t p, const char* stage, float* dst);
 /* in-situ timing of the dominant kernel: between begin and end, every fused-QKV GEMM launch of (eager) f5_sample /
  * f5_dit_forward calls on this plan is bracketed by a HIP event pair on the caller's stream; end synchronises the stream and

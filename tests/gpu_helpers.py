@@ -940,3 +940,195 @@ def attn_emulate_ref(qkv, mask, precision, base2=False, leak_padding_key=False):
         m_i = m_new
     inv = torch.where(l_i > 0, 1.0 / l_i, torch.zeros_like(l_i))
     return round_to(precision, (o * inv[..., None]).transpose(1, 2).reshape(B, N, H * 64))
+
+
+# ----------------------------------------------------------------------------- the text path (compute_text_embed, csrc/eval_common.hip): fp64
+# reference, the CPU restatement of the kernel chain with its planted defects, and the per-row bound (tests/test_text_embed_bound_host.py,
+# tests/test_gpu_text_embed.py)
+TEXT_MARGIN = 4.0  # a result passes when its worst row error is within TEXT_MARGIN x the restatement's worst row error of the same case
+TEXT_DEFECTS = ("none", "last_token_gathers_filler", "position_off_by_one", "mask_after_drop_text", "conv_across_batch", "grn_over_flattened_batch",
+                "no_mask_after_last_block", "position_wraps")
+
+
+def text_clamp_ids(text, vocab):
+    """What text_gather_kernel makes of an id outside [-1, vocab): the nearer end of that range (-1 is the filler)."""
+    return text.clamp(min=-1, max=vocab - 1)
+
+
+def text_pos_table_f32(td, rows):
+    """The position table as f5_model_finalize fills it (csrc/model.hip), in float32 on the host: inv_j = 1 / powf(10000, 2j / td) with the C
+    library's powf (through ctypes, numpy's power where no libm is found), ang = p * inv_j, [cos | sin] -> [rows, td]."""
+    import ctypes.util
+
+    import numpy as np
+    half = td // 2
+    expo = (np.arange(half, dtype=np.float32) * np.float32(2)) / np.float32(td)
+    name = ctypes.util.find_library("m")
+    if name:
+        powf = C.CDLL(name).powf
+        powf.restype, powf.argtypes = C.c_float, [C.c_float, C.c_float]
+        pw = np.array([powf(10000.0, float(e)) for e in expo], dtype=np.float32)
+    else:
+        pw = np.power(np.float32(10000), expo)
+    inv = (np.float32(1) / pw).astype(np.float32)
+    ang = (np.arange(rows, dtype=np.float32)[:, None] * inv[None, :]).astype(np.float32)
+    return torch.from_numpy(np.concatenate([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32))
+
+
+def text_reference(W, cfg, text, N, drop_text, mmdit=False):
+    """R: oracle/cpu_ref's text embedding evaluated in float64 on the weights cast to double -> [B, N, td] (MMDiT: [B, nt, dim])."""
+    from oracle import cpu_ref
+    Wd = {k: v.double() for k, v in W.items() if k.startswith("text_embed.")}
+    if mmdit:
+        return cpu_ref.mmdit_text_embedding(Wd, cfg, text, drop_text=drop_text)
+    return cpu_ref.text_embedding(Wd, cfg, text, N, drop_text=drop_text)
+
+
+def text_emulate(precision, W, cfg, text, N, drop_text, mmdit=False, defect="none"):
+    """CPU restatement of compute_text_embed in float32: text_gather_kernel (ids clamped into the table, filler flags before drop_text, the
+    position index clamped at the table's last row), mask_rows_kernel, then per ConvNeXt-V2 block dwconv7_ln -> the mode's type, pwconv1 + GELU
+    (weights and output in the mode's type), GRN in place in the mode's type, pwconv2 (weights in the mode's type) added to the fp32 output, and
+    the mask again.  `defect` (TEXT_DEFECTS) plants what tests/test_gpu_text_embed.py is there to catch:
+        last_token_gathers_filler    the last real token row of every batch item reads table row 0
+        position_off_by_one          row p takes position p + 1
+        mask_after_drop_text         the filler flags are taken from the ids drop_text has zeroed
+        conv_across_batch            the depthwise conv's taps run over the flattened B * N rows (zero padding only at the two ends)
+        grn_over_flattened_batch     GRN's sequence norm runs over all B * N rows
+        no_mask_after_last_block     the filler rows are not zeroed again after the last block
+        position_wraps               positions past the table wrap around instead of clamping to its last row"""
+    assert defect in TEXT_DEFECTS
+    table = W["text_embed.text_embed.weight"].float()
+    B, nt = text.shape
+    N = nt if mmdit else N
+    n = min(nt, N)
+    ids = torch.zeros(B, N, dtype=torch.long)
+    ids[:, :n] = text_clamp_ids(text[:, :n].long(), table.shape[0] - 1) + 1
+    filler = ids == 0
+    if defect == "last_token_gathers_filler":
+        for b in range(B):
+            real = (~filler[b]).nonzero()
+            if real.numel():
+                ids[b, int(real[-1])] = 0
+    if drop_text:
+        ids = torch.zeros_like(ids)
+        if defect == "mask_after_drop_text":
+            filler = ids == 0
+    x = table[ids]
+    n_conv = 0 if mmdit else cfg.get("conv_layers", 0)
+    mp = bool(cfg.get("text_mask_padding", True))
+    if not (mmdit or n_conv > 0):
+        return x
+    pos_rows = 1024 if mmdit else 4096
+    p = torch.arange(N) + (1 if defect == "position_off_by_one" else 0)
+    p = p % pos_rows if defect == "position_wraps" else p.clamp(max=pos_rows - 1)
+    x = x + text_pos_table_f32(x.shape[-1], min(pos_rows, N + 1))[p][None]
+    if mp:
+        x = x.masked_fill(filler[..., None], 0.0)
+    td = x.shape[-1]
+    for i in range(n_conv):
+        pre = f"text_embed.text_blocks.{i}."
+        w = {k: W[pre + k].float() for k in ("dwconv.weight", "dwconv.bias", "norm.weight", "norm.bias", "pwconv1.weight", "pwconv1.bias", "grn.gamma",
+                                            "grn.beta", "pwconv2.weight", "pwconv2.bias")}
+        xin = x.reshape(1, B * N, td) if defect == "conv_across_batch" else x
+        y = F.conv1d(xin.transpose(1, 2), w["dwconv.weight"], w["dwconv.bias"], padding=3, groups=td).transpose(1, 2).reshape(B, N, td)
+        mean = y.mean(dim=-1, keepdim=True)
+        d = y - mean
+        y = round_to(precision, d * torch.rsqrt((d * d).mean(dim=-1, keepdim=True) + 1e-6) * w["norm.weight"] + w["norm.bias"])
+        h = round_to(precision, F.gelu(y @ round_to(precision, w["pwconv1.weight"]).t() + w["pwconv1.bias"]))
+        hs = h.reshape(1, B * N, 2 * td) if defect == "grn_over_flattened_batch" else h
+        g = torch.sqrt((hs * hs).sum(dim=1, keepdim=True))
+        nx = g / (g.mean(dim=-1, keepdim=True) + 1e-6)
+        h = round_to(precision, w["grn.gamma"].reshape(-1) * (h * nx) + w["grn.beta"].reshape(-1) + h)
+        x = x + (h @ round_to(precision, w["pwconv2.weight"]).t() + w["pwconv2.bias"])
+        if mp and not (defect == "no_mask_after_last_block" and i == n_conv - 1):
+            x = x.masked_fill(filler[..., None], 0.0)
+    return x
+
+
+def text_row_errors(X, R):
+    """The row metric: e[b, p] = max_c |X - R| / max_c |R[b, p, :]| over the rows whose reference is not all zero (0 elsewhere), and the mask of
+    the rows the reference zeroes (the filler rows under text_mask_padding)."""
+    R = R.double()
+    top = R.abs().amax(dim=-1)
+    zero = top == 0
+    e = (X.double() - R).abs().amax(dim=-1) / top.clamp(min=1e-300)
+    return torch.where(zero, torch.zeros_like(e), e), zero
+
+
+def check_text_rows(name, X, R, E, margin=TEXT_MARGIN):
+    """Every row of X within margin x the restatement E's worst row error against R, and exact zeros on the rows R zeroes.  Prints the
+    restatement's worst row error, the margin and X's worst row as a share of the bound; returns that share."""
+    eE, _ = text_row_errors(E, R)
+    eX, zero = text_row_errors(X, R)
+    bound = margin * float(eE.max())
+    assert torch.isfinite(X).all(), name
+    nz = int((X[zero] != 0).sum())
+    worst = float(eX.max())
+    share = worst / bound if bound > 0 else (0.0 if worst == 0 else float("inf"))
+    print(f"  {name}: restatement's worst row {float(eE.max()):.3e}, margin {margin:g}, worst row {worst:.3e} = {share:.3f} of the bound "
+          f"(row {tuple(int(i) for i in (eX == eX.max()).nonzero()[0])}); rel-L2 {float((X.double() - R.double()).norm() / R.double().norm().clamp(min=1e-300)):.3e}; "
+          f"{int(zero.sum())} zeroed rows")
+    assert nz == 0, f"{name}: {nz} non-zero elements on rows the reference zeroes"
+    bad = eX > bound
+    assert not bad.any(), f"{name}: {int(bad.sum())} rows out of bound (worst {share:.3f} of it), first at {bad.nonzero()[0].tolist()}"
+    return share
+
+
+TEXT_V = 200  # vocabulary of the text cases: ids 0 .. 199, table of 201 rows
+# id -> (backbone, text_dim, conv_layers, text_mask_padding, B, N, nt, real tokens per batch item)
+TEXT_CASES = {
+    "td512_c4_mask_3x77": ("dit", 512, 4, True, 3, 77, 90, (77, 40, 90)),    # no filler / -1 padded / nt = 90 > N: curtailed at N
+    "td512_c4_nomask_3x77": ("dit", 512, 4, False, 3, 77, 90, (77, 40, 90)),
+    "td512_c4_mask_2x5": ("dit", 512, 4, True, 2, 5, 5, (5, 3)),             # a sequence shorter than the 7-tap conv
+    "td512_c4_mask_2x300": ("dit", 512, 4, True, 2, 300, 200, (200, 0)),     # 600 rows: whole and ragged GEMM tiles; one item all filler
+    "td128_c2_nomask_3x77": ("dit", 128, 2, False, 3, 77, 90, (77, 40, 90)),  # the tiny goldens' width
+    "td100_c0_2x77": ("unett", 100, 0, True, 2, 77, 77, (77, 40)),           # E2-TTS / UNetT form: the gather alone, no position table
+    "mmdit128_mask_nt1030": ("mmdit", 128, 0, True, 2, 1030, 1030, (1030, 1000)),  # positions 1024 .. 1029 clamp to row 1023 of the table
+    "mmdit128_nomask_nt1030": ("mmdit", 128, 0, False, 2, 1030, 1030, (1030, 1000)),
+}
+_TEXT_CASE_CACHE = {}
+
+
+def text_case(cid):
+    """One line of TEXT_CASES as a dict: arch (the smallest model create() accepts: dim 128), seeded weights W, text and a second text with
+    the same filler pattern [B, nt] (-1 padded), B, N, backbone, mmdit.  Built once and shared; nothing writes to it."""
+    if cid in _TEXT_CASE_CACHE:
+        return _TEXT_CASE_CACHE[cid]
+    from oracle import cpu_ref
+    backbone, td, conv, mp, B, N, nt, real = TEXT_CASES[cid]
+    seed = 7000 + sorted(TEXT_CASES).index(cid)
+    if backbone == "mmdit":
+        arch = dict(dim=128, depth=1, heads=2, ff_mult=2, text_mask_padding=mp)
+        W = cpu_ref.random_mmdit_weights(arch, TEXT_V, seed=seed)
+    elif backbone == "unett":
+        arch = dict(dim=128, depth=2, heads=2, ff_mult=2, text_dim=td, conv_layers=conv, text_mask_padding=mp, pe_attn_head=1, skip_connect_type="concat")
+        W = cpu_ref.random_unett_weights(arch, TEXT_V, seed=seed)
+    else:
+        arch = dict(dim=128, depth=1, heads=2, ff_mult=2, text_dim=td, conv_layers=conv, text_mask_padding=mp, pe_attn_head=1)
+        W = cpu_ref.random_dit_weights(arch, TEXT_V, seed=seed)
+    g = torch.Generator().manual_seed(seed + 1)
+    texts = []
+    for _ in range(2):
+        t = torch.randint(0, TEXT_V, (B, nt), generator=g)
+        for b, n in enumerate(real):
+            t[b, n:] = -1
+        texts.append(t)
+    texts[0][0, 0], texts[0][0, min(real[0], nt) - 1] = TEXT_V - 1, 0  # the two ends of the table are gathered
+    case = dict(arch=arch, W=W, text=texts[0], text2=texts[1], B=B, N=N, backbone=backbone, mmdit=backbone == "mmdit")
+    _TEXT_CASE_CACHE[cid] = case
+    return case
+
+
+_TEXT_REF_CACHE = {}
+
+
+def text_case_terms(cid, precision, drop_text):
+    """(R, E_p) of a case: the fp64 reference and the restatement in the mode `precision`; computed once per key, shared, never written to."""
+    key = (cid, drop_text)
+    c = text_case(cid)
+    if key not in _TEXT_REF_CACHE:
+        _TEXT_REF_CACHE[key] = text_reference(c["W"], c["arch"], c["text"], c["N"], drop_text, c["mmdit"])
+    ekey = (cid, precision, drop_text)
+    if ekey not in _TEXT_REF_CACHE:
+        _TEXT_REF_CACHE[ekey] = text_emulate(precision, c["W"], c["arch"], c["text"], c["N"], drop_text, c["mmdit"])
+    return _TEXT_REF_CACHE[key], _TEXT_REF_CACHE[ekey]
