@@ -703,6 +703,12 @@ extern "C" int f5_plan_get_option(f5_plan_t p, const char* key, int* value) {
         *value = g_gemm_w4;
     else if (strcmp(key, "residual_fallbacks") == 0)
         *value = p->fallbacks;
+    // read-only counters of run_sample_loop over the plan's life: loops captured into a hipGraph (the capture's own launch included), and
+    // launches of a capture found in the cache.  A call that took the graph path raised exactly one of them; an eager call raised neither.
+    else if (strcmp(key, "graph_captures") == 0)
+        *value = p->graph_captures;
+    else if (strcmp(key, "graph_replays") == 0)
+        *value = p->graph_replays;
     else if (strcmp(key, "residual_guard_amax_bits") == 0)  // diagnostic: float bits of the largest finite |element| the last event saw
         *value = (int)p->sat_amax_bits;
     else if (strcmp(key, "residual_guard_nan") == 0)

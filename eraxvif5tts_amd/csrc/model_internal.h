@@ -217,6 +217,7 @@ struct f5_plan_s {
     std::vector<float> mod_tv;  // evaluation times the AdaLN rows in `mod` were computed for (empty = stale); see f5_sample
     hipStream_t mod_stream = nullptr;  // ... and the stream they were computed on (a call on another stream recomputes them)
     std::vector<GraphEntry> graphs;
+    int graph_captures = 0, graph_replays = 0;  // run_sample_loop: loops captured / launches of a capture found in `graphs` (f5_plan_get_option; never reset)
     hipStream_t cap_stream = nullptr;  // capture happens on a private stream (the caller's may be the legacy null stream)
     // in-situ timing of the block kernels: HIP event pairs around every launch of an eager sample() (f5_plan_timing_*)
     // The pairs live in a BOUNDED ring (F5_EV_RING pairs, created once per plan and reused): when it is full the older half is folded into

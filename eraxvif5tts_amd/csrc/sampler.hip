@@ -151,6 +151,9 @@ static int run_sample_loop(f5_plan_s* p, const SampleArgs& a, int use_graph, hip
             if (p->graphs.size() >= 32) p->graphs.erase(p->graphs.begin());
             p->graphs.push_back(std::move(g));
             ge = p->graphs.end() - 1;
+            ++p->graph_captures;  // (the launch below is the capture's own: it does not count as a replay)
+        } else {
+            ++p->graph_replays;
         }
         F5_HIP(hipGraphLaunch(ge->exec, st));
     } else {
@@ -241,9 +244,14 @@ static int acquire_fold(f5_plan_s* p, const std::vector<float>& tv, hipStream_t 
         if (p->fold) --p->fold->users;
         p->fold = want;
         if (want) ++want->users;
-        const uint64_t id = want ? want->id : 0;  // captures that baked another table's addresses
-        drop_graphs_where(p, [id](const GraphEntry& g) { return g.key.fold_id != id; });
     }
+    // A capture bakes its table's addresses and carries the table's id in its key (GraphKey::fold_id), so it is launched only while the plan
+    // points at that very table: captures of the model's other live tables stay, and a caller that alternates between two grids replays both.
+    // Captures of a table that no longer exists (evicted above, or by another plan of the model) can never be found again -- ids are not
+    // reused -- and are destroyed here.
+    drop_graphs_where(p, [m](const GraphEntry& g) {
+        return g.key.fold_id != 0 && std::none_of(m->folds.begin(), m->folds.end(), [&](const FoldTable* t) { return t->id == g.key.fold_id; });
+    });
     return 0;
 }
 

@@ -333,7 +333,12 @@ F5_API int f5_plan_set_option(f5_plan_t p, const char* key, int value);
  * storage because the range guard fired ("residual_f16" then reads 0); "attn_prescale_active" = 1 when this plan wants pre-scaled q and may run it (0 e.g.
  * while a stage tap is set).  That is the plan's part only: an evaluation uses pre-scaled q where it also runs the LayerNorm fold, which
  * under automatic kernel choice needs at least 512 token rows and a time grid of at most 64 evaluation times -- a smaller call on a plan
- * that reports 1 still runs q as projected. */
+ * that reports 1 still runs q as projected.
+ * "graph_captures" / "graph_replays" (read-only; f5_plan_set_option refuses them as unknown keys): counters over the plan's life of the sample
+ * loops of f5_sample* (use_graph != 0) and f5_sample_ragged* ("ragged_graph" = 1).  A loop that found no hipGraph of its key captured one and
+ * launched it: graph_captures + 1, graph_replays unchanged (a capture's own launch is no replay).  A loop that launched a graph captured by
+ * an earlier call: graph_replays + 1.  An eager loop raises neither; the fp32 rerun of the range guard is a loop of its own.  Dropping the
+ * plan's graphs (a changed kernel option, tuning knob, block subset, dropout setting) does not reset them. */
 F5_API int f5_plan_get_option(f5_plan_t p, const char* key, int* value);
 /* Attention dropout, opt-in: the reference's F.scaled_dot_product_attention(dropout_p = 0.1) stays live under
  * model.eval() (modules.py:490, :582).  prob in [0, 1), 0 = off (the default: every output bit and launch as without this call).  With it on,

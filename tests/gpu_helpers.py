@@ -1132,3 +1132,59 @@ def text_case_terms(cid, precision, drop_text):
     if ekey not in _TEXT_REF_CACHE:
         _TEXT_REF_CACHE[ekey] = text_emulate(precision, c["W"], c["arch"], c["text"], c["N"], drop_text, c["mmdit"])
     return _TEXT_REF_CACHE[key], _TEXT_REF_CACHE[ekey]
+
+
+# ----------------------------------------------------------------------------- plan read-backs and the input sets of the graph-replay tests
+def plan_option(model, key):
+    """f5_plan_get_option(key) of the ONE plan `model` (a DiT / UNetT / MMDiT) holds."""
+    (_, h), = model._plans
+    v = C.c_int(-1)
+    _lib.check(_lib.load().f5_plan_get_option(h, key.encode(), C.byref(v)), f"f5_plan_get_option({key})")
+    return v.value
+
+
+REPLAY_FIELDS = ("cond", "text_ids", "text_len", "lens", "durations", "y0", "cond_mask")
+
+
+def replay_inputs(B, N, nt, mel, V, seed):
+    """Two input sets (A, B) of one native_sample() shape -- dicts over REPLAY_FIELDS, host tensors -- in which every value differs:
+        cond, y0     f32 [B, N, mel]  other seeds (cond = randn * 2 - 3, as a log-mel prompt; y0 = randn)
+        text_ids     int [B, nt]      B's id at every position is another id than A's
+        text_len     int [B]          valid tokens per row, all in [nt - 9, nt]: both texts have nt columns (replay_text pads with -1)
+        lens         int [B]          prompt frames, around N / 3
+        durations    int [B]          A = (N, N - 43, ...), B = (..., N - 89, N): max = N in both (the same key), every row differs, row 0
+                                      shrinks and the last row grows from A to B
+        cond_mask    bool [B, N]      lens prefix with 1 frame in 5 edited out (f5_sample_masked), drawn per set
+    Needs B >= 2 (one row cannot change its duration under a fixed N), nt >= 12 and N >= 100 (durations stay above text and prompt)."""
+    assert B >= 2 and nt >= 12 and N >= 100 and V >= 3
+    ga, gb = torch.Generator().manual_seed(seed), torch.Generator().manual_seed(seed + 7919)
+    rows = torch.arange(B)
+    ids_a = torch.randint(0, V, (B, nt), generator=ga)
+    sets = []
+    for which, g in enumerate((ga, gb)):
+        d = dict(cond=torch.randn(B, N, mel, generator=g) * 2 - 3, y0=torch.randn(B, N, mel, generator=g))
+        d["text_ids"] = ids_a if which == 0 else (ids_a + 1 + torch.randint(0, V - 1, (B, nt), generator=g)) % V
+        d["text_len"] = nt - (rows * 7) % 5 if which == 0 else nt - 5 - (rows * 3) % 5
+        d["lens"] = N // 3 - 23 * rows % (N // 4) if which == 0 else N // 3 - 11 + (9 * rows) % 20
+        dur = N - 43 * rows - 13 * (rows > 1) if which == 0 else N - 82 - 7 * (B - 1 - rows)
+        dur[0 if which == 0 else B - 1] = N
+        d["durations"] = dur.clamp(min=N // 2 + 1)
+        d["cond_mask"] = (torch.arange(N)[None, :] < d["lens"][:, None]) & (torch.rand(B, N, generator=g) > 0.2)
+        assert int(d["durations"].max()) == N and bool((d["durations"] > torch.maximum(d["text_len"], d["lens"])).all())
+        sets.append(d)
+    a, b = sets
+    for k in REPLAY_FIELDS:
+        differs = a[k] != b[k]
+        assert bool(differs.any(dim=1).all() if k == "cond_mask" else differs.all()), k
+    return a, b
+
+
+def replay_swap(a, b, field):
+    """`a` with exactly the one field of REPLAY_FIELDS taken from `b` (a new dict; the tensors are shared and never written to)."""
+    assert field in REPLAY_FIELDS
+    return {**a, field: b[field]}
+
+
+def replay_text(d):
+    """The text tensor [B, nt] of an input set: text_ids with the columns from text_len on set to the pad -1."""
+    return torch.where(torch.arange(d["text_ids"].shape[1])[None, :] < d["text_len"][:, None], d["text_ids"], torch.full_like(d["text_ids"], -1))

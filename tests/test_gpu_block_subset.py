@@ -166,13 +166,6 @@ def test_sample_bf16_equals_the_unfolded_pruned_model(weights, inputs, S):
     assert torch.isfinite(got).all()
 
 
-def _plan_option(dit, key):
-    (_, h), = dit._plans
-    v = C.c_int(-1)
-    _lib.check(_lib.load().f5_plan_get_option(h, key.encode(), C.byref(v)))
-    return v.value
-
-
 def test_clearing_the_subset_restores_the_folded_sampler(weights):
     """512 token rows (one utterance of 256 frames, both CFG halves): the bf16 sampler runs the LayerNorm fold.  Under a subset no table is held
     and the result is the unfolded pruned model's; cleared, the table is back and the bits are those of the first call, eager and replayed."""
@@ -185,18 +178,18 @@ def test_clearing_the_subset_restores_the_folded_sampler(weights):
               cfg_strength=2.0, sway_sampling_coef=-1.0, y0=torch.randn(1, n, 100, generator=g))
     before = [cfm.sample(**kw, use_graph=ug)[0] for ug in (False, True, True)]
     assert torch.equal(before[0], before[1]) and torch.equal(before[0], before[2])
-    folded = _plan_option(dit, "ln_fold_active")
+    folded = G.plan_option(dit, "ln_fold_active")
     S = [0, 1, 4, 5]
     dit.set_active_blocks(S)
     got = [cfm.sample(**kw, use_graph=ug)[0] for ug in (False, True, True)]
-    assert _plan_option(dit, "ln_fold_active") == 0
+    assert G.plan_option(dit, "ln_fold_active") == 0
     with G.knobs(ln_fold=0):
         want, _ = _pruned_cfm(cfm, S).sample(**kw, use_graph=False)
     for t in got:
         assert torch.equal(t, want)
     dit.set_active_blocks(None)
     after = [cfm.sample(**kw, use_graph=ug)[0] for ug in (True, False)]
-    assert _plan_option(dit, "ln_fold_active") == folded
+    assert G.plan_option(dit, "ln_fold_active") == folded
     assert torch.equal(after[0], before[0]) and torch.equal(after[1], before[0])
 
 

@@ -12,7 +12,6 @@ and the row-wise time MLP / AdaLN kernel (K = dim: 8 vectors per lane above 1024
 Reference: the CPU oracle (oracle/cpu_ref.py, fp32; it differs from its own fp64 evaluation by rel-L2 5e-7 .. 7e-7 at these widths, two orders
 of magnitude below the tightest tolerance) on seeded weights.  Tolerances: the project's own -- tests/test_gpu_model.py (fp32 2e-4, bf16 2e-2;
 stages 1e-4 / 1.5e-2) and tests/test_gpu_fp16_model.py (fp16 5e-3; stages 3.75e-3), imported from there.  Every test prints its figures."""
-import ctypes as C
 import glob
 import os
 
@@ -80,14 +79,6 @@ def _oracle_sample(key, W, cfg, pr):
 
 def _sample(cfm, pr, **kw):
     return cfm.sample(cond=pr["cond"].cuda(), text=pr["text"].cuda(), duration=pr["dur"].cuda(), lens=pr["lens"].cuda(), y0=pr["y0"], **SAMPLE_KW, **kw)
-
-
-def _plan_option(model, key):
-    from eraxvif5tts_amd import _lib
-    (_, h), = model._plans
-    v = C.c_int(-1)
-    _lib.check(_lib.load().f5_plan_get_option(h, key.encode(), C.byref(v)))
-    return v.value
 
 
 def _check_sample(tag, cfm, pr, ref, prec, graph_and_repeat=False):
@@ -190,7 +181,7 @@ def test_small_dit_sampler_matches_oracle(B, N, prec):
     cfm = G.make_cfm(SMALL_DIT, V, W, prec)
     _check_sample(f"dit768/12 {B}x{N}", cfm, pr, ref, prec, graph_and_repeat=prec == "bf16")
     if prec != "fp32" and 2 * B * N >= 512:
-        assert _plan_option(cfm.transformer, "ln_fold_active") == 1
+        assert G.plan_option(cfm.transformer, "ln_fold_active") == 1
     del cfm
     torch.cuda.empty_cache()
 
@@ -220,7 +211,7 @@ def test_small_dit_knob_equalities(B, N):
     run = lambda c: _sample(c, pr, use_graph=False, return_trajectory=False)[0].cpu()
     cfm = G.make_cfm(SMALL_DIT, V, W, "bf16")
     fold = run(cfm)
-    assert torch.isfinite(fold).all() and _plan_option(cfm.transformer, "ln_fold_active") == 1
+    assert torch.isfinite(fold).all() and G.plan_option(cfm.transformer, "ln_fold_active") == 1
     with G.knobs(gemm_w4=0):
         out = run(cfm)
     assert torch.equal(out, fold), ("gemm_w4 = 0", float((out - fold).abs().max()))
@@ -234,7 +225,7 @@ def test_small_dit_knob_equalities(B, N):
     with G.knobs(ln_fold=0):
         cfm = G.make_cfm(SMALL_DIT, V, W, "bf16")
         passes = run(cfm)
-        assert cfm.transformer.residual_fallbacks() == 0 and _plan_option(cfm.transformer, "ln_fold_active") == 0  # (the leg really ran the passes)
+        assert cfm.transformer.residual_fallbacks() == 0 and G.plan_option(cfm.transformer, "ln_fold_active") == 0  # (the leg really ran the passes)
         del cfm
     cfm = G.make_cfm(SMALL_DIT, V, W, "fp32")
     want = run(cfm)
@@ -413,7 +404,7 @@ def _check_width(wid, prec, taps):
     cfm = G.make_cfm(arch, V, W, prec, mel_dim=mel)
     _check_sample(f"dit{wid} 2x300", cfm, pr, ref, prec, graph_and_repeat=prec != "fp32")
     if prec != "fp32":
-        assert _plan_option(cfm.transformer, "ln_fold_active") == 1
+        assert G.plan_option(cfm.transformer, "ln_fold_active") == 1
     del cfm
     torch.cuda.empty_cache()
     if taps:
