@@ -114,6 +114,7 @@ _PROTOS = {
     "f5_plan_timing_end": (_I, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int), _P]),
     "f5_plan_timing_site": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "f5_plan_set_tap": (_I, [_P, C.c_char_p, _P]),
+    "f5_plan_set_probe": (_I, [_P, C.c_char_p, _P]),
     "f5_plan_set_option": (_I, [_P, C.c_char_p, _I]),
     "f5_plan_set_attn_dropout": (_I, [_P, _F, C.c_uint64]),
     "f5_plan_get_option": (_I, [_P, C.c_char_p, C.POINTER(C.c_int)]),
@@ -148,6 +149,7 @@ _PROTOS = {
     "f5_tuning_key": (C.c_char_p, [_I]),
     "f5_debug_gemm_clock": (_I, [_P]),
     "f5_debug_last_gemm": (_I, [C.POINTER(C.c_int)] * 5),
+    "f5_debug_site_gemm": (_I, [_I] + [C.POINTER(C.c_int)] * 6),
     "f5_debug_eval_modes": (_I, [_P, _I, _I, _I, C.POINTER(C.c_int32)]),
     "f5_vocoder_create": (_I, [C.POINTER(VocosConfig), C.POINTER(_P)]),
     "f5_vocoder_set_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),

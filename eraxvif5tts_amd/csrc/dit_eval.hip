@@ -103,6 +103,26 @@ extern "C" int f5_debug_eval_modes(f5_plan_t p, int nb, int N, int per_batch_row
     return 0;
 }
 
+int dit_probe_check(f5_plan_s* p, int nb, int N, int mod_bstride, int nev) {
+    if (p->probes.empty()) return 0;
+    if (p->m->cfg.backbone != F5_BACKBONE_DIT) return f5_fail(F5_ENOTSUP, "stage probes: DiT backbone only");
+    if (p->probe_eval >= nev) return f5_fail(F5_EINVAL, "stage probes: probe_eval %d, the call makes %d evaluation(s)", p->probe_eval, nev);
+    p->fold_eval = mod_bstride ? -1 : p->probe_eval;  // (as net_eval sets it for that evaluation)
+    DitEvalModes md;
+    F5_TRY(dit_eval_modes(p, nb, N, mod_bstride, &md));
+    for (const auto& kv : p->probes) {
+        int j;
+        std::string s;
+        F5_TRY(probe_parse(kv.first, plan_depth(p), &j, &s));
+        const char* why = nullptr;
+        if ((s == "x_in" || s == "x_attn" || s == "x_ff") && !md.rmw) why = "the residual stream is not updated in place";
+        if (s == "n1" && md.lnf && j > 0) why = "the LayerNorm fold runs no first pass in this block";
+        if ((s == "stats1" || s == "stats2") && !md.lnf) why = "no LayerNorm fold";
+        if (why) return f5_fail(F5_ESTATE, "stage probe '%s': %s in this evaluation", kv.first.c_str(), why);
+    }
+    return 0;
+}
+
 namespace {
 // the block at position j of the walk: model block l, its weights, its AdaLN rows, its prefetch sets, its rows of the fold table
 struct DitBlock {
@@ -134,6 +154,14 @@ struct DitEval {
     DitBlock block(int j, int l, int l_next) const;
     int attention(const DitBlock& k) const;
     int feed_forward(const DitBlock& k) const;
+    // stage probes: copies of what this evaluation holds anyway, of its token rows (md.rows, never the padding rows of the block GEMMs)
+    const bool probing = plan_probing(p);
+    int stream_prec() const { return md.r16 ? F5_PREC_FP16 : F5_PREC_FP32; }
+    const void* stream() const { return md.r16 ? p->xres16 : (const void*)p->xres; }
+    int probe(int j, const char* stage, int prec, const void* src, int cols, int ld = 0, int rows = 0) const {
+        if (!probing) return 0;
+        return probe_copy(p, j < 0 ? std::string(stage) : "blk" + std::to_string(j) + "." + stage, prec, src, ld ? ld : cols, rows ? rows : md.rows, cols, st);
+    }
 };
 }  // namespace
 
@@ -210,7 +238,10 @@ int DitEval::attention(const DitBlock& k) const {
     const int rows = md.rows, j = k.j, l = k.l;
     const Ragged* rg = p->rg;  // ragged sample(): N = rows of one half, the utterances sit inside it between zero gaps
     const std::string tn = "blk" + std::to_string(j);
+    if (j == 0) F5_TRY(probe(-1, "input_embed", stream_prec(), stream(), D));
     if (!k.lnf1) F5_TRY(timed(p, F5_SITE_LN1, st, [&] { return layernorm(1, j, k.ml + D, k.ml, md.wpf ? &k.pf1 : nullptr); }));
+    if (j == 0 && md.rmw) F5_TRY(probe(0, "x_in", F5_PREC_FP16, p->xres16, D));
+    if (!k.lnf1) F5_TRY(probe(j, "n1", P, p->hT, D));
     if (j == 0) F5_TRY(tap_f32(p, "input_embed", p->xres, D, rows, D, st));
     if (j == 0 && c.long_skip)  // residual = x  (dit.py:217-218)
         F5_HIP(hipMemcpyAsync(p->skips[0], p->xres, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -244,6 +275,8 @@ int DitEval::attention(const DitBlock& k) const {
         if (!rc && c.qk_norm) rc = launch_qknorm_rope(P, p->qkv, 3 * inner, rows, inner, c.heads, m->rope_heads, b.w_qn, b.w_kn, rope, N, st);
         return !rc && split_v ? run_gemm(p, gv, GEMM_DENSE, EPI_STORE_T, st) : rc;
     }));
+    if (k.lnf1) F5_TRY(probe(j, "stats1", F5_PREC_FP32, lnf_table(2 * l - 1), 2));
+    F5_TRY(probe(j, "qkv", P, p->qkv, 3 * inner));
     if (rg) {  // every utterance gets the computation of the launch its own batch-1 sample() makes, on its rows of both halves; the ones
                // that launch would give to the pipelined kernel share launches (grid.z = utterance x branch, 12 utterances per table)
         const AttnDropout drop = plan_attn_dropout(p, j, 0, (uint32_t)rg->n.size());  // batch word = branch * B + u
@@ -253,6 +286,7 @@ int DitEval::attention(const DitBlock& k) const {
         const AttnDropout drop = plan_attn_dropout(p, j);  // batch word = row of the (CFG-doubled) batch
         F5_TRY(timed(p, F5_SITE_ATTN, st, [&] { return launch_attention(P, plan_attn_kind(p, N), nb, N, c.heads, p->qkv, 3 * inner, mask, p->cT, inner, st, 0, md.qs, &drop); }));
     }
+    F5_TRY(probe(j, "ctx", P, p->cT, inner));
     if (float* d = tap_dst(p, tn + ".attn"))  // Attention module output before gating (extra GEMM, debug only)
         F5_TRY(run_gemm(p, gp_linear_f32(p->cT, b.w_o, b.b_o, rows, D, inner, d), GEMM_DENSE, EPI_STORE_F32, st));
     g = gp_out_proj(p, b.w_o, b.b_o, md.rows_g, N, k.ml + 2 * D, mod_bstride, mask, md.defer ? p->yA : p->yT, true);
@@ -260,7 +294,8 @@ int DitEval::attention(const DitBlock& k) const {
     if (md.rmw) g = gp_resid_stream(g, p->xres16, true);
     // partial row sums of the updated stream (site 2l); pivot = the row's previous mean (none yet at site 0: the tables are this evaluation's)
     if (md.lnf) lnf_producer(g, 2 * l, k.pf2f, md.ink_ff1);  // (prefetch: the weights of FF1 and FF2)
-    return timed(p, F5_SITE_OUT, st, [&] { return run_gemm(p, g, GEMM_DENSE, md.rmw ? EPI_RESID : EPI_GATE_T, st); });
+    F5_TRY(timed(p, F5_SITE_OUT, st, [&] { return run_gemm(p, g, GEMM_DENSE, md.rmw ? EPI_RESID : EPI_GATE_T, st); }));
+    return md.rmw ? probe(j, "x_attn", F5_PREC_FP16, p->xres16, D) : 0;
 }
 
 // feed-forward half of a block: x += y; n2 = LN(x) * (1 + scale_mlp) + shift_mlp; y = gate_mlp * ff(n2)  (modules.py:639)
@@ -274,10 +309,13 @@ int DitEval::feed_forward(const DitBlock& k) const {
         F5_TRY(lnf_consumer(g, 2 * l, md.ink_ff1, F5_SITE_LN2, 2 | (l << 4), md.wpf ? &k.pf2f : nullptr));
     }
     F5_TRY(timed(p, F5_SITE_FF1, st, [&] { return run_gemm(p, g, GEMM_DENSE, EPI_STORE_T, st); }));
+    if (md.lnf) F5_TRY(probe(k.j, "stats2", F5_PREC_FP32, lnf_table(2 * l), 2));
+    F5_TRY(probe(k.j, "ff1", P, p->ffh, ff));
     g = gp_ff2(p, b.w_ff2, b.b_ff2, md.rows_g, N, k.ml + 5 * D, mod_bstride, p->yT, true);
     if (md.rmw) g = gp_resid_stream(g, p->xres16, true);
     if (k.lnf_next) lnf_producer(g, 2 * l + 1, k.pf1f, md.ink_qkv);  // site 2l + 1 (prefetch: the next block's q|k|v weights and its out-projection)
-    return timed(p, F5_SITE_FF2, st, [&] { return run_gemm(p, g, GEMM_DENSE, md.rmw ? EPI_RESID : EPI_GATE_T, st); });
+    F5_TRY(timed(p, F5_SITE_FF2, st, [&] { return run_gemm(p, g, GEMM_DENSE, md.rmw ? EPI_RESID : EPI_GATE_T, st); }));
+    return md.rmw ? probe(k.j, "x_ff", F5_PREC_FP16, p->xres16, D) : 0;
 }
 
 // one network evaluation over `nb` batch rows (rows = nb*N) whose noisy mel rows are x[xrows, mel] (xrows divides rows);
@@ -290,6 +328,8 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
     const bool r16 = plan_res_f16(p);
     F5_TRY(input_embed(p, x, xrows, rows, N, r16 ? p->xres16 : (void*)p->xres, r16, true, st));
     F5_TRY(dit_eval_modes(p, nb, N, mod_bstride, &e.md));
+    F5_TRY(e.probe(-1, "adaln", F5_PREC_FP32, modp, e.m->modrow, 0, 1));
+    F5_TRY(e.probe(-1, "base", F5_PREC_FP32, p->base, D));  // (the hoisted half of the input embedding: what the x-projection adds)
     // Block subset (f5_plan_set_blocks): position j of the walk runs model block l = sub[j] -- its weights, its AdaLN rows, its prefetch sets --
     // and everything that speaks of the first, the previous or the last block (the position-conv branch, the long-skip copy, tap names, guard
     // tags, the dropout call word) keys on j: the evaluation of the model whose blocks are the subset renumbered.  No subset: l = j.
@@ -312,5 +352,7 @@ int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float
         F5_TRY(launch_layernorm(P, p->xres, D, rows, D, mf, mf + D, mod_bstride, N, 1, p->hT, D, st));
     }
     F5_TRY(tap_t(p, "final_norm", p->hT, D, rows, D, st));
-    return run_gemm(p, gp_proj_out(p, rows, p->vout), GEMM_DENSE, EPI_STORE_F32, st);
+    F5_TRY(e.probe(-1, "final_norm", P, p->hT, D));
+    F5_TRY(run_gemm(p, gp_proj_out(p, rows, p->vout), GEMM_DENSE, EPI_STORE_F32, st));
+    return e.probe(-1, "vout", F5_PREC_FP32, p->vout, c.mel_dim, MELP);
 }

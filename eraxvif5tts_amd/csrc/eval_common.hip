@@ -42,12 +42,27 @@ GemmParams gp_zero() {
     memset(&g, 0, sizeof(g));
     return g;
 }
+static struct { GemmLaunchRecord last{-1, 0, 0, 0, 0}; int launches = 0; } g_site_gemm[5];
 int run_gemm(f5_plan_s* p, const GemmParams& g, int mode, int epi, hipStream_t st) {
     const int prec = p->m->cfg.precision;
     // 1 = tuned kernel wherever it can run; -1 (auto) = tuned kernel from 512 token rows on (narrower tiles keep the CUs busy at small M)
     int kind = 0;
     if (p->gemm_kernel != 0 && gemm_fast_supported(g, prec, mode, epi) && (p->gemm_kernel == 1 || g.M >= 512)) kind = 1;
-    return launch_gemm(g, prec, mode, epi, kind, st);
+    const int rc = launch_gemm(g, prec, mode, epi, kind, st);
+    if (g.site >= 1 && g.site <= 4) {  // host-side record per block call site (f5_debug_site_gemm)
+        g_site_gemm[g.site].last = g_last_gemm;
+        ++g_site_gemm[g.site].launches;
+    }
+    return rc;
+}
+// diagnostic: the last launch of one of the DiT block's four call sites (GemmParams::site: 1 QKV, 2 out-projection, 3 FF1, 4 FF2) and the number of
+// launches the site has made in this process (a QKV projection with v apart makes two per block)
+extern "C" int f5_debug_site_gemm(int site, int* family, int* bm, int* bn, int* schedule, int* flags, int* launches) {
+    if (site < 1 || site > 4 || !family || !bm || !bn || !schedule || !flags || !launches) return f5_fail(F5_EINVAL, "f5_debug_site_gemm: site 1 .. 4, no null argument");
+    const GemmLaunchRecord& r = g_site_gemm[site].last;
+    *family = r.family; *bm = r.bm; *bn = r.bn; *schedule = r.schedule; *flags = r.flags;
+    *launches = g_site_gemm[site].launches;
+    return 0;
 }
 // ---- call-site builders: the GemmParams of the linears every backbone shares.  `site`: the launch is one of the DiT block's four call sites of the
 // per-site tile-walk knobs (GemmParams::site = 1 .. 4); the other backbones' linears carry none.
@@ -145,6 +160,27 @@ int tap_t(f5_plan_s* p, const std::string& name, const void* src, int ld, int ro
     float* d = tap_dst(p, name);
     if (!d) return 0;
     return launch_convert_back(p->m->cfg.precision, src, ld, rows, cols, d, cols, st);
+}
+
+int probe_parse(const std::string& name, int depth, int* j, std::string* stage) {
+    *j = -1;
+    *stage = name;
+    if (name == "adaln" || name == "base" || name == "input_embed" || name == "final_norm" || name == "vout") return 0;
+    static const char* const kBlockStages[] = {"x_in", "n1", "stats1", "stats2", "qkv", "ctx", "x_attn", "ff1", "x_ff"};
+    const size_t dot = name.find('.');
+    if (name.compare(0, 3, "blk") == 0 && dot != std::string::npos && dot > 3 && dot <= 3 + 4 &&
+        name.find_first_not_of("0123456789", 3) == dot) {
+        *j = atoi(name.c_str() + 3);
+        *stage = name.substr(dot + 1);
+        for (const char* s : kBlockStages)
+            if (*stage == s && *j < depth && !(*stage == "x_in" && *j != 0) && !(*stage == "stats1" && *j == 0)) return 0;
+    }
+    return f5_fail(F5_EINVAL, "unknown stage probe '%s'", name.c_str());
+}
+int probe_copy(f5_plan_s* p, const std::string& name, int precision, const void* src, int ld, int rows, int cols, hipStream_t st) {
+    auto it = p->probes.find(name);
+    if (it == p->probes.end()) return 0;
+    return launch_convert_back(precision, src, ld, rows, cols, it->second, cols, st);
 }
 
 // time values (device, n of them) -> modulation rows [n][modrow] (AdaLN of every block + final), t_emb in p->temb
@@ -245,6 +281,7 @@ extern "C" int f5_dit_forward(f5_plan_t p, int B, int N, const float* x, const f
     F5_TRY(finish_if_pending(p));
     hipStream_t st = (hipStream_t)stream;
     f5_model_s* m = p->m;
+    F5_TRY(dit_probe_check(p, B, N, m->modrow, 1));
     p->mod_tv.clear();  // p->mod is overwritten with per-sample times
     F5_TRY(compute_modulation(p, time, B, st));
     F5_TRY(compute_base(p, cond, nullptr, text_embed, B, N, drop_audio_cond, 0, st));

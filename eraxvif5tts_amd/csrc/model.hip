@@ -606,6 +606,9 @@ extern "C" int f5_plan_set_option(f5_plan_t p, const char* key, int value) {
         p->res_f16 = v;
     } else if (strcmp(key, "ragged_graph") == 0) {
         p->ragged_graph = value != 0;  // (host-side only: which path the next f5_sample_ragged takes)
+    } else if (strcmp(key, "probe_eval") == 0) {
+        if (value < 0) return f5_fail(F5_EINVAL, "probe_eval must not be negative");
+        p->probe_eval = value;  // (host-side only: probes keep the sample loops eager)
     } else if (strcmp(key, "residual_guard") == 0) {
         p->sat_check = value < 0 ? 0 : (value > 2 ? 2 : value);  // 0 off, 1 checked inside f5_sample, 2 deferred to f5_sample_finish (host-side only)
     } else {
@@ -697,6 +700,8 @@ extern "C" int f5_plan_get_option(f5_plan_t p, const char* key, int* value) {
         *value = p->sat_check;
     else if (strcmp(key, "ragged_graph") == 0)
         *value = p->ragged_graph;
+    else if (strcmp(key, "probe_eval") == 0)
+        *value = p->probe_eval;
     else if (strcmp(key, "ln_fold_active") == 0)  // the staged time grid has a LayerNorm-fold table and the knob is on (what the next sample() runs)
         *value = (p->fold && g_ln_fold) ? 1 : 0;
     else if (strcmp(key, "gemm_w4") == 0)  // the one-wave-per-SIMD kernel's knob (which launches take it: gemm_w4_ok, by shape)
@@ -768,3 +773,17 @@ extern "C" int f5_plan_set_tap(f5_plan_t p, const char* stage, float* dst) {
     return 0;
 }
 
+// stage probes (f5hip.h): the name is checked here, whether the running mode holds its buffer by the call that would write it (dit_probe_check)
+extern "C" int f5_plan_set_probe(f5_plan_t p, const char* stage, float* dst) {
+    if (!p) return f5_fail(F5_EINVAL, "null plan");
+    if (!stage || !dst) {
+        p->probes.clear();
+        return 0;
+    }
+    if (p->m->cfg.backbone != F5_BACKBONE_DIT) return f5_fail(F5_ENOTSUP, "f5_plan_set_probe: DiT backbone only");
+    int j;
+    std::string s;
+    F5_TRY(probe_parse(stage, p->m->cfg.depth, &j, &s));
+    p->probes[stage] = dst;
+    return 0;
+}

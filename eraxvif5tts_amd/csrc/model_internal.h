@@ -214,6 +214,10 @@ struct f5_plan_s {
     // plan then behaves as a plan of the model whose blocks are these renumbered 0 .. size - 1 (plan_depth); the LayerNorm fold is off under one.
     std::vector<int> sub;
     std::map<std::string, float*> taps;
+    // Stage probes (f5_plan_set_probe): copies of buffers the evaluation holds anyway, written by evaluation `probe_eval` of a sample loop.  No
+    // mode decision reads them (plan_res_f16, plan_attn_prescale, dit_eval_modes); the sample loops run eagerly while any is set.
+    std::map<std::string, float*> probes;
+    int probe_eval = 0;  // plan option "probe_eval"
     std::vector<float> mod_tv;  // evaluation times the AdaLN rows in `mod` were computed for (empty = stale); see f5_sample
     hipStream_t mod_stream = nullptr;  // ... and the stream they were computed on (a call on another stream recomputes them)
     std::vector<GraphEntry> graphs;
@@ -294,6 +298,12 @@ int input_embed(f5_plan_s* p, const float* x, int xrows, int rows, int N, void* 
 float* tap_dst(f5_plan_s* p, const std::string& name);
 int tap_f32(f5_plan_s* p, const std::string& name, const float* src, int ld, int rows, int cols, hipStream_t st);
 int tap_t(f5_plan_s* p, const std::string& name, const void* src, int ld, int rows, int cols, hipStream_t st);
+// Stage probes.  probe_parse: "adaln" | "base" | "input_embed" | "final_norm" | "vout" (*j = -1) or "blk<J>.<stage>" with J < depth -> F5_EINVAL for anything
+// else.  plan_probing: the running evaluation (p->drop_eval) is the one that writes them.  probe_copy: src [rows, cols] of `precision` elements -> the
+// probe's f32 destination, when `name` is set.
+int probe_parse(const std::string& name, int depth, int* j, std::string* stage);
+inline bool plan_probing(const f5_plan_s* p) { return !p->probes.empty() && p->drop_eval == p->probe_eval; }
+int probe_copy(f5_plan_s* p, const std::string& name, int precision, const void* src, int ld, int rows, int cols, hipStream_t st);
 int compute_modulation(f5_plan_s* p, const float* tvals_dev, int n, hipStream_t st);
 int compute_text_embed(f5_plan_s* p, const int32_t* text, int nt, int B, int N, int drop_text, float* out, hipStream_t st);
 // cmask: u8 [nb, N] condition mask that replaces the lens prefix (f5_sample_masked), or null
@@ -318,6 +328,9 @@ struct DitEvalModes {
 };
 // F5_ESTATE where the plan cannot run the fold table it holds (pre-scaled q rows)
 int dit_eval_modes(const f5_plan_s* p, int nb, int N, int mod_bstride, DitEvalModes* out);
+// Every probe of the plan names a buffer that evaluation `eval` (of `nev`; per-sample time rows: mod_bstride != 0, eval 0 of 1) of nb x N rows holds
+// in its modes; F5_ESTATE otherwise, F5_EINVAL for "probe_eval" past the loop.  Called before a call stages its inputs.  No probes: 0.
+int dit_probe_check(f5_plan_s* p, int nb, int N, int mod_bstride, int nev);
 int dit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float* modp, int mod_bstride, const uint8_t* mask, hipStream_t st);
 int unett_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float* temb, int temb_bstride, const uint8_t* mask, hipStream_t st);
 int mmdit_eval(f5_plan_s* p, const float* x, int xrows, int nb, int N, const float* modp, int mod_bstride, const uint8_t* mask, hipStream_t st);

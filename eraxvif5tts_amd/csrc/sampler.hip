@@ -132,7 +132,7 @@ template <typename Pred> static void drop_graphs_where(f5_plan_s* p, Pred stale)
 
 // the ODE loop of one sample() on the staged inputs: replay of the hipGraph captured for this exact problem, or eager launches
 static int run_sample_loop(f5_plan_s* p, const SampleArgs& a, int use_graph, hipStream_t st) {
-    if (use_graph && p->taps.empty() && !p->timing) {
+    if (use_graph && p->taps.empty() && p->probes.empty() && !p->timing) {  // (taps, probes, timing: eager, and no cached capture is touched)
         // a tuning knob changed since the capture: the graph baked the old kernel choice
         drop_graphs_where(p, [](const GraphEntry& g) { return g.key.epoch != g_tuning_epoch; });
         const GraphKey key{a, g_tuning_epoch, p->fold && g_ln_fold ? p->fold->id : 0, p->rg ? p->rg->n : std::vector<int>()};
@@ -301,6 +301,7 @@ static int sample_impl(f5_plan_t p, int B, int N, const float* cond, const int32
     const int nt_eff = (mmdit || nt < N) ? nt : N;  // tokens beyond the frame count are curtailed (dit.py:51; MMDiT keeps them all, mmdit.py:40)
 
     F5_TRY(stage_time_grid(p, tgrid_host, steps, ode_method, st));
+    F5_TRY(dit_probe_check(p, cfg_strength >= 1e-5f ? 2 * B : B, N, 0, ode_method_of(ode_method)->evals * steps));  // (needs the grid's fold table)
     F5_HIP(hipMemcpyAsync(p->cond_in, cond, state * sizeof(float), hipMemcpyDeviceToDevice, st));
     F5_HIP(hipMemcpyAsync(p->traj, y0, state * sizeof(float), hipMemcpyDeviceToDevice, st));
     F5_HIP(hipMemcpy2DAsync(p->text_in, (size_t)nt_eff * 4, text, (size_t)nt * 4, (size_t)nt_eff * 4, B, hipMemcpyDeviceToDevice, st));
@@ -397,6 +398,7 @@ static int sample_ragged_impl(f5_plan_t p, int B, const int32_t* frames_host, co
     hipStream_t st = (hipStream_t)stream;
     const int mel = m->cfg.mel_dim, D = m->cfg.dim, td = m->cfg.text_dim, T = rg.T;
     F5_TRY(stage_time_grid(p, tgrid_host, steps, ode_method, st));
+    F5_TRY(dit_probe_check(p, cfg_on ? 2 : 1, T, 0, ode_method_of(ode_method)->evals * steps));  // (needs the grid's fold table)
     // stage the inputs at their row offsets; everything between the utterances is zero
     F5_HIP(hipMemsetAsync(p->cond_in, 0, (size_t)T * mel * sizeof(float), st));
     F5_HIP(hipMemsetAsync(p->traj, 0, (size_t)T * mel * sizeof(float), st));

@@ -550,3 +550,7 @@ class DiT(nn.Module):
 
     def set_tap(self, plan, name, dst):
         _lib.check(_lib.load().f5_plan_set_tap(plan, None if name is None else name.encode(), _lib.ptr(dst)))
+
+    def set_probe(self, plan, name, dst):
+        """Stage probe (include/f5hip.h: f5_plan_set_probe): unlike a tap it leaves the evaluation's modes as they are.  name None clears all."""
+        _lib.check(_lib.load().f5_plan_set_probe(plan, None if name is None else name.encode(), _lib.ptr(dst)))

@@ -298,6 +298,27 @@ F5_API int f5_duration_loss(int B, int nt, const float* logw, const float* durat
  * "adaln" (the AdaLN modulation rows of every block and the final norm, [times, the model's modulation width]; DiT and MMDiT),
  * "input_embed", "blk<i>.n1", "blk<i>.attn", "blk<i>.out", "final_norm".  Pass dst = NULL to clear all taps. */
 F5_API int f5_plan_set_tap(f5_plan_t p, const char* stage, float* dst);
+/* Stage probes of the DiT backbone: as a tap, copy a named internal stage (f32, row-major) into `dst` (dev f32) -- but of the evaluation as it
+ * runs WITHOUT them.  A tap switches the fp16 residual stream, the in-place residual epilogues, the LayerNorm fold and pre-scaled q off; a probe
+ * enters no mode decision: it is a copy of a buffer the evaluation holds anyway, of its token rows only (never the padding rows of the block
+ * GEMMs).  One evaluation writes them: f5_dit_forward's, or evaluation number "probe_eval" (f5_plan_set_option; default 0) of a sample loop.
+ * While probes are set f5_sample* runs the loop eagerly and neither launches nor captures a graph; f5_sample_ragged* accepts probes.  Names
+ * (J = position of the block in the walk, D = dim):
+ *   "adaln"            this evaluation's AdaLN row                                                        [modulation width]
+ *   "base"             the hoisted half of the input embedding (fp32; the x-projection adds its fp16 copy)   [rows, D]
+ *   "input_embed"      the stream before block 0's first LayerNorm pass                                   [rows, D]
+ *   "blk0.x_in"        the stream after that pass has added the position-conv branch (in-place stream)    [rows, D]
+ *   "blkJ.n1"          the first LayerNorm pass's output (J = 0; every J of an unfolded evaluation)       [rows, D]
+ *   "blkJ.stats1" J>0, "blkJ.stats2"   (mean, rstd) as the folded QKV / FF1 launch of block J consumed them    [rows, 2]
+ *   "blkJ.qkv"         q|k|v after RoPE, q as the attention kernel reads it                               [rows, 3 inner]
+ *   "blkJ.ctx"         attention output                                                                   [rows, inner]
+ *   "blkJ.x_attn", "blkJ.x_ff"   the in-place stream after the out-projection / after FF2                 [rows, D]
+ *   "blkJ.ff1"         FF1 output                                                                         [rows, ff]
+ *   "final_norm", "vout"                                                                                  [rows, D], [rows, mel]
+ * An unknown name is F5_EINVAL here (another backbone: F5_ENOTSUP).  A name whose buffer the running mode does not hold ("blk1.n1" under the
+ * fold, "blk0.x_attn" on an fp32 stream) is F5_ESTATE from the call that would write it, before it stages an input or launches an evaluation.
+ * stage = NULL or dst = NULL clears all probes.  Captured graphs are left alone. */
+F5_API int f5_plan_set_probe(f5_plan_t p, const char* stage, float* dst);
 /* in-situ timing of the dominant kernel: between begin and end, every fused-QKV GEMM launch of (eager) f5_sample /
  * f5_dit_forward calls on this plan is bracketed by a HIP event pair on the caller's stream; end synchronises the stream and
  * returns the mean device time per launch.  Used by bench.py for roofline.achieved. */
@@ -327,7 +348,8 @@ F5_API int f5_plan_timing_site(f5_plan_t p, int site, float* avg_ms, int* launch
  * Key "attn_prescale" (default -1 = the process-wide knob, which is on): 1 = the softmax scale times log2(e) is folded into the weights that
  * project q and the attention kernels apply none (bf16 DiT on the tuned attention kernels, no qk_norm, no stage taps, LayerNorm-fold
  * evaluations; everything else keeps q as projected), 0 = q as projected everywhere.  An F5_PREC_FP16 plan never pre-scales q, whatever the key says:
- * the reference-free attention build needs bf16's exponent range. */
+ * the reference-free attention build needs bf16's exponent range.
+ * Key "probe_eval" (default 0, >= 0): the evaluation of a sample loop that writes the stage probes (f5_plan_set_probe); host-side only. */
 F5_API int f5_plan_set_option(f5_plan_t p, const char* key, int value);
 /* reads an option back; besides the keys above: "residual_fallbacks" = f5_sample calls of this plan that were repeated with fp32 residual
  * storage because the range guard fired ("residual_f16" then reads 0); "attn_prescale_active" = 1 when this plan wants pre-scaled q and may run it (0 e.g.
@@ -539,6 +561,9 @@ F5_API int f5_debug_gemm_clock(void* dev_buf);
  * feature tile (conv31: tokens per workgroup x 64); schedule 0 = plain ring, 1 = staggered wave groups, 2 = persistent grid; flags: 1 = fp16
  * elements, 4 = fp32 elements (neither: bf16), 2 = LayerNorm-fold build, 8 = grouped conv as an implicit GEMM. */
 F5_API int f5_debug_last_gemm(int* family, int* bm, int* bn, int* schedule, int* flags);
+/* the same record for the last launch of one of the DiT block's four call sites -- site 1 the QKV projection, 2 the out-projection, 3 FF1, 4 FF2 --
+ * and the number of launches that site has made in this process so far (a QKV projection that launches v apart makes two per block). */
+F5_API int f5_debug_site_gemm(int site, int* family, int* bm, int* bn, int* schedule, int* flags, int* launches);
 /* Which launch forms one DiT evaluation of nb x N token rows takes in the plan's present state (its options, stage taps, block subset, the fold
  * table and evaluation index its last call left, the tuning knobs in force); per_batch_rows != 0: per-sample times, as f5_dit_forward evaluates.
  * The function the evaluation itself decides with, called alone: no launch, no side effect.  out[F5_EVAL_MODES_N] = rows, rows_g (rows the block

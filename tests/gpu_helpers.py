@@ -1188,3 +1188,429 @@ def replay_swap(a, b, field):
 def replay_text(d):
     """The text tensor [B, nt] of an input set: text_ids with the columns from text_len on set to the pad -1."""
     return torch.where(torch.arange(d["text_ids"].shape[1])[None, :] < d["text_len"][:, None], d["text_ids"], torch.full_like(d["text_ids"], -1))
+
+
+# ----------------------------------------------------------------------------- the production-mode DiT evaluation, stage by stage (stage probes,
+# include/f5hip.h: f5_plan_set_probe): per stage the fp64 restatement of THAT stage from the probe of the stage before it, the CPU restatement
+# with the kernel's roundings (stage_emulate) and its planted defects, and the per-row bound (tests/test_production_stage_bound_host.py,
+# tests/test_gpu_production_stages.py)
+STAGE_MARGIN = 3.0  # a row passes when its error is within STAGE_MARGIN x the restatement's worst row error of the same stage and case
+STAGE_EPS = 1e-6    # LayerNorm eps (modules.py:308,624)
+STAGE_DEFECTS = ("none", "stats_quarter_row", "stats_of_previous_site", "v_c1_c2_shifted_by_inner", "fold_rows_of_another_time", "q_not_scaled",
+                 "q_scaled_twice", "gate_mlp_for_gate_msa", "blk0_unscaled_weight_copy", "final_pair_swapped", "rope_position_is_row_index")
+
+
+def site_gemm(site):
+    """include/f5hip.h: f5_debug_site_gemm -- ((family, bm, bn, schedule, flags) of the last launch of block call site 1 QKV / 2 out-projection /
+    3 FF1 / 4 FF2, launches of that site in this process so far)."""
+    v = [C.c_int(0) for _ in range(6)]
+    _lib.check(_lib.load().f5_debug_site_gemm(site, *[C.byref(t) for t in v]), "f5_debug_site_gemm")
+    return tuple(t.value for t in v[:5]), v[5].value
+
+
+def stage_layout(nb, N, durations=None, frames=None):
+    """The rows of one evaluation: nb batch items of N rows.  durations [nb] (a key mask: item b's first durations[b] rows are keys and valid
+    queries) or frames (a ragged call: N = T, nb = 2 halves, utterance u at rows [off[u], off[u] + frames[u]) of each half, the rest gaps) or
+    neither.  -> dict: rows, N, seg [rows] (attention sequence of the row, -1 = gap), seg_rows {id: (first row, rows)}, key [rows] bool (the row
+    is a key of its sequence and a valid query), pos [rows] (RoPE position)."""
+    rows = nb * N
+    seg = torch.full((rows,), -1, dtype=torch.long)
+    key = torch.zeros(rows, dtype=torch.bool)
+    pos = torch.zeros(rows, dtype=torch.long)
+    seg_rows = {}
+    if frames is None:
+        for b in range(nb):
+            seg_rows[b] = (b * N, N)
+            seg[b * N:(b + 1) * N] = b
+            key[b * N:b * N + (N if durations is None else int(durations[b]))] = True
+            pos[b * N:(b + 1) * N] = torch.arange(N)
+    else:
+        off, T = [], 0
+        for n in frames:
+            off.append(T)
+            T = -(-(T + n + 16) // 16) * 16
+        assert T == N and nb == 2, (T, N, nb)
+        for br in range(2):
+            for u, n in enumerate(frames):
+                r0 = br * T + off[u]
+                seg_rows[br * len(frames) + u] = (r0, n)
+                seg[r0:r0 + n] = br * len(frames) + u
+                key[r0:r0 + n] = True
+                pos[r0:r0 + n] = torch.arange(n)
+    return dict(rows=rows, N=N, seg=seg, seg_rows=seg_rows, key=key, pos=pos)
+
+
+def stage_sample_rows(lay, seed=0, rows_real=None):
+    """The rows a stage is compared on: the first and last row of every 128-row tile (which holds those of every 256-row tile), the last real row
+    (rows_real: the evaluation's token rows when the buffers hold more), the rows on both sides of every boundary between attention sequences,
+    and 64 seeded rows.  -> (valid rows: keys / queries of their sequence, padded rows: inside a sequence, behind its key mask), both sorted."""
+    rows = rows_real or lay["rows"]
+    pick = set(range(0, rows, 128)) | set(min(r + 127, rows - 1) for r in range(0, rows, 128)) | {rows - 1}
+    for r0, n in lay["seg_rows"].values():
+        pick |= {r0, r0 + n - 1, max(r0 - 1, 0), min(r0 + n, rows - 1)}
+        nk = int(lay["key"][r0:r0 + n].sum())
+        pick |= {r0 + nk - 1, min(r0 + nk, rows - 1)}
+    g = torch.Generator().manual_seed(1000 + seed)
+    pick |= set(torch.randint(0, rows, (64,), generator=g).tolist())
+    idx = torch.tensor(sorted(pick))
+    return idx[lay["key"][idx]], idx[(~lay["key"][idx]) & (lay["seg"][idx] >= 0)]
+
+
+def stage_weights(W, depth, mel=100):
+    """The fp32 weights the stages use, from a DiT state dict: per block qkv_w [3 inner, D] (to_q | to_k | to_v), qkv_b, o_w, o_b, f1_w, f1_b,
+    f2_w, f2_b; out_w, out_b; x_w (the noisy-mel columns of the input projection); conv (w0, b0, w1, b1)."""
+    f = lambda k: W[k].detach().float().cpu()
+    blocks = []
+    for i in range(depth):
+        p = f"transformer_blocks.{i}."
+        blocks.append(dict(qkv_w=torch.cat([f(p + f"attn.{n}.weight") for n in ("to_q", "to_k", "to_v")]),
+                           qkv_b=torch.cat([f(p + f"attn.{n}.bias") for n in ("to_q", "to_k", "to_v")]),
+                           o_w=f(p + "attn.to_out.0.weight"), o_b=f(p + "attn.to_out.0.bias"), f1_w=f(p + "ff.ff.0.0.weight"), f1_b=f(p + "ff.ff.0.0.bias"),
+                           f2_w=f(p + "ff.ff.2.weight"), f2_b=f(p + "ff.ff.2.bias")))
+    return dict(blocks=blocks, out_w=f("proj_out.weight"), out_b=f("proj_out.bias"), x_w=f("input_embed.proj.weight")[:, :mel],
+                conv=tuple(f(f"input_embed.conv_pos_embed.conv1d.{i}.{k}") for i in (0, 2) for k in ("weight", "bias")))
+
+
+def stage_ada(ada, l, D, depth):
+    """The AdaLN row's slots of block l: (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp) (modules.py:312); l = depth: the final
+    pair (scale, shift) (modules.py:333)."""
+    a = ada.reshape(-1)
+    n = 6 if l < depth else 2
+    return tuple(a[l * 6 * D + i * D:l * 6 * D + (i + 1) * D] for i in range(n))
+
+
+def _ln64(x):
+    x = x.double()
+    d = x - x.mean(dim=-1, keepdim=True)
+    return d * torch.rsqrt((d * d).mean(dim=-1, keepdim=True) + STAGE_EPS)
+
+
+def _rope_table(pos, f64):
+    """(cos, sin) [len(pos), 32, 2] of the positions: angle = pos * 10000^(-2j / 64); fp32 as the plan's table, or fp64"""
+    dt = torch.float64 if f64 else torch.float32
+    inv = 1.0 / (10000.0 ** (torch.arange(0, 64, 2, dtype=dt) / 64.0))
+    ang = pos.to(dt)[:, None] * inv[None, :]
+    return torch.stack([ang.cos(), ang.sin()], dim=-1)
+
+
+def _rope_apply(lin, cs, inner, rope_heads):
+    out = lin.clone()
+    cos, sin = cs[..., 0], cs[..., 1]
+    for part in range(2):
+        for h in range(rope_heads):
+            c0 = part * inner + h * 64
+            v = lin[:, c0:c0 + 64].reshape(-1, 32, 2)
+            out[:, c0:c0 + 64] = torch.stack([v[..., 0] * cos - v[..., 1] * sin, v[..., 1] * cos + v[..., 0] * sin], dim=-1).reshape(-1, 64)
+    return out
+
+
+def _fp16_clamp(t):
+    return t.clamp(min=-65504.0, max=65504.0)
+
+
+def stage_ref(stage, **kw):
+    """fp64 restatement of ONE stage from the probe of the stage before it (kw: what stage_emulate takes; the model's own weights, in fp64)."""
+    d = lambda t: t.double()
+    if stage in ("n1", "final_norm"):
+        return _ln64(kw["x"]) * (1.0 + d(kw["scale"])) + d(kw["shift"])
+    if stage == "stats":
+        x = d(kw["x"])
+        dd = x - x.mean(dim=-1, keepdim=True)
+        return torch.stack([x.mean(dim=-1), torch.rsqrt((dd * dd).mean(dim=-1) + STAGE_EPS)], dim=-1)
+    if stage in ("qkv", "qkv_folded"):
+        n = d(kw["n1"]) if stage == "qkv" else _ln64(kw["x"]) * (1.0 + d(kw["scale"])) + d(kw["shift"])
+        lin = n @ d(kw["w"]).t() + d(kw["b"])
+        inner = lin.shape[1] // 3
+        ref, _ = rope_ref(lin, lin.abs(), _rope_table(kw["pos"], True), len(kw["pos"]), kw["rope_heads"])  # (row i takes table row i)
+        if kw["qs"]:
+            ref[:, :inner] *= QSCALE
+        return ref
+    if stage == "ff1":
+        n = _ln64(kw["x"]) * (1.0 + d(kw["scale"])) + d(kw["shift"])
+        return F.gelu(n @ d(kw["w"]).t() + d(kw["b"]), approximate="tanh")
+    if stage == "resid":  # clamp_fp16(x + gate (a W^T + b))
+        return _fp16_clamp(d(kw["x"]) + d(kw["gate"]) * (d(kw["a"]) @ d(kw["w"]).t() + d(kw["b"])))
+    if stage == "vout":
+        return d(kw["h"]) @ d(kw["w"]).t() + d(kw["b"])
+    if stage == "ctx":  # attn_ref_terms' softmax (base 2 under qs) for the sampled queries alone: q [S, H, 64], k / v [keys, H, 64] of their sequence
+        q, k, v = d(kw["q"]).transpose(0, 1), d(kw["k"]).transpose(0, 1), d(kw["v"]).transpose(0, 1)
+        s = q @ k.transpose(-1, -2) * (LN2 if kw["qs"] else 0.125)
+        return (torch.softmax(s, dim=-1) @ v).transpose(0, 1).reshape(q.shape[1], -1)
+    if stage == "input_embed":
+        return _fp16_clamp(d(kw["x"]) @ d(kw["w"]).t() + d(kw["base"]))
+    if stage == "x_in":  # ie [B, L, D]: the stream plus mish(conv(mish(conv(.)))) of it, every utterance by itself
+        w0, b0, w1, b1 = kw["conv"]
+        ie = d(kw["ie"])
+        return _fp16_clamp(ie + F.mish(conv31_ref(F.mish(conv31_ref(ie, w0, b0)), w1, b1)))
+    raise ValueError(stage)
+
+
+def _stage_stats_f32(x, pivot, quarter=False):
+    """(mean, rstd) as the residual epilogues and lnf_row_stats take them: fp32 sums of (h - pivot) and (h - pivot)^2 per 64-feature tile, added
+    tile by tile; mean = pivot + s1 / D, var = s2 / D - (s1 / D)^2.  quarter: the defect -- the first quarter of the row alone."""
+    x = x.float()
+    D = x.shape[1]
+    pv = torch.zeros(x.shape[0]) if pivot is None else pivot.float()
+    dd = x - pv[:, None]
+    if quarter:
+        dd, D = dd[:, :D // 4], D // 4
+    s1, s2 = torch.zeros(x.shape[0]), torch.zeros(x.shape[0])
+    for c in range(0, D, 64):
+        s1 = s1 + dd[:, c:c + 64].sum(dim=1)
+        s2 = s2 + (dd[:, c:c + 64] * dd[:, c:c + 64]).sum(dim=1)
+    md = s1 / D
+    var = (s2 / D - md * md).clamp(min=0.0)
+    return pv + md, 1.0 / torch.sqrt(var + STAGE_EPS)
+
+
+def _stage_folded_f32(x, mean, rstd, w, b, scale, shift, q_rows, defect="none", v_rows=None):
+    """rstd (x . W'^T - mean c1) + c2 with W' = fp16(W (1 + scale) qs), c1 = rowsum W', c2 = (b + W . shift) qs (lnfold.hip); q_rows > 0: the
+    first q_rows rows carry QSCALE.  v_rows = (first, count): the v rows of a fused projection (the defect moves their c1 / c2)."""
+    qsv = torch.ones(w.shape[0])
+    if q_rows:
+        qsv[:q_rows] = {"q_not_scaled": 1.0, "q_scaled_twice": QSCALE * QSCALE}.get(defect, QSCALE)
+    qsv = qsv.float()
+    wt = (w.float() * (1.0 + scale.float())[None, :] * qsv[:, None]).half().float()
+    c1 = wt.sum(dim=1)
+    c2 = (b.float() + w.float() @ shift.float()) * qsv
+    if defect == "v_c1_c2_shifted_by_inner" and v_rows:
+        v0, n = v_rows
+        c1, c2 = c1.clone(), c2.clone()
+        c1[v0:v0 + n], c2[v0:v0 + n] = c1[v0 - n:v0].clone(), c2[v0 - n:v0].clone()
+    return rstd.float()[:, None] * (x.float() @ wt.t() - mean.float()[:, None] * c1[None, :]) + c2[None, :]
+
+
+def stage_emulate(precision, stage, defect="none", **kw):
+    """CPU restatement of ONE stage of the production-mode evaluation (csrc/dit_eval.hip) with the kernel's roundings, in float32: the fp16
+    stream, 16-bit operands of the mode `precision` with fp32 accumulation, W' = fp16(W (1 + scale)) with c1 and c2 under the fold, one rounding
+    to the stored type (the mode's; fp16 saturating for the stream; fp32 for the statistics and proj_out).  Stages and their inputs:
+        n1, final_norm  x, scale, shift                                       LayerNorm pass of the fp16 stream
+        stats           x, pivot [S] or None                                  (mean, rstd) [S, 2] of the stream rows
+        qkv             n1, w, b, pos, rope_heads, qs                         block 0's unfolded projection (qs: the q rows of w, b carry QSCALE)
+        qkv_folded      x, scale, shift, w, b, pos, rope_heads, qs [, xstat]  the folded projection from the stream itself
+        ff1             x, scale, shift, w, b [, xstat]                       folded FF1 + GELU(tanh)
+        resid           x, a, w, b, gate                                      x + gate (a W^T + b) into the stream
+        ctx             q [S, H, 64], k, v [keys, H, 64], qs                  softmax attention of the sampled queries over their sequence's keys
+        vout            h, w, b
+        input_embed     x, w, base;  x_in: ie [B, L, D], conv
+    `defect` (STAGE_DEFECTS) plants what tests/test_gpu_production_stages.py is there to catch, at the stage it belongs to; xstat: the stream
+    rows whose statistics a folded projection uses when they are not its own input's (the previous site's: a defect)."""
+    assert defect in STAGE_DEFECTS
+    rnd = lambda t: round_to(precision, t)
+    if stage in ("n1", "final_norm"):
+        x = kw["x"].float()
+        dd = x - x.mean(dim=-1, keepdim=True)
+        scale, shift = (kw["shift"], kw["scale"]) if (defect == "final_pair_swapped" and stage == "final_norm") else (kw["scale"], kw["shift"])
+        return rnd(dd * torch.rsqrt((dd * dd).mean(dim=-1, keepdim=True) + STAGE_EPS) * (1.0 + scale.float()) + shift.float())
+    if stage == "stats":
+        return torch.stack(_stage_stats_f32(kw["x"], kw.get("pivot"), quarter=defect == "stats_quarter_row"), dim=-1)
+    if stage in ("qkv", "qkv_folded"):
+        inner = kw["w"].shape[0] // 3
+        if stage == "qkv":
+            w, b = kw["w"].float().clone(), kw["b"].float().clone()
+            if kw["qs"]:
+                s = {"q_not_scaled": 1.0, "blk0_unscaled_weight_copy": 1.0, "q_scaled_twice": QSCALE * QSCALE}.get(defect, QSCALE)
+                w[:inner] *= torch.tensor(s, dtype=torch.float32)
+                b[:inner] *= torch.tensor(s, dtype=torch.float32)
+            lin = rnd(kw["n1"]) @ rnd(w).t() + b
+        else:
+            mean, rstd = _stage_stats_f32(kw.get("xstat", kw["x"]), None, quarter=defect == "stats_quarter_row")
+            lin = _stage_folded_f32(kw["x"], mean, rstd, kw["w"], kw["b"], kw["scale"], kw["shift"], inner if kw["qs"] else 0, defect, (2 * inner, inner))
+        return rnd(_rope_apply(lin, _rope_table(kw["pos"], False), inner, kw["rope_heads"]))
+    if stage == "ff1":
+        mean, rstd = _stage_stats_f32(kw.get("xstat", kw["x"]), None, quarter=defect == "stats_quarter_row")
+        return rnd(F.gelu(_stage_folded_f32(kw["x"], mean, rstd, kw["w"], kw["b"], kw["scale"], kw["shift"], 0), approximate="tanh"))
+    if stage == "resid":
+        t = (rnd(kw["a"]) @ rnd(kw["w"]).t() + kw["b"].float()) * kw["gate"].float()
+        return (kw["x"].float() + t).clamp(min=-65504.0, max=65504.0).half().float()
+    if stage == "vout":
+        return rnd(kw["h"]) @ rnd(kw["w"]).t() + kw["b"].float()
+    if stage == "ctx":  # fp32 scores, numerators exp2(s c - m) rounded once to the mode's type for the PV product, the row sum from the unrounded ones
+        q, k, v = [rnd(kw[n]).transpose(0, 1) for n in ("q", "k", "v")]
+        c = torch.tensor(1.0 if kw["qs"] else QSCALE, dtype=torch.float32)
+        s = q @ k.transpose(-1, -2)
+        m = (s * c).amax(dim=-1, keepdim=True)
+        num = torch.exp2(torch.addcmul(-m, s, c))
+        o = rnd(num) @ v / num.sum(dim=-1, keepdim=True)
+        return rnd(o.transpose(0, 1).reshape(q.shape[1], -1))
+    if stage == "input_embed":
+        return (rnd(kw["x"]) @ rnd(kw["w"]).t() + kw["base"].half().float()).clamp(min=-65504.0, max=65504.0).half().float()
+    if stage == "x_in":
+        w0, b0, w1, b1 = [t.float() for t in kw["conv"]]
+        ie = kw["ie"].float()
+        conv = lambda t, w, b: F.conv1d(t.transpose(1, 2), rnd(w), b, padding=15, groups=16).transpose(1, 2)
+        y = rnd(F.mish(conv(rnd(F.mish(conv(rnd(ie), w0, b0))), w1, b1)))
+        return (ie + y).clamp(min=-65504.0, max=65504.0).half().float()
+    raise ValueError(stage)
+
+
+def stage_row_errors(X, R, parts=1, stats=False):
+    """The row metric.  e[r] = max over the `parts` equal column groups of a row (q | k | v) of max_c |X - R| / max_c |R| within the group.
+    stats: X, R = (mean, rstd) [S, 2]: max(|mean error| in units of the row's standard deviation, relative rstd error)."""
+    X, R = X.double(), R.double()
+    if stats:
+        return torch.maximum((X[:, 0] - R[:, 0]).abs() * R[:, 1], (X[:, 1] - R[:, 1]).abs() / R[:, 1])
+    S = R.shape[0]
+    err = (X - R).abs().reshape(S, parts, -1).amax(dim=-1)
+    return (err / R.abs().reshape(S, parts, -1).amax(dim=-1).clamp(min=1e-300)).amax(dim=-1)
+
+
+def stage_row_bias(X, R, parts=1):
+    """The second row metric: |sum_c (X - R) sign(R)| / sum_c |R| per column group, the largest group.  A rounding error changes sign from column
+    to column and averages out over a row (1 / sqrt(columns) of the first metric); a wrong row factor -- a row's rstd, a gate -- or a wrong
+    row offset does not."""
+    X, R = X.double(), R.double()
+    S = R.shape[0]
+    num = ((X - R) * torch.sign(R)).reshape(S, parts, -1).sum(dim=-1).abs()
+    return (num / R.abs().reshape(S, parts, -1).sum(dim=-1).clamp(min=1e-300)).amax(dim=-1)
+
+
+def _take(t, idx):
+    return t[idx.to(t.device)].float().cpu()
+
+
+def stage_shares(probes, Wst, lay, idx, precision, qs, depth, rope_heads, heads, margin=None, only=None, say=print):
+    """Every probed stage of one evaluation against the fp64 restatement R of that stage, computed from the probe of the stage before it, on the
+    rows idx (valid rows: stage_sample_rows); the bound per stage is margin x the worst row error of the restatement E with the kernel's
+    roundings (stage_emulate) from the same inputs.  probes: name -> tensor [rows.., cols] (host or device; rows beyond the sample are read only
+    for the keys of attention).  Folded evaluations (stats probes present) and unfolded ones alike.
+    -> {stage: (worst row of the probe / bound, restatement's worst row error, probe's worst row error)}; prints one line per stage."""
+    margin = STAGE_MARGIN if margin is None else margin
+    D = Wst["blocks"][0]["o_w"].shape[0]
+    inner = Wst["blocks"][0]["o_w"].shape[1]
+    ada = probes["adaln"].float().cpu()
+    pos = lay["pos"][idx]
+    out = {}
+
+    def judge(name, X, R, E, **kw):
+        eE, eX = stage_row_errors(E, R, **kw), stage_row_errors(X, R, **kw)
+        bound = margin * float(eE.max())
+        assert torch.isfinite(X).all(), name
+        share = float(eX.max()) / bound if bound > 0 else (0.0 if float(eX.max()) == 0 else float("inf"))
+        line = (f"  {name}: restatement's worst row {float(eE.max()):.3e}, worst row {float(eX.max()):.3e} = {share:.3f} of the bound "
+                f"(row {int(idx[int(eX.argmax())])})")
+        if not kw.get("stats"):  # the signed row sum, held to the restatement's in the same way
+            bE, bX = stage_row_bias(E, R, kw.get("parts", 1)), stage_row_bias(X, R, kw.get("parts", 1))
+            bshare = float(bX.max()) / (margin * float(bE.max())) if float(bE.max()) > 0 else (0.0 if float(bX.max()) == 0 else float("inf"))
+            line += f"; row bias {float(bE.max()):.3e} / {float(bX.max()):.3e} = {bshare:.3f} (row {int(idx[int(bX.argmax())])})"
+            share = max(share, bshare)
+        out[name] = (share, float(eE.max()), float(eX.max()))
+        say(line)
+
+    x_prev = _take(probes["blk0.x_in"], idx)
+    pivot = None  # the previous site's means (site 0 has none)
+    for l in range(depth):
+        Wb = Wst["blocks"][l]
+        sh_a, sc_a, g_a, sh_m, sc_m, g_m = stage_ada(ada, l, D, depth)
+        t = f"blk{l}."
+        folded1 = (t + "stats1") in probes
+        if not folded1:
+            n1 = _take(probes[t + "n1"], idx)
+            kw = dict(x=x_prev, scale=sc_a, shift=sh_a)
+            judge(t + "n1", n1, stage_ref("n1", **kw), stage_emulate(precision, "n1", **kw))
+            kw = dict(n1=n1, w=Wb["qkv_w"], b=Wb["qkv_b"], pos=pos, rope_heads=rope_heads, qs=qs)
+            stage = "qkv"
+        else:
+            kw = dict(x=x_prev, pivot=pivot)
+            st1 = _take(probes[t + "stats1"], idx)
+            judge(t + "stats1", st1, stage_ref("stats", **kw), stage_emulate(precision, "stats", **kw), stats=True)
+            pivot = st1[:, 0]
+            kw = dict(x=x_prev, scale=sc_a, shift=sh_a, w=Wb["qkv_w"], b=Wb["qkv_b"], pos=pos, rope_heads=rope_heads, qs=qs)
+            stage = "qkv_folded"
+        qkv = _take(probes[t + "qkv"], idx)
+        judge(t + "qkv", qkv, stage_ref(stage, **kw), stage_emulate(precision, stage, **kw), parts=3)
+        # attention: the sampled queries of a sequence over that sequence's probed keys
+        ctx = _take(probes[t + "ctx"], idx)
+        R, E = torch.empty(len(idx), inner, dtype=torch.float64), torch.empty(len(idx), inner)
+        for sid in lay["seg"][idx].unique().tolist():
+            r0, n = lay["seg_rows"][sid]
+            sel = (lay["seg"][idx] == sid).nonzero().reshape(-1)
+            keys = probes[t + "qkv"][r0:r0 + n].float().cpu()[lay["key"][r0:r0 + n]].reshape(-1, 3, heads, 64)
+            kw = dict(q=qkv[sel].reshape(-1, 3, heads, 64)[:, 0], k=keys[:, 1], v=keys[:, 2], qs=qs)
+            R[sel], E[sel] = stage_ref("ctx", **kw), stage_emulate(precision, "ctx", **kw)
+        judge(t + "ctx", ctx, R, E)
+        x_attn = _take(probes[t + "x_attn"], idx)
+        kw = dict(x=x_prev, a=ctx, w=Wb["o_w"], b=Wb["o_b"], gate=g_a)
+        judge(t + "x_attn", x_attn, stage_ref("resid", **kw), stage_emulate(precision, "resid", **kw))
+        if (t + "stats2") in probes:
+            kw = dict(x=x_attn, pivot=pivot)
+            st2 = _take(probes[t + "stats2"], idx)
+            judge(t + "stats2", st2, stage_ref("stats", **kw), stage_emulate(precision, "stats", **kw), stats=True)
+            pivot = st2[:, 0]
+        ff1 = _take(probes[t + "ff1"], idx)
+        kw = dict(x=x_attn, scale=sc_m, shift=sh_m, w=Wb["f1_w"], b=Wb["f1_b"])
+        judge(t + "ff1", ff1, stage_ref("ff1", **kw), stage_emulate(precision, "ff1", **kw))
+        x_ff = _take(probes[t + "x_ff"], idx)
+        kw = dict(x=x_attn, a=ff1, w=Wb["f2_w"], b=Wb["f2_b"], gate=g_m)
+        judge(t + "x_ff", x_ff, stage_ref("resid", **kw), stage_emulate(precision, "resid", **kw))
+        x_prev = x_ff
+    scale, shift = stage_ada(ada, depth, D, depth)
+    fn = _take(probes["final_norm"], idx)
+    kw = dict(x=x_prev, scale=scale, shift=shift)
+    judge("final_norm", fn, stage_ref("final_norm", **kw), stage_emulate(precision, "final_norm", **kw))
+    kw = dict(h=fn, w=Wst["out_w"], b=Wst["out_b"])
+    judge("vout", _take(probes["vout"], idx), stage_ref("vout", **kw), stage_emulate(precision, "vout", **kw))
+    return out
+
+
+def stage_check(name, shares):
+    """asserts every stage of stage_shares within its bound; the message names the stages that are not"""
+    bad = {k: round(v[0], 3) for k, v in shares.items() if not v[0] <= 1.0}
+    assert not bad, f"{name}: stages out of bound (worst row / bound): {bad}"
+
+
+def stage_chain(precision, Wst, ada, lay, x_in, qs, depth, rope_heads, heads, defect="none", ada_other=None):
+    """A whole folded evaluation restated on the CPU with stage_emulate, every stage from the one before it over ALL rows of the layout: the
+    probes a device would give (the host stand-in of tests/test_production_stage_bound_host.py).  `defect` (STAGE_DEFECTS) is planted where the
+    library would carry it:
+        stats_quarter_row            every statistics site sums the first quarter of the row
+        stats_of_previous_site       a folded projection reads the statistics table of site k - 1
+        v_c1_c2_shifted_by_inner     the v rows of a folded QKV projection take the c1 / c2 of the k rows
+        fold_rows_of_another_time    W', c1, c2 come from the AdaLN row ada_other (another evaluation time's rows of the fold table)
+        q_not_scaled, q_scaled_twice the q rows carry no / twice the softmax scale (qs)
+        gate_mlp_for_gate_msa        the out-projection takes slot 5 of the AdaLN row
+        blk0_unscaled_weight_copy    block 0 projects with the copy whose q rows carry no scale (qs)
+        final_pair_swapped           the final AdaLN reads (shift, scale)
+        rope_position_is_row_index   RoPE position = row % N, not the row's position in its utterance (a ragged batch)"""
+    D = Wst["blocks"][0]["o_w"].shape[0]
+    inner = Wst["blocks"][0]["o_w"].shape[1]
+    rows = lay["rows"]
+    pos = torch.arange(rows) % lay["N"] if defect == "rope_position_is_row_index" else lay["pos"]
+    probes = {"adaln": ada.clone(), "blk0.x_in": x_in.clone()}
+    fold_ada = ada_other if defect == "fold_rows_of_another_time" else ada
+    x, x_site_before, pivot = x_in, None, None  # x_site_before: the stream as the site before the current one saw it
+    emu = lambda stage, **kw: stage_emulate(precision, stage, defect=defect, **kw)
+    for l in range(depth):
+        Wb = Wst["blocks"][l]
+        t = f"blk{l}."
+        sh_a, sc_a, g_a, sh_m, sc_m, g_m = stage_ada(ada, l, D, depth)
+        fsh_a, fsc_a, _, fsh_m, fsc_m, _ = stage_ada(fold_ada, l, D, depth)
+        if l == 0:
+            probes[t + "n1"] = emu("n1", x=x, scale=sc_a, shift=sh_a)
+            probes[t + "qkv"] = emu("qkv", n1=probes[t + "n1"], w=Wb["qkv_w"], b=Wb["qkv_b"], pos=pos, rope_heads=rope_heads, qs=qs)
+        else:
+            probes[t + "stats1"] = emu("stats", x=x, pivot=pivot)
+            pivot = probes[t + "stats1"][:, 0]
+            xstat = x_site_before if defect == "stats_of_previous_site" else x
+            probes[t + "qkv"] = emu("qkv_folded", x=x, xstat=xstat, scale=fsc_a, shift=fsh_a, w=Wb["qkv_w"], b=Wb["qkv_b"], pos=pos, rope_heads=rope_heads, qs=qs)
+        qkv = probes[t + "qkv"].reshape(rows, 3, heads, 64)
+        ctx = torch.zeros(rows, inner)
+        for sid, (r0, n) in lay["seg_rows"].items():
+            kmask = lay["key"][r0:r0 + n]
+            ctx[r0:r0 + n] = emu("ctx", q=qkv[r0:r0 + n, 0], k=qkv[r0:r0 + n, 1][kmask], v=qkv[r0:r0 + n, 2][kmask], qs=qs)
+        probes[t + "ctx"] = ctx
+        gate = g_m if defect == "gate_mlp_for_gate_msa" else g_a
+        x_attn = emu("resid", x=x, a=ctx, w=Wb["o_w"], b=Wb["o_b"], gate=gate)
+        pad = (~lay["key"]) & (lay["seg"] >= 0)
+        x_attn[pad] = x[pad]  # rowbits: a padded query row keeps its bits
+        probes[t + "x_attn"] = x_attn
+        probes[t + "stats2"] = emu("stats", x=x_attn, pivot=pivot)
+        pivot = probes[t + "stats2"][:, 0]
+        probes[t + "ff1"] = emu("ff1", x=x_attn, xstat=x if defect == "stats_of_previous_site" else x_attn, scale=fsc_m, shift=fsh_m, w=Wb["f1_w"], b=Wb["f1_b"])
+        x_ff = emu("resid", x=x_attn, a=probes[t + "ff1"], w=Wb["f2_w"], b=Wb["f2_b"], gate=g_m)
+        probes[t + "x_ff"] = x_ff
+        x_site_before, x = x_attn, x_ff
+    scale, shift = stage_ada(ada, depth, D, depth)
+    probes["final_norm"] = emu("final_norm", x=x, scale=scale, shift=shift)
+    probes["vout"] = emu("vout", h=probes["final_norm"], w=Wst["out_w"], b=Wst["out_b"])
+    return probes
