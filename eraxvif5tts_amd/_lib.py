@@ -49,6 +49,13 @@ class SpeakerConfig(C.Structure):  # struct f5_speaker_config
     _fields_ = [(n, C.c_int32) for n in ("feat_dim", "channels", "emb_dim", "layers", "cat_channels", "se_bottleneck", "attention_channels", "scale")]
 
 
+class WavLMConfig(C.Structure):  # struct f5_wavlm_config
+    _fields_ = [("num_conv_layers", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8)] + \
+               [(n, C.c_int32) for n in ("conv_bias", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size",
+                                         "num_conv_pos_embeddings", "num_conv_pos_embedding_groups", "num_buckets", "max_bucket_distance",
+                                         "feat_extract_norm", "do_stable_layer_norm", "add_adapter", "normalize_input")] + [("layer_norm_eps", C.c_float)]
+
+
 class MelConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_fft", "hop", "win", "n_mels", "sample_rate", "mel_type")]
 
@@ -205,6 +212,18 @@ _PROTOS = {
     "f5_op_speaker_res2": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
     "f5_op_speaker_se": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f5_op_speaker_pool": (_I, [_I, C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "f5_wavlm_create": (_I, [C.POINTER(WavLMConfig), C.POINTER(_P)]),
+    "f5_wavlm_set_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),
+    "f5_wavlm_has_tensor": (_I, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
+    "f5_wavlm_finalize": (_I, [_P]),
+    "f5_wavlm_destroy": (_I, [_P]),
+    "f5_wavlm_frames": (_I, [_P, C.c_int64]),
+    "f5_wavlm_set_buckets": (_I, [_P, _I, C.POINTER(C.c_int32)]),
+    "f5_wavlm_extract_ragged": (_I, [_P, _I, C.POINTER(C.c_int32), _P, _I, _P, _P]),
+    "f5_wavlm_set_tap": (_I, [_P, C.c_char_p, _P]),
+    "f5_op_wavlm_attention": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    "f5_op_wavlm_pos_conv": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "f5_op_wavlm_conv_ln_gelu": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 

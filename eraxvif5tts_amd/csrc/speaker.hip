@@ -1,6 +1,6 @@
 // speaker.hip -- the ECAPA-TDNN speaker-verification head behind the reference's "SIM" figure: eval/ecapa_tdnn.py (ECAPA_TDNN.get_feat / forward,
 // :283-309, global_context_att = False as ECAPA_TDNN_SMALL builds it) as utils_eval.run_sim calls it.  Forward only, eval mode, fp32 storage.  The
-// feature extractor in front of it (WavLM-large from s3prl) is not in the reference tree and not here: the caller hands in its hidden states.
+// feature extractor in front of it (WavLM-large from s3prl) is wavlm.hip: this head takes its hidden states, packed as f5_wavlm_extract_ragged writes them.
 //   x[t][f] = sum_l softmax(feature_weight)[l] hs[l][t][f] + 1e-6;  InstanceNorm1d(F) per utterance over time (biased variance, eps 1e-5, no affine)
 //   layer1  Conv1dReluBn(F -> C, k 5, pad 2)                        (conv -> ReLU -> BatchNorm: the BN cannot be folded into its own conv)
 //   layer2..4  SE_Res2Block(C, k 3, dilation = padding = 2, 3, 4, scale 8):  Conv1dReluBn(1 x 1) -> Res2Conv1dReluBn -> Conv1dReluBn(1 x 1) -> SE_Connect, + x

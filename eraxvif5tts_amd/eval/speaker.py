@@ -8,9 +8,11 @@ layer mix, instance norm, layer1, the three SE-Res2 blocks, the wide convolution
 linear -- plus run_sim's resample (``f5_frontend_resample``) and cosine around it.  The published checkpoint ``wavlm_large_finetune.pth`` loads
 by its own key names (``torch.load(...)["model"]``).
 
-What does NOT: the feature extractor.  The reference takes WavLM-large from s3prl over ``torch.hub``; neither its source nor its weights are
-in the reference tree, and nothing here fetches anything.  It is a plug point: a callable ``feature_extractor(list_of_16kHz_waves)`` that
-returns the hidden states, as s3prl's ``{"hidden_states": [L tensors [B, T, F]]}`` or one stacked tensor, running under PyTorch-ROCm.
+The feature extractor in front of it is a plug point.  ``eval/wavlm.py``'s ``WavLMExtractor`` fills it on the device (``csrc/wavlm.hip``;
+``WavLMExtractor.from_speaker_checkpoint`` reads its tensors from the same ``wavlm_large_finetune.pth``): an object with ``extract`` gets all
+2 n waves in ONE ragged call and its packed hidden states go to the head as they are.  Any other callable
+``feature_extractor(list_of_16kHz_waves)`` that returns the hidden states, as s3prl's ``{"hidden_states": [L tensors [B, T, F]]}`` or one
+stacked tensor, is called one wave at a time as before.  Nothing here fetches anything.
 ``global_context_att=True`` checkpoints are refused (another function, not approximated)."""
 from __future__ import annotations
 
@@ -169,18 +171,40 @@ class SpeakerEncoder:
         ``[B, emb_dim]`` fp32 on the device.  One call is one ragged launch set (per 64 utterances) and nothing synchronises with the host; an
         utterance's embedding has the same bits whatever shares the call with it."""
         frames = self.check_features(features)
-        lib = _lib.load()
-        hd = self.native()
+        self.native()
         if isinstance(features, torch.Tensor):
             L, B, T, Fd = features.shape
             hs = features.to(device="cuda", dtype=torch.float32).reshape(L, B * T, Fd).contiguous()
         else:
             hs = torch.cat([f.to(device="cuda", dtype=torch.float32) for f in features], dim=1).contiguous()
+        return self._embed_rows(hs, frames)
+
+    def _embed_rows(self, hs, frames):
+        lib = _lib.load()
+        hd = self.native()
         B = len(frames)
         emb = torch.empty(B, self.emb_dim, device=hs.device, dtype=torch.float32)
         with torch.cuda.device(hs.device):
             _lib.check(lib.f5_speaker_embed_ragged(hd, B, (C.c_int32 * B)(*frames), _lib.ptr(hs), _lib.ptr(emb), _lib.stream_ptr()), "speaker_embed_ragged")
         return emb
+
+    @torch.no_grad()
+    def embed_packed(self, hs, frames):
+        """``hs``: one contiguous fp32 device tensor ``[L, sum(frames), F]``, the utterances back to back along the row axis -- what
+        ``WavLMExtractor.extract`` returns, taken as it is (no concatenation).  The same launches, and so the same bits, as ``embed`` on the list of
+        its slices."""
+        frames = [int(t) for t in frames]
+        if not isinstance(hs, torch.Tensor) or hs.ndim != 3 or not hs.is_cuda or hs.dtype != torch.float32 or not hs.is_contiguous():
+            raise ValueError("embed_packed: hs must be a contiguous fp32 device tensor [L, rows, F]")
+        if int(hs.shape[0]) != self.cfg["layers"] or int(hs.shape[2]) != self.cfg["feat_dim"]:
+            raise ValueError(f"features have {int(hs.shape[0])} layers of {int(hs.shape[2])} features; the encoder was built for "
+                             f"{self.cfg['layers']} x {self.cfg['feat_dim']}")
+        if not frames or sum(frames) != int(hs.shape[1]):
+            raise ValueError(f"embed_packed: frames sum to {sum(frames)}, hs has {int(hs.shape[1])} rows")
+        for u, t in enumerate(frames):
+            if t < 2:
+                raise ValueError(f"utterance {u} has {t} frame(s): the speaker head needs at least 2 (InstanceNorm1d over one frame raises in the reference too)")
+        return self._embed_rows(hs, frames)
 
 
 def _hidden_states(out, n):
@@ -206,6 +230,8 @@ def speaker_similarity(encoder, pairs, feature_extractor=None, sample_rate=24000
     (an int, or one ``(rate_generated, rate_prompt)`` tuple).  Each wave is resampled to 16 kHz on the device (``f5_frontend_resample``, the
     ``torchaudio.transforms.Resample`` both sides agree on) and handed to ``feature_extractor`` ONE AT A TIME, as run_sim does (batch 1: no
     padding frames enter the statistics); all 2 n utterances are then embedded in ragged launches and compared with ``F.cosine_similarity``.
+    A ``feature_extractor`` with an ``extract`` method (``WavLMExtractor``) gets all 2 n waves in one ragged call instead, which keeps batch-1
+    semantics per utterance and gives the same bits as the one-at-a-time route.
     Returns ``(similarities [n] on the device, their mean as a float)``; the ``float`` is the call's one synchronisation."""
     if not isinstance(encoder, SpeakerEncoder):
         raise TypeError("speaker_similarity: encoder must be a SpeakerEncoder")
@@ -217,7 +243,8 @@ def speaker_similarity(encoder, pairs, feature_extractor=None, sample_rate=24000
     if len(rates) != 2 or any(int(r) <= 0 for r in rates):
         raise ValueError("speaker_similarity: sample_rate is a positive int or a (generated, prompt) pair of them")
     from .. import frontend
-    feats = []
+    ragged = hasattr(feature_extractor, "extract")
+    feats, waves = [], []
     for i, pair in enumerate(pairs):
         if not isinstance(pair, (list, tuple)) or len(pair) != 2:
             raise ValueError(f"speaker_similarity: pair {i} is not a (generated, prompt) pair")
@@ -230,8 +257,11 @@ def speaker_similarity(encoder, pairs, feature_extractor=None, sample_rate=24000
             w = w.to(device="cuda", dtype=torch.float32)
             if int(rate) != SIM_SAMPLE_RATE:
                 w = frontend.resample(w, int(rate), SIM_SAMPLE_RATE)
-            feats.extend(_hidden_states(feature_extractor([w]), 1))
-    emb = encoder.embed(feats)
+            if ragged:
+                waves.append(w)
+            else:
+                feats.extend(_hidden_states(feature_extractor([w]), 1))
+    emb = encoder.embed_packed(*feature_extractor.extract(waves)) if ragged else encoder.embed(feats)
     sim = F.cosine_similarity(emb[0::2], emb[1::2])
     return sim, float(sim.mean())
 

@@ -905,7 +905,7 @@ F5_API int f5_frontend_resample(f5_frontend_t h, int B, int n, int orig_freq, in
 /* ------------------------------------------------------------------ speaker-similarity head (ECAPA-TDNN, the "SIM" figure)
  * Everything of the reference's eval/ecapa_tdnn.py behind `self.feature_extract(...)` (ECAPA_TDNN.get_feat / forward, :283-309) with
  * global_context_att = False, as ECAPA_TDNN_SMALL and utils_eval.run_sim use it: forward only, eval mode, fp32 storage.  The feature extractor
- * (WavLM-large from s3prl in the reference) is NOT part of this library: the caller hands in its hidden states.
+ * (WavLM-large from s3prl in the reference) is a handle of its own (f5_wavlm_*, below): this one takes the hidden states.
  *   x = sum_l softmax(feature_weight)[l] hs[l] + 1e-6 -> InstanceNorm1d per utterance (biased variance, eps 1e-5) -> layer1 Conv1dReluBn(k 5)
  *   -> three SE_Res2Blocks (dilation 2, 3, 4; Res2 scale `scale`) -> cat -> Conv1d(3C -> cat_channels) + ReLU -> AttentiveStatsPool
  *   -> BatchNorm1d(2 cat_channels) -> Linear(-> emb_dim)
@@ -961,6 +961,80 @@ F5_API int f5_op_speaker_se(int cnt, const int32_t* frames_host, int C, int bott
                             const float* b1_host, const float* w2_host, const float* b2_host, float* out, f5_stream_t stream);
 F5_API int f5_op_speaker_pool(int cnt, const int32_t* frames_host, int C, int att, const float* x, const float* w1_host, const float* b1_host,
                               const float* w2_host, const float* b2_host, float* out, f5_stream_t stream);
+
+/* ------------------------------------------------------------------ WavLM feature extractor (in front of the speaker head: the "SIM" figure)
+ * The network run_sim takes from s3prl as "wavlm_large", with the arithmetic of transformers' WavLMModel at feat_extract_norm = "layer",
+ * do_stable_layer_norm = True (microsoft/wavlm-large): forward only, fp32 storage and accumulation, batch-1 semantics per utterance (no padding,
+ * no mask).  Per utterance: optional F.layer_norm over the wave -> conv layers (Conv1d, LayerNorm over channels, GELU) -> LayerNorm + Linear ->
+ * x + GELU(grouped positional Conv1d) -> N pre-LayerNorm encoder layers whose attention adds WavLM's gated relative position bias.
+ * Tensor names are WavLMModel.state_dict()'s, with ONE exception: the positional convolution's weight-norm is folded by the caller and set as
+ * encoder.pos_conv_embed.conv.weight [hidden, hidden / groups, k] (W = g * v / ||v||, the norm over dims (0, 1) per tap).  masked_spec_embed is
+ * not a tensor of this handle.  create refuses, with F5_EINVAL and the field's name: feat_extract_norm other than "layer",
+ * do_stable_layer_norm = 0, add_adapter, a hidden size the heads do not divide, a head dimension other than 16 or 64, widths that are not multiples
+ * of 32, hidden / groups not a multiple of 16.
+ * The relative position bucket of a distance uses a float log; it is evaluated by the caller exactly as the model does and handed over with
+ * set_buckets (below) -- the device never computes a bucket. */
+typedef struct f5_wavlm_s* f5_wavlm_t;
+typedef struct f5_wavlm_config {
+    int32_t num_conv_layers;      /* 7; at most 8 */
+    int32_t conv_dim[8];          /* 512 x 7; multiples of 32 */
+    int32_t conv_kernel[8];       /* 10, 3, 3, 3, 3, 2, 2 */
+    int32_t conv_stride[8];       /* 5, 2, 2, 2, 2, 2, 2 */
+    int32_t conv_bias;            /* 0 / 1 */
+    int32_t hidden_size;          /* 1024 */
+    int32_t num_hidden_layers;    /* 24 */
+    int32_t num_attention_heads;  /* 16 */
+    int32_t intermediate_size;    /* 4096 */
+    int32_t num_conv_pos_embeddings;       /* 128 */
+    int32_t num_conv_pos_embedding_groups; /* 16 */
+    int32_t num_buckets;          /* 320 */
+    int32_t max_bucket_distance;  /* 800 */
+    int32_t feat_extract_norm;    /* 0 = "layer" (the only one implemented), 1 = "group" */
+    int32_t do_stable_layer_norm; /* 1 (the only one implemented) */
+    int32_t add_adapter;          /* 0 (the only one implemented) */
+    int32_t normalize_input;      /* 1: F.layer_norm(wave, wave.shape), eps 1e-5, fp64 sums in a fixed order (s3prl's expert for the large model) */
+    float layer_norm_eps;         /* 1e-5 */
+} f5_wavlm_config;
+F5_API int f5_wavlm_create(const f5_wavlm_config* cfg, f5_wavlm_t* out);
+F5_API int f5_wavlm_set_tensor(f5_wavlm_t h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+F5_API int f5_wavlm_has_tensor(f5_wavlm_t h, const char* name, int64_t* numel);
+F5_API int f5_wavlm_finalize(f5_wavlm_t h);
+F5_API int f5_wavlm_destroy(f5_wavlm_t h);
+/* frames an utterance of n_samples gives (per conv layer (T - k) / stride + 1, rounded down), or a negative number when it is too short for one */
+F5_API int f5_wavlm_frames(f5_wavlm_t h, int64_t n_samples);
+/* buckets_host: host int32 [2 n - 1], the model's relative position bucket of the distances d = key - query = -(n - 1) .. n - 1.  Builds the
+ * device table R[h][d] = rel_attn_embed[bucket(d)][h] (layer 0's embedding, shared by all layers) that every later extract call reads; an
+ * utterance of more than n frames is refused by extract until a larger table is set.  After finalize; waits for the device. */
+F5_API int f5_wavlm_set_buckets(f5_wavlm_t h, int n, const int32_t* buckets_host);
+/* B utterances of DIFFERENT lengths through one set of launches.  samples_host: host int32 [B], read before the call returns; wave_cat: dev f32,
+ * the 16 kHz waves back to back; hs_out: dev f32 [L, sum(frames), hidden], L = num_hidden_layers + 1, the utterances back to back along the row
+ * axis -- exactly what f5_speaker_embed_ragged takes.  Entry 0 is the encoder's input behind the positional convolution, entry i the output of
+ * layer i; final_norm = 1 applies the encoder's LayerNorm to the last entry (WavLMModel(output_hidden_states=True)), 0 leaves it as the layer
+ * left it.  Row-wise kernels run once over all rows; convolutions and attention work on one utterance's own extent, so an utterance's hidden
+ * states have the same bits alone or in any ragged call, at any position.  Lists of more than 64 utterances or 2048 frames are cut, in order,
+ * into several launch sets, which changes no bit.  F5_EINVAL before any launch: B <= 0, an utterance too short for one frame, a call beyond
+ * 32-bit indexing; F5_ESTATE: not finalized, or no bucket table covers the longest utterance (f5_wavlm_set_buckets comes first, also for a caller
+ * in C).  Nothing synchronises (workspace growth aside).  The workspace grows to the largest launch set seen and stays: about 0.6 GiB for a full
+ * set at wavlm-large sizes, most of it the rows behind conv layer 0. */
+F5_API int f5_wavlm_extract_ragged(f5_wavlm_t h, int B, const int32_t* samples_host, const float* wave_cat, int final_norm, float* hs_out,
+                                   f5_stream_t stream);
+/* Test hook: the next extract calls also copy an intermediate tensor, time-major and packed as the output is, into `dev` (NULL: stop).  Names:
+ * conv{i} (behind LayerNorm and GELU, [sum frames_i, conv_dim[i]]), proj, posconv (= entry 0), layer{i}.attn (the stream behind the attention
+ * residual), layer{i}.out (behind the layer, before any final norm): [sum frames, hidden]. */
+F5_API int f5_wavlm_set_tap(f5_wavlm_t h, const char* name, float* dev);
+/* The new kernels one by one (device tensors x, qkv, gate, rel, out; parameters marked host are HOST arrays in PyTorch's layouts, staged by the
+ * op, which then waits for the stream):
+ *   attention     qkv [T, 3 H dh] (q | k | v), gate [T, H] (the gate g itself), rel [H, 2 T - 1] (R[h][d] at column d + T - 1) -> out [T, H dh];
+ *                 softmax((q . k) dh^-0.5 + g R) v, online softmax in fp32, dh 16 or 64
+ *   pos_conv      x [T, C] -> out = x + gelu(Conv1d(C, C, k, padding k / 2, groups)(x)) without the last frame when k is even; w host
+ *                 [C][C / groups][k] (weight-norm folded), b host [C]; out must not be x
+ *   conv_ln_gelu  x [T_in, cin] -> gelu(LayerNorm(Conv1d(cin, cout, k, stride)(x))) [(T_in - k) / stride + 1, cout], eps 1e-5; w host
+ *                 [cout][cin][k], b host [cout] or NULL; cin 1 (the direct kernel of conv layer 0) or a multiple of 32 */
+F5_API int f5_op_wavlm_attention(int T, int H, int dh, const float* qkv, const float* gate, const float* rel, float* out, f5_stream_t stream);
+F5_API int f5_op_wavlm_pos_conv(int T, int C, int k, int groups, const float* x, const float* w_host, const float* b_host, float* out,
+                                f5_stream_t stream);
+F5_API int f5_op_wavlm_conv_ln_gelu(int T_in, int cin, int cout, int k, int stride, const float* x, const float* w_host, const float* b_host_or_null,
+                                    const float* ln_w_host, const float* ln_b_host, float* out, f5_stream_t stream);
 
 #ifdef __cplusplus
 }
